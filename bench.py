@@ -27,6 +27,7 @@ import torch  # noqa: E402
 
 MFMA_PEAK_TFLOPS = 2500.0     # bf16 dense, /opt/skills/guides/MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0
+DUMP_BYTES = 64_000_000       # --dump-outputs: cap on all .npy files together
 
 
 from unirestore_amd.init import init_random_  # noqa: E402,F401  (seeded random weights of the reference architecture)
@@ -106,6 +107,21 @@ def cpu_baseline(model, denoise_steps):
                        f"{step_s[0]:.2f} / {step_s[1]:.2f}s), extrapolated to {denoise_steps} steps ({total:.1f}s/image)"), parity
 
 
+def dump_outputs(d, arrays):
+    """--dump-outputs: each array (host copy of a timed step's result) as <d>/<name>.npy in float32.  An array larger than its
+    share of DUMP_BYTES is replaced by a fixed seeded sample of its flattened elements (same shape -> same indices), so the
+    files of two builds compare element for element."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1) - 1024          # (1 KB per file for the .npy header)
+    for name, a in arrays.items():
+        a = a.float().numpy()
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def other_configs(model, dev, reps=3):
     """Per-GPU shards of BASELINE.json configs[3] (TIR segmentation 1024x1024, B=1/GPU, 20 steps, bf16, task 'seg') and configs[4]
     (512x512, B=8/GPU, 50 steps, fp16): 1 capture + 1 warm replay, then `reps` timed hipGraph replays each."""
@@ -150,7 +166,11 @@ def main():
     ap.add_argument("--no-fp16", action="store_true", help="skip the second timed loop in fp16 (headline dtype stays bf16)")
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL and run the weight broadcast / output all-gather even "
                     "at world size 1 (exercises the N>1 code path - graph capture beside the RCCL watchdog - on a one-GPU box)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed loops, write what each loop's last step returned as "
+                    "DIR/<name>.npy (float32, at most 64 MB in all; inputs and weights are seeded, so runs compare file for file)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     local = int(os.environ.get("LOCAL_RANK", 0))
@@ -215,6 +235,11 @@ def main():
         # the all-gather figure includes waiting for the slowest rank's forward)
         comm_split = {"compute_ms": round(float(t[1].item()), 3), "allgather_ms": round(float(t[2].item()), 3)}
     finite = bool(torch.isfinite(out).all())
+    dumps = {}          # --dump-outputs: host copies of the last timed step's results (the fp16 loop below reuses `gathered`)
+    if args.dump_outputs and rank == 0:
+        dumps[f"restored_{args.dtype}"] = out.cpu()
+        if world > 1:
+            dumps[f"restored_{args.dtype}_all_ranks"] = gathered.cpu()
 
     # ---- the same timed loop in fp16: the 16-bit type that meets the north-star 1e-3 parity (bf16 operands alone cost 3e-3) ----
     fp16 = None
@@ -238,6 +263,10 @@ def main():
             e16 = float(t.item())
         fp16 = {"images_per_s": world * B * args.steps / e16, "ms_per_step": e16 / args.steps * 1e3,
                 "output_finite": bool(torch.isfinite(out16).all())}
+        if args.dump_outputs and rank == 0:
+            dumps["restored_fp16"] = out16.cpu()
+            if world > 1:
+                dumps["restored_fp16_all_ranks"] = gathered.cpu()
         model.set_dtype("bf16")
 
     result = None
@@ -350,6 +379,8 @@ def main():
         result["library_launches_per_forward"] = int(sum(v["launches"] for v in rep.values()))
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"], result["parity_vs_oracle"] = cpu_baseline(model, args.denoise_steps)
+    if dumps:
+        dump_outputs(args.dump_outputs, dumps)
     if rank == 0:
         print(json.dumps(result))
     if use_dist:
