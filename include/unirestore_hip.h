@@ -278,6 +278,17 @@ int ur_add_noise(const float* z0, const float* noise_nchw, float* zt, void* zt_1
 /* DDIM update (unifie.py:150): zt <- c_x*zt + c_e*eps, eps fp32 NHWC [M, ld_eps]; refreshes the 16-bit copy */
 int ur_ddim_step(float* zt, const float* eps, int ld_eps, void* zt_16, long long M, int Clat, int Cpad,
                  float c_x, float c_e, int dtype, ur_stream_t stream);
+/* Tiled latent sampling (unirestore_amd/tiling.py).  Latents fp32 NHWC [N,LH,LW,Cpad]; tile batch [N*T,th,tw,.] with image n's
+ * tile k at index n*T+k; origins device int [T][2] = (y0, x0), every tile inside the latent (others are skipped).
+ * gather: tiles_16 <- 16-bit copy of each tile's window of z. */
+int ur_latent_tiles_gather(const float* z, void* tiles_16, int N, int LH, int LW, int Cpad, int T, int th, int tw,
+                           const int* origins, int dtype, ur_stream_t stream);
+/* Blended DDIM step, output-stationary per latent pixel p: eps(p) = sum_k wn[k](p) * eps_tiles_k(p) over the covering tiles in
+ * ascending k (fp32), zt <- c_x*zt + c_e*eps, and the 16-bit zt into every covering tile slot of zt_tiles_16.  eps_tiles fp32
+ * [N*T,th,tw,ld_eps], wn fp32 [T,th,tw] (normalised weights), Clat <= 8. */
+int ur_latent_tiles_blend_ddim(float* zt, const float* eps_tiles, int ld_eps, void* zt_tiles_16, const float* wn, int N, int LH,
+                               int LW, int Clat, int Cpad, int T, int th, int tw, const int* origins, float c_x, float c_e,
+                               int dtype, ur_stream_t stream);
 /* y_16[M][Cpad] = x_f32[M][ld] * mul (latents / scaling_factor before post_quant_conv) */
 int ur_f32_to_bf16_scaled(const float* x, int ld, void* y, long long M, int C, int Cpad, float mul, int dtype, ur_stream_t stream);
 

@@ -91,6 +91,8 @@ SIGNATURES = {
     "ur_vae_sample": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P]),
     "ur_add_noise": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _I, _P]),
     "ur_ddim_step": (_I, [_P, _P, _I, _P, _LL, _I, _I, _F, _F, _I, _P]),
+    "ur_latent_tiles_gather": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "ur_latent_tiles_blend_ddim": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _F, _F, _I, _P]),
     "ur_f32_to_bf16_scaled": (_I, [_P, _I, _P, _LL, _I, _I, _F, _I, _P]),
     "ur_profile_enable": (_I, [_I]),
     "ur_profile_report": (_I, [C.c_char_p, _SZ]),

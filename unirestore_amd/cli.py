@@ -71,6 +71,15 @@ def resolve(cfg: dict, allow_16bit: bool = False) -> dict:
     for k in ("frenc", "cnet", "tedit"):
         if mk.get(k) and str(mk[k].get("ckpt_path", "")).startswith("$"):      # "$path_to_stage1_ckpt$" placeholders of val.yaml
             mk[k] = dict(mk[k], ckpt_path=None)
+    cn = mk.get("cnet") or {}
+    if cn.get("tile_size") is not None or cn.get("tile_stride") is not None:     # tiled latent sampling (opt-in)
+        from .tiling import check_tile_stride, default_tile_stride
+        if cn.get("tile_size") is None:
+            raise ValueError("cnet.tile_stride needs cnet.tile_size (the latent tile edge, e.g. 64)")
+        tile = int(cn["tile_size"])
+        stride = int(cn["tile_stride"]) if cn.get("tile_stride") is not None else default_tile_stride(tile)
+        check_tile_stride(tile, stride)
+        mk["cnet"] = dict(cn, tile_size=tile, tile_stride=stride)
     dcp = da.get("class_path", "unirestore_amd.data.SyntheticImages")
     if dcp not in DATA_CLASSES:
         raise KeyError(f"data.class_path {dcp!r} unknown: {sorted(DATA_CLASSES)}")

@@ -417,6 +417,64 @@ __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restric
     for (int c = 0; c < Cpad; ++c) y[i * Cpad + c] = c < C ? f2h16<F16>(x[i * ld + c] * mul) : (uint16_t)0;
 }
 
+// ---- tiled latent sampling (unirestore_amd/tiling.py): tile gather + blended DDIM step ---------------------------------
+// origins: device int [T][2] = (y0, x0); a tile that would not lie inside the latent is skipped (gather writes zeros for it).
+template <bool F16>
+__global__ __launch_bounds__(256) void latent_tiles_gather_kernel(const float* __restrict__ z, uint16_t* __restrict__ tiles,
+                                                                  int LH, int LW, int Cpad, int T, int th, int tw,
+                                                                  const int* __restrict__ origins, long long total) {
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {   // i = tile-batch pixel
+    const int x = (int)(i % tw);
+    const long long r = i / tw;
+    const int y = (int)(r % th);
+    const long long nk = r / th;
+    const int k = (int)(nk % T), n = (int)(nk / T);
+    const int y0 = origins[2 * k], x0 = origins[2 * k + 1];
+    const bool ok = y0 >= 0 && x0 >= 0 && y0 + th <= LH && x0 + tw <= LW;
+    const float* src = z + (((long long)n * LH + (y0 + y)) * LW + (x0 + x)) * Cpad;
+    for (int c = 0; c < Cpad; ++c) tiles[i * Cpad + c] = ok ? f2h16<F16>(src[c]) : (uint16_t)0;
+  }
+}
+
+// Output-stationary over full-latent pixels: eps(p) = sum_k wn_k(p) eps_k(p) over the covering tiles in ascending k (fp32),
+// zt' = cx*zt + ce*eps, then zt' to the fp32 latent and its 16-bit copy to every covering tile slot (each slot has exactly
+// one writer: no atomics, bit-reproducible).
+template <bool F16>
+__global__ __launch_bounds__(256) void latent_tiles_blend_ddim_kernel(float* __restrict__ zt, const float* __restrict__ eps,
+                                                                      int ld_eps, uint16_t* __restrict__ tiles,
+                                                                      const float* __restrict__ wn, int LH, int LW, int Clat,
+                                                                      int Cpad, int T, int th, int tw,
+                                                                      const int* __restrict__ origins, float cx, float ce,
+                                                                      long long total) {
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {   // i = latent pixel
+    const int x = (int)(i % LW);
+    const long long r = i / LW;
+    const int y = (int)(r % LH);
+    const long long n = r / LH;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < T; ++k) {
+      const int ty = y - origins[2 * k], tx = x - origins[2 * k + 1];
+      if (ty < 0 || tx < 0 || ty >= th || tx >= tw || origins[2 * k] + th > LH || origins[2 * k + 1] + tw > LW) continue;
+      const long long q = ((long long)k * th + ty) * tw + tx;
+      const float w = wn[q];
+      const float* e = eps + ((n * T) * th * tw + q) * ld_eps;
+#pragma unroll
+      for (int c = 0; c < 8; ++c)
+        if (c < Clat) acc[c] += w * e[c];
+    }
+    float v[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) v[c] = c < Clat ? cx * zt[i * Cpad + c] + ce * acc[c] : 0.f;
+    for (int c = 0; c < Cpad; ++c) zt[i * Cpad + c] = c < 8 ? v[c] : 0.f;
+    for (int k = 0; k < T; ++k) {
+      const int ty = y - origins[2 * k], tx = x - origins[2 * k + 1];
+      if (ty < 0 || tx < 0 || ty >= th || tx >= tw || origins[2 * k] + th > LH || origins[2 * k + 1] + tw > LW) continue;
+      uint16_t* d = tiles + ((n * T + k) * th * tw + (long long)ty * tw + tx) * Cpad;
+      for (int c = 0; c < Cpad; ++c) d[c] = c < 8 ? f2h16<F16>(v[c]) : (uint16_t)0;
+    }
+  }
+}
+
 inline int nblocks(long long total) { return (int)std::min<long long>((total + 255) / 256, 8192); }
 
 }  // namespace
@@ -576,6 +634,30 @@ int ur_ddim_step(float* zt, const float* eps, int ld_eps, void* zt_16, long long
   UR_DT_SWITCH(dtype, hipLaunchKernelGGL(ddim_step_kernel<F16>, dim3(nblocks(M)), dim3(256), 0, (hipStream_t)stream, zt, eps, ld_eps,
                      (uint16_t*)zt_16, Clat, Cpad, c_x, c_e, M));
   return ur::check_launch("ur_ddim_step");
+}
+
+int ur_latent_tiles_gather(const float* z, void* tiles_16, int N, int LH, int LW, int Cpad, int T, int th, int tw,
+                           const int* origins, int dtype, ur_stream_t stream) {
+  UR_REQUIRE_DT(dtype);
+  UR_REQUIRE(z && tiles_16 && origins, "null pointer");
+  UR_REQUIRE(N > 0 && LH > 0 && LW > 0 && Cpad > 0 && T > 0 && th > 0 && tw > 0 && th <= LH && tw <= LW, "bad shape");
+  const long long total = (long long)N * T * th * tw;
+  UR_DT_SWITCH(dtype, hipLaunchKernelGGL(latent_tiles_gather_kernel<F16>, dim3(nblocks(total)), dim3(256), 0, (hipStream_t)stream, z,
+                     (uint16_t*)tiles_16, LH, LW, Cpad, T, th, tw, origins, total));
+  return ur::check_launch("ur_latent_tiles_gather");
+}
+
+int ur_latent_tiles_blend_ddim(float* zt, const float* eps_tiles, int ld_eps, void* zt_tiles_16, const float* wn, int N, int LH,
+                               int LW, int Clat, int Cpad, int T, int th, int tw, const int* origins, float c_x, float c_e,
+                               int dtype, ur_stream_t stream) {
+  UR_REQUIRE_DT(dtype);
+  UR_REQUIRE(zt && eps_tiles && zt_tiles_16 && wn && origins, "null pointer");
+  UR_REQUIRE(N > 0 && LH > 0 && LW > 0 && T > 0 && th > 0 && tw > 0 && th <= LH && tw <= LW, "bad shape");
+  UR_REQUIRE(Clat > 0 && Clat <= 8 && Cpad >= Clat && ld_eps >= Clat, "channels: Clat <= 8, Cpad >= Clat, ld_eps >= Clat");
+  const long long total = (long long)N * LH * LW;
+  UR_DT_SWITCH(dtype, hipLaunchKernelGGL(latent_tiles_blend_ddim_kernel<F16>, dim3(nblocks(total)), dim3(256), 0, (hipStream_t)stream,
+                     zt, eps_tiles, ld_eps, (uint16_t*)zt_tiles_16, wn, LH, LW, Clat, Cpad, T, th, tw, origins, c_x, c_e, total));
+  return ur::check_launch("ur_latent_tiles_blend_ddim");
 }
 
 int ur_f32_to_bf16_scaled(const float* x, int ld, void* y, long long M, int C, int Cpad, float mul, int dtype, ur_stream_t stream) {

@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import ops, schedule
+from .. import ops, schedule, tiling
 from .adapters import SPADE, CSCEAdapter, TaskFeatureAdapter, cfrm_blocks
 from . import nn as nnmod
 from .nn import (DEV, AutoencoderKL, Conv2d, DownBlock, MidBlock, ResnetBlock2D, TimestepEmbedding, UNet2DConditionModel,
@@ -26,6 +26,12 @@ from .nn import (DEV, AutoencoderKL, Conv2d, DownBlock, MidBlock, ResnetBlock2D,
 stablesr_config = dict(in_channels=4, model_channels=256, out_channels=256, num_res_blocks=2, dropout=0,
                        channel_mult=(1, 1, 2, 2), downsample_type="conv", num_heads=4,
                        down_block_types=("AttnDownBlock2D",) * 3 + ("DownBlock2D",), mid_block_type="UNetMidBlock2D")
+
+
+# Tiled latent sampling: most images one batched Controller pass may stack (S steps x N images x T tiles).  400 is the largest
+# batched schedule the untiled path already runs at the same 64x64 shape (configs[4]: 8 images x 50 steps); a larger tile batch
+# runs the schedule in chunks of whole steps, one step at a time (controller.run) once N*T alone reaches the limit.
+TILE_CONTROLLER_MAX_IMAGES = 400
 
 
 def _use_dtype(module):
@@ -131,6 +137,16 @@ class Controller(nn.Module):
             x._gn = (g[0].repeat(nsteps, 1, 1, 1), g[1])
         out = self.run(x, "all")
         return [{k: v[i * b:(i + 1) * b] for k, v in out.items()} for i in range(nsteps)]
+
+    def run_steps(self, stem, s0, s1):
+        """run_schedule for steps s0..s1-1 only (a chunk of the schedule in one batched pass)."""
+        b, n = stem.shape[0], s1 - s0
+        x = stem.repeat(n, 1, 1, 1)
+        g = ops.gn_of(stem)
+        if g is not None:
+            x._gn = (g[0].repeat(n, 1, 1, 1), g[1])
+        out = self.run(x, slice(s0, s1))
+        return [{k: v[i * b:(i + 1) * b] for k, v in out.items()} for i in range(n)]
 
     def forward(self, x, timesteps, encoder_hidden_states=None):
         """Reference signature: x (B,4,h,w) fp32 NCHW, timesteps (1,) or (B,) -> {width: (B,256,h',w') fp32}."""
@@ -358,6 +374,10 @@ class DiffUIE(nn.Module):
             self.timesteps = schedule.ddim_timesteps(self.num_inference_steps)       # host int64, bit-exact
             self._tables_ready = False
             self._table_epochs = None
+        self.latent_tiling = None              # (tile, stride) of tiled latent sampling, or None: whole-latent denoising
+        if cnet and cnet.get("tile_size") is not None:
+            tile = int(cnet["tile_size"])
+            self.set_latent_tiling(tile, int(cnet.get("tile_stride") or tiling.default_tile_stride(tile)))
         self._own_dtype()
         self._arm_load_hooks()
 
@@ -388,6 +408,32 @@ class DiffUIE(nn.Module):
         self.timesteps = schedule.ddim_timesteps(self.num_inference_steps)
         self._tables_ready = False
         return self
+
+    def set_latent_tiling(self, tile=64, stride=48):
+        """Tiled latent sampling (off by default): the denoise loop runs the UNet / Controller on overlapping tile x tile latent
+        tiles (origins `stride` apart) as one batch and blends their noise predictions with Gaussian weights before every
+        DDIM step (tiling.py).  A latent that fits one tile is denoised whole, exactly as without tiling.
+        set_latent_tiling(None) turns it off.  Captured graphs are dropped."""
+        if tile is None:
+            self.latent_tiling = None
+        else:
+            tiling.check_tile_stride(tile, stride)
+            self.latent_tiling = (int(tile), int(stride))
+        self._graphs.clear()
+        return self
+
+    def _tile_plan(self, lh, lw):
+        """(T, (th, tw), device origins int32 [T,2], device wn fp32 [T,th,tw]) of the current tiling for an lh x lw latent, or
+        None when tiling is off or one tile covers the latent.  Cached: captured graphs hold the device tensors' addresses."""
+        if self.latent_tiling is None:
+            return None
+        key = ("tile_plan", lh, lw) + self.latent_tiling
+        cache = self.__dict__.setdefault("_tile_plans", {})
+        if key not in cache:
+            origins, (th, tw), wn = tiling.latent_tile_plan(lh, lw, *self.latent_tiling)
+            cache[key] = None if len(origins) == 1 else \
+                (len(origins), (th, tw), torch.tensor(origins, dtype=torch.int32).to(DEV), torch.from_numpy(wn).to(DEV))
+        return cache[key]
 
     def set_dtype(self, dtype):
         """Switch the 16-bit compute type; packed weights are kept per type, captured graphs are dropped."""
@@ -456,7 +502,10 @@ class DiffUIE(nn.Module):
         h, w, pad_h, pad_w = plan
         z0, z0b, mids = self.ae.encode_run(images, n_vae, enable_fr=self.fr_type is not None, plan=plan)
         zt = z0
-        if self.control_type:
+        tp = self._tile_plan(z0.shape[1], z0.shape[2]) if self.control_type else None
+        if tp is not None:
+            zt = self._denoise_tiled(z0, n_t, tp)
+        elif self.control_type:
             ac = schedule.alphas_cumprod_f64()
             zt, ztb = ops.add_noise(z0, n_t, lat, float(np.float32(ac[999] ** 0.5)), float(np.float32((1 - ac[999]) ** 0.5)))
             stem = self.controller.stem(z0b)
@@ -470,6 +519,30 @@ class DiffUIE(nn.Module):
                     self.trace_zt.append(ops.nhwc_to_nchw(zt, c=lat).cpu())      # parity instrumentation (eager runs only)
         preds = self.ae.decode_run(zt, mids, task, out_plan=((h, w), tuple(images.shape[-2:]), quantize))
         return preds, z0, zt
+
+    def _denoise_tiled(self, z0, n_t, tp):
+        """Denoise loop of tiled latent sampling: z0 / zt tiles gathered into an N*T batch (image n's tile k at n*T+k), the
+        Controller and UNet run on the tile batch, and one blend + DDIM launch per step writes the full fp32 zt and the next
+        step's 16-bit tile batch.  Returns the final full-latent zt (fp32 NHWC)."""
+        lat = self.ae.vae.latent_channels
+        _, (th, tw), origins, wn = tp
+        ac = schedule.alphas_cumprod_f64()
+        zt, _ = ops.add_noise(z0, n_t, lat, float(np.float32(ac[999] ** 0.5)), float(np.float32((1 - ac[999]) ** 0.5)))
+        stem = self.controller.stem(ops.latent_tiles_gather(z0, origins, th, tw))
+        ztt = ops.latent_tiles_gather(zt, origins, th, tw)
+        nsteps = len(self.timesteps)
+        chunk = min(nsteps, TILE_CONTROLLER_MAX_IMAGES // stem.shape[0]) if self.batch_controller else 1
+        controls = None
+        for i, t in enumerate(self.timesteps):
+            if chunk > 1 and i % chunk == 0:
+                controls = self.controller.run_steps(stem, i, min(i + chunk, nsteps))
+            control = controls[i % chunk] if chunk > 1 else self.controller.run(stem, i)
+            eps = self.base_model.run(ztt, control, i)
+            c_x, c_e = schedule.ddim_coefficients(int(t), self.num_inference_steps)
+            ops.latent_tiles_blend_ddim_(zt, ztt, eps, wn, origins, lat, c_x, c_e)
+            if self.trace_zt is not None and not torch.cuda.is_current_stream_capturing():
+                self.trace_zt.append(ops.nhwc_to_nchw(zt, c=lat).cpu())
+        return zt
 
     @torch.no_grad()
     def forward(self, images, task: str, noise=None, return_latents=False, quantize=False):
@@ -505,7 +578,7 @@ class DiffUIE(nn.Module):
 
     # ---- hipGraph: the whole fixed-length forward (encode, N denoise steps, decode) is one captured graph --------------
     def _graph_forward(self, images, task, n_vae, n_t, plan, quantize=False):
-        key = (tuple(images.shape), task, bool(quantize), self.dtype)
+        key = (tuple(images.shape), task, bool(quantize), self.dtype, self.latent_tiling)
         g = self._graphs.get(key)
         if g is None:
             static = dict(images=images.clone(), n_vae=n_vae.clone(), n_t=n_t.clone())

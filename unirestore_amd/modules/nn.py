@@ -133,23 +133,27 @@ class ResnetBlock2D(nn.Module):
         cb = self.conv1.bias.detach().float().to(DEV)
         self.tbias = ops.linear_f32(silu_emb, w, b + cb)
 
-    def _tbias_all(self, b):
-        """[S*b, cout] bias rows for a schedule-batched pass (image n = step*b + i uses the row of its step)."""
-        key = ("cache", "tb_all", b)
+    def _tbias_all(self, b, steps=None):
+        """[S*b, cout] bias rows for a schedule-batched pass (image n = step*b + i uses the row of its step); steps: a slice of
+        the schedule for a pass that stacks only those steps."""
+        key = ("cache", "tb_all", b) if steps is None else ("cache", "tb_all", b, steps.start, steps.stop)
         if key not in self.__dict__:
-            self.__dict__[key] = self.tbias.repeat_interleave(b, dim=0).contiguous()
+            rows = self.tbias if steps is None else self.tbias[steps]
+            self.__dict__[key] = rows.repeat_interleave(b, dim=0).contiguous()
         return self.__dict__[key]
 
     def run(self, x, x2=None, step=None, sample_bias=None, control=None):
-        """x (+x2: virtual concat) NHWC bf16.  step: row of the time table, or "all" when the batch stacks every step of
-        the schedule (step-major); sample_bias: explicit [N,cout] per-image rows; control: {width: NHWC map} for a grafted
-        SPADE (base_model.py:56-92)."""
+        """x (+x2: virtual concat) NHWC bf16.  step: row of the time table, "all" when the batch stacks every step of
+        the schedule (step-major), or slice(s0, s1) when it stacks steps s0..s1-1; sample_bias: explicit [N,cout] per-image rows;
+        control: {width: NHWC map} for a grafted SPADE (base_model.py:56-92)."""
         bias = None
         if self.time_emb_proj is not None:
             if sample_bias is not None:
                 bias = sample_bias
             elif isinstance(step, str):
                 bias = self._tbias_all(x.shape[0] // self.tbias.shape[0])
+            elif isinstance(step, slice):
+                bias = self._tbias_all(x.shape[0] // (step.stop - step.start), step)
             else:
                 bias = self.tbias[step]
         h = gn_silu_conv(self.norm1, x, self.conv1.packed(), x2=x2, bias=bias, gn=True)

@@ -563,6 +563,24 @@ def ddim_step_(zt, zt_bf16, eps_f32, clat, c_x, c_e):
                            c_x, c_e, _dt(zt_bf16), _stream()))
 
 
+def latent_tiles_gather(z, origins_dev, th, tw):
+    """z fp32 NHWC [N,LH,LW,Cpad] -> 16-bit tile batch [N*T,th,tw,Cpad] (origins_dev: device int32 [T,2])."""
+    n, lh, lw, cp = z.shape
+    t = origins_dev.shape[0]
+    out = torch.empty((n * t, th, tw, cp), dtype=_act, device=z.device)
+    check(lib.ur_latent_tiles_gather(z.data_ptr(), out.data_ptr(), n, lh, lw, cp, t, th, tw, origins_dev.data_ptr(), _dt(), _stream()))
+    return out
+
+
+def latent_tiles_blend_ddim_(zt, zt_tiles, eps_tiles, wn, origins_dev, clat, c_x, c_e):
+    """Blended DDIM step of tiled sampling: zt (fp32 [N,LH,LW,Cpad]) and zt_tiles (16-bit [N*T,th,tw,Cpad]) updated in place from
+    the per-tile eps (fp32 [N*T,th,tw,ld]) and the normalised weights wn (fp32 [T,th,tw])."""
+    n, lh, lw, cp = zt.shape
+    t, th, tw = wn.shape
+    check(lib.ur_latent_tiles_blend_ddim(zt.data_ptr(), eps_tiles.data_ptr(), eps_tiles.shape[-1], zt_tiles.data_ptr(), wn.data_ptr(),
+                                         n, lh, lw, clat, cp, t, th, tw, origins_dev.data_ptr(), c_x, c_e, _dt(zt_tiles), _stream()))
+
+
 def f32_to_bf16(x, c, mul=1.0, cpad=8):
     ld = x.shape[-1]
     out = torch.empty((*x.shape[:-1], cpad), dtype=_act, device=x.device)
