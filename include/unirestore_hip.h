@@ -292,6 +292,17 @@ int ur_latent_tiles_blend_ddim(float* zt, const float* eps_tiles, int ld_eps, vo
 /* y_16[M][Cpad] = x_f32[M][ld] * mul (latents / scaling_factor before post_quant_conv) */
 int ur_f32_to_bf16_scaled(const float* x, int ld, void* y, long long M, int C, int Cpad, float mul, int dtype, ur_stream_t stream);
 
+/* ---- full-reference image metrics (evaluator side; the GPU counterpart of runner.psnr_per_image / runner.ssim) ----------
+ * Full-reference metrics per image (skimage semantics, fp64 accumulation, fixed-order reductions): pred / target fp32 NCHW
+ * [N,C,H,W] contiguous; psnr / ssim fp64 [N]; ws fp64 workspace of ur_image_metrics_ws_size(...) bytes.
+ *   psnr[n] = 10 log10(data_range^2 / mean over C*H*W of (pred - target)^2)   (+inf for identical images)
+ *   ssim[n] = mean over channels and the valid (H-win+1) x (W-win+1) interior of the SSIM map: uniform win x win window
+ *             (win odd, >= 3; skimage's default is 7), K1 = 0.01, K2 = 0.03, sample covariance (win^2 / (win^2 - 1)).
+ * Arguments are checked before any HIP call (UR_E_INVALID).  ur_image_metrics_ws_size returns UR_E_INVALID for a bad shape. */
+int ur_image_metrics(const float* pred, const float* target, int N, int C, int H, int W, int win, double data_range,
+                     double* psnr, double* ssim, void* ws, long long ws_bytes, ur_stream_t stream);
+long long ur_image_metrics_ws_size(int N, int C, int H, int W, int win);
+
 /* ---- live per-kernel-family timing (HIP events on the launch stream) ------------------------------*/
 int ur_profile_enable(int on);
 /* writes a JSON object {family: {launches, ms, flops, bytes}} into buf (host); synchronises the events */

@@ -95,7 +95,7 @@ def resolve(cfg: dict, allow_16bit: bool = False) -> dict:
                 caller_args={k: init[k] for k in ("save_image", "eval_mode", "need_crop") if k in init}, data_args=dargs)
 
 
-def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_16bit=False) -> dict:
+def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_16bit=False, metrics_device="cpu") -> dict:
     import torch
     r = resolve(cfg, allow_16bit=allow_16bit)
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
@@ -111,7 +111,7 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
     from . import runner
     from .data import SyntheticImages
     from .dist import all_gather_images, broadcast_weights_sharded, shard_range
-    lit = runner.LitUniFIE(r["model_kwargs"], dtype=r["dtype"], hf_root=hf_root, **r["caller_args"])
+    lit = runner.LitUniFIE(r["model_kwargs"], dtype=r["dtype"], hf_root=hf_root, metrics_device=metrics_device, **r["caller_args"])
     no_ckpt = not any((r["model_kwargs"].get(k) or {}).get("ckpt_path") for k in ("frenc", "cnet", "tedit")) and not hf_root
     if no_ckpt and random_init:                           # no checkpoint reachable: seeded random weights of the architecture
         from .init import init_random_
@@ -139,9 +139,11 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
             secs += time.perf_counter() - t0
             n_img += out.shape[0]
         finite = finite and bool(torch.isfinite(out).all())
-        lit.update_metrics(preds[-1], batch[1])           # this rank's shard; reduced over the ranks below (fp64 CPU PSNR / SSIM: untimed)
+        lit.update_metrics(preds[-1], batch[1])           # this rank's shard; reduced over the ranks below (fp64 PSNR / SSIM: untimed)
     if world > 1:                                         # the reference's metric states reduce with dist_reduce_fx="sum"
-        tot = torch.tensor([lit.totals["psnr"], lit.totals["ssim"], float(lit.totals["images"])], dtype=torch.float64, device=dev)
+        # the totals are host floats (metrics_device "cpu") or 0-d fp64 device tensors ("gpu")
+        tot = torch.stack([torch.as_tensor(v, dtype=torch.float64, device=dev)
+                           for v in (lit.totals["psnr"], lit.totals["ssim"], float(lit.totals["images"]))])
         dist.all_reduce(tot)
         lit.totals.update(psnr=float(tot[0]), ssim=float(tot[1]), images=int(tot[2]))
     res = dict(config=r["data_args"], dtype=r["dtype"], n_gpus=world, denoise_steps=r["model_kwargs"]["cnet"]["num_inference_steps"],
@@ -160,13 +162,15 @@ def main(argv=None):
     ap.add_argument("--hf-root", default=None, help="folder with unet/ and vae/ diffusion_pytorch_model.safetensors (sd-turbo)")
     ap.add_argument("--max-batches", type=int, default=None)
     ap.add_argument("--allow-16bit", action="store_true", help="run a `precision: 32` config in fp16 (fp32 accumulation) instead of refusing it")
+    ap.add_argument("--metrics-device", choices=["cpu", "gpu"], default="cpu",
+                    help="where PSNR / SSIM run: cpu = host fp64 (default), gpu = the HIP metric kernels (fp64, no per-batch host sync)")
     a = ap.parse_args(argv)
     cfg = load_config(a.config, a.set)
     if a.command == "print_config":
         print(yaml.safe_dump(cfg, sort_keys=False))
         print(json.dumps(resolve(cfg, allow_16bit=a.allow_16bit)))
         return 0
-    res = validate(cfg, hf_root=a.hf_root, max_batches=a.max_batches, allow_16bit=a.allow_16bit)
+    res = validate(cfg, hf_root=a.hf_root, max_batches=a.max_batches, allow_16bit=a.allow_16bit, metrics_device=a.metrics_device)
     if res is not None:
         print(json.dumps(res))
     return 0

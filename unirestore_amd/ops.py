@@ -588,6 +588,35 @@ def f32_to_bf16(x, c, mul=1.0, cpad=8):
     return out
 
 
+def image_metrics(pred: torch.Tensor, target: torch.Tensor, data_range: float = 1.0, win: int = 7):
+    """Per-image PSNR and SSIM of fp32 NCHW batches on the GPU -> (psnr, ssim), fp64 [N] device tensors.  Same semantics as
+    runner.psnr_per_image / runner.ssim per image (skimage defaults: uniform win x win window, K1 0.01, K2 0.03, sample
+    covariance, valid interior); fp64 moments and fixed-order sums, so two calls give the same bits.  No host sync."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    for name, t in (("pred", pred), ("target", target)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.ndim != 4:
+            raise ValueError(f"image_metrics: {name} must be a 4-d fp32 NCHW tensor, got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        if t.device != dev:
+            raise ValueError(f"image_metrics: {name} is on {t.device}, not on the current device {dev}")
+        if not t.is_contiguous():
+            raise ValueError(f"image_metrics: {name} must be contiguous")
+    if pred.shape != target.shape:
+        raise ValueError(f"image_metrics: shapes differ: {tuple(pred.shape)} vs {tuple(target.shape)}")
+    n, c, h, w = pred.shape
+    if not data_range > 0:
+        raise ValueError(f"image_metrics: data_range must be > 0, got {data_range}")
+    ws_bytes = lib.ur_image_metrics_ws_size(n, c, h, w, int(win))
+    if ws_bytes < 0:
+        check(int(ws_bytes))
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    psnr = torch.empty(n, dtype=torch.float64, device=dev)
+    ssim = torch.empty(n, dtype=torch.float64, device=dev)
+    check(lib.ur_image_metrics(pred.data_ptr(), target.data_ptr(), n, c, h, w, int(win), float(data_range), psnr.data_ptr(),
+                               ssim.data_ptr(), ws.data_ptr(), ws_bytes, _stream()))
+    return psnr, ssim
+
+
 def profile_enable(on: bool):
     check(lib.ur_profile_enable(int(on)))
 

@@ -73,14 +73,22 @@ def ssim(pred: torch.Tensor, target: torch.Tensor, data_range: float = 1.0, win:
     return float(s.mean())
 
 
+# where the evaluator's PSNR / SSIM run: "cpu" = psnr_per_image / ssim above (host fp64); "gpu" = ops.image_metrics (HIP, fp64,
+# totals kept on the device: no host sync per batch)
+METRICS_DEVICES = ("cpu", "gpu")
+
+
 class LitUniFIE:
     """The caller the reference builds around the path (`LitUniFIE{IR,MTL}`, src/core/engine_unifie.py:29-42,227-236 +
     ImageRestorationEvaluator.validation_step) without Lightning: owns a `DiffUIE`, maps `forward` over the input list and
     runs the evaluator's crop / restore / quantise / metric steps on a batch tuple `(lq, hq, gt, fname, task)`."""
 
     def __init__(self, model_kwargs: dict, save_image: bool = False, eval_mode: str = "FR", need_crop: bool = True,
-                 dtype: str = "bf16", hf_root: str = None, model=None, **_ignored):
+                 dtype: str = "bf16", hf_root: str = None, model=None, metrics_device: str = "cpu", **_ignored):
         from . import checkpoint
+        if metrics_device not in METRICS_DEVICES:
+            raise ValueError(f"metrics_device={metrics_device!r}: choose from {METRICS_DEVICES}")
+        self.metrics_device = metrics_device
         self.model_kwargs, self.need_crop, self.eval_mode = model_kwargs, need_crop, eval_mode
         tedit = model_kwargs.get("tedit") or {}
         self.task_dict = tedit.get("task", [])
@@ -98,10 +106,20 @@ class LitUniFIE:
         if metrics and hq_c is not None and self.eval_mode in ("FR", "ALL") and preds[-1].shape == (crop_tensor(hq) if self.need_crop else hq).shape:
             tgt = crop_tensor(hq) if self.need_crop else hq
             n = preds[-1].shape[0]
-            self.totals["psnr"] += float(psnr_per_image(preds[-1], tgt).sum())          # sum over images (SKPSNR state)
-            self.totals["ssim"] += ssim(preds[-1], tgt) * n
+            if self.metrics_device == "gpu":
+                self._add_gpu_metrics(preds[-1], tgt)
+            else:
+                self.totals["psnr"] += float(psnr_per_image(preds[-1], tgt).sum())          # sum over images (SKPSNR state)
+                self.totals["ssim"] += ssim(preds[-1], tgt) * n
             self.totals["images"] += n
         return preds
+
+    def _add_gpu_metrics(self, preds: torch.Tensor, tgt: torch.Tensor):
+        """Per-image PSNR / SSIM sums of the batch into fp64 device totals (0-d tensors): no device-to-host copy per batch."""
+        from . import ops
+        ps, ss = ops.image_metrics(preds.contiguous(), tgt.contiguous())
+        self.totals["psnr"] = self.totals["psnr"] + ps.sum()
+        self.totals["ssim"] = self.totals["ssim"] + ss.sum()
 
     # ---- the training step's FORWARD halves (engine_unifie.py:135-191), values only: the HIP path has no autograd ------------
     @torch.no_grad()
@@ -147,10 +165,14 @@ class LitUniFIE:
         tgt = crop_tensor(hq) if self.need_crop else hq
         if self.eval_mode in ("FR", "ALL") and preds.shape == tgt.shape:
             n = preds.shape[0]
-            self.totals["psnr"] += float(psnr_per_image(preds, tgt).sum())
-            self.totals["ssim"] += ssim(preds, tgt) * n
+            if self.metrics_device == "gpu":
+                self._add_gpu_metrics(preds, tgt)
+            else:
+                self.totals["psnr"] += float(psnr_per_image(preds, tgt).sum())
+                self.totals["ssim"] += ssim(preds, tgt) * n
             self.totals["images"] += n
 
     def metrics(self) -> dict:
         n = max(self.totals["images"], 1)
-        return {"val_lq/psnr": self.totals["psnr"] / n, "val_lq/ssim": self.totals["ssim"] / n, "images": self.totals["images"]}
+        psnr_sum, ssim_sum = float(self.totals["psnr"]), float(self.totals["ssim"])     # (the one device read of the "gpu" totals)
+        return {"val_lq/psnr": psnr_sum / n, "val_lq/ssim": ssim_sum / n, "images": self.totals["images"]}
