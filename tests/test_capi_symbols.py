@@ -102,16 +102,16 @@ def test_ctypes_struct_layout_matches_the_header(tmp_path):
     assert int(out["sizeof"]) == ctypes.sizeof(capi.ConvDesc) and int(out["plan"]) == ctypes.sizeof(capi.ConvPlan)
 
 
-def test_generated_asm_blocks_are_current(tmp_path, monkeypatch):
-    """csrc/tchain_asm.inc, csrc/igemm_asm.inc, csrc/attention_pp_asm.inc and the timing-only variants tools/ab/*_abl{4,5}.inc are
-    GENERATED (tools/gen_chain_asm.py, tools/gen_igemm_asm.py, tools/gen_attn_asm.py): the committed files must be exactly what
-    the generators emit (with no ATTN_* environment switches set)."""
+def test_shipped_asm_blocks_are_current(tmp_path, monkeypatch):
+    """csrc/tchain_asm.inc, csrc/igemm_asm.inc and csrc/attention_pp_asm.inc are GENERATED (tools/gen_chain_asm.py,
+    tools/gen_igemm_asm.py, tools/gen_attn_asm.py): the committed files must be exactly what the generators emit (with no ATTN_*
+    environment switches set)."""
     import importlib.util
     import shutil
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     tools = tmp_path / "tools"
     out = tmp_path / "unirestore_amd" / "csrc"
-    tools.mkdir(parents=True); out.mkdir(parents=True); (tools / "ab").mkdir()
+    tools.mkdir(parents=True); out.mkdir(parents=True)
     for f in ("gen_chain_asm.py", "gen_igemm_asm.py", "gen_attn_asm.py"):
         shutil.copy(os.path.join(root, "tools", f), tools / f)
     import sys
@@ -136,7 +136,3 @@ def test_generated_asm_blocks_are_current(tmp_path, monkeypatch):
     assert made == ["attention_pp_asm.inc", "igemm_asm.inc", "tchain_asm.inc"]
     for f in made:
         assert (out / f).read_text() == open(os.path.join(root, "unirestore_amd", "csrc", f)).read(), f
-    made_ab = sorted(os.listdir(tools / "ab"))
-    assert made_ab == ["igemm_asm_abl4.inc", "igemm_asm_abl5.inc", "tchain_asm_abl4.inc", "tchain_asm_abl5.inc"]
-    for f in made_ab:
-        assert (tools / "ab" / f).read_text() == open(os.path.join(root, "tools", "ab", f)).read(), f

@@ -1,4 +1,8 @@
-"""Phase timers of the ping-pong attention kernel (a library built with ATTN_DBG=1 tools/ab_attn.sh "dbg:0:-DUR_ATTN_PP_DBG"):
+"""Phase timers of the ping-pong attention kernel, run against a timer build of the library:
+    ATTN_DBG=1 python tools/gen_attn_asm.py /tmp/attn_dbg.inc
+    UR_EXTRA_FLAGS='-DUR_ATTN_PP_INC="/tmp/attn_dbg.inc" -DUR_ATTN_PP_DBG' UR_LIB_OUT=/tmp/libur_dbg.so python -m unirestore_amd.build --force
+    UR_LIB=/tmp/libur_dbg.so python tools/attn_phase_timers.py
+
 every wave overwrites the first 16 bytes of its queries' output rows with four cycle sums -
 softmax phase (DMA issue + arithmetic) | DMA wait + fragment prefetch + barrier | MFMA phase | barrier behind it."""
 import os, sys

@@ -1,6 +1,6 @@
 """Which part of the UNet step puts fp16 zt above the emulated budget?  B=1, 512x512, 1 DDIM step, full-size weights: the UNet step is
 run from the ORACLE's own z0 / zt / control inputs (so encoder error is excluded) under the environment switches given on the command line
-of the calling shell (UR_CHAIN=0, UR_FUSE_LN=0, UR_ATTN_NOPP=1 ...), and eps is compared with the oracle's.  The oracle tensors are cached
+of the calling shell (UR_CHAIN=0, UR_ATTN_NOPP=1 ...), and eps is compared with the oracle's.  The oracle tensors are cached
 in gpurun_out/fp16_attrib_ref.pt by the first run.   python tools/fp16_zt_attrib.py <label>"""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))

@@ -571,46 +571,9 @@ def program_epilogue(p):
     return p.lines
 
 
-ABL = int(os.environ.get("ATTN_ABL", "0"))     # timing-only ablations (tools/ab_attn.sh): 1 = v_mov for v_exp, 2 = no MFMAs, 3 = no fragment
-                                               # reads, 4 = no softmax arithmetic at all, 5 = no s_setprio, 6 = no DMA in the loop
-
-
-def ablate(lines):
-    out = []
-    for ln in lines:
-        if ABL in (7, 8) and ln == "s_barrier":          # 7 = no softmax arithmetic and no barriers, 8 = everything but the barriers
-            continue
-        if ABL == 7 and ln.startswith(f"v_add_f32 {v(PSUM)}, {v(PS0)}"):
-            ln = f"v_mov_b32 {v(PSUM)}, 0"
-        if ABL == 7 and (ln.startswith("@EXP@") or ln.startswith("@CVT@") or ln.startswith("v_add_f32") or ln.startswith("v_sub_f32")):
-            continue
-        if ABL in (2, 3, 4, 7, 8):      # garbage scores must not reach the slow path: always take the fast one
-            if ln == "s_cmp_eq_u64 vcc, exec":
-                ln = "s_cmp_eq_u32 0, 0"
-            if ln == f"s_mov_b32 {OP['first']}, 1":
-                ln = f"s_mov_b32 {OP['first']}, 0"
-        if ABL == 1 and ln.startswith("@EXP@"):
-            ln = "v_mov_b32" + ln[5:]
-        if ABL == 2 and ln.startswith("@MN@"):
-            continue
-        if ABL == 3 and (ln.startswith("ds_read") or ln.startswith("s_waitcnt lgkmcnt")):
-            continue
-        if ABL == 4 and ln.startswith(f"v_add_f32 {v(PSUM)}, {v(PS0)}"):
-            ln = f"v_mov_b32 {v(PSUM)}, 0"
-        if ABL == 4 and (ln.startswith("@EXP@") or ln.startswith("@CVT@") or ln.startswith("v_add_f32") or ln.startswith("v_sub_f32")):
-            continue
-        if ABL == 5 and ln.startswith("s_setprio"):
-            continue
-        if ABL == 6 and ln.startswith("buffer_load"):
-            continue
-        out.append(ln)
-    return out
-
-
 def emit(lines, name):
     out = [f"#define {name}(MN, CVT, DOT, ONES) \\"]
     body_lines = []
-    lines = ablate(lines) if ABL else lines
     for ln in lines:
         if ln.startswith("@MN@"):
             body_lines.append('  MN "' + ln[4:] + '\\n\\t"')

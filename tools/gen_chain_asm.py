@@ -36,14 +36,7 @@ def dma_lines(j, o_vo, o_rs, o_so, o_ld):
     return out
 
 
-ABL = 0        # timing-only ablation variants of the whole file (main(): tchain_asm_abl{4,5}.inc): 4 = no fragment reads, 5 = no MFMAs
-
-
 def fmt(name, header, lines, has_mn=True):
-    if ABL == 4 and has_mn:
-        lines = [ln for ln in lines if not ln.startswith("ds_read") and not ln.startswith("s_waitcnt lgkmcnt")]
-    if ABL == 5 and has_mn:
-        lines = [ln for ln in lines if not ln.startswith("@MN@")]
     txt = f"// {name}: {header}\n#define {name}{'(MN)' if has_mn else ''} \\\n"
     parts = []
     for ln in lines:
@@ -142,10 +135,8 @@ def ff1(kb0, nkb):
 
 
 def main():
-    global ABL
     here = os.path.dirname(os.path.abspath(__file__))
-    for ABL in (4, 5, 0):
-        write(os.path.join(here, "ab", f"tchain_asm_abl{ABL}.inc") if ABL else os.path.join(here, "..", "unirestore_amd", "csrc", "tchain_asm.inc"))
+    write(os.path.join(here, "..", "unirestore_amd", "csrc", "tchain_asm.inc"))
 
 
 def write(out):

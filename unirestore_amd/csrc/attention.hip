@@ -24,9 +24,6 @@ template <int D, bool F16>
 #ifndef UR_ATTN_WAVES
 #define UR_ATTN_WAVES 3
 #endif
-#ifndef UR_ATTN_ABL
-#define UR_ATTN_ABL 0      // timing-only ablations (profiles/r2_c_pmc_attention.txt): 1 = no exp2, 2 = one P.V MFMA per tile, 3 = no row maximum
-#endif
 __global__ __launch_bounds__(256, (D == 64 ? UR_ATTN_WAVES : 1)) void attn_fwd_kernel(const AttnP p) {
   constexpr int KROW = D * 2;                 // bytes per K row in LDS
   constexpr int KSLOTS = KROW / 16;           // 16-B slots per K row (8 or 16)
@@ -170,10 +167,8 @@ __global__ __launch_bounds__(256, (D == 64 ? UR_ATTN_WAVES : 1)) void attn_fwd_k
     }
     // online softmax in the exp2 domain on RAW scores: p = exp2(c*s - c*m), c = scale*log2(e) folded into one FMA.
     float mx = s[0];
-#if UR_ATTN_ABL != 3
 #pragma unroll
     for (int i = 1; i < 32; ++i) mx = fmaxf(mx, s[i]);
-#endif
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
     const float c = p.scale_log2e;
     // deferred rescale: while no row's maximum grew by more than 2^8 (in the exp2 domain) keep the old reference
@@ -192,11 +187,7 @@ __global__ __launch_bounds__(256, (D == 64 ? UR_ATTN_WAVES : 1)) void attn_fwd_k
     float psum = 0.f;
 #pragma unroll
     for (int i = 0; i < 32; ++i) {
-#if UR_ATTN_ABL == 1
-      s[i] = fmaf(s[i], c, -mc);
-#else
       s[i] = __builtin_amdgcn_exp2f(fmaf(s[i], c, -mc));
-#endif
       psum += s[i];
     }
     l_run += psum;
@@ -213,12 +204,7 @@ __global__ __launch_bounds__(256, (D == 64 ? UR_ATTN_WAVES : 1)) void attn_fwd_k
       for (int f = 0; f < DF; ++f) {
         const int row = f * 32 + l31;
         const frag_t vf = *reinterpret_cast<const frag_t*>(vs + row * 128 + (((kk * 2 + hf) ^ ((row >> 1) & 7)) << 4));
-#if UR_ATTN_ABL == 2
-        if (f == 0 && kk == 0) oacc[f] = mfma16t(vf, pf, oacc[f]);
-        else oacc[f][0] += __builtin_bit_cast(float, __builtin_bit_cast(uint4, vf).x) * s[kk * 8 + f];
-#else
         oacc[f] = mfma16t(vf, pf, oacc[f]);
-#endif
       }
     }
     if (more) store_tile(stage ^ 1);

@@ -16,12 +16,10 @@ struct AttnP {
 // ONE rule for the ping-pong kernel's grid (used by ur_attention_workspace_bytes, the dispatcher's fill estimate and the launch):
 // n = (Tq / 256) * B * H query tiles; when n = whole rounds of the 256 CUs + r with 0 < r <= 128, the last r tiles are split in two
 // key halves (2r <= 256 workgroups fill the last round) - if a workspace of attn_pp_ws_bytes(r) is there and Tk % 512 == 0.
-// Returns r (0: unsplit).  UR_ATTN_NOSPLIT=1 disables the split everywhere.
-#include <cstdlib>
+// Returns r (0: unsplit).
 static inline size_t attn_pp_ws_bytes(long long r) { return (size_t)r * 2 * 256 * 68 * 4; }
 static inline long long attn_pp_split_tiles(int B, int H, int Tq, int Tk, int D) {
-  static const bool nosplit = getenv("UR_ATTN_NOSPLIT") && atoi(getenv("UR_ATTN_NOSPLIT")) != 0;
-  if (nosplit || D != 64 || Tq % 256 || Tk % 512) return 0;
+  if (D != 64 || Tq % 256 || Tk % 512) return 0;
   const long long n = (long long)(Tq / 256) * B * H, full = n / 256 * 256, r = n - full;
   return (full >= 256 && r > 0 && r <= 128) ? r : 0;
 }

@@ -21,9 +21,8 @@
 // this file computes what enters it: descriptors, per-lane offsets, the Q fragments, fragment addresses, the first stages' DMA.
 #include "common.h"
 #include "attention_params.h"
-#include <cstdlib>
 #ifndef UR_ATTN_PP_INC
-#define UR_ATTN_PP_INC "attention_pp_asm.inc"       // (A/B builds substitute a variant of the generated block: tools/ab_attn.sh)
+#define UR_ATTN_PP_INC "attention_pp_asm.inc"       // (the timer build substitutes a variant: tools/attn_phase_timers.py)
 #endif
 #include UR_ATTN_PP_INC
 
@@ -134,7 +133,7 @@ __global__ __launch_bounds__(512) void attn_pp64_kernel(const AttnP p) {
     // derives the k-steps with v_xor: smem_lds is a multiple of 128, dynamic LDS starts the allocation)
     const unsigned ka_a[2] = {smem_lds + ka[0] - TILE, smem_lds + ka[1] - TILE}, va_a[2] = {smem_lds + va[0], smem_lds + va[1]};
     unsigned t0, t1, t2, t3, t4;
-#ifdef UR_ATTN_PP_DBG          // phase-timer build (tools/ab_attn.sh with ATTN_DBG=1): five more SGPR temporaries
+#ifdef UR_ATTN_PP_DBG          // phase-timer build (tools/attn_phase_timers.py): five more SGPR temporaries
     unsigned d0, d1, d2, d3, d4, d5, d6;
 #define PP_DBG_OUT , "=&s"(d0), "=&s"(d1), "=&s"(d2), "=&s"(d3), "=&s"(d4), "=&s"(d5), "=&s"(d6)
 #else
@@ -214,14 +213,7 @@ int UR_ATTN_PP_LAUNCH(const void* pp, size_t ws_bytes, hipStream_t s) {
 
   constexpr bool F16 = UR_TU_F16 != 0;
   dim3 grid(p.n_full + 2 * n_split), block(512);
-  // UR_ATTN_PP_LDS (bytes, >= 32768): a larger request keeps further workgroups off the CU (occupancy experiments)
-  static const int lds_env = getenv("UR_ATTN_PP_LDS") ? atoi(getenv("UR_ATTN_PP_LDS")) : 0;
-  const int lds = lds_env > 4 * 16384 ? lds_env : 4 * 16384;
-  static ur::DeviceOnce attr_once;
-  if (lds > 65536)
-  if (auto once_guard = attr_once.first())
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_pp64_kernel<F16>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL((attn_pp64_kernel<F16>), grid, block, lds, s, p);
+  hipLaunchKernelGGL((attn_pp64_kernel<F16>), grid, block, 4 * 16384, s, p);
   if (n_split) hipLaunchKernelGGL((attn_pp_combine_kernel<F16>), dim3(n_split * 8), dim3(256), 0, s, p, n_split);
   return ur::check_launch("ur_attention_fwd (ping-pong)");
 }

@@ -24,18 +24,12 @@ namespace {
 
 constexpr int WS_PW = 10, WS_HP = 100, WS_PIECES = 25, WS_PATCH = WS_PIECES * 1024;      // 2 images x 10 x 10 halo pixels x 128 B
 constexpr int WS_LDS = 4 * 32768;                                                       // exchange round 1 (>= 4 patches = 102 400 B)
-#ifndef UR_WS_TL
-#define UR_WS_TL 0
-#endif
 constexpr int WS_D = 8;                                                                 // weight units (tap, k-step) in flight per wave
 
 template <bool F16, int CPW>         // CPW = consecutive 64-channel chunks per wave (compile time: the chunk loop is unrolled, see below)
 __global__ __launch_bounds__(256, 1) void conv3x3_wstream8_kernel(const ConvK p) {
   typedef typename Frag<F16>::type frag_t;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-#if UR_WS_TL                                              // workgroup time line (A/B build): 100 MHz ticks -> ws + 32 Mi floats
-  const unsigned long long tl0 = __builtin_amdgcn_s_memrealtime();
-#endif
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   // blockIdx -> (image pair, channel tile, split): id % 8 = XCD; the tiles_m image pairs of one (channel tile, split) are consecutive
@@ -89,9 +83,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wstream8_kernel(const ConvK p)
     for (int a = 0; a < 4; ++a) wr[u][a] = wpa[a][u * 256];
   __builtin_amdgcn_sched_barrier(0);
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * WS_D) : "memory");
-#if UR_WS_TL
-  const unsigned long long tl1 = __builtin_amdgcn_s_memrealtime();
-#endif
 
   f32x16 acc[4][4];
 #pragma unroll
@@ -162,10 +153,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wstream8_kernel(const ConvK p)
   // ---- the four chunk partials of the workgroup -> one: two exchange rounds through LDS, fixed order ((w + w^1) + (w^2 + w^3)) ------
   // accumulator a of wave w holds channel fragment a ^ sperm(w): every wave sends acc[2..3] to wave w ^ 1 (whose acc[0..1] are the same
   // fragments), then acc[1] to wave w ^ 2, and ends with the workgroup's sum of fragment sperm(w) in acc[0] - all indices static.
-#if UR_WS_TL
-  asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
-  const unsigned long long tl2 = __builtin_amdgcn_s_memrealtime();
-#endif
   __syncthreads();                                           // every wave is done with its patch
   {
     float4* mine = reinterpret_cast<float4*>(smem + wid * 32768);
@@ -205,9 +192,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wstream8_kernel(const ConvK p)
       }
   }
 
-#if UR_WS_TL
-  const unsigned long long tl3 = __builtin_amdgcn_s_memrealtime();
-#endif
   // ---- partial plane `sz`: fp32 [M][Cout]; lane = pixel, 4 x 4 consecutive channels per accumulator tile ------------------------
   float* plane = p.ws + (long long)sz * p.M * p.Cout;
 #pragma unroll
@@ -220,13 +204,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wstream8_kernel(const ConvK p)
         *reinterpret_cast<float4*>(row + q * 8) = make_float4(acc[0][b][4 * q], acc[0][b][4 * q + 1], acc[0][b][4 * q + 2], acc[0][b][4 * q + 3]);
     }
   }
-#if UR_WS_TL
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (lane == 0) {
-    unsigned long long* o = reinterpret_cast<unsigned long long*>(p.ws + (32 << 20)) + (blockIdx.x * 4 + wid) * 8;
-    o[0] = tl0; o[1] = tl1; o[2] = tl2; o[3] = tl3; o[4] = __builtin_amdgcn_s_memrealtime();
-  }
-#endif
 }
 
 }  // namespace

@@ -490,8 +490,7 @@ int ur_dwconv3x3_nhwc(const void* x, const float* w9c, const float* bias, void* 
   const double elems = (double)N * H * W * C;
   ur::ProfScope prof("dwconv3x3", 18.0 * elems, 2.0 * elems * (gate ? 1.5 : 2.0), s);
   const long long total = (long long)N * H * W * ((gate ? C / 2 : C) / 8);
-  static const bool no_strip = getenv("UR_DW_NOSTRIP") != nullptr;
-  if (!no_strip && W % 4 == 0) {
+  if (W % 4 == 0) {
     UR_DT_SWITCH(dtype, hipLaunchKernelGGL(dwconv3x3_strip_kernel<F16>, dim3(nblocks(total / 4)), dim3(256), 0, s, (const uint16_t*)x, w9c, bias, (uint16_t*)y,
                        N, H, W, C, gate));
     return ur::check_launch("ur_dwconv3x3_nhwc");

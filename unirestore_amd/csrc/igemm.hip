@@ -84,17 +84,13 @@ static inline int himg_8x8x4(void* kp, hipStream_t s) { return static_cast<ConvK
 int wstream_8x8_bf16(void* kp, hipStream_t s);
 int wstream_8x8_f16(void* kp, hipStream_t s);
 static inline int wstream_8x8(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? wstream_8x8_f16(kp, s) : wstream_8x8_bf16(kp, s); }
-#ifdef UR_AB_VARIANTS
-int g1_ab_bf16(void* kp, hipStream_t s, int id);
-#endif
 }  // namespace urk
 
 namespace {
 
 int dispatch_conv(ConvK& k, hipStream_t s, bool pair) {
   k.patch_tw = 0;
-  static const bool no_halo = getenv("UR_IGEMM_NOHALO") != nullptr;
-  if (!no_halo && k.KH == 3 && k.stride == 1 && k.pad_t == 1 && k.pad_l == 1 && k.kcm && k.staged_ok_ && !pair && k.nbatch == 1 &&
+  if (k.KH == 3 && k.stride == 1 && k.pad_t == 1 && k.pad_l == 1 && k.kcm && k.staged_ok_ && !pair && k.nbatch == 1 &&
       k.OW % 32 == 0 && k.OH % 8 == 0 && k.OH == (k.ups ? 2 * k.H : k.H) && k.OW == (k.ups ? 2 * k.W : k.W) && !k.yt) {
     // tile width: 128 or 160 output channels, whichever divides Cout; when both do, the one whose tile count fills whole
     // rounds of 256 CUs better (e.g. 1280 channels at 32 x 32: 8 x 160 -> 256 tiles = one round, 10 x 128 -> 320 = two)
@@ -102,8 +98,7 @@ int dispatch_conv(ConvK& k, hipStream_t s, bool pair) {
     const long long tm8 = (long long)k.N * (k.OH / 8) * (k.OW / 32);
     // (<= 128 tiles are split over channel chunks into floor(256 / tiles) workgroups each)
     auto eff = [](long long t) { return t <= 128 ? (double)(t * (256 / t)) / 256.0 : (double)t / (double)(((t + 255) / 256) * 256); };
-    static const bool old_w = getenv("UR_IGEMM_OLDW") != nullptr;
-    bool use160 = ok160 && (!ok128 || (!old_w && eff(tm8 * (k.Cout / 160)) >= eff(tm8 * (k.Cout / 128))));
+    const bool use160 = ok160 && (!ok128 || eff(tm8 * (k.Cout / 160)) >= eff(tm8 * (k.Cout / 128)));
     const long long tiles8 = tm8 * (use160 ? k.Cout / 160 : k.Cout / 128);
     if ((ok128 || ok160) && tiles8 >= 64) {
       if (use160) return urk::halo_8x32_160(&k, s);
@@ -111,20 +106,16 @@ int dispatch_conv(ConvK& k, hipStream_t s, bool pair) {
     }
   }
   // conv_out layers: <= 32 output channels (fp32 or 16-bit) of a 3x3 / stride 1 / pad 1 conv with chunk-major weights
-  static const bool no_thin = getenv("UR_IGEMM_NOTHIN") != nullptr;
-  if (!no_thin && !no_halo && k.KH == 3 && k.stride == 1 && k.pad_t == 1 && k.pad_l == 1 && k.kcm && !pair && k.nbatch == 1 && !k.ups && k.C2 == 0 &&
+  if (k.KH == 3 && k.stride == 1 && k.pad_t == 1 && k.pad_l == 1 && k.kcm && !pair && k.nbatch == 1 && !k.ups && k.C2 == 0 &&
       k.Cout <= 32 && k.OW % 32 == 0 && k.OH % 8 == 0 && k.OH == k.H && k.OW == k.W && !k.yt && !k.gn_part && !k.gn_ab && !k.row_stats && !k.ln_stats &&
       !k.bias_img && (long long)k.N * (k.OH / 8) * (k.OW / 32) >= 128)
     return urk::halo_thin_32(&k, s);
-  static const bool no_himg = getenv("UR_IGEMM_NOHIMG") != nullptr;
-  static const bool no_himg_ups = getenv("UR_IGEMM_NOHIMGUPS") != nullptr;
   // (round 6: the 8 x 8 -> 16 x 16 upsampling conv runs on the whole-image tile too - the patch pieces read their nearest source pixel)
-  const bool himg_ups = !no_himg_ups && k.ups && k.OH == 16 && k.OW == 16 && k.H == 8 && k.W == 8;
-  if (!no_himg && k.KH == 3 && k.stride == 1 && k.pad_t == 1 && k.pad_l == 1 && k.kcm && k.staged_ok_ && !pair && k.nbatch == 1 &&
+  const bool himg_ups = k.ups && k.OH == 16 && k.OW == 16 && k.H == 8 && k.W == 8;
+  if (k.KH == 3 && k.stride == 1 && k.pad_t == 1 && k.pad_l == 1 && k.kcm && k.staged_ok_ && !pair && k.nbatch == 1 &&
       ((!k.ups && k.OH == k.H && k.OW == k.W) || himg_ups) && !k.yt && k.Cout % 128 == 0 && k.nk >= 36) {
     // 8 x 8 maps of a few images: a weight stream (csrc/conv_wstream.hip) when the caller packed the fragment-major copy
-    static const bool no_wstream = getenv("UR_IGEMM_NOWSTREAM") != nullptr;
-    if (!no_wstream && k.wf && k.OH == 8 && k.OW == 8 && k.N <= 16 && k.Cin % 256 == 0 && k.nk >= 72 && k.y && k.ws && !k.gn_ab && !k.row_stats && !k.ln_stats &&
+    if (k.wf && k.OH == 8 && k.OW == 8 && k.N <= 16 && k.Cin % 256 == 0 && k.nk >= 72 && k.y && k.ws && !k.gn_ab && !k.row_stats && !k.ln_stats &&
         (long long)(k.nk / 36) * k.M * k.Cout * 4 <= (long long)k.ws_bytes_)
       return urk::wstream_8x8(&k, s);
     if (k.OH == 16 && k.OW == 16) return urk::himg_16x16(&k, s);
@@ -132,42 +123,33 @@ int dispatch_conv(ConvK& k, hipStream_t s, bool pair) {
       return urk::himg_8x8x4(&k, s);
     }
   }
-  static const bool no_g256 = getenv("UR_IGEMM_NOG256") != nullptr;
-  if (!no_g256 && k.KH == 1 && k.stride == 1 && !k.ups && k.C2 == 0 && k.staged_ok_ && k.Cout % 256 == 0 && !k.yt && (k.act == UR_ACT_GEGLU || k.act == UR_ACT_GATE) &&
+  if (k.KH == 1 && k.stride == 1 && !k.ups && k.C2 == 0 && k.staged_ok_ && k.Cout % 256 == 0 && !k.yt && (k.act == UR_ACT_GEGLU || k.act == UR_ACT_GATE) &&
       (long long)((k.M + 255) / 256) * (k.Cout / 256) * k.nbatch >= 200 && (long long)k.M * k.ldx < (1ll << 31) - 256)
   {
     // 320-wide tiles when they land on whole rounds of CUs (2048 x 10240: 8 x 32 = 256 tiles instead of 320)
-    static const bool no_g320 = getenv("UR_IGEMM_NOG320") != nullptr;
     auto fill = [](long long t) { return (double)t / (double)(((t + 255) / 256) * 256); };
     const long long tm = (k.M + 255) / 256;
-    if (!no_g320 && k.Cout % 320 == 0 && k.nbatch == 1 && !k.bias_img && fill(tm * (k.Cout / 320)) > fill(tm * (k.Cout / 256)))
+    if (k.Cout % 320 == 0 && k.nbatch == 1 && !k.bias_img && fill(tm * (k.Cout / 320)) > fill(tm * (k.Cout / 256)))
       return urk::gemm_256x320_pair(&k, s);
     return urk::gemm_256x256(&k, s);
   }
-  static const bool force_v1 = getenv("UR_IGEMM_V1") != nullptr;
   // short-K GEMMs (<= 10 K tiles: per-workgroup prologue/epilogue latency dominates): 128-row tiles, 2 workgroups per CU
-  const bool use_v1 = force_v1 || (k.KH == 1 && k.nk <= 10);
+  const bool use_v1 = k.KH == 1 && k.nk <= 10;
   const long long blocks128 = (long long)((k.M + 127) / 128) * ((k.Cout + 127) / 128) * k.nbatch;
-  static const bool no_t64 = getenv("UR_IGEMM_NOT64") != nullptr;
   // pure GEMMs that will not be split: the LDS-DMA twin of the register-staged kernel (no staging registers / ds_writes)
-  static const bool g1dma = getenv("UR_IGEMM_NOG1DMA") == nullptr;
-  const bool g1 = g1dma && k.KH == 1 && k.stride == 1 && !k.ups && k.C2 == 0 && k.pad_t == 0 && k.pad_l == 0 && k.OH == k.H && k.OW == k.W &&
+  const bool g1 = k.KH == 1 && k.stride == 1 && !k.ups && k.C2 == 0 && k.pad_t == 0 && k.pad_l == 0 && k.OH == k.H && k.OW == k.W &&
                   (long long)k.M * k.ldx + k.Ktot < (1ll << 31) - 256;
-#ifdef UR_AB_VARIANTS
-  if (const char* ab = getenv("UR_AB_ID")) if (g1 && !pair && !k.f16 && atoi(ab) >= 0) return urk::g1_ab_bf16(&k, s, atoi(ab));
-#endif
   auto nosplit = [&](int bm, int bn) { return (long long)((k.M + bm - 1) / bm) * ((k.Cout + bn - 1) / bn) * k.nbatch >= 200 || k.nk < 8 || !k.ws; };
-  if (!no_t64 && k.KH == 1 && !pair && k.Cout > 64) {
+  if (k.KH == 1 && !pair && k.Cout > 64) {
     // too few 128 x 128 tiles to fill 256 CUs and K too short for split-K to pay for its reduce pass: 64 x 64 tiles
     // (>= 128 such tiles run faster unsplit up to K = 3072 than split with a reduce pass: 512 x 1280 x 1280 11.3 vs 14.6 us,
-    //  2048 x 1280 x 2560 29 vs 34 us - tools/ab_gemm_sweep.py)
+    //  2048 x 1280 x 2560 29 vs 34 us)
     const long long blocks64 = (long long)((k.M + 63) / 64) * ((k.Cout + 63) / 64) * k.nbatch;
     // (grids of <= 256 workgroups - the 8x8 level - are latency-bound per K tile: four ring stages, and K up to 2560 stays unsplit:
     //  512 x 1280 x 1280 12.9 -> 9.1 us, x 2560 20.8 (split + reduce) -> 14.3 us; profiles/r5_wreg_ab.txt)
-    static const bool no_deep = getenv("UR_IGEMM_NODEEP") != nullptr;
-    if (!no_deep && blocks128 < 200 && g1 && blocks64 >= 128 && blocks64 <= 256 && k.nk >= 8 && k.nk <= 48) return urk::g1_64x64_deep(&k, s);
+    if (blocks128 < 200 && g1 && blocks64 >= 128 && blocks64 <= 256 && k.nk >= 8 && k.nk <= 48) return urk::g1_64x64_deep(&k, s);
     // long-K GEMMs of the 16x16 level: 128 x 64 tiles, three stages, unsplit (2048 x 1280 x 2560 25.9 -> 23.3 us, x 5120 49.1 -> 43.7 us)
-    if (!no_deep && g1 && blocks128 < 200 && k.nk > 24 && k.nk <= 96 && (long long)((k.M + 127) / 128) * ((k.Cout + 63) / 64) * k.nbatch >= 256)
+    if (g1 && blocks128 < 200 && k.nk > 24 && k.nk <= 96 && (long long)((k.M + 127) / 128) * ((k.Cout + 63) / 64) * k.nbatch >= 256)
       return urk::g1_128x64_deep(&k, s);
     if (blocks128 < 200 && g1 && ((blocks64 >= 128 && k.nk <= 24) || (blocks64 >= 256 && k.nk <= 48))) return urk::g1_64x64(&k, s);
     if (blocks128 < 200 && k.nk <= 24) return g1 && nosplit(64, 64) ? urk::g1_64x64(&k, s) : urk::v1_64x64(&k, s);
@@ -186,8 +168,7 @@ int dispatch_conv(ConvK& k, hipStream_t s, bool pair) {
   if (k.Cout <= 64 && !pair) return urk::v2_128x64(&k, s);
   const bool n160 = !pair && k.Cout % 160 == 0 && k.Cout % 128 != 0;
   const long long big_tiles = (long long)((k.M + 255) / 256) * ((k.Cout + (n160 ? 159 : 127)) / (n160 ? 160 : 128)) * k.nbatch;
-  static const bool no_fill = getenv("UR_IGEMM_NOFILL") != nullptr;
-  if (!no_fill && g1 && !pair && big_tiles < 256) {
+  if (g1 && !pair && big_tiles < 256) {
     // 256-row tiles would leave CUs without a workgroup (e.g. 8192 x 640: 160 tiles): 128-row LDS-DMA tiles, two per CU,
     // in the width that lands closest to whole CUs (8192 x 640 -> 64 x 4 tiles of 160 = 256)
     const long long t160 = k.Cout % 160 == 0 ? (long long)((k.M + 127) / 128) * (k.Cout / 160) : 0;
@@ -198,7 +179,7 @@ int dispatch_conv(ConvK& k, hipStream_t s, bool pair) {
   }
   if (big_tiles >= 160) {
     // pure GEMMs onto 320/960-wide outputs: two 128 x 160 workgroups per CU beat one 256 x 160 (32768 x 320 x 1280: 41 vs 44.5 us)
-    if (n160 && g1 && !no_fill) return urk::g1_128x160(&k, s);
+    if (n160 && g1) return urk::g1_128x160(&k, s);
     if (n160) return urk::v2_256x160(&k, s);
     return urk::v2_256x128(&k, s);
   }
@@ -240,7 +221,6 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, int dry, ur_conv
   UR_REQUIRE(k.M > 0, "empty problem");
   UR_REQUIRE((long long)d->N * d->H * d->W * (long long)std::max(d->ldx, d->ldx2) < (1ll << 31) &&
                  (long long)d->Cout * d->ldw < (1ll << 31), "tensor too large for 32-bit element offsets");
-  { const char* e = getenv("UR_IGEMM_DBG"); k.dbg = e ? atoi(e) : 0; }
 
   k.kcm = d->k_chunk_major; k.wf = (const uint16_t*)d->w_frag; k.wmajor = 0; k.xgm = 0; k.xbn = 0;
   UR_REQUIRE(!k.kcm || (k.Cin % 64 == 0 && d->C1 % 64 == 0), "k_chunk_major needs C1 and C1+C2 to be multiples of 64");
@@ -293,8 +273,7 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, int dry, ur_conv
   // Grouped 3x3 convolutions whose groups are halo-kernel sized (chunk-major weights, >= 64 channels in, a multiple of 128 out):
   // one halo launch per group on the channel slice instead of the batched generic kernel, which gathers 64-byte runs per pixel and
   // tap (CFRM's AdaNAFV2.group_conv, densified to 128-channel blocks by the caller: 2.19 ms -> 4 x ~0.2 ms at 256 x 256 x 512)
-  static const bool no_ghalo = getenv("UR_IGEMM_NOGHALO") != nullptr;
-  if (!no_ghalo && k.nbatch > 1 && d->KH == 3 && k.kcm && k.stride == 1 && !pair && !k.gn_part && !k.row_stats && !k.ln_stats && !k.yt && !k.gn_ab &&
+  if (k.nbatch > 1 && d->KH == 3 && k.kcm && k.stride == 1 && !pair && !k.gn_part && !k.row_stats && !k.ln_stats && !k.yt && !k.gn_ab &&
       !k.out_f32 && k.staged_ok_ && k.Cout % 128 == 0 && !k.bias_img && k.C2 == 0) {
     for (int b = 0; b < d->nbatch; ++b) {
       ConvK kb = k;

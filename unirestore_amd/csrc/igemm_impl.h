@@ -39,7 +39,7 @@ struct ConvK {
   int M, Ktot, nk, tiles_m, tiles_n, splitk, nk_per_split, nbatch;
   long long bs_x, bs_x2, bs_w, bs_bias, bs_y, bs_r, bias_img;
   size_t ws_bytes_;
-  int dbg, gn_fused, gn_parts, gn_silu, f16, staged_ok_, prologue_ok;
+  int gn_fused, gn_parts, gn_silu, f16, staged_ok_, prologue_ok;
   int patch_tw, patch_m0_unused;   // >0: tile rows are an (BM/patch_tw) x patch_tw pixel patch of one image (halo kernel)
   int kcm;   // 1: K runs (64-channel chunk, tap, channel) - the 9 taps of a chunk are consecutive K tiles (L2 reuse)
   const uint16_t* wf;   // fragment-major copy of w (ur_conv_desc.w_frag) or null
@@ -75,11 +75,6 @@ static inline void pick_xcd_grid(ConvK& k, double W, double A) {
   if (off || k.nbatch != 1) return;
   const long long nt = (long long)k.tiles_m * k.tiles_n;
   double best = 0.9 * (8.0 * W + A);
-  static const int force = getenv("UR_XCD_FORCE") ? atoi(getenv("UR_XCD_FORCE")) : 0;      // A/B: this row-band count wherever the grid divides
-  if (force && nt % 8 == 0 && 8 % force == 0 && k.tiles_m % force == 0 && k.tiles_n % (8 / force) == 0) {
-    if (force < 8) { k.xgm = force; k.xbn = k.tiles_n / (8 / force); }
-    return;
-  }
   if (nt % 8 == 0)
     for (int gm = 4; gm >= 1; gm >>= 1) {
       const int gn = 8 / gm;
@@ -378,7 +373,6 @@ __device__ __forceinline__ void staged_epilogue(const ConvK& p, f32x16 (&acc)[FN
     }
 #undef UR_EPI_PASS
   }
-  if (p.dbg & 16) return;
   __syncthreads();
   if (p.gn_fused) {
     // Fused GroupNorm statistics of the tile just produced (exactly the 16-bit values the consumer will read), deterministic:
@@ -498,16 +492,7 @@ __device__ __forceinline__ void igemm_epilogue(const ConvK& p, f32x16 (&acc)[FN]
 // fragment reads run a register pool ahead of the MFMAs, every MFMA waits with a counted lgkmcnt for its own operands.
 // ab[b] = LDS byte address of activation fragment b at k-step 0 (row * 128 + ((lane half ^ swizzle) << 4)), aw = the same for the
 // wave's first weight fragment (fragment a: + a * 4096); rows are 128-byte, 128-aligned, slots XOR-swizzled with (row >> 1) & 7.
-#if UR_IGASM_ABL == 4
-#include "../../tools/ab/igemm_asm_abl4.inc"
-#elif UR_IGASM_ABL == 5
-#include "../../tools/ab/igemm_asm_abl5.inc"
-#else
 #include "igemm_asm.inc"
-#endif
-#ifndef UR_HALO_ABL
-#define UR_HALO_ABL 0      // timing-only ablations of igemm_halo_kernel (A/B builds): 1 = no DMA waits, 2 = no MFMA body
-#endif
 #define IG_MN(ASM, ...)                                                                      \
   do {                                                                                       \
     if constexpr (F16) asm volatile(ASM("v_mfma_f32_32x32x16_f16") __VA_ARGS__);             \
@@ -919,8 +904,7 @@ struct ReducePlan { int kind, ri; };
 static ReducePlan plan_splitk_reduce(const ConvK& k) {
   const bool pair = k.act == UR_ACT_GEGLU || k.act == UR_ACT_GATE;
   if (k.row_stats || k.ln_stats) return {1, 0};
-  static const bool no_gnred = getenv("UR_IGEMM_NOGNRED") != nullptr;
-  if (!no_gnred && k.gn_part && k.y && !pair && k.staged_ok_ && k.nbatch == 1 && !k.yt && k.OHW % 64 == 0) {
+  if (k.gn_part && k.y && !pair && k.staged_ok_ && k.nbatch == 1 && !k.yt && k.OHW % 64 == 0) {
     // rows per block 64 / 32 / 16: the largest that still gives >= 512 workgroups (M = 512 at the 8x8 level needs the
     // 16-row version: 160 workgroups of 64 rows left a third of the CUs idle in a latency-bound pass)
     const long long colb = (k.Cout / 4 + 15) / 16;
@@ -992,8 +976,7 @@ int launch_cfg(ConvK& k, hipStream_t s) {
   }
   dim3 grid(k.tiles_m * k.tiles_n, k.nbatch, k.splitk);
   pick_xcd_grid(k, (double)k.Cout * k.Ktot, (double)k.N * k.H * k.W * k.Cin);
-  static const bool no_g1 = getenv("UR_IGEMM_NOG1") != nullptr;
-  const bool g1 = !no_g1 && k.KH == 1 && k.stride == 1 && !k.ups && k.C2 == 0 && k.pad_t == 0 && k.pad_l == 0 && k.OH == k.H && k.OW == k.W &&
+  const bool g1 = k.KH == 1 && k.stride == 1 && !k.ups && k.C2 == 0 && k.pad_t == 0 && k.pad_l == 0 && k.OH == k.H && k.OW == k.W &&
                   (long long)k.M * k.ldx + k.Ktot < (1ll << 31);
   if (g1) UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, true, F16>), grid, dim3(256), lds, s, k));
   else UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, false, F16>), grid, dim3(256), lds, s, k));
@@ -1093,8 +1076,7 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_glds_kernel(const ConvK p) 
       bool v = kval && wok[j];
       const uint16_t* g = v ? Wt + woff[j] + kcur : zero;
       const int base_row = wrow_lds[j] - (lane >> 3);               // wave-uniform first row of this 1-KiB piece
-      if (p.dbg & 128) __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(wsm + base_row * 128), 16, 0, 2);   // nt: stream past L1
-      else __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(wsm + base_row * 128), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(wsm + base_row * 128), 16, 0, 0);
     }
     kcur += 64;
     if (p.kcm) { if (++tap == ntap) { tap = 0; cch += 64; } }
@@ -1151,7 +1133,7 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_glds_kernel(const ConvK p) 
   // lands in the stage that was read in THIS iteration, and hipcc otherwise leaves the last fragment reads outstanding across
   // the barrier (it sinks the last MFMAs below it) - under LDS contention from a co-resident kernel the DMA then overwrote
   // fragments that had not been read yet (found in round 2 as run-to-run differences with the SC-Tuner side stream on).
-  const int ntile = (p.dbg & 8) ? 0 : kt_end - kt_begin;
+  const int ntile = kt_end - kt_begin;
   if (ntile > 0) {
     int issued = 0;
 #pragma unroll
@@ -1164,7 +1146,7 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_glds_kernel(const ConvK p) 
     int cs = 0, is = (NST - 1) % NST;
     for (int t = 0; t < ntile; ++t) {
       const bool more = issued < ntile;
-      if (more) { if (!(p.dbg & 1)) issue_tile(is); ++issued; is = (is + 1 == NST) ? 0 : is + 1; }
+      if (more) { issue_tile(is); ++issued; is = (is + 1 == NST) ? 0 : is + 1; }
       compute(cs);                                        // (no run-time condition around the asm K tile: hipcc spills its operands then)
       cs = (cs + 1 == NST) ? 0 : cs + 1;
       // tile t+1 must have landed before anyone reads it: all but the newest (NST-2) tiles' DMAs retired
@@ -1173,7 +1155,6 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_glds_kernel(const ConvK p) 
       __builtin_amdgcn_s_barrier();
     }
   }
-  if (p.dbg & 4) { if (acc[0][0][0] == 123.456f) reinterpret_cast<float*>(p.y)[0] = 1.f; return; }
   if constexpr (ktile_gemm_ok<FM, FN>()) asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");      // last asm MFMA -> VALU reads of the accumulators
   igemm_epilogue<FM, FN, WTM, WTN, BM, BN, NT, F16>(p, acc, m0, n0, wm, wn, lane, gb, sz, smem);
 }
@@ -1284,7 +1265,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_glds_kernel(const ConvK p) {
   const unsigned kt_x0 = (unsigned)(uintptr_t)(lptr_t)smem + (wm * WTM + frow) * 128 + ((fhalf ^ ((frow >> 1) & 7)) << 4);
   const unsigned kt_w0 = (unsigned)(uintptr_t)(lptr_t)smem + (BM + wn * WTN + frow) * 128 + ((fhalf ^ ((frow >> 1) & 7)) << 4);
   static_assert(WTM % 32 == 0 && ((WTN >> 1) & 7) == 0, "fragment rows must keep the swizzle phase of row 0");
-  const int ntile = (p.dbg & 8) ? 0 : p.nk;               // (dbg bits: timing-only ablations, UR_IGEMM_DBG)
+  const int ntile = p.nk;
   int issued = 0;
 #pragma unroll
   for (int s = 0; s < NST - 1; ++s)
@@ -1305,7 +1286,6 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_glds_kernel(const ConvK p) {
       for (int b = 0; b < FM; ++b) ab[b] = kt_x0 + cs * STAGE + b * 4096;
       ktile_mma<FM, FN, F16>(acc, ab, kt_w0 + cs * STAGE);
     } else
-    if (!(p.dbg & 2))
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const int slot = ks * 2 + fhalf;
@@ -1331,7 +1311,6 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_glds_kernel(const ConvK p) {
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
   }
-  if (p.dbg & 4) { if (acc[0][0][0] == 123.456f) reinterpret_cast<float*>(p.y)[0] = 1.f; return; }
   if constexpr (ktile_gemm_ok<FM, FN>()) asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");      // last asm MFMA -> VALU reads of the accumulators
   igemm_epilogue<FM, FN, WTM, WTN, BM, BN, NT, F16, DIRECT, PAIRC>(p, acc, m0, n0, wm, wn, lane, gb, 0, smem);
 }
@@ -1415,7 +1394,7 @@ __device__ __forceinline__ void gn_piece_inplace(unsigned char* piece, const GnA
 // asm blocks (PHASE 1 = first half, 2 = second half + the first fragment reads of the NEXT tile, 3 = second half of the last tile)
 // with the workgroup's "next weight tile landed" wait + barrier between them; PHASE 0 issues the first tile's prefetch.  The
 // fragment rings ra / rb live across the blocks.  Without it the matrix pipe drains at every per-tile barrier: the first MFMA
-// behind the barrier waits a full LDS round trip (~150-250 of ~1300 cycles per tile, tools/probe + UR_IGASM_ABL timings).
+// behind the barrier waits a full LDS round trip (~150-250 of ~1300 cycles per tile, tools/probe and ablation-build timings).
 template <int FM, int FN> struct KPipeRings { ig_u32x4 ra[FN == 5 ? 10 : 4], rb[4]; };      // (ring sizes of tools/gen_igemm_asm.py)
 template <int FM, int FN, bool F16, int PHASE>
 __device__ __forceinline__ void kpipe(f32x16 (&acc)[FN][FM], KPipeRings<FM, FN>& r, const unsigned (&ab)[FM], unsigned aw, const unsigned (&abn)[FM],
@@ -1531,11 +1510,7 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_halo_kernel(const ConvK p) 
     woff[i] = row < p.Cout ? row * p.ldw : -1;
   }
   // blockIdx.y splits the channel-chunk range (few-tile layers: tiles * splits <= one round of CUs)
-#if UR_HALO_ABL == 3                                          // timing-only: prologue + epilogue, no K loop
-  const int cps = p.nk_per_split / 9, c_begin = sz * cps, nchunk = p.N < 0 ? 1 : 0;
-#else
   const int cps = p.nk_per_split / 9, c_begin = sz * cps, nchunk = min(p.nk / 9, c_begin + cps) - c_begin;
-#endif
   const int nk = nchunk * 9, kt0 = c_begin * 9;
 
 #ifdef UR_HALO_DMA_BUILTIN                                  // A/B: the global_load_lds loaders of rounds 1-2
@@ -1645,11 +1620,6 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_halo_kernel(const ConvK p) 
   constexpr bool stagger = ktile_asm_ok<FM, FN>();
   const bool early_grp = wid_s < NW / 2;                   // (waves w and w + NW/2 share a SIMD)
 #endif
-#if UR_HALO_ABL == 6
-  unsigned long long ts[63];
-#pragma unroll
-  for (int i = 0; i < 63; ++i) ts[i] = 0;
-#endif
   KPipeRings<FM, FN> rings;
   if constexpr (ktile_asm_ok<FM, FN>()) {
     kpipe_init(rings);
@@ -1670,22 +1640,13 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_halo_kernel(const ConvK p) 
       const bool more_w = kt + 2 < nk;
       const bool more_h = tap < HSLOTS && next_chunk;
       // The DMA path of a CU takes ~24 cycles per 1-KiB piece and a wave sits in its buffer_load until the queue has room: with all
-      // eight waves issuing at the top of the tap nobody feeds the matrix pipe meanwhile (0.37 us of a 1.2 us tap, UR_HALO_ABL=5).
+      // eight waves issuing at the top of the tap nobody feeds the matrix pipe meanwhile (0.37 us of a 1.2 us tap, measured against a build without the DMA).
       // So the two waves of a SIMD issue half a tap apart: waves 0..NW/2-1 here, the others between the two MFMA halves.
       auto issue_tap = [&]() {
-#if UR_HALO_ABL != 5                                        // (5: timing-only, no DMA in the loop at all)
         if (more_w) issue_w(kt + 2, (tap + 2) % 3);
         if (tap < HSLOTS) { if (next_chunk) issue_h(c + 1, tap < HSLOTS ? tap : 0); }
-#endif
       };
-#if UR_HALO_ABL == 6                                        // in-kernel phase timers (shader cycles) of chunk 1, workgroup 0, waves 0 and NW/2
-#define IG_TS(i) do { if (c == 1) ts[tap * 7 + (i)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define IG_TS(i) do { } while (0)
-#endif
-      IG_TS(0);
       if (!stagger || early_grp) issue_tap();
-      IG_TS(1);
       const bool ab_now = gnp && tap == 0 && next_chunk;    // (+1 DMA op in this iteration, counted in the wait below)
       if (ab_now) issue_ab(c + 1);
       // piece (tap - 2) of the next chunk landed with the previous iteration's wait: normalise it in LDS next to this tap's MFMAs
@@ -1693,7 +1654,6 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_halo_kernel(const ConvK p) 
       if (gnp && tap >= 2 && tap - 2 < HSLOTS && next_chunk) gn_slot(c + 1, (tap >= 2 && tap - 2 < HSLOTS) ? tap - 2 : 0);
       // everything issued in EARLIER iterations has landed once only this iteration's pieces may still be in flight
       auto dma_wait = [&]() {
-#if UR_HALO_ABL != 1 && UR_HALO_ABL != 5                    // (1: timing-only, never wait for the DMA)
         if (ab_now) {                                       // tap 0 with the next chunk's affine table in flight as well
           if (more_w) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WPW + 2) : "memory");
           else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
@@ -1701,7 +1661,6 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_halo_kernel(const ConvK p) 
         else if (more_w) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WPW) : "memory");
         else if (more_h) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
       };
       if constexpr (ktile_asm_ok<FM, FN>()) {
         // hand-scheduled, tap-crossing pipeline (kpipe above).  Barrier 1 (mid-tap) publishes weight tile kt + 1 and every halo /
@@ -1711,16 +1670,11 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_halo_kernel(const ConvK p) 
         unsigned ab[FM], abn[FM];
         const unsigned aw = tap_addr(c, tap, ab), awn = tap_addr(c + (tap == 8 ? 1 : 0), (tap + 1) % 9, abn);
         kpipe<FM, FN, F16, 1>(acc, rings, ab, aw, abn, awn);
-        IG_TS(2);
         if (stagger && !early_grp) issue_tap();
         dma_wait();
-        IG_TS(3);
         __builtin_amdgcn_s_barrier();
-        IG_TS(4);
         kpipe<FM, FN, F16, 2>(acc, rings, ab, aw, abn, awn);      // (the last tap prefetches too - valid LDS, never used: one code path)
-        IG_TS(5);
         __builtin_amdgcn_s_barrier();
-        IG_TS(6);
       } else {
         const int dy = tap / 3, dx = tap % 3;
         const unsigned char* wsm = wring + (tap % 3) * WBYTES;
@@ -1759,19 +1713,8 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_halo_kernel(const ConvK p) 
   }
   if constexpr (ktile_asm_ok<FM, FN>()) kpipe_drain(rings);      // the last tap's prefetch lands in the rings: they stay reserved until here
   asm volatile("s_waitcnt vmcnt(0)\n\ts_nop 15\n\ts_nop 7" ::: "memory");      // last MFMA of the asm tap body -> VALU reads of the accumulators
-#if UR_HALO_ABL == 6                                          // phase timers -> the first bytes of y (no epilogue)
-  if (acc[0][0][0] == 123.456f) reinterpret_cast<uint16_t*>(p.y)[0] = 1;
-  if (blockIdx.x == 0 && blockIdx.y == 0 && lane == 0 && (wid == 0 || wid == NW / 2)) {
-    unsigned long long* o = reinterpret_cast<unsigned long long*>(p.y) + (wid ? 64 : 0);
-#pragma unroll
-    for (int i = 0; i < 63; ++i) o[i] = ts[i];
-  }
-#elif UR_HALO_ABL == 4                                        // timing-only: no epilogue (one store keeps the loop alive)
-  if (acc[0][0][0] == 123.456f) reinterpret_cast<uint16_t*>(p.y)[0] = 1;
-#else
   // (BN == 32: the thin tile of the conv_out layers - fp32 output, 4-8 channels - leaves through the direct stores)
   igemm_epilogue<FM, FN, WTM, WTN, BM, BN, NT, F16, BN == 32>(p, acc, m0, n0, wm, wn, lane, 0, sz, smem);
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1803,9 +1746,6 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const
   constexpr bool gnp = GNP;
   typedef __attribute__((address_space(3))) void* lptr_t;
 
-#if UR_HALO_ABL == 7                                          // workgroup time line in 100 MHz ticks (A/B build): start, K loop, end
-  const unsigned long long wg_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wid_s = __builtin_amdgcn_readfirstlane(wid);
   const int sz = blockIdx.y;
@@ -1880,14 +1820,6 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const
       const unsigned vo = lane < 32 ? (unsigned)((img * 2 + (lane >> 4 & 1)) * p.Cin + (lane & 15) * 4) * 4u : IG_OOB;
       ig_lds_dma16(abuf_lds + (c & 1) * 1024, vo, rs_ab, (unsigned)((c_begin + min(c, nchunk - 1)) * 64) * 4u);
     };
-#if UR_HALO_ABL == 6
-    unsigned long long lts[45];
-#pragma unroll
-    for (int i = 0; i < 45; ++i) lts[i] = 0;
-#define LD_TS(i) do { if (c == 1) lts[tap * 5 + (i)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define LD_TS(i) do { } while (0)
-#endif
     // Prologue: the compute waves fetch patch 0 and weight tile 0 themselves (nine waves feed the DMA path 2-3x faster than one, and
     // they have nothing else to do yet); the loader issues the affine table and weight tile 1 - which its own tap-0 wait covers - and
     // builds its pixel table while those fly.
@@ -1907,36 +1839,24 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap) {
         const int kt = c * 9 + tap;
-        LD_TS(0);
         if (do_w) dma_w(kt + 2, (tap + 2) % 3, 0, WH);
         if (do_h) {
           dma_h(c + 1, 2 * tap);
           if (gnp && tap == 0) dma_ab(c + 1);
         }
-        LD_TS(1);
         // everything this wave issued in EARLIER taps has landed once only this tap's first half may still be in flight
         if (kt + 1 == nk) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // last tap: nothing may land behind the barrier (the epilogue reuses LDS)
         else if (do_w && do_h) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WH + halo_count(2 * tap) + ((gnp && tap == 0) ? 1 : 0)) : "memory");
         else if (do_w) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WH) : "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(halo_count(2 * tap) + ((gnp && tap == 0) ? 1 : 0)) : "memory");
-        LD_TS(2);
         __builtin_amdgcn_s_barrier();
-        LD_TS(3);
         if (kt + 1 < nk) {
           if (do_w) dma_w(kt + 2, (tap + 2) % 3, WH, WPIECES);
           if (do_h) dma_h(c + 1, 2 * tap + 1);
         }
-        LD_TS(4);
         __builtin_amdgcn_s_barrier();
       }
     }
-#if UR_HALO_ABL == 6
-    if (blockIdx.x == 0 && blockIdx.y == 0 && lane == 0) {
-      unsigned long long* o = reinterpret_cast<unsigned long long*>(p.y) + 128;
-#pragma unroll
-      for (int i = 0; i < 45; ++i) o[i] = lts[i];
-    }
-#endif
     return;
   }
 
@@ -1995,14 +1915,6 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const
     }
     return aw_lds + (tp % 3) * WBYTES;
   };
-#if UR_HALO_ABL == 6
-  unsigned long long ts[45];
-#pragma unroll
-  for (int i = 0; i < 45; ++i) ts[i] = 0;
-#define WS_TS(i) do { if (c == 1) ts[tap * 5 + (i)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define WS_TS(i) do { } while (0)
-#endif
   KPipeRings<FM, FN> rings;
   kpipe_init(rings);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's pieces of patch 0 / weight tile 0
@@ -2018,12 +1930,6 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const
     const unsigned aw0 = tap_addr(0, 0, ab0);
     kpipe<FM, FN, F16, 0>(acc, rings, ab0, aw0, ab0, aw0);
   }
-#if UR_HALO_ABL == 6
-  const unsigned long long loop_c0 = __builtin_readcyclecounter(), loop_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
-#if UR_HALO_ABL == 7
-  const unsigned long long wg_t1 = __builtin_amdgcn_s_memrealtime();
-#endif
   for (int c = 0; c < nchunk; ++c) {
     const bool next_chunk = c + 1 < nchunk;
 #pragma unroll
@@ -2034,43 +1940,15 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const
       if (gnp && tap == 0 && c > 0) gn_slot(c, 7);
       unsigned ab[FM], abn[FM];
       const unsigned aw = tap_addr(c, tap, ab), awn = tap_addr(c + (tap == 8 ? 1 : 0), (tap + 1) % 9, abn);
-      WS_TS(0);
       kpipe<FM, FN, F16, 1>(acc, rings, ab, aw, abn, awn);
-      WS_TS(1);
       __builtin_amdgcn_s_barrier();                       // weight tile kt + 1 (and every older piece) is in LDS
-      WS_TS(2);
       kpipe<FM, FN, F16, 2>(acc, rings, ab, aw, abn, awn);
-      WS_TS(3);
       __builtin_amdgcn_s_barrier();                       // everyone has read weight tile kt: its slot takes tile kt + 3
-      WS_TS(4);
     }
   }
   kpipe_drain(rings);
   asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");       // last MFMA of the asm tap body -> VALU reads of the accumulators
-#if UR_HALO_ABL == 6                                          // phase timers -> the first bytes of y (no epilogue)
-  if (acc[0][0][0] == 123.456f) reinterpret_cast<uint16_t*>(p.y)[0] = 1;
-  if (blockIdx.x == 0 && blockIdx.y == 0 && lane == 0 && (wid == 0 || wid == NW / 2)) {
-    unsigned long long* o = reinterpret_cast<unsigned long long*>(p.y) + (wid ? 64 : 0);
-#pragma unroll
-    for (int i = 0; i < 45; ++i) o[i] = ts[i];
-  }
-  if (lane == 0 && wid == 0 && blockIdx.x < 256) {            // K-loop duration of every workgroup in shader cycles and in 100 MHz ticks
-    unsigned long long* o = reinterpret_cast<unsigned long long*>(p.y) + 256 + 2 * blockIdx.x;
-    o[0] = __builtin_readcyclecounter() - loop_c0;
-    o[1] = __builtin_amdgcn_s_memrealtime() - loop_r0;
-  }
-#elif UR_HALO_ABL == 7
-  const unsigned long long wg_t2 = __builtin_amdgcn_s_memrealtime();
   igemm_epilogue<FM, FN, WTM, WTN, BM, BN, NT, F16, false>(p, acc, m0, n0, wm, wn, lane, 0, sz, smem);
-  __syncthreads();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (lane == 0 && wid == 0 && blockIdx.x < 256 && blockIdx.y == 0) {
-    unsigned long long* o = reinterpret_cast<unsigned long long*>(p.y) + 4 * blockIdx.x;
-    o[0] = wg_t0; o[1] = wg_t1; o[2] = wg_t2; o[3] = __builtin_amdgcn_s_memrealtime();
-  }
-#else
-  igemm_epilogue<FM, FN, WTM, WTN, BM, BN, NT, F16, false>(p, acc, m0, n0, wm, wn, lane, 0, sz, smem);
-#endif
 }
 
 // Thin-N halo launch (round 5): 3x3 convolutions onto <= 32 output channels - the three conv_out layers (VAE decoder 128 -> 3 at 512 x 512:
@@ -2115,8 +1993,7 @@ int launch_halo(ConvK& k, hipStream_t s) {
   const int nchunk = k.nk / 9;
   const long long tiles = (long long)k.tiles_m * k.tiles_n;
   int splitk = 1;
-  static const bool no_hsplit = getenv("UR_IGEMM_NOHSPLIT") != nullptr;
-  if (!no_hsplit && tiles <= 128 && k.ws && k.y) {     // <= half a round of CUs: split the chunk range, reduce in a second pass
+  if (tiles <= 128 && k.ws && k.y) {     // <= half a round of CUs: split the chunk range, reduce in a second pass
     splitk = (int)std::min<long long>(256 / tiles, std::max(1, nchunk / 2));
     while (splitk > 1 && (long long)splitk * k.M * k.Cout * 4 > (long long)k.ws_bytes_) --splitk;
   }

@@ -270,8 +270,7 @@ static void gn_geom(int N, int HW, int C, int ppt, int& cvs, int& slabs, int& ch
   slabs = cv / cvs;
   const int R = 256 / cvs;
   // aim for >= ~2048 blocks (8 per CU) but keep >= ppt pixel rows per thread when the tensor is big enough
-  static const int wantb = getenv("UR_GN_BLOCKS") ? atoi(getenv("UR_GN_BLOCKS")) : 2048;
-  const long long want = std::max<long long>(1, wantb / ((long long)N * slabs));
+  const long long want = std::max<long long>(1, 2048 / ((long long)N * slabs));
   // (8x8 maps: 2 pixel rows per thread - 40 workgroups of 8-deep loops were pure latency)
   chunks = (int)std::min<long long>(want, std::max(1, HW / ((HW <= 64 ? std::min(ppt, 2) : ppt) * R)));
   ppb = (HW + chunks - 1) / chunks;
@@ -342,9 +341,8 @@ int ur_groupnorm_apply_act(const void* x, const void* x2, void* y, const float* 
   ur::ProfScope prof(fam, 0.0, 4.0 * N * HW * (double)C, s);
   const uint16_t* src[2] = {(const uint16_t*)x, (const uint16_t*)x2};
   const int cs[2] = {C1, x2 ? C2 : 0}, off[2] = {0, C1};
-  static const int ppt = getenv("UR_GN_PPT") ? atoi(getenv("UR_GN_PPT")) : 2;      // (8 -> 2 pixel rows per thread: -0.8 ms per forward, same-box A/B)
-  static const bool one_launch = getenv("UR_GN_TWO_LAUNCHES") == nullptr;
-  if (one_launch && cs[1] > 0) {                          // virtual concat: one launch for both sources
+  constexpr int ppt = 2;                                 // (8 -> 2 pixel rows per thread: -0.8 ms per forward, same-box A/B)
+  if (cs[1] > 0) {                          // virtual concat: one launch for both sources
     int cvs1, slabs1, chunks1, ppb1, cvs2, slabs2, chunks2, ppb2;
     gn_geom(N, HW, cs[0], ppt, cvs1, slabs1, chunks1, ppb1);
     gn_geom(N, HW, cs[1], ppt, cvs2, slabs2, chunks2, ppb2);

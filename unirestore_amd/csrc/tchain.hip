@@ -25,16 +25,7 @@
 //   TAIL  h1 = h0 + to_out(o1); h2 = h1 + to_out2(softmax(to_q2(LN2 h1) Kc^T) Vc); h3 = h2 + FF(LN3 h2);
 //         y = x + proj_out(h3), + GroupNorm partial sums of y                         (ur_transformer_tail_fused)
 #include "common.h"
-#ifndef UR_CHAIN_ABL
-#define UR_CHAIN_ABL 0      // timing-only ablations for A/B builds (tools/bench_chain.py): 1 = no MFMA phases, 2 = no weight DMA, 3 = no GELU,
-#endif                      // 4 = MFMA phases without their fragment reads, 5 = without their MFMAs, 6 = cycle stamps of one FF chunk
-#if UR_CHAIN_ABL == 4
-#include "../../tools/ab/tchain_asm_abl4.inc"
-#elif UR_CHAIN_ABL == 5
-#include "../../tools/ab/tchain_asm_abl5.inc"
-#else
 #include "tchain_asm.inc"
-#endif
 
 namespace {
 
@@ -68,13 +59,9 @@ struct TChain {
   int lane, wid, h, voff;
   int ti, ntiles, islot, cslot;             // next tile to issue, its ring slot; ring slot of the next tile to consume
   int aoff[4];                              // lane's LDS offsets of the A fragment for the 4 k-steps of a [rows][128 B] block
-#if UR_CHAIN_ABL == 6
-  unsigned long long* dbg = nullptr;        // ablation 6: cycle stamps of one FF chunk (tools/bench_chain.py)
-#endif
 
 #define TC_MFMA_BLOCK(ASM, ...)                                                              \
   do {                                                                                       \
-    if constexpr (UR_CHAIN_ABL == 1) break;                                                  \
     if constexpr (F16) asm volatile(ASM("v_mfma_f32_32x32x16_f16") __VA_ARGS__);              \
     else asm volatile(ASM("v_mfma_f32_32x32x16_bf16") __VA_ARGS__);                           \
   } while (0)
@@ -110,7 +97,6 @@ struct TChain {
   __device__ __forceinline__ void dma_alone() {
     unsigned so, ld;
     dma_args(so, ld);
-    if constexpr (UR_CHAIN_ABL == 2) return;
     asm volatile(TC_ASM_DMA : "+s"(so), "+s"(ld) : "v"(voff), "s"(rs) : "memory", "scc");      // (s_add_u32 inside: SCC is clobbered)
   }
   // Tile `tc` is ready in its slot for every wave, and the slot of the tile before it is free again (the phase that follows
@@ -119,7 +105,7 @@ struct TChain {
   // lgkmcnt(0): this wave's fragment reads of the previous tile are retired before anyone overwrites its slot.
   template <int EXTRA = 0>
   __device__ __forceinline__ unsigned acquire() {
-    if constexpr (UR_CHAIN_ABL == 2) TC_WAIT(0); else TC_WAIT(11 + EXTRA);
+    TC_WAIT(11 + EXTRA);
     __builtin_amdgcn_s_barrier();
     const unsigned slot = lds0 + (unsigned)cslot * TC_TILE;
     cslot = cslot == TC_NS - 1 ? 0 : cslot + 1;
@@ -315,7 +301,7 @@ __device__ __forceinline__ typename Frag<F16>::type ff1_epilogue(const TChain<F1
     const float ca = f4e(q[4 + (e >> 2)], e & 3), cg = f4e(q[6 + (e >> 2)], e & 3);
     const float a = fmaf(rstd, ag[0][8 * U + e], fmaf(-mr, ca, ba));
     const float g = fmaf(rstd, ag[1][8 * U + e], fmaf(-mr, cg, bg));
-    v[e] = UR_CHAIN_ABL == 3 ? a * g : a * gelu_f(g);
+    v[e] = a * gelu_f(g);
   }
   return TChain<F16>::pack(v);
 }
@@ -332,36 +318,20 @@ __device__ __forceinline__ unsigned ff_stage(TChain<F16>& tc, f32x16 (&acc)[10],
   typedef typename Frag<F16>::type frag_t;
   const float mr = mean * rstd;
   unsigned last = 0;
-#if UR_CHAIN_ABL == 6
-  unsigned long long ts[12];
-#define TC_TS(i) do { if (c == 10) ts[i] = __builtin_readcyclecounter(); } while (0)
-#else
-#define TC_TS(i) do {} while (0)
-#endif
   for (int c = 0; c < nchunk; ++c) {
     frag_t hid[4];
-    TC_TS(0);
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       const unsigned slot = tc.acquire();
-      TC_TS(1 + 3 * half);
       tc.ff1_tile(ag, xb, slot);               // (zeroes ag: its first MFMAs take C = 0)
-      TC_TS(2 + 3 * half);
       hid[half * 2] = ff1_epilogue<F16, 0>(tc, ag, slot, rstd, mr);
       __builtin_amdgcn_sched_barrier(0);       // (one half-fragment's temporaries at a time: interleaved, the two spill)
       hid[half * 2 + 1] = ff1_epilogue<F16, 1>(tc, ag, slot, rstd, mr);
       __builtin_amdgcn_sched_barrier(0);
-      TC_TS(3 + 3 * half);
     }
     last = tc.acquire();
-    TC_TS(7);
     tc.template gemm_tile<false>(acc, hid[0], hid[1], hid[2], hid[3], last);     // (acc starts at zero: see the callers)
-    TC_TS(8);
   }
-#if UR_CHAIN_ABL == 6
-  if (tc.dbg && blockIdx.x == 17 && tc.lane == 0)
-    for (int i = 0; i < 9; ++i) tc.dbg[tc.wid * 16 + i] = ts[i];
-#endif
   return last;
 }
 
@@ -396,9 +366,6 @@ __global__ __launch_bounds__(256, 1) void tchain_mlp_kernel(const MlpP p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   TChain<F16> tc;
   tc.init(smem, p.stream, p.ntiles);
-#if UR_CHAIN_ABL == 6
-  tc.dbg = reinterpret_cast<unsigned long long*>(p.y + (long long)(p.T - 128) * p.ldy);      // (timing build: stamps land in the last rows of y)
-#endif
   const long long tok = (long long)blockIdx.x * TC_TOK + tc.wid * 32 + (tc.lane & 31);
   frag_t xb[20];
   load_frags<F16>(p.x, tok, p.ldx, tc.h, xb);
@@ -412,9 +379,6 @@ __global__ __launch_bounds__(256, 1) void tchain_mlp_kernel(const MlpP p) {
 #pragma unroll
   for (int s = 0; s < 20; ++s) asm volatile("" : "+v"(xb[s]));      // opaque: hipcc would otherwise keep the 160 fp32 values row_stats unpacked alive (in scratch) across the loop
   tc.template bias_res_pack<true>(acc, last, xb, xb);
-#if UR_CHAIN_ABL == 6
-  if (blockIdx.x != gridDim.x - 1)               // (timing build: the stamps live in the last workgroup's rows)
-#endif
   store_frags<F16>(p.y, tok, p.ldy, tc.h, xb);
   TC_WAIT(0);                                    // no LDS-DMA may outlive the workgroup
 }

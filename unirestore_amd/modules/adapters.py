@@ -4,7 +4,6 @@ Same constructor signatures, parameter names and forward semantics as the refere
 (scedit.py:24-38, nafnet_arch.py:28-131, cfrm.py:12-54, taskeditor.py:10-108); `forward` takes/returns NCHW fp32
 tensors like the reference operators, `run` is the NHWC bf16 fast path the model graph uses.
 """
-import os
 
 import torch
 import torch.nn as nn
@@ -16,8 +15,7 @@ from .nn import DEV, Conv2d, LayerNorm, Linear, GroupNorm
 
 
 # LayerNorm2d of the NAFBlocks folded into the consuming 1x1 convs (the mechanism of the transformer blocks' LayerNorms): 25 of the
-# 28 LayerNorm passes of a forward disappear.  UR_FUSE_LN2D=0: separate passes (A/B).
-FUSE_LN2D = os.environ.get("UR_FUSE_LN2D", "1") == "1"
+# 28 LayerNorm passes of a forward disappear.
 
 
 def _named(**mods):
@@ -145,7 +143,7 @@ class NAFBlock(nn.Module):
 
     def run(self, inp):
         w9c, b2, wsca, bsca = self._dw()
-        st = ops.ln_of(inp) if FUSE_LN2D else None
+        st = ops.ln_of(inp)
         if st is not None:                        # the producer (previous NAFBlock / AdaNAFV2.pwconv) left per-pixel channel sums
             x = ops.conv(inp, self._ln_folded(self.conv1, self.norm1, False), ln_stats=st)
         else:
@@ -153,12 +151,9 @@ class NAFBlock(nn.Module):
         x = ops.dwconv3x3(x, w9c, b2, gate=True)                               # depthwise + SimpleGate
         s = ops.linear_f32(ops.avgpool(x), wsca, bsca)                         # simplified channel attention
         x = ops.scale_channels(x, s)
-        y = ops.conv(x, self.conv3.packed(scale=self.beta), residual=inp, rows=FUSE_LN2D)      # inp + conv3(x)*beta (beta folded)
-        if FUSE_LN2D:
-            x = ops.conv(y, self._ln_folded(self.conv4, self.norm2, True), ln_stats=ops.ln_of(y), act=UR_ACT_GATE)
-        else:
-            x = ops.conv(self.norm2.run(y), self.conv4.packed(pair=True), act=UR_ACT_GATE)
-        return ops.conv(x, self.conv5.packed(scale=self.gamma), residual=y, gn=True, rows=FUSE_LN2D)    # y + conv5(x)*gamma
+        y = ops.conv(x, self.conv3.packed(scale=self.beta), residual=inp, rows=True)      # inp + conv3(x)*beta (beta folded)
+        x = ops.conv(y, self._ln_folded(self.conv4, self.norm2, True), ln_stats=ops.ln_of(y), act=UR_ACT_GATE)
+        return ops.conv(x, self.conv5.packed(scale=self.gamma), residual=y, gn=True, rows=True)    # y + conv5(x)*gamma
 
     def forward(self, inp):
         _fresh()
@@ -196,7 +191,7 @@ class AdaNAFV2(nn.Module):
         if key not in self.__dict__:
             gc = self.group_conv
             w, cg, g = gc.weight.detach().float(), gc.weight.shape[1], gc.groups          # [W, Cg, 3, 3]
-            if 32 <= cg < 128 and w.shape[0] % 128 == 0 and 128 % cg == 0 and os.environ.get("UR_GC_DENSE", "1") == "1":
+            if 32 <= cg < 128 and w.shape[0] % 128 == 0 and 128 % cg == 0:
                 wd = torch.zeros(w.shape[0], 128, 3, 3)
                 o = torch.arange(w.shape[0])
                 off = ((o // cg) * cg) % 128                                                 # first input channel of o's group inside its 128-block
@@ -217,7 +212,7 @@ class AdaNAFV2(nn.Module):
         pooled2 = ops.vec_mul_group(pooled, s_intra, s_intra.shape[1])         # mean(x*s) = s*mean(x)
         iga = ops.linear_f32(pooled2, wie, bie)                                # per-group scale
         x = ops.scale_channels(x, ops.vec_mul_group(s_intra, iga, g))
-        return self.nafblock.run(ops.conv(x, self.pwconv.packed(), residual=inp, rows=FUSE_LN2D))    # (row sums for the NAFBlock's norm1)
+        return self.nafblock.run(ops.conv(x, self.pwconv.packed(), residual=inp, rows=True))    # (row sums for the NAFBlock's norm1)
 
     def forward(self, inp):
         _fresh()

@@ -362,7 +362,6 @@ class DiffUIE(nn.Module):
         self.use_graph = use_graph
         self.trace_zt = None                   # parity instrumentation: a list collects zt after every DDIM step (eager runs only)
         self.check_fp16_overflow = True        # fp16 only: one isfinite reduction over the restored images per forward (+ a sync)
-        self.batch_controller = os.environ.get("UR_BATCH_CONTROLLER", "1") == "1"
         self._graphs = {}
         if self.control_type:
             ccfg = controller_cfg or stablesr_config
@@ -509,10 +508,9 @@ class DiffUIE(nn.Module):
             ac = schedule.alphas_cumprod_f64()
             zt, ztb = ops.add_noise(z0, n_t, lat, float(np.float32(ac[999] ** 0.5)), float(np.float32((1 - ac[999]) ** 0.5)))
             stem = self.controller.stem(z0b)
-            controls = self.controller.run_schedule(stem, len(self.timesteps)) if self.batch_controller else None
+            controls = self.controller.run_schedule(stem, len(self.timesteps))
             for i, t in enumerate(self.timesteps):
-                control = controls[i] if controls is not None else self.controller.run(stem, i)
-                eps = self.base_model.run(ztb, control, i)
+                eps = self.base_model.run(ztb, controls[i], i)
                 c_x, c_e = schedule.ddim_coefficients(int(t), self.num_inference_steps)
                 ops.ddim_step_(zt, ztb, eps, lat, c_x, c_e)
                 if self.trace_zt is not None and not torch.cuda.is_current_stream_capturing():
@@ -531,7 +529,7 @@ class DiffUIE(nn.Module):
         stem = self.controller.stem(ops.latent_tiles_gather(z0, origins, th, tw))
         ztt = ops.latent_tiles_gather(zt, origins, th, tw)
         nsteps = len(self.timesteps)
-        chunk = min(nsteps, TILE_CONTROLLER_MAX_IMAGES // stem.shape[0]) if self.batch_controller else 1
+        chunk = min(nsteps, TILE_CONTROLLER_MAX_IMAGES // stem.shape[0])
         controls = None
         for i, t in enumerate(self.timesteps):
             if chunk > 1 and i % chunk == 0:

@@ -19,7 +19,6 @@ from .. import chain, ops
 from ..ops import UR_ACT_GEGLU, UR_ACT_GELU, UR_ACT_NONE, UR_ACT_SILU
 
 DEV = "cuda"
-FUSE_LN = __import__("os").environ.get("UR_FUSE_LN", "1") == "1"   # LayerNorm folded into the consuming GEMMs
 # Token-stationary fused chains (csrc/tchain.hip) for the 320-channel transformer blocks: 3 launches per Transformer2DModel
 # (HEAD chain, self-attention, TAIL chain) instead of 12.  UR_CHAIN=0 selects the per-layer path (A/B, and the shapes the
 # chains do not cover take it anyway).
@@ -170,21 +169,20 @@ class ResnetBlock2D(nn.Module):
         return gn_silu_conv(self.norm2, h, pc2, residual=sc, gn=True)
 
 
-FUSE_GN = os.environ.get("UR_FUSE_GN", "1") == "1"       # GroupNorm apply + SiLU inside the consuming 3x3 conv's loader
-# Measured (tools/ab_micro.py, MI355X): the in-LDS pass costs the halo conv ~15 us per launch on top of its MFMA time (the two
+# GroupNorm apply + SiLU inside the consuming 3x3 conv's loader.  Measured (tools/ab_micro.py, MI355X): the in-LDS pass costs the halo conv ~15 us per launch on top of its MFMA time (the two
 # waves of a SIMD meet at a barrier every tap, so little of the VALU work hides), which beats the separate apply pass (HBM read
 # + write of the whole activation) only on the VAE's large maps: 128 ch @ 512x512 245 vs 253 us, 320 ch @ 64x64 85 vs 79.5 us.
 # The in-loader pass is repeated by every output-channel tile of the same pixels (and by neighbouring patches for the halo), so
 # it only pays where the conv has one or two channel tiles: Cout <= 256 (VAE levels, Controller), not the UNet's 320-1280.
-FUSE_GN_MIN_PIXELS = int(os.environ.get("UR_FUSE_GN_MIN_PIXELS", str(256 * 256)))
-FUSE_GN_MAX_COUT = int(os.environ.get("UR_FUSE_GN_MAX_COUT", "256"))
+FUSE_GN_MIN_PIXELS = 256 * 256
+FUSE_GN_MAX_COUT = 256
 
 
 def gn_silu_conv(norm: "GroupNorm", x, pc, x2=None, **kw):
     """conv(SiLU(GroupNorm(x | x2))): statistics -> per-(image, channel) affine, then either the conv applies it while it
     loads its input patch (no normalised tensor in HBM) or a separate apply pass runs first."""
     ab = norm.coeffs(x, x2=x2)
-    if FUSE_GN and x.shape[1] * x.shape[2] >= FUSE_GN_MIN_PIXELS and pc.cout_out <= FUSE_GN_MAX_COUT and \
+    if x.shape[1] * x.shape[2] >= FUSE_GN_MIN_PIXELS and pc.cout_out <= FUSE_GN_MAX_COUT and \
             ops.conv_plan(x, pc, x2=x2, gn=kw.get("gn", False), gn_ab=True, residual=kw.get("residual") is not None).prologue_ok:
         return ops.conv(x, pc, x2=x2, gn_ab=ab, gn_silu=True, **kw)
     return ops.conv(ops.gn_apply(x, ab, silu=True, x2=x2), pc, **kw)
@@ -255,9 +253,6 @@ def _fused_ln(mod, key, names, norm, pair=False, q_scale=1.0):
     return mod.__dict__[ck]
 
 
-NO_FLASH512 = os.environ.get("UR_NO_FLASH512", "0") == "1"     # A/B switch: chunked GEMM form for the d = 512 VAE attention
-
-
 def self_attention(mod, h, heads, residual, gn_kw={}, ln=None, rows=False):
     """h: [B,T,C] bf16.  One fused QKV GEMM (V written transposed), flash attention, output projection with the
     residual in its epilogue.  ln=(norm, row_stats): h is the RAW residual stream and LayerNorm is folded into the QKV
@@ -273,7 +268,7 @@ def self_attention(mod, h, heads, residual, gn_kw={}, ln=None, rows=False):
         qk = ops.linear(h, _fused_ln(mod, "qkv", ("to_q", "to_k", "to_v"), ln[0], q_scale=qs), ln_stats=ln[1], yt=vt, n_split=2 * c, t_rows=t)
     else:
         qk = ops.linear(h, _fused_qkv(mod, ("to_q", "to_k", "to_v"), q_scale=qs), yt=vt, n_split=2 * c, t_rows=t)   # [B,T,3C] (V cols unused)
-    if d in (64, 128) or (d == 512 and not NO_FLASH512):
+    if d in (64, 128, 512):
         o = ops.attention(qk, qk[:, :, c:], vt, heads, d, t, t, LN2 if d == 64 else scale, ldq=3 * c, ldk=3 * c,
                           bs_q=t * 3 * c, bs_k=t * 3 * c, bs_vt=c * ldvt, batch=b)
     else:
@@ -282,8 +277,10 @@ def self_attention(mod, h, heads, residual, gn_kw={}, ln=None, rows=False):
 
 
 def attention_gemm(q, k, vt, heads, d, t, s_bytes=256 << 20):
-    """Large-head-dim attention (VAE mid block: 1 head x 512) as S = QK^T (fp32) -> row softmax -> P V, in QUERY CHUNKS so
-    that the fp32 score block stays bounded (<= s_bytes = 256 MB, instead of B x T x T x 4 = 1 GiB per image at 1024x1024)."""
+    """Attention at head dims the flash kernels do not take (not 64 / 128 / 512): the VAE mid block's one head is
+    block_out_channels[-1] wide and an AttentionBlock's is channels / num_heads, so other channel configurations land here.
+    S = QK^T (fp32) -> row softmax -> P V, in QUERY CHUNKS so that the fp32 score block stays bounded (<= s_bytes = 256 MB,
+    instead of B x T x T x 4 = 1 GiB per image at 1024x1024)."""
     b = q.shape[0]
     rows = max(256, min(t, (s_bytes // (4 * b * t)) // 256 * 256))
     out = torch.empty((b, t, heads * d), dtype=q.dtype, device=q.device)
@@ -431,7 +428,7 @@ class Transformer2DModel(nn.Module):
             o1 = ops.attention(q, k, vt, heads, d, t, t, LN2, ldq=c, ldk=c, bs_q=t * c, bs_k=t * c, bs_vt=c * t, batch=n)   # (q pre-scaled)
             y = chain.transformer_tail_fused(o1, h0, x, tail, n, 4 * c, heads, ctx.shape[1], b.norm1.eps, 1.0 / math.sqrt(d))
             return ops.carry(y, y.view(n, hh, ww, c))
-        h = ops.linear(self.norm.run(x).view(n, hh * ww, c), self.proj_in.packed(), rows=FUSE_LN)
+        h = ops.linear(self.norm.run(x).view(n, hh * ww, c), self.proj_in.packed(), rows=True)
         h = self.transformer_blocks[0].run(h, ctx)
         o = ops.linear(h, self.proj_out.packed(), residual=x.view(n, hh * ww, c), gn=True, gn_hw=(n, hh * ww))
         return ops.carry(o, o.view(n, hh, ww, c))

@@ -3,7 +3,6 @@
 Activations are NHWC bf16 tensors ([N,H,W,C] or [rows, C]); C is always a multiple of 8 (thin tensors such as
 images / latents are zero-padded to 8 channels).  PyTorch only owns memory and the stream here.
 """
-import os
 from dataclasses import dataclass
 from typing import Optional
 
@@ -88,26 +87,6 @@ def round_up(v, m):
 
 
 # ------------------------------------------------------------------------------------------------ weights
-# A/B (UR_WEIGHT_ARENA=<GiB per block>): packed weights live in a few multi-GiB allocations instead of one allocation each - one UNet
-# step walks 1.7 GB of weights, and how many address translations that costs depends on how the driver can map them.
-_ARENA_GB = float(os.environ.get("UR_WEIGHT_ARENA", "0") or 0)
-_arenas = {}
-
-
-def _arena_place(t: torch.Tensor) -> torch.Tensor:
-    if _ARENA_GB <= 0 or not t.is_cuda:
-        return t
-    nbytes = round_up(t.numel() * t.element_size(), 4096)
-    blocks = _arenas.setdefault(t.device, [])
-    if not blocks or blocks[-1][1] + nbytes > blocks[-1][0].numel():
-        blocks.append([torch.empty(max(int(_ARENA_GB * (1 << 30)), nbytes), dtype=torch.uint8, device=t.device), 0])
-    buf, off = blocks[-1]
-    blocks[-1][1] = off + nbytes
-    v = buf[off:off + t.numel() * t.element_size()].view(t.dtype).view(t.shape)
-    v.copy_(t)
-    return v
-
-
 @dataclass
 class PackedConv:
     """16-bit [Cout][KH*KW*Cin] weight (K runs tap-major, channel-minor) + fp32 bias, padded for the kernel."""
@@ -129,15 +108,14 @@ class PackedConv:
         if self.w_frag is None:
             nt, nc = self.cout // 128, self.cin // 64
             w = self.w.view(nt, 4, 32, nc, 9, 4, 2, 8)                    # [nt][row block][row][chunk][tap][k-step][half][8]
-            self.w_frag = _arena_place(w.permute(0, 3, 4, 5, 1, 6, 2, 7).contiguous())  # lane = half * 32 + row
+            self.w_frag = w.permute(0, 3, 4, 5, 1, 6, 2, 7).contiguous()  # lane = half * 32 + row
         return self.w_frag
 
 
 def wants_frag(pc: "PackedConv", n, h, w_, c1, c2, stride, upsample, groups) -> bool:
     """The launches csrc/igemm.hip sends to the weight-streaming kernel (it also checks): 3x3 on 8 x 8 maps of <= 16 images."""
     return (pc.k == 3 and pc.kcm and groups == 1 and stride == 1 and not upsample and h == 8 and w_ == 8 and n <= 16 and not pc.pair
-            and pc.cout % 128 == 0 and (c1 + c2) % 256 == 0 and (c1 + c2) >= 512 and (c2 == 0 or c1 % 64 == 0)
-            and os.environ.get("UR_IGEMM_NOWSTREAM") is None)
+            and pc.cout % 128 == 0 and (c1 + c2) % 256 == 0 and (c1 + c2) >= 512 and (c2 == 0 or c1 % 64 == 0))
 
 
 def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor], dev, *, pair=False, groups=1, cin_pad=None, c1=None, group_halo=False) -> PackedConv:
@@ -175,10 +153,10 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor], dev, *, pair=F
     # chunk-major K for 3x3 kernels: [Cout][kh*kw][Cin/64][64] -> [Cout][Cin/64][kh*kw][64]; c1 = channels of the first
     # source when the input is a virtual concat (chunks must not straddle it)
     # (grouped convs too when every group is chunk-sized: each group then runs the halo kernel on its channel slice)
-    kcm = kh == 3 and (groups == 1 or (group_halo and cout_p == cout)) and cin_p % 64 == 0 and (c1 is None or c1 % 64 == 0) and os.environ.get("UR_KCM", "1") == "1"
+    kcm = kh == 3 and (groups == 1 or (group_halo and cout_p == cout)) and cin_p % 64 == 0 and (c1 is None or c1 % 64 == 0)
     if kcm:
         wp = wp.reshape(cout_p, kh * kw, cin_p // 64, 64).permute(0, 2, 1, 3)
-    return PackedConv(_arena_place(wp.reshape(cout_p, kh * kw * cin_p).to(_act).contiguous()),
+    return PackedConv(wp.reshape(cout_p, kh * kw * cin_p).to(_act).contiguous(),
                       None if b is None else b.contiguous(), cin_p, cout_p, cout_out, kh, groups, pair, kcm=kcm)
 
 
