@@ -206,35 +206,37 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wstream8_kernel(const ConvK p)
   }
 }
 
+// eligibility is decided by igemm.hip (dispatch_conv): 3x3 / stride 1 / pad 1 on 8 x 8 maps, chunk-major + fragment-major weights,
+// Cout % 128 == 0, (C1 + C2) % 256 == 0, >= 8 chunks, a 16-bit staged output and a workspace for nchunk / 4 partial planes.
+struct WStream8 {
+  static int plan(ConvK& k, size_t ws_bytes) {
+    const int nchunk = k.nk / 9;
+    k.tiles_m = (k.N + 1) / 2;
+    k.tiles_n = k.Cout / 128;
+    // one or two chunks per wave: two when that brings the launch down to one workgroup per CU (K = 9 x 2560 at B = 8: 400 -> 200)
+    const long long wg1 = (long long)k.tiles_m * k.tiles_n * (nchunk / 4);
+    const int cpw = (wg1 > 256 && nchunk % 8 == 0 && nchunk >= 16) ? 2 : 1;
+    plan_splitk(k, ws_bytes, nchunk / (4 * cpw), 36 * cpw);     // a split = 4 waves x cpw chunks: nk_per_split = cpw * 36
+    set_gn_plan(k, false, 0);
+    return 0;
+  }
+  static int launch(ConvK& k, hipStream_t s) {
+    static ur::DeviceOnce attr_once;      // the attribute is per device
+    if (auto once_guard = attr_once.first())
+    {
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wstream8_kernel<UR_TU_F16 != 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS);
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wstream8_kernel<UR_TU_F16 != 0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS);
+    }
+    const int groups = (k.tiles_n * k.splitk + 7) / 8 * 8;
+    if (k.nk_per_split == 2 * 36) UR_F16_SWITCH(k, hipLaunchKernelGGL((conv3x3_wstream8_kernel<F16, 2>), dim3(groups * k.tiles_m), dim3(256), WS_LDS, s, k));
+    else UR_F16_SWITCH(k, hipLaunchKernelGGL((conv3x3_wstream8_kernel<F16, 1>), dim3(groups * k.tiles_m), dim3(256), WS_LDS, s, k));
+    launch_splitk_reduce(k, s);
+    return ur::check_launch("ur_conv2d_nhwc");
+  }
+};
+
 }  // namespace
 
 namespace urk {
-// eligibility is decided by igemm.hip (dispatch_conv): 3x3 / stride 1 / pad 1 on 8 x 8 maps, chunk-major + fragment-major weights,
-// Cout % 128 == 0, (C1 + C2) % 256 == 0, >= 8 chunks, a 16-bit staged output and a workspace for nchunk / 4 partial planes.
-int URK(wstream_8x8)(void* kp, hipStream_t s) {
-  ConvK& k = *static_cast<ConvK*>(kp);
-  const int nchunk = k.nk / 9;
-  k.tiles_m = (k.N + 1) / 2;
-  k.tiles_n = k.Cout / 128;
-  // one or two chunks per wave: two when that brings the launch down to one workgroup per CU (K = 9 x 2560 at B = 8: 400 -> 200)
-  const long long wg1 = (long long)k.tiles_m * k.tiles_n * (nchunk / 4);
-  const int cpw = (wg1 > 256 && nchunk % 8 == 0 && nchunk >= 16) ? 2 : 1;
-  k.splitk = nchunk / (4 * cpw);
-  k.nk_per_split = cpw * 36;                              // (the reduce pass does not read it)
-  k.patch_tw = 0;
-  k.prologue_ok = 0;
-  set_gn_plan(k, false, 0);
-  if (k.dry) { k.plan_tn = 1; return UR_OK; }
-  static ur::DeviceOnce attr_once;      // the attribute is per device
-  if (auto once_guard = attr_once.first())
-  {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wstream8_kernel<UR_TU_F16 != 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wstream8_kernel<UR_TU_F16 != 0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS);
-  }
-  const int groups = (k.tiles_n * k.splitk + 7) / 8 * 8;
-  if (cpw == 2) UR_F16_SWITCH(k, hipLaunchKernelGGL((conv3x3_wstream8_kernel<F16, 2>), dim3(groups * k.tiles_m), dim3(256), WS_LDS, s, k));
-  else UR_F16_SWITCH(k, hipLaunchKernelGGL((conv3x3_wstream8_kernel<F16, 1>), dim3(groups * k.tiles_m), dim3(256), WS_LDS, s, k));
-  launch_splitk_reduce(k, s);
-  return ur::check_launch("ur_conv2d_nhwc");
-}
+UR_LAUNCHER(wstream_8x8, WStream8)
 }  // namespace urk

@@ -14,82 +14,19 @@
 //   * block id -> tile map is XCD-aware (blocks that share an activation tile land on one XCD's L2).
 #include "igemm_impl.h"
 
-namespace urk {   // launcher instantiations live in igemm_v1a/v1b/v2/halo/g1.hip, one object per 16-bit type (parallel compilation)
-int v1_128x128_bf16(void* kp, hipStream_t s);
-int v1_128x128_f16(void* kp, hipStream_t s);
-static inline int v1_128x128(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? v1_128x128_f16(kp, s) : v1_128x128_bf16(kp, s); }
-int v1_128x160_bf16(void* kp, hipStream_t s);
-int v1_128x160_f16(void* kp, hipStream_t s);
-static inline int v1_128x160(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? v1_128x160_f16(kp, s) : v1_128x160_bf16(kp, s); }
-int v1_128x64_bf16(void* kp, hipStream_t s);
-int v1_128x64_f16(void* kp, hipStream_t s);
-static inline int v1_128x64(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? v1_128x64_f16(kp, s) : v1_128x64_bf16(kp, s); }
-int v1_256x32_bf16(void* kp, hipStream_t s);
-int v1_256x32_f16(void* kp, hipStream_t s);
-static inline int v1_256x32(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? v1_256x32_f16(kp, s) : v1_256x32_bf16(kp, s); }
-int v1_64x64_bf16(void* kp, hipStream_t s);
-int v1_64x64_f16(void* kp, hipStream_t s);
-static inline int v1_64x64(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? v1_64x64_f16(kp, s) : v1_64x64_bf16(kp, s); }
-int v2_256x32_bf16(void* kp, hipStream_t s);
-int v2_256x32_f16(void* kp, hipStream_t s);
-static inline int v2_256x32(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? v2_256x32_f16(kp, s) : v2_256x32_bf16(kp, s); }
-int v2_128x64_bf16(void* kp, hipStream_t s);
-int v2_128x64_f16(void* kp, hipStream_t s);
-static inline int v2_128x64(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? v2_128x64_f16(kp, s) : v2_128x64_bf16(kp, s); }
-int v2_256x160_bf16(void* kp, hipStream_t s);
-int v2_256x160_f16(void* kp, hipStream_t s);
-static inline int v2_256x160(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? v2_256x160_f16(kp, s) : v2_256x160_bf16(kp, s); }
-int v2_256x128_bf16(void* kp, hipStream_t s);
-int v2_256x128_f16(void* kp, hipStream_t s);
-static inline int v2_256x128(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? v2_256x128_f16(kp, s) : v2_256x128_bf16(kp, s); }
-int gemm_256x256_bf16(void* kp, hipStream_t s);
-int gemm_256x256_f16(void* kp, hipStream_t s);
-static inline int gemm_256x256(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? gemm_256x256_f16(kp, s) : gemm_256x256_bf16(kp, s); }
-int gemm_256x320_pair_bf16(void* kp, hipStream_t s);
-int gemm_256x320_pair_f16(void* kp, hipStream_t s);
-static inline int gemm_256x320_pair(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? gemm_256x320_pair_f16(kp, s) : gemm_256x320_pair_bf16(kp, s); }
-int g1_128x128_bf16(void* kp, hipStream_t s);
-int g1_128x128_f16(void* kp, hipStream_t s);
-static inline int g1_128x128(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? g1_128x128_f16(kp, s) : g1_128x128_bf16(kp, s); }
-int g1_128x160_bf16(void* kp, hipStream_t s);
-int g1_128x160_f16(void* kp, hipStream_t s);
-static inline int g1_128x160(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? g1_128x160_f16(kp, s) : g1_128x160_bf16(kp, s); }
-int g1_128x64_bf16(void* kp, hipStream_t s);
-int g1_128x64_f16(void* kp, hipStream_t s);
-static inline int g1_128x64(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? g1_128x64_f16(kp, s) : g1_128x64_bf16(kp, s); }
-int g1_64x64_bf16(void* kp, hipStream_t s);
-int g1_64x64_f16(void* kp, hipStream_t s);
-static inline int g1_64x64(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? g1_64x64_f16(kp, s) : g1_64x64_bf16(kp, s); }
-int g1_64x64_deep_bf16(void* kp, hipStream_t s);
-int g1_64x64_deep_f16(void* kp, hipStream_t s);
-static inline int g1_64x64_deep(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? g1_64x64_deep_f16(kp, s) : g1_64x64_deep_bf16(kp, s); }
-int g1_128x64_deep_bf16(void* kp, hipStream_t s);
-int g1_128x64_deep_f16(void* kp, hipStream_t s);
-static inline int g1_128x64_deep(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? g1_128x64_deep_f16(kp, s) : g1_128x64_deep_bf16(kp, s); }
-int halo_8x32_160_bf16(void* kp, hipStream_t s);
-int halo_8x32_160_f16(void* kp, hipStream_t s);
-static inline int halo_8x32_160(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? halo_8x32_160_f16(kp, s) : halo_8x32_160_bf16(kp, s); }
-int halo_8x32_128_bf16(void* kp, hipStream_t s);
-int halo_8x32_128_f16(void* kp, hipStream_t s);
-static inline int halo_8x32_128(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? halo_8x32_128_f16(kp, s) : halo_8x32_128_bf16(kp, s); }
-int halo_thin_32_bf16(void* kp, hipStream_t s);
-int halo_thin_32_f16(void* kp, hipStream_t s);
-static inline int halo_thin_32(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? halo_thin_32_f16(kp, s) : halo_thin_32_bf16(kp, s); }
-int himg_16x16_bf16(void* kp, hipStream_t s);
-int himg_16x16_f16(void* kp, hipStream_t s);
-static inline int himg_16x16(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? himg_16x16_f16(kp, s) : himg_16x16_bf16(kp, s); }
-int himg_8x8x4_bf16(void* kp, hipStream_t s);
-int himg_8x8x4_f16(void* kp, hipStream_t s);
-static inline int himg_8x8x4(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? himg_8x8x4_f16(kp, s) : himg_8x8x4_bf16(kp, s); }
-int wstream_8x8_bf16(void* kp, hipStream_t s);
-int wstream_8x8_f16(void* kp, hipStream_t s);
-static inline int wstream_8x8(void* kp, hipStream_t s) { return static_cast<ConvK*>(kp)->f16 ? wstream_8x8_f16(kp, s) : wstream_8x8_bf16(kp, s); }
+namespace urk {   // the launchers of the instantiation units, one object per 16-bit type (parallel compilation): ConvK::f16 picks
+#define UR_DECLARE(name)                                                                                             \
+  ConvLaunch name##_bf16(void* k, size_t ws_bytes);                                                                 \
+  ConvLaunch name##_f16(void* k, size_t ws_bytes);                                                                  \
+  static ConvLaunch name(ConvK& k, size_t ws_bytes) { return (k.f16 ? name##_f16 : name##_bf16)(&k, ws_bytes); }
+UR_CONV_LAUNCHERS(UR_DECLARE)
+#undef UR_DECLARE
 }  // namespace urk
 
 namespace {
 
-int dispatch_conv(ConvK& k, hipStream_t s, bool pair) {
-  k.patch_tw = 0;
+// The launcher for k, planned (host only: no HIP call).
+ConvLaunch dispatch_conv(ConvK& k, bool pair, size_t ws_bytes) {
   if (k.KH == 3 && k.stride == 1 && k.pad_t == 1 && k.pad_l == 1 && k.kcm && k.staged_ok_ && !pair && k.nbatch == 1 &&
       k.OW % 32 == 0 && k.OH % 8 == 0 && k.OH == (k.ups ? 2 * k.H : k.H) && k.OW == (k.ups ? 2 * k.W : k.W) && !k.yt) {
     // tile width: 128 or 160 output channels, whichever divides Cout; when both do, the one whose tile count fills whole
@@ -101,26 +38,26 @@ int dispatch_conv(ConvK& k, hipStream_t s, bool pair) {
     const bool use160 = ok160 && (!ok128 || eff(tm8 * (k.Cout / 160)) >= eff(tm8 * (k.Cout / 128)));
     const long long tiles8 = tm8 * (use160 ? k.Cout / 160 : k.Cout / 128);
     if ((ok128 || ok160) && tiles8 >= 64) {
-      if (use160) return urk::halo_8x32_160(&k, s);
-      return urk::halo_8x32_128(&k, s);
+      if (use160) return urk::halo_8x32_160(k, ws_bytes);
+      return urk::halo_8x32_128(k, ws_bytes);
     }
   }
   // conv_out layers: <= 32 output channels (fp32 or 16-bit) of a 3x3 / stride 1 / pad 1 conv with chunk-major weights
   if (k.KH == 3 && k.stride == 1 && k.pad_t == 1 && k.pad_l == 1 && k.kcm && !pair && k.nbatch == 1 && !k.ups && k.C2 == 0 &&
       k.Cout <= 32 && k.OW % 32 == 0 && k.OH % 8 == 0 && k.OH == k.H && k.OW == k.W && !k.yt && !k.gn_part && !k.gn_ab && !k.row_stats && !k.ln_stats &&
       !k.bias_img && (long long)k.N * (k.OH / 8) * (k.OW / 32) >= 128)
-    return urk::halo_thin_32(&k, s);
+    return urk::halo_thin_32(k, ws_bytes);
   // (round 6: the 8 x 8 -> 16 x 16 upsampling conv runs on the whole-image tile too - the patch pieces read their nearest source pixel)
   const bool himg_ups = k.ups && k.OH == 16 && k.OW == 16 && k.H == 8 && k.W == 8;
   if (k.KH == 3 && k.stride == 1 && k.pad_t == 1 && k.pad_l == 1 && k.kcm && k.staged_ok_ && !pair && k.nbatch == 1 &&
       ((!k.ups && k.OH == k.H && k.OW == k.W) || himg_ups) && !k.yt && k.Cout % 128 == 0 && k.nk >= 36) {
     // 8 x 8 maps of a few images: a weight stream (csrc/conv_wstream.hip) when the caller packed the fragment-major copy
     if (k.wf && k.OH == 8 && k.OW == 8 && k.N <= 16 && k.Cin % 256 == 0 && k.nk >= 72 && k.y && k.ws && !k.gn_ab && !k.row_stats && !k.ln_stats &&
-        (long long)(k.nk / 36) * k.M * k.Cout * 4 <= (long long)k.ws_bytes_)
-      return urk::wstream_8x8(&k, s);
-    if (k.OH == 16 && k.OW == 16) return urk::himg_16x16(&k, s);
+        (long long)(k.nk / 36) * k.M * k.Cout * 4 <= (long long)ws_bytes)
+      return urk::wstream_8x8(k, ws_bytes);
+    if (k.OH == 16 && k.OW == 16) return urk::himg_16x16(k, ws_bytes);
     if (k.OH == 8 && k.OW == 8 && k.N % 4 == 0) {
-      return urk::himg_8x8x4(&k, s);
+      return urk::himg_8x8x4(k, ws_bytes);
     }
   }
   if (k.KH == 1 && k.stride == 1 && !k.ups && k.C2 == 0 && k.staged_ok_ && k.Cout % 256 == 0 && !k.yt && (k.act == UR_ACT_GEGLU || k.act == UR_ACT_GATE) &&
@@ -130,8 +67,8 @@ int dispatch_conv(ConvK& k, hipStream_t s, bool pair) {
     auto fill = [](long long t) { return (double)t / (double)(((t + 255) / 256) * 256); };
     const long long tm = (k.M + 255) / 256;
     if (k.Cout % 320 == 0 && k.nbatch == 1 && !k.bias_img && fill(tm * (k.Cout / 320)) > fill(tm * (k.Cout / 256)))
-      return urk::gemm_256x320_pair(&k, s);
-    return urk::gemm_256x256(&k, s);
+      return urk::gemm_256x320_pair(k, ws_bytes);
+    return urk::gemm_256x256(k, ws_bytes);
   }
   // short-K GEMMs (<= 10 K tiles: per-workgroup prologue/epilogue latency dominates): 128-row tiles, 2 workgroups per CU
   const bool use_v1 = k.KH == 1 && k.nk <= 10;
@@ -147,25 +84,25 @@ int dispatch_conv(ConvK& k, hipStream_t s, bool pair) {
     const long long blocks64 = (long long)((k.M + 63) / 64) * ((k.Cout + 63) / 64) * k.nbatch;
     // (grids of <= 256 workgroups - the 8x8 level - are latency-bound per K tile: four ring stages, and K up to 2560 stays unsplit:
     //  512 x 1280 x 1280 12.9 -> 9.1 us, x 2560 20.8 (split + reduce) -> 14.3 us; profiles/r5_wreg_ab.txt)
-    if (blocks128 < 200 && g1 && blocks64 >= 128 && blocks64 <= 256 && k.nk >= 8 && k.nk <= 48) return urk::g1_64x64_deep(&k, s);
+    if (blocks128 < 200 && g1 && blocks64 >= 128 && blocks64 <= 256 && k.nk >= 8 && k.nk <= 48) return urk::g1_64x64_deep(k, ws_bytes);
     // long-K GEMMs of the 16x16 level: 128 x 64 tiles, three stages, unsplit (2048 x 1280 x 2560 25.9 -> 23.3 us, x 5120 49.1 -> 43.7 us)
     if (g1 && blocks128 < 200 && k.nk > 24 && k.nk <= 96 && (long long)((k.M + 127) / 128) * ((k.Cout + 63) / 64) * k.nbatch >= 256)
-      return urk::g1_128x64_deep(&k, s);
-    if (blocks128 < 200 && g1 && ((blocks64 >= 128 && k.nk <= 24) || (blocks64 >= 256 && k.nk <= 48))) return urk::g1_64x64(&k, s);
-    if (blocks128 < 200 && k.nk <= 24) return g1 && nosplit(64, 64) ? urk::g1_64x64(&k, s) : urk::v1_64x64(&k, s);
+      return urk::g1_128x64_deep(k, ws_bytes);
+    if (blocks128 < 200 && g1 && ((blocks64 >= 128 && k.nk <= 24) || (blocks64 >= 256 && k.nk <= 48))) return urk::g1_64x64(k, ws_bytes);
+    if (blocks128 < 200 && k.nk <= 24) return g1 && nosplit(64, 64) ? urk::g1_64x64(k, ws_bytes) : urk::v1_64x64(k, ws_bytes);
     // 1 < tiles/CU < 2 at 128 x 128: halve the N tile so every CU gets the same work
-    if (use_v1 && blocks128 > 256 && blocks128 < 400 && k.Cout % 128 == 0) return g1 && nosplit(128, 64) ? urk::g1_128x64(&k, s) : urk::v1_128x64(&k, s);
+    if (use_v1 && blocks128 > 256 && blocks128 < 400 && k.Cout % 128 == 0) return g1 && nosplit(128, 64) ? urk::g1_128x64(k, ws_bytes) : urk::v1_128x64(k, ws_bytes);
   }
   if (use_v1) {
-    if (pair) return urk::v1_128x128(&k, s);  // a|g 32-row blocks must sit in one wave tile
-    if (k.Cout <= 32) return urk::v1_256x32(&k, s);
-    if (k.Cout <= 64) return urk::v1_128x64(&k, s);
-    if (k.Cout % 160 == 0 && k.Cout % 128 != 0) return g1 && nosplit(128, 160) ? urk::g1_128x160(&k, s) : urk::v1_128x160(&k, s);
-    return g1 && nosplit(128, 128) ? urk::g1_128x128(&k, s) : urk::v1_128x128(&k, s);
+    if (pair) return urk::v1_128x128(k, ws_bytes);  // a|g 32-row blocks must sit in one wave tile
+    if (k.Cout <= 32) return urk::v1_256x32(k, ws_bytes);
+    if (k.Cout <= 64) return urk::v1_128x64(k, ws_bytes);
+    if (k.Cout % 160 == 0 && k.Cout % 128 != 0) return g1 && nosplit(128, 160) ? urk::g1_128x160(k, ws_bytes) : urk::v1_128x160(k, ws_bytes);
+    return g1 && nosplit(128, 128) ? urk::g1_128x128(k, ws_bytes) : urk::v1_128x128(k, ws_bytes);
   }
   // v2 (LDS-DMA ring).  One workgroup per CU: pick the 256-row / 8-wave tiles when they still fill the chip.
-  if (k.Cout <= 32) return urk::v2_256x32(&k, s);
-  if (k.Cout <= 64 && !pair) return urk::v2_128x64(&k, s);
+  if (k.Cout <= 32) return urk::v2_256x32(k, ws_bytes);
+  if (k.Cout <= 64 && !pair) return urk::v2_128x64(k, ws_bytes);
   const bool n160 = !pair && k.Cout % 160 == 0 && k.Cout % 128 != 0;
   const long long big_tiles = (long long)((k.M + 255) / 256) * ((k.Cout + (n160 ? 159 : 127)) / (n160 ? 160 : 128)) * k.nbatch;
   if (g1 && !pair && big_tiles < 256) {
@@ -174,23 +111,24 @@ int dispatch_conv(ConvK& k, hipStream_t s, bool pair) {
     const long long t160 = k.Cout % 160 == 0 ? (long long)((k.M + 127) / 128) * (k.Cout / 160) : 0;
     const long long t128 = (long long)((k.M + 127) / 128) * ((k.Cout + 127) / 128);
     auto fill = [](long long t) { return t <= 0 ? 0.0 : (double)t / (double)(((t + 255) / 256) * 256); };
-    if (t160 >= 200 && fill(t160) >= fill(t128)) return urk::g1_128x160(&k, s);
-    if (t128 >= 200) return urk::g1_128x128(&k, s);
+    if (t160 >= 200 && fill(t160) >= fill(t128)) return urk::g1_128x160(k, ws_bytes);
+    if (t128 >= 200) return urk::g1_128x128(k, ws_bytes);
   }
   if (big_tiles >= 160) {
     // pure GEMMs onto 320/960-wide outputs: two 128 x 160 workgroups per CU beat one 256 x 160 (32768 x 320 x 1280: 41 vs 44.5 us)
-    if (n160 && g1) return urk::g1_128x160(&k, s);
-    if (n160) return urk::v2_256x160(&k, s);
-    return urk::v2_256x128(&k, s);
+    if (n160 && g1) return urk::g1_128x160(k, ws_bytes);
+    if (n160) return urk::v2_256x160(k, ws_bytes);
+    return urk::v2_256x128(k, ws_bytes);
   }
   // small problems: the register-staged kernel (two workgroups per CU), split-K when few tiles meet a long K
-  if (k.Cout % 160 == 0 && k.Cout % 128 != 0 && !pair) return urk::v1_128x160(&k, s);
-  return urk::v1_128x128(&k, s);
+  if (k.Cout % 160 == 0 && k.Cout % 128 != 0 && !pair) return urk::v1_128x160(k, ws_bytes);
+  return urk::v1_128x128(k, ws_bytes);
 }
 
 }  // namespace
 
-static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, int dry, ur_conv_plan* plan) {
+// plan != nullptr: only plan the launch (ur_conv2d_plan), nothing runs
+static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, ur_conv_plan* plan) {
   UR_REQUIRE(d && d->x && d->w, "null x/w");
   UR_REQUIRE(d->KH == d->KW && (d->KH == 1 || d->KH == 3), "only 1x1 and 3x3 kernels");
   UR_REQUIRE(d->C1 > 0 && d->C1 % 8 == 0 && d->C2 % 8 == 0 && d->ldx % 8 == 0, "Cin/ldx must be multiples of 8");
@@ -209,7 +147,7 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, int dry, ur_conv
   ConvK k;
   k.x = (const uint16_t*)d->x; k.x2 = (const uint16_t*)d->x2; k.w = (const uint16_t*)d->w; k.bias = d->bias;
   k.res = (const uint16_t*)d->residual; k.y = d->y; k.yt = (uint16_t*)d->yt;
-  k.ws = d->workspace; k.ws_bytes_ = d->workspace_bytes;
+  k.ws = d->workspace;
   k.N = d->N; k.H = d->H; k.W = d->W; k.C1 = d->C1; k.ldx = d->ldx; k.C2 = d->C2; k.ldx2 = d->ldx2;
   k.Cin = d->C1 + d->C2; k.Cout = d->Cout; k.ldw = d->ldw; k.ldy = d->ldy; k.ldr = d->ldr;
   k.KH = d->KH; k.KW = d->KW; k.stride = d->stride; k.pad_t = d->pad_t; k.pad_l = d->pad_l;
@@ -222,10 +160,10 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, int dry, ur_conv
   UR_REQUIRE((long long)d->N * d->H * d->W * (long long)std::max(d->ldx, d->ldx2) < (1ll << 31) &&
                  (long long)d->Cout * d->ldw < (1ll << 31), "tensor too large for 32-bit element offsets");
 
-  k.kcm = d->k_chunk_major; k.wf = (const uint16_t*)d->w_frag; k.wmajor = 0; k.xgm = 0; k.xbn = 0;
+  k.kcm = d->k_chunk_major; k.wf = (const uint16_t*)d->w_frag; k.wmajor = 0; k.xgm = 0; k.xbn = 0; k.patch_tw = 0;
   UR_REQUIRE(!k.kcm || (k.Cin % 64 == 0 && d->C1 % 64 == 0), "k_chunk_major needs C1 and C1+C2 to be multiples of 64");
-  k.gn_part = d->gn_part; k.gn_ab = d->gn_ab; k.gn_silu = d->gn_silu; k.f16 = d->dtype == UR_DT_F16; k.gn_fused = 0; k.gn_parts = 0; k.prologue_ok = 0;
-  k.dry = dry; k.plan_tn = 0; k.ln_parts = d->ln_parts;
+  k.gn_part = d->gn_part; k.gn_ab = d->gn_ab; k.gn_silu = d->gn_silu; k.f16 = d->dtype == UR_DT_F16; k.gn_fused = 0; k.gn_parts = 0;
+  k.ln_parts = d->ln_parts;
   k.row_stats = d->row_stats; k.ln_stats = d->ln_stats; k.ln_colsum = d->ln_colsum; k.ln_eps = d->ln_eps; k.ln_dim = d->ln_dim;
   UR_REQUIRE(!d->ln_stats || (d->ln_colsum && d->ln_dim > 0), "ln_stats needs ln_colsum / ln_dim");
   // feature combinations the specialised epilogues cover (each is one compiled instance; see epi_frag_pass)
@@ -246,28 +184,17 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, int dry, ur_conv
              k.nbatch, d->act);
     fam = interned.emplace(buf, 0).first->first.c_str();
   }
-  if (dry) {
-    const int rc0 = dispatch_conv(k, s, pair);
-    if (plan) {
-      plan->row_stat_parts = d->row_stats ? k.plan_tn : 0;
-      plan->gn_parts = k.gn_parts; plan->gn_fused = k.gn_fused; plan->prologue_ok = k.prologue_ok;
-    }
-    return rc0;
+  const ConvLaunch launch = dispatch_conv(k, pair, d->workspace_bytes);
+  if (plan) {      // row-stat planes: one per N tile, or the single one of a split-K reduce pass
+    plan->row_stat_parts = d->row_stats ? (k.splitk > 1 ? 1 : k.tiles_n) : 0;
+    plan->gn_parts = k.gn_parts; plan->gn_fused = k.gn_fused; plan->prologue_ok = launch.prologue_ok;
+    return UR_OK;
   }
-  if (!d->y && d->gn_part) {            // statistics-only launch: only where the epilogue itself produces the partials
-    k.dry = 1;
-    const int rc0 = dispatch_conv(k, s, pair);
-    if (rc0 != UR_OK) return rc0;
-    if (!k.gn_fused || k.splitk > 1) return ur::fail(UR_E_UNSUPPORTED, "ur_conv2d_nhwc: y == NULL needs a launch whose epilogue writes gn_part (see ur_conv2d_plan)");
-    k.dry = 0;
-  }
-  if (d->gn_ab) {
-    k.dry = 1;
-    const int rc0 = dispatch_conv(k, s, pair);
-    if (rc0 != UR_OK) return rc0;
-    if (!k.prologue_ok) return ur::fail(UR_E_UNSUPPORTED, "ur_conv2d_nhwc: gn_ab is not supported by this launch (see ur_conv2d_plan.prologue_ok)");
-    k.dry = 0;
-  }
+  // statistics-only launch: only where the epilogue itself produces the partials
+  if (!d->y && d->gn_part && (!k.gn_fused || k.splitk > 1))
+    return ur::fail(UR_E_UNSUPPORTED, "ur_conv2d_nhwc: y == NULL needs a launch whose epilogue writes gn_part (see ur_conv2d_plan)");
+  if (d->gn_ab && !launch.prologue_ok)
+    return ur::fail(UR_E_UNSUPPORTED, "ur_conv2d_nhwc: gn_ab is not supported by this launch (see ur_conv2d_plan.prologue_ok)");
   ur::ProfScope prof(fam, flops, bytes, s);
   UR_REQUIRE(!(d->row_stats || d->ln_stats) || (k.staged_ok_ && k.nbatch == 1 && !d->yt == !d->yt), "row_stats / ln fusion need a bf16 staged output");
   // Grouped 3x3 convolutions whose groups are halo-kernel sized (chunk-major weights, >= 64 channels in, a multiple of 128 out):
@@ -282,12 +209,12 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, int dry, ur_conv
       kb.res = k.res ? k.res + b * k.bs_r : nullptr;
       kb.y = reinterpret_cast<uint16_t*>(k.y) + b * k.bs_y;
       kb.bs_x = kb.bs_w = kb.bs_bias = kb.bs_y = kb.bs_r = 0;
-      const int rcb = dispatch_conv(kb, s, pair);
+      const int rcb = dispatch_conv(kb, pair, d->workspace_bytes).launch(&kb, s);
       if (rcb != UR_OK) return rcb;
     }
     return UR_OK;
   }
-  const int rc = dispatch_conv(k, s, pair);
+  const int rc = launch.launch(&k, s);
   if (rc != UR_OK) return rc;
   if (k.gn_part && !k.gn_fused) {   // this launch could not fuse the statistics: one extra pass over the output
     const int ctot = (pair ? k.Cout / 2 : k.Cout) * k.nbatch;
@@ -297,7 +224,7 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, int dry, ur_conv
   return UR_OK;
 }
 
-extern "C" int ur_conv2d_nhwc(const ur_conv_desc* d, ur_stream_t stream) { return conv_impl(d, stream, 0, nullptr); }
+extern "C" int ur_conv2d_nhwc(const ur_conv_desc* d, ur_stream_t stream) { return conv_impl(d, stream, nullptr); }
 
 // Host-only plan of the launch of `d` (no kernel runs): partial row-sum planes ([parts][M][2] fp32, one per N tile - the
 // partial layout keeps the producer free of atomics), GroupNorm partials per image and who writes them, prologue support.
@@ -305,7 +232,7 @@ extern "C" int ur_conv2d_plan(const ur_conv_desc* d, ur_conv_plan* plan) {
   UR_REQUIRE(d && plan, "null pointer");
   ur_conv_desc t = *d;
   if (!t.y && !t.yt && !t.gn_part) t.y = reinterpret_cast<void*>(16);    // any non-null value: only the plan is wanted
-  return conv_impl(&t, nullptr, 1, plan);
+  return conv_impl(&t, nullptr, plan);
 }
 
 extern "C" int ur_gemm_bias_act(const void* x, const void* w, const float* bias, const void* residual, void* y, long long M, int N, int K,
@@ -317,7 +244,7 @@ extern "C" int ur_gemm_bias_act(const void* x, const void* w, const float* bias,
   d.workspace = workspace; d.workspace_bytes = workspace_bytes;
   d.N = 1; d.H = 1; d.W = (int)M; d.C1 = K; d.ldx = ldx; d.Cout = N; d.ldw = ldw; d.ldy = ldy; d.ldr = ldr;
   d.KH = d.KW = 1; d.stride = 1; d.OH = 1; d.OW = (int)M; d.act = act; d.out_scale = 1.f; d.nbatch = 1; d.dtype = dtype;
-  return conv_impl(&d, stream, 0, nullptr);
+  return conv_impl(&d, stream, nullptr);
 }
 
 extern "C" int ur_groupconv3x3_nhwc(const void* x, const void* w, const float* bias, void* y, int N, int H, int W, int Cg, int Cog,
@@ -329,5 +256,5 @@ extern "C" int ur_groupconv3x3_nhwc(const void* x, const void* w, const float* b
   d.N = N; d.H = H; d.W = W; d.C1 = Cg; d.ldx = Cg * groups; d.Cout = Cog; d.ldw = 9 * Cg; d.ldy = Cog * groups;
   d.KH = d.KW = 3; d.stride = 1; d.pad_t = d.pad_l = 1; d.OH = H; d.OW = W; d.act = act; d.out_scale = 1.f; d.nbatch = groups;
   d.bs_x = Cg; d.bs_w = (long long)Cog * 9 * Cg; d.bs_bias = Cog; d.bs_y = Cog; d.dtype = dtype;
-  return conv_impl(&d, stream, 0, nullptr);
+  return conv_impl(&d, stream, nullptr);
 }

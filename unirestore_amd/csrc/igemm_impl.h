@@ -26,21 +26,26 @@
 static __device__ uint4 g_zero_page[8];
 typedef uint32_t ig_u32x4 __attribute__((ext_vector_type(4)));
 
+// A planned conv / GEMM launch (see UR_LAUNCHER): its launch step, and whether that launch applies gn_ab in its loader.  The plan
+// step has left the geometry in ConvK; ConvK has internal linkage, so between translation units it travels as void*.
+struct ConvLaunch {
+  int (*launch)(void* k, hipStream_t s);
+  int prologue_ok;
+};
+
 namespace {
 
 struct ConvK {
   const uint16_t* x; const uint16_t* x2; const uint16_t* w; const float* bias; const uint16_t* res;
   void* y; uint16_t* yt; float* ws; float* gn_part; const float* gn_ab;
   float* row_stats; const float* ln_stats; const float* ln_colsum; float ln_eps; int ln_dim, ln_parts;
-  int dry, plan_tn;
   int N, H, W, C1, ldx, C2, ldx2, Cin, Cout, ldw, ldy, ldr, KH, KW, stride, pad_t, pad_l, OH, OW, OHW;
   int ups, act, out_f32, n_split, t_rows, t_ld;
   float out_scale;
   int M, Ktot, nk, tiles_m, tiles_n, splitk, nk_per_split, nbatch;
   long long bs_x, bs_x2, bs_w, bs_bias, bs_y, bs_r, bias_img;
-  size_t ws_bytes_;
-  int gn_fused, gn_parts, gn_silu, f16, staged_ok_, prologue_ok;
-  int patch_tw, patch_m0_unused;   // >0: tile rows are an (BM/patch_tw) x patch_tw pixel patch of one image (halo kernel)
+  int gn_fused, gn_parts, gn_silu, f16, staged_ok_;
+  int patch_tw;   // >0: tile rows are an (BM/patch_tw) x patch_tw pixel patch of one image (halo kernel)
   int kcm;   // 1: K runs (64-channel chunk, tap, channel) - the 9 taps of a chunk are consecutive K tiles (L2 reuse)
   const uint16_t* wf;   // fragment-major copy of w (ur_conv_desc.w_frag) or null
   int wmajor;           // 1: weight-major XCD map (igemm_halo_img_kernel: 1-D grid; GEMM kernels: an XCD owns a band of columns)
@@ -893,6 +898,20 @@ __global__ __launch_bounds__(256) void splitk_reduce_gn_kernel(const ConvK p) {
 #else
 #define URK(name) name##_bf16
 #endif
+// Every launcher family L splits into L::plan(k, ws_bytes) - host only, no HIP call: tiles, split-K, GroupNorm partials; returns
+// prologue support - and L::launch(k, s), which only launches what the plan left in k (LDS attribute, instantiation, kernel, split-K
+// reduce).  UR_LAUNCHER(name, L) exports `ConvLaunch name_<type>(void* k, size_t ws_bytes)`: plan k, return its launch step.
+#define UR_LAUNCHER(name, ...)                                                                                   \
+  ConvLaunch URK(name)(void* kp, size_t ws_bytes) {                                                              \
+    return {[](void* k, hipStream_t s) { return __VA_ARGS__::launch(*static_cast<ConvK*>(k), s); },              \
+            __VA_ARGS__::plan(*static_cast<ConvK*>(kp), ws_bytes)};                                              \
+  }
+// The launchers of the instantiation units (igemm_v1a/v1b/v2/halo/g1.hip, conv_wstream.hip); igemm.hip declares them from this list.
+#define UR_CONV_LAUNCHERS(X)                                                                                      \
+  X(v1_128x128) X(v1_128x160) X(v1_128x64) X(v1_256x32) X(v1_64x64)                                               \
+  X(v2_256x32) X(v2_128x64) X(v2_256x160) X(v2_256x128) X(gemm_256x256) X(gemm_256x320_pair)                      \
+  X(g1_128x128) X(g1_128x160) X(g1_128x64) X(g1_64x64) X(g1_64x64_deep) X(g1_128x64_deep)                         \
+  X(halo_8x32_160) X(halo_8x32_128) X(halo_thin_32) X(himg_16x16) X(himg_8x8x4) X(wstream_8x8)
 #define UR_F16_SWITCH(k, ...)                  \
   do {                                         \
     constexpr bool F16 = UR_TU_F16 != 0;       \
@@ -915,8 +934,8 @@ static ReducePlan plan_splitk_reduce(const ConvK& k) {
   return {0, 0};
 }
 
-// Where the GroupNorm partial plane of this launch comes from (decided BEFORE the launch so that the dry-run plan and the
-// real launch agree): the conv epilogue (one partial per M tile of an image), the split-K reduce, or an extra pass over y.
+// Where the GroupNorm partial plane of this launch comes from (part of the plan, so that ur_conv2d_plan and the launch
+// agree): the conv epilogue (one partial per M tile of an image), the split-K reduce, or an extra pass over y.
 static void set_gn_plan(ConvK& k, bool direct_ok, int direct_parts) {
   k.gn_fused = 0; k.gn_parts = 0;
   if (!k.gn_part) return;
@@ -930,6 +949,17 @@ static void set_gn_plan(ConvK& k, bool direct_ok, int direct_parts) {
     const bool pair = k.act == UR_ACT_GEGLU || k.act == UR_ACT_GATE;
     k.gn_parts = ur::gn_stats_parts(k.N, k.OHW, (pair ? k.Cout / 2 : k.Cout) * k.nbatch);
   }
+}
+
+// Split-K sizing of every splitting launcher: `want` splits of the K loop, in granules of `gran` K tiles (1, or 9 = one 64-channel
+// chunk of a 3x3 conv), fewer while their fp32 partial planes (splitk * nbatch * M * Cout) overflow the workspace; then renormalised
+// so that no split is empty.  Sets k.splitk and k.nk_per_split.
+static void plan_splitk(ConvK& k, size_t ws_bytes, long long want, int gran = 1) {
+  int splitk = (int)std::max<long long>(want, 1);
+  while (splitk > 1 && (long long)splitk * k.nbatch * k.M * k.Cout * 4 > (long long)ws_bytes) --splitk;
+  const int units = k.nk / gran, per = (units + splitk - 1) / splitk;
+  k.splitk = (units + per - 1) / per;
+  k.nk_per_split = per * gran;
 }
 
 static void launch_splitk_reduce(ConvK& k, hipStream_t s) {
@@ -948,41 +978,38 @@ static void launch_splitk_reduce(ConvK& k, hipStream_t s) {
   }
 }
 
+// register-staged igemm_kernel, two workgroups per CU; split-K when fewer than 200 workgroups meet >= 8 K tiles
 template <int BM, int BN, int WM, int WN>
-int launch_cfg(ConvK& k, hipStream_t s) {
-  k.tiles_m = (k.M + BM - 1) / BM;
-  k.tiles_n = (k.Cout + BN - 1) / BN;
-  const long long blocks = (long long)k.tiles_m * k.tiles_n * k.nbatch;
-  int splitk = 1;
-  if (blocks < 200 && k.nk >= 8 && k.ws && k.y) {      // (a statistics-only launch has no y for a reduce pass to write)
-    long long want = (384 + blocks - 1) / blocks;
-    long long cap_k = k.nk / 4;
-    splitk = (int)std::min<long long>(std::min<long long>(want, cap_k), 16);
-    long long need = (long long)splitk * k.nbatch * k.M * k.Cout * 4;
-    while (splitk > 1 && need > (long long)k.ws_bytes_) { --splitk; need = (long long)splitk * k.nbatch * k.M * k.Cout * 4; }
-    if (splitk < 1) splitk = 1;
-  }
-  k.splitk = splitk;
-  k.nk_per_split = (k.nk + splitk - 1) / splitk;
-  k.splitk = (k.nk + k.nk_per_split - 1) / k.nk_per_split;
-  set_gn_plan(k, k.staged_ok_ && BN >= 32 && (k.OHW % BM) == 0, k.OHW / BM);
-  if (k.dry) { k.plan_tn = k.splitk > 1 ? 1 : k.tiles_n; return UR_OK; }     // row-stat planes this launch writes
-  constexpr int lds = 2 * (BM + BN) * 128;
+struct Cfg {
+  static constexpr int lds = 2 * (BM + BN) * 128;
   static_assert(epi_lds_bytes<BM, BN, 256>() <= lds, "epilogue staging must fit the K ring");
-  static ur::DeviceOnce attr_once;      // the attribute is per device
-  if (auto once_guard = attr_once.first()) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_kernel<BM, BN, WM, WN, false, UR_TU_F16 != 0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_kernel<BM, BN, WM, WN, true, UR_TU_F16 != 0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  static int plan(ConvK& k, size_t ws_bytes) {
+    k.tiles_m = (k.M + BM - 1) / BM;
+    k.tiles_n = (k.Cout + BN - 1) / BN;
+    const long long blocks = (long long)k.tiles_m * k.tiles_n * k.nbatch;
+    long long want = 1;
+    if (blocks < 200 && k.nk >= 8 && k.ws && k.y)      // (a statistics-only launch has no y for a reduce pass to write)
+      want = std::min<long long>(std::min<long long>((384 + blocks - 1) / blocks, k.nk / 4), 16);
+    plan_splitk(k, ws_bytes, want);
+    set_gn_plan(k, k.staged_ok_ && BN >= 32 && (k.OHW % BM) == 0, k.OHW / BM);
+    return 0;
   }
-  dim3 grid(k.tiles_m * k.tiles_n, k.nbatch, k.splitk);
-  pick_xcd_grid(k, (double)k.Cout * k.Ktot, (double)k.N * k.H * k.W * k.Cin);
-  const bool g1 = k.KH == 1 && k.stride == 1 && !k.ups && k.C2 == 0 && k.pad_t == 0 && k.pad_l == 0 && k.OH == k.H && k.OW == k.W &&
-                  (long long)k.M * k.ldx + k.Ktot < (1ll << 31);
-  if (g1) UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, true, F16>), grid, dim3(256), lds, s, k));
-  else UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, false, F16>), grid, dim3(256), lds, s, k));
-  if (k.splitk > 1) launch_splitk_reduce(k, s);
-  return ur::check_launch("ur_conv2d_nhwc");
-}
+  static int launch(ConvK& k, hipStream_t s) {
+    static ur::DeviceOnce attr_once;      // the attribute is per device
+    if (auto once_guard = attr_once.first()) {
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_kernel<BM, BN, WM, WN, false, UR_TU_F16 != 0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_kernel<BM, BN, WM, WN, true, UR_TU_F16 != 0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    }
+    dim3 grid(k.tiles_m * k.tiles_n, k.nbatch, k.splitk);
+    pick_xcd_grid(k, (double)k.Cout * k.Ktot, (double)k.N * k.H * k.W * k.Cin);
+    const bool g1 = k.KH == 1 && k.stride == 1 && !k.ups && k.C2 == 0 && k.pad_t == 0 && k.pad_l == 0 && k.OH == k.H && k.OW == k.W &&
+                    (long long)k.M * k.ldx + k.Ktot < (1ll << 31);
+    if (g1) UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, true, F16>), grid, dim3(256), lds, s, k));
+    else UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, false, F16>), grid, dim3(256), lds, s, k));
+    if (k.splitk > 1) launch_splitk_reduce(k, s);
+    return ur::check_launch("ur_conv2d_nhwc");
+  }
+};
 
 
 // =====================================================================================================================
@@ -1315,54 +1342,59 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_glds_kernel(const ConvK p) {
   igemm_epilogue<FM, FN, WTM, WTN, BM, BN, NT, F16, DIRECT, PAIRC>(p, acc, m0, n0, wm, wn, lane, gb, 0, smem);
 }
 
+// gemm_glds_kernel: pure GEMMs, LDS-DMA ring of NST stages, never split
 template <int BM, int BN, int WM, int WN, int NST, bool DIRECT = false, bool PAIRC = false>
-int launch_gemm(ConvK& k, hipStream_t s) {
-  k.tiles_m = (k.M + BM - 1) / BM;
-  k.tiles_n = (k.Cout + BN - 1) / BN;
-  k.splitk = 1;
-  k.nk_per_split = k.nk;
-  set_gn_plan(k, k.staged_ok_ && (k.OHW % BM) == 0, k.OHW / BM);
-  if (k.dry) { k.plan_tn = k.tiles_n; return UR_OK; }
-  constexpr int lds_loop = NST * (BM + BN) * 128, lds_epi = epi_lds_bytes<BM, BN, WM * WN * 64, PAIRC>();
-  constexpr int lds = lds_loop > lds_epi ? lds_loop : lds_epi;
+struct Gemm {
+  static constexpr int lds_loop = NST * (BM + BN) * 128, lds_epi = epi_lds_bytes<BM, BN, WM * WN * 64, PAIRC>();
+  static constexpr int lds = lds_loop > lds_epi ? lds_loop : lds_epi;
   static_assert(lds <= 160 * 1024, "LDS budget");
-  static ur::DeviceOnce attr_once;      // the attribute is per device
-  if (auto once_guard = attr_once.first()) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds_kernel<BM, BN, WM, WN, NST, DIRECT, PAIRC, UR_TU_F16 != 0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  static int plan(ConvK& k, size_t) {
+    k.tiles_m = (k.M + BM - 1) / BM;
+    k.tiles_n = (k.Cout + BN - 1) / BN;
+    k.splitk = 1;
+    k.nk_per_split = k.nk;
+    set_gn_plan(k, k.staged_ok_ && (k.OHW % BM) == 0, k.OHW / BM);
+    return 0;
   }
-  pick_xcd_grid(k, (double)k.Cout * k.Ktot, (double)k.M * k.Cin);
-  UR_F16_SWITCH(k, hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NST, DIRECT, PAIRC, F16>), dim3(k.tiles_m * k.tiles_n, k.nbatch, 1), dim3(WM * WN * 64), lds, s, k));
-  return ur::check_launch("ur_conv2d_nhwc");
-}
+  static int launch(ConvK& k, hipStream_t s) {
+    static ur::DeviceOnce attr_once;      // the attribute is per device
+    if (auto once_guard = attr_once.first()) {
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds_kernel<BM, BN, WM, WN, NST, DIRECT, PAIRC, UR_TU_F16 != 0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    }
+    pick_xcd_grid(k, (double)k.Cout * k.Ktot, (double)k.M * k.Cin);
+    UR_F16_SWITCH(k, hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NST, DIRECT, PAIRC, F16>), dim3(k.tiles_m * k.tiles_n, k.nbatch, 1), dim3(WM * WN * 64), lds, s, k));
+    return ur::check_launch("ur_conv2d_nhwc");
+  }
+};
 
-template <int BM, int BN, int WM, int WN, int NST>
-int launch_glds(ConvK& k, hipStream_t s, int min_blocks) {
-  k.tiles_m = (k.M + BM - 1) / BM;
-  k.tiles_n = (k.Cout + BN - 1) / BN;
-  const long long blocks = (long long)k.tiles_m * k.tiles_n * k.nbatch;
-  int splitk = 1;
-  if (blocks < min_blocks && k.nk >= 8 && k.ws && k.y && !k.row_stats && !k.ln_stats) {
-    long long want = (256 + blocks - 1) / blocks;
-    splitk = (int)std::min<long long>(std::min<long long>(want, k.nk / 4), 16);
-    while (splitk > 1 && (long long)splitk * k.nbatch * k.M * k.Cout * 4 > (long long)k.ws_bytes_) --splitk;
-    if (splitk < 1) splitk = 1;
+// igemm_glds_kernel (LDS-DMA ring, any conv); split-K when fewer than MIN_BLOCKS workgroups meet >= 8 K tiles
+template <int BM, int BN, int WM, int WN, int NST, int MIN_BLOCKS>
+struct Glds {
+  static constexpr int lds_loop = NST * (BM + BN) * 128, lds_epi = epi_lds_bytes<BM, BN, WM * WN * 64>();
+  static constexpr int lds = lds_loop > lds_epi ? lds_loop : lds_epi;
+  static int plan(ConvK& k, size_t ws_bytes) {
+    k.tiles_m = (k.M + BM - 1) / BM;
+    k.tiles_n = (k.Cout + BN - 1) / BN;
+    const long long blocks = (long long)k.tiles_m * k.tiles_n * k.nbatch;
+    long long want = 1;
+    if (blocks < MIN_BLOCKS && k.nk >= 8 && k.ws && k.y && !k.row_stats && !k.ln_stats)
+      want = std::min<long long>(std::min<long long>((256 + blocks - 1) / blocks, k.nk / 4), 16);
+    plan_splitk(k, ws_bytes, want);
+    set_gn_plan(k, k.staged_ok_ && BN >= 32 && (k.OHW % BM) == 0, k.OHW / BM);
+    return 0;
   }
-  k.nk_per_split = (k.nk + splitk - 1) / splitk;
-  k.splitk = (k.nk + k.nk_per_split - 1) / k.nk_per_split;
-  set_gn_plan(k, k.staged_ok_ && BN >= 32 && (k.OHW % BM) == 0, k.OHW / BM);
-  if (k.dry) { k.plan_tn = k.splitk > 1 ? 1 : k.tiles_n; return UR_OK; }
-  constexpr int lds_loop = NST * (BM + BN) * 128, lds_epi = epi_lds_bytes<BM, BN, WM * WN * 64>();
-  constexpr int lds = lds_loop > lds_epi ? lds_loop : lds_epi;
-  static ur::DeviceOnce attr_once;      // the attribute is per device
-  if (auto once_guard = attr_once.first()) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_glds_kernel<BM, BN, WM, WN, NST, UR_TU_F16 != 0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  static int launch(ConvK& k, hipStream_t s) {
+    static ur::DeviceOnce attr_once;      // the attribute is per device
+    if (auto once_guard = attr_once.first()) {
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_glds_kernel<BM, BN, WM, WN, NST, UR_TU_F16 != 0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    }
+    dim3 grid(k.tiles_m * k.tiles_n, k.nbatch, k.splitk);
+    pick_xcd_grid(k, (double)k.Cout * k.Ktot, (double)k.N * k.H * k.W * k.Cin);
+    UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_glds_kernel<BM, BN, WM, WN, NST, F16>), grid, dim3(WM * WN * 64), lds, s, k));
+    if (k.splitk > 1) launch_splitk_reduce(k, s);
+    return ur::check_launch("ur_conv2d_nhwc");
   }
-  dim3 grid(k.tiles_m * k.tiles_n, k.nbatch, k.splitk);
-  pick_xcd_grid(k, (double)k.Cout * k.Ktot, (double)k.N * k.H * k.W * k.Cin);
-  UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_glds_kernel<BM, BN, WM, WN, NST, F16>), grid, dim3(WM * WN * 64), lds, s, k));
-  if (k.splitk > 1) launch_splitk_reduce(k, s);
-  return ur::check_launch("ur_conv2d_nhwc");
-}
+};
 
 
 // GroupNorm apply (+ SiLU) on one 16-byte piece of an LDS-resident input patch, in place: 8 channels of one pixel,
@@ -1957,75 +1989,75 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const
 // do), tile = 8 x 32 pixels x 32 channel rows (rows >= Cout read zero through the descriptor's range check), hipcc-scheduled 1 x 1 fragment
 // body.  The launch is bound by reading the input once (x 1.3 for the halo), not by the matrix pipe.
 template <int TH, int BN, int WM, int WN>
-int launch_halo_thin(ConvK& k, hipStream_t s) {
-  constexpr int NW = WM * WN, HPIX = (TH + 2) * 34, HSLOTS = (HPIX + 8 * NW - 1) / (8 * NW);
-  constexpr int HBYTES = HSLOTS * NW * 1024;
-  constexpr int lds = 2 * HBYTES + 3 * (BN * 128 > NW * 1024 ? BN * 128 : NW * 1024) + 2048;
+struct HaloThin {
+  static constexpr int NW = WM * WN, HPIX = (TH + 2) * 34, HSLOTS = (HPIX + 8 * NW - 1) / (8 * NW);
+  static constexpr int HBYTES = HSLOTS * NW * 1024;
+  static constexpr int lds = 2 * HBYTES + 3 * (BN * 128 > NW * 1024 ? BN * 128 : NW * 1024) + 2048;
   static_assert(lds <= 160 * 1024, "LDS budget");
-  k.prologue_ok = 0;
-  k.tiles_m = k.N * (k.OH / TH) * (k.OW / 32);
-  k.tiles_n = (k.Cout + BN - 1) / BN;
-  k.splitk = 1;
-  k.nk_per_split = k.nk;
-  set_gn_plan(k, false, 0);
-  if (k.dry) { k.plan_tn = k.tiles_n; return UR_OK; }
-  k.patch_tw = 32;
-  static ur::DeviceOnce attr_once;      // the attribute is per device
-  if (auto once_guard = attr_once.first()) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_kernel<TH, BN, WM, WN, UR_TU_F16 != 0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  static int plan(ConvK& k, size_t) {
+    k.tiles_m = k.N * (k.OH / TH) * (k.OW / 32);
+    k.tiles_n = (k.Cout + BN - 1) / BN;
+    k.splitk = 1;
+    k.nk_per_split = k.nk;
+    set_gn_plan(k, false, 0);
+    return 0;
   }
-  UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_kernel<TH, BN, WM, WN, F16, false>), dim3(k.tiles_m * k.tiles_n, 1), dim3(NW * 64), lds, s, k));
-  return ur::check_launch("ur_conv2d_nhwc");
-}
+  static int launch(ConvK& k, hipStream_t s) {
+    k.patch_tw = 32;
+    static ur::DeviceOnce attr_once;      // the attribute is per device
+    if (auto once_guard = attr_once.first()) {
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_kernel<TH, BN, WM, WN, UR_TU_F16 != 0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    }
+    UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_kernel<TH, BN, WM, WN, F16, false>), dim3(k.tiles_m * k.tiles_n, 1), dim3(NW * 64), lds, s, k));
+    return ur::check_launch("ur_conv2d_nhwc");
+  }
+};
 
 template <int TH, int BN, int WM, int WN>
-int launch_halo(ConvK& k, hipStream_t s) {
-  constexpr int NW = WM * WN, BM = TH * 32, HPIX = (TH + 2) * 34, HSLOTS = (HPIX + 8 * NW - 1) / (8 * NW);
-  constexpr int HBYTES = HSLOTS * NW * 1024;
-  constexpr int lds_loop = 2 * HBYTES + 3 * BN * 128 + 2048, lds_epi = epi_lds_bytes<BM, BN, NW * 64>();     // (+ 2 x 1 KiB affine tables)
-  constexpr int lds = lds_loop > lds_epi ? lds_loop : lds_epi;
+struct Halo {
+  static constexpr int NW = WM * WN, BM = TH * 32, HPIX = (TH + 2) * 34, HSLOTS = (HPIX + 8 * NW - 1) / (8 * NW);
+  static constexpr int HBYTES = HSLOTS * NW * 1024;
+  static constexpr int lds_loop = 2 * HBYTES + 3 * BN * 128 + 2048, lds_epi = epi_lds_bytes<BM, BN, NW * 64>();     // (+ 2 x 1 KiB affine tables)
+  static constexpr int lds = lds_loop > lds_epi ? lds_loop : lds_epi;
   static_assert(lds <= 160 * 1024, "LDS budget");
   // in-loader GroupNorm: the 128-wide tile only (the 160-wide variant's 5 x 16 accumulators leave no registers for it: it spilled)
-  constexpr bool GN_OK = BN <= 128;
-  k.prologue_ok = GN_OK ? 1 : 0;
-  k.tiles_m = k.N * (k.OH / TH) * (k.OW / 32);
-  k.tiles_n = (k.Cout + BN - 1) / BN;
-  const int nchunk = k.nk / 9;
-  const long long tiles = (long long)k.tiles_m * k.tiles_n;
-  int splitk = 1;
-  if (tiles <= 128 && k.ws && k.y) {     // <= half a round of CUs: split the chunk range, reduce in a second pass
-    splitk = (int)std::min<long long>(256 / tiles, std::max(1, nchunk / 2));
-    while (splitk > 1 && (long long)splitk * k.M * k.Cout * 4 > (long long)k.ws_bytes_) --splitk;
+  static constexpr bool GN_OK = BN <= 128;
+  static int plan(ConvK& k, size_t ws_bytes) {
+    k.tiles_m = k.N * (k.OH / TH) * (k.OW / 32);
+    k.tiles_n = (k.Cout + BN - 1) / BN;
+    const int nchunk = k.nk / 9;
+    const long long tiles = (long long)k.tiles_m * k.tiles_n;
+    // <= half a round of CUs: split the chunk range, reduce in a second pass
+    plan_splitk(k, ws_bytes, tiles <= 128 && k.ws && k.y ? std::min<long long>(256 / tiles, std::max(1, nchunk / 2)) : 1, 9);
+    set_gn_plan(k, true, (k.OH / TH) * (k.OW / 32));         // a patch never leaves its image: one partial per patch
+    return GN_OK;
   }
-  const int cps = (nchunk + splitk - 1) / splitk;
-  k.splitk = (nchunk + cps - 1) / cps;
-  k.nk_per_split = cps * 9;
-  set_gn_plan(k, true, (k.OH / TH) * (k.OW / 32));         // a patch never leaves its image: one partial per patch
-  if (k.dry) { k.plan_tn = k.splitk > 1 ? 1 : k.tiles_n; return UR_OK; }
-  k.patch_tw = 32;
-  static ur::DeviceOnce attr_once;      // the attribute is per device
-  if (auto once_guard = attr_once.first()) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_kernel<TH, BN, WM, WN, UR_TU_F16 != 0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_kernel<TH, BN, WM, WN, UR_TU_F16 != 0, GN_OK>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_ws_kernel<TH, BN, WM, WN, UR_TU_F16 != 0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_ws_kernel<TH, BN, WM, WN, UR_TU_F16 != 0, GN_OK>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  static int launch(ConvK& k, hipStream_t s) {
+    k.patch_tw = 32;
+    static ur::DeviceOnce attr_once;      // the attribute is per device
+    if (auto once_guard = attr_once.first()) {
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_kernel<TH, BN, WM, WN, UR_TU_F16 != 0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_kernel<TH, BN, WM, WN, UR_TU_F16 != 0, GN_OK>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_ws_kernel<TH, BN, WM, WN, UR_TU_F16 != 0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_ws_kernel<TH, BN, WM, WN, UR_TU_F16 != 0, GN_OK>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    }
+    static const bool no_ws = getenv("UR_HALO_NOWS") != nullptr;          // A/B: every wave loads for itself (rounds 1-2 structure)
+    if (no_ws) {
+      if (GN_OK && k.gn_ab) UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_kernel<TH, BN, WM, WN, F16, GN_OK>), dim3(k.tiles_m * k.tiles_n, k.splitk), dim3(NW * 64), lds, s, k));
+      else UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_kernel<TH, BN, WM, WN, F16, false>), dim3(k.tiles_m * k.tiles_n, k.splitk), dim3(NW * 64), lds, s, k));
+    } else {
+      static const bool ld1 = getenv("UR_HALO_LD1") != nullptr;             // A/B: one loader wave for weights AND patch pieces (rounds 3-5)
+      const dim3 blk((NW + (ld1 ? 1 : 2)) * 64);
+      if (GN_OK && k.gn_ab) UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_ws_kernel<TH, BN, WM, WN, F16, GN_OK>), dim3(k.tiles_m * k.tiles_n, k.splitk), blk, lds, s, k));
+      else UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_ws_kernel<TH, BN, WM, WN, F16, false>), dim3(k.tiles_m * k.tiles_n, k.splitk), blk, lds, s, k));
+    }
+    if (k.splitk > 1) {
+      k.patch_tw = 0;                                        // the partial planes are plain [M][Cout]
+      launch_splitk_reduce(k, s);
+    }
+    return ur::check_launch("ur_conv2d_nhwc");
   }
-  static const bool no_ws = getenv("UR_HALO_NOWS") != nullptr;          // A/B: every wave loads for itself (rounds 1-2 structure)
-  if (no_ws) {
-    if (GN_OK && k.gn_ab) UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_kernel<TH, BN, WM, WN, F16, GN_OK>), dim3(k.tiles_m * k.tiles_n, k.splitk), dim3(NW * 64), lds, s, k));
-    else UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_kernel<TH, BN, WM, WN, F16, false>), dim3(k.tiles_m * k.tiles_n, k.splitk), dim3(NW * 64), lds, s, k));
-  } else {
-    static const bool ld1 = getenv("UR_HALO_LD1") != nullptr;             // A/B: one loader wave for weights AND patch pieces (rounds 3-5)
-    const dim3 blk((NW + (ld1 ? 1 : 2)) * 64);
-    if (GN_OK && k.gn_ab) UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_ws_kernel<TH, BN, WM, WN, F16, GN_OK>), dim3(k.tiles_m * k.tiles_n, k.splitk), blk, lds, s, k));
-    else UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_ws_kernel<TH, BN, WM, WN, F16, false>), dim3(k.tiles_m * k.tiles_n, k.splitk), blk, lds, s, k));
-  }
-  if (k.splitk > 1) {
-    k.patch_tw = 0;                                        // the partial planes are plain [M][Cout]
-    launch_splitk_reduce(k, s);
-  }
-  return ur::check_launch("ur_conv2d_nhwc");
-}
+};
 
 // =====================================================================================================================
 // Whole-image halo tiles for the small feature maps (16 x 16: one image per tile; 8 x 8: four images per tile; BM = 256).
@@ -2420,48 +2452,45 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_img_ws_kernel(c
 }
 
 template <int TH, int TW, int NIMG, int BN, int WM, int WN>
-int launch_halo_img(ConvK& k, hipStream_t s) {
-  constexpr int NW = WM * WN, BM = TH * TW * NIMG, HPIX = (TH + 2) * (TW + 2) * NIMG, HSLOTS = (HPIX + 8 * NW - 1) / (8 * NW);
-  constexpr int HBYTES = HSLOTS * NW * 1024;
-  constexpr bool GN_OK = NIMG == 1 && HSLOTS <= 7;          // must match the kernel's
-  constexpr int lds_loop = 2 * HBYTES + 3 * BN * 128 + (GN_OK ? 2048 : 0), lds_epi = epi_lds_bytes<BM, BN, NW * 64>();
-  constexpr int lds = lds_loop > lds_epi ? lds_loop : lds_epi;
+struct HaloImg {
+  static constexpr int NW = WM * WN, BM = TH * TW * NIMG, HPIX = (TH + 2) * (TW + 2) * NIMG, HSLOTS = (HPIX + 8 * NW - 1) / (8 * NW);
+  static constexpr int HBYTES = HSLOTS * NW * 1024;
+  static constexpr bool GN_OK = NIMG == 1 && HSLOTS <= 7;          // must match the kernel's
+  static constexpr int lds_loop = 2 * HBYTES + 3 * BN * 128 + (GN_OK ? 2048 : 0), lds_epi = epi_lds_bytes<BM, BN, NW * 64>();
+  static constexpr int lds = lds_loop > lds_epi ? lds_loop : lds_epi;
   static_assert(lds <= 160 * 1024, "LDS budget");
-  k.prologue_ok = GN_OK ? 1 : 0;
-  k.tiles_m = (k.N + NIMG - 1) / NIMG;
-  k.tiles_n = (k.Cout + BN - 1) / BN;
-  const int nchunk = k.nk / 9;
-  const long long tiles = (long long)k.tiles_m * k.tiles_n;
-  int splitk = 1;
-  if (tiles < 200 && k.ws && k.y) {      // one workgroup per CU: split the chunk range so that tiles * splits <= 256 (a single round)
-    splitk = (int)std::min<long long>(std::max<long long>(256 / tiles, 1), std::max(1, nchunk / 2));
-    while (splitk > 1 && (long long)splitk * k.M * k.Cout * 4 > (long long)k.ws_bytes_) --splitk;
+  static int plan(ConvK& k, size_t ws_bytes) {
+    k.tiles_m = (k.N + NIMG - 1) / NIMG;
+    k.tiles_n = (k.Cout + BN - 1) / BN;
+    const int nchunk = k.nk / 9;
+    const long long tiles = (long long)k.tiles_m * k.tiles_n;
+    // one workgroup per CU: split the chunk range so that tiles * splits <= 256 (a single round)
+    plan_splitk(k, ws_bytes, tiles < 200 && k.ws && k.y ? std::min<long long>(std::max<long long>(256 / tiles, 1), std::max(1, nchunk / 2)) : 1, 9);
+    set_gn_plan(k, (k.OHW % BM) == 0, k.OHW / BM);
+    return GN_OK;
   }
-  const int cps = (nchunk + splitk - 1) / splitk;
-  k.splitk = (nchunk + cps - 1) / cps;
-  k.nk_per_split = cps * 9;
-  set_gn_plan(k, (k.OHW % BM) == 0, k.OHW / BM);
-  if (k.dry) { k.plan_tn = k.splitk > 1 ? 1 : k.tiles_n; return UR_OK; }
-  static ur::DeviceOnce attr_once;      // the attribute is per device
-  if (auto once_guard = attr_once.first()) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_img_kernel<TH, TW, NIMG, BN, WM, WN, UR_TU_F16 != 0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_img_kernel<TH, TW, NIMG, BN, WM, WN, UR_TU_F16 != 0, GN_OK>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  static int launch(ConvK& k, hipStream_t s) {
+    static ur::DeviceOnce attr_once;      // the attribute is per device
+    if (auto once_guard = attr_once.first()) {
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_img_kernel<TH, TW, NIMG, BN, WM, WN, UR_TU_F16 != 0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_img_kernel<TH, TW, NIMG, BN, WM, WN, UR_TU_F16 != 0, GN_OK>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    }
+    // weight-major XCD map when the weights outweigh the activations and the per-XCD share still fits one round of its 32 CUs
+    static const bool no_wmajor = getenv("UR_HIMG_NOWMAJOR") != nullptr;
+    const int slices = k.tiles_n * k.splitk, per_xcd = ((slices + 7) / 8) * k.tiles_m;
+    k.wmajor = !no_wmajor && (long long)k.Cout * k.Ktot > (long long)k.N * k.H * k.W * k.Cin && per_xcd <= 32 && slices >= 8;
+    const dim3 grid = k.wmajor ? dim3(8 * per_xcd, 1) : dim3(k.tiles_m * k.tiles_n, k.splitk);
+    static const bool himg_ws = getenv("UR_HIMG_NOWS") == nullptr;        // wave-specialised form (8 compute + 2 loader waves); A/B: every wave loads for itself
+    if (himg_ws && !k.gn_ab) {
+      static ur::DeviceOnce ws_once;
+      if (auto g2 = ws_once.first())
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_img_ws_kernel<TH, TW, NIMG, BN, WM, WN, UR_TU_F16 != 0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_img_ws_kernel<TH, TW, NIMG, BN, WM, WN, F16>), grid, dim3((NW + 2) * 64), lds, s, k));
+    } else if (GN_OK && k.gn_ab) UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_img_kernel<TH, TW, NIMG, BN, WM, WN, F16, GN_OK>), grid, dim3(NW * 64), lds, s, k));
+    else UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_img_kernel<TH, TW, NIMG, BN, WM, WN, F16, false>), grid, dim3(NW * 64), lds, s, k));
+    if (k.splitk > 1) launch_splitk_reduce(k, s);
+    return ur::check_launch("ur_conv2d_nhwc");
   }
-  // weight-major XCD map when the weights outweigh the activations and the per-XCD share still fits one round of its 32 CUs
-  static const bool no_wmajor = getenv("UR_HIMG_NOWMAJOR") != nullptr;
-  const int slices = k.tiles_n * k.splitk, per_xcd = ((slices + 7) / 8) * k.tiles_m;
-  k.wmajor = !no_wmajor && (long long)k.Cout * k.Ktot > (long long)k.N * k.H * k.W * k.Cin && per_xcd <= 32 && slices >= 8;
-  const dim3 grid = k.wmajor ? dim3(8 * per_xcd, 1) : dim3(k.tiles_m * k.tiles_n, k.splitk);
-  static const bool himg_ws = getenv("UR_HIMG_NOWS") == nullptr;        // wave-specialised form (8 compute + 2 loader waves); A/B: every wave loads for itself
-  if (himg_ws && !k.gn_ab) {
-    static ur::DeviceOnce ws_once;
-    if (auto g2 = ws_once.first())
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_img_ws_kernel<TH, TW, NIMG, BN, WM, WN, UR_TU_F16 != 0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_img_ws_kernel<TH, TW, NIMG, BN, WM, WN, F16>), grid, dim3((NW + 2) * 64), lds, s, k));
-  } else if (GN_OK && k.gn_ab) UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_img_kernel<TH, TW, NIMG, BN, WM, WN, F16, GN_OK>), grid, dim3(NW * 64), lds, s, k));
-  else UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_img_kernel<TH, TW, NIMG, BN, WM, WN, F16, false>), grid, dim3(NW * 64), lds, s, k));
-  if (k.splitk > 1) launch_splitk_reduce(k, s);
-  return ur::check_launch("ur_conv2d_nhwc");
-}
+};
 
 }  // namespace

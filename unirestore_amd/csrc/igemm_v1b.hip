@@ -2,7 +2,7 @@
 #include "igemm_impl.h"
 
 namespace urk {
-int URK(v1_128x64)(void* kp, hipStream_t s) { ConvK& k = *static_cast<ConvK*>(kp); return launch_cfg<128, 64, 2, 2>(k, s); }
-int URK(v1_256x32)(void* kp, hipStream_t s) { ConvK& k = *static_cast<ConvK*>(kp); return launch_cfg<256, 32, 4, 1>(k, s); }
-int URK(v1_64x64)(void* kp, hipStream_t s) { ConvK& k = *static_cast<ConvK*>(kp); return launch_cfg<64, 64, 2, 2>(k, s); }
+UR_LAUNCHER(v1_128x64, Cfg<128, 64, 2, 2>)
+UR_LAUNCHER(v1_256x32, Cfg<256, 32, 4, 1>)
+UR_LAUNCHER(v1_64x64, Cfg<64, 64, 2, 2>)
 }  // namespace urk

@@ -161,6 +161,41 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor], dev, *, pair=F
 
 
 # ------------------------------------------------------------------------------------------------ conv / gemm
+def _conv_desc(x, pc: PackedConv, x2, stride, pad, upsample, out_hw, plan_only) -> ConvDesc:
+    """ur_conv_desc of `pc` over x (| x2): input and weight pointers, geometry, weight layout, workspace, ldy = dense output.
+    The caller adds outputs, epilogue inputs and activation.  plan_only: placeholder pointers (ur_conv2d_plan reads no data)."""
+    n, h, w_, c1 = x.shape
+    c2 = 0 if x2 is None else x2.shape[-1]
+    k, g = pc.k, pc.groups
+    if pad is None:
+        pad = (k // 2, k // 2)
+    if out_hw is None:
+        hin, win = (h * 2, w_ * 2) if upsample else (h, w_)
+        out_hw = ((hin + 2 * pad[0] - k) // stride + 1, (win + 2 * pad[1] - k) // stride + 1)
+    d = ConvDesc()
+    d.dtype = _dt(x)
+    if plan_only:
+        d.x, d.x2, d.w = 16, (16 if c2 else None), 16
+    else:
+        d.x, d.x2, d.w = _ptr(x), _ptr(x2), _ptr(pc.w)
+    ws = workspace(x.device)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    d.N, d.H, d.W = n, h, w_
+    d.C1, d.ldx, d.C2, d.ldx2 = (c1 // g if g > 1 else c1), c1, c2, c2
+    d.Cout, d.ldw, d.ldy = pc.cout // g, pc.w.shape[1], pc.cout_out
+    d.KH = d.KW = k
+    d.stride, d.pad_t, d.pad_l = stride, pad[0], pad[1]
+    d.OH, d.OW = out_hw
+    d.upsample2x, d.out_scale = int(upsample), 1.0
+    d.k_chunk_major = int(pc.kcm and (c2 == 0 or c1 % 64 == 0))
+    if wants_frag(pc, n, h, w_, c1, c2, stride, upsample, g) and pad == (1, 1):
+        d.w_frag = 16 if plan_only else pc.frag().data_ptr()
+    d.nbatch = g
+    if g > 1:
+        d.bs_x, d.bs_w, d.bs_bias, d.bs_y, d.bs_r = c1 // g, (pc.cout // g) * pc.w.shape[1], pc.cout // g, pc.cout_out // g, pc.cout_out // g
+    return d
+
+
 def conv(x: torch.Tensor, pc: PackedConv, *, x2=None, residual=None, bias=None, act=UR_ACT_NONE, stride=1, pad=None,
          out_hw=None, upsample=False, out_f32=False, out_scale=1.0, out=None, yt=None, n_split=0, t_rows=0,
          gn=False, store=True, rows=False, ln_stats=None, gn_ab=None, gn_silu=False):
@@ -173,23 +208,16 @@ def conv(x: torch.Tensor, pc: PackedConv, *, x2=None, residual=None, bias=None, 
         raise ValueError(f"conv: x must be a contiguous 4-d {pc.w.dtype} tensor, got {x.dtype} {tuple(x.shape)}")
     n, h, w_, c1 = x.shape
     c2 = 0 if x2 is None else x2.shape[-1]
-    g = pc.groups
-    if (c1 + c2) != pc.cin * g:
-        raise ValueError(f"conv: Cin mismatch: {c1}+{c2} vs {pc.cin}*{g}")
-    k = pc.k
-    if pad is None:
-        pad = (k // 2, k // 2)
-    hin, win = (h * 2, w_ * 2) if upsample else (h, w_)
-    if out_hw is None:
-        out_hw = ((hin + 2 * pad[0] - k) // stride + 1, (win + 2 * pad[1] - k) // stride + 1)
-    oh, ow = out_hw
+    if (c1 + c2) != pc.cin * pc.groups:
+        raise ValueError(f"conv: Cin mismatch: {c1}+{c2} vs {pc.cin}*{pc.groups}")
+    d = _conv_desc(x, pc, x2, stride, pad, upsample, out_hw, plan_only=False)
+    assert not pc.kcm or d.k_chunk_major, "chunk-major weights need a 64-aligned concat boundary"
+    oh, ow = d.OH, d.OW
     co_total = pc.cout_out
     if out is None and store:
         out = torch.empty((n, oh, ow, co_total), dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
-    d = ConvDesc()
-    d.dtype = _dt(x)
     bias_t = pc.bias if bias is None else bias          # override: per-step (time-embedding) or per-image bias rows
-    d.x, d.x2, d.w, d.bias = _ptr(x), _ptr(x2), _ptr(pc.w), _ptr(bias_t)
+    d.bias = _ptr(bias_t)
     if bias is not None and bias.dim() == 2 and bias.shape[0] > 1:
         d.bias_img_stride = bias.shape[1]
     d.residual, d.y, d.yt = _ptr(residual), _ptr(out), _ptr(yt)
@@ -199,28 +227,12 @@ def conv(x: torch.Tensor, pc: PackedConv, *, x2=None, residual=None, bias=None, 
         d.ln_stats, d.ln_colsum, d.ln_eps, d.ln_dim, d.ln_parts = st.data_ptr(), pc.ln_colsum.data_ptr(), pc.ln_eps, pc.cin, parts
     if gn_ab is not None:
         d.gn_ab, d.gn_silu = gn_ab.data_ptr(), int(gn_silu)
-    ws = workspace(x.device)
-    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-    d.N, d.H, d.W = n, h, w_
-    d.C1, d.ldx, d.C2, d.ldx2 = (c1 // g if g > 1 else c1), c1, c2, c2
-    d.Cout = pc.cout // g
-    d.ldw = pc.w.shape[1]
-    d.ldy = out.shape[-1] if out is not None else co_total
+    if out is not None:
+        d.ldy = out.shape[-1]
     d.ldr = residual.shape[-1] if residual is not None else 0
-    d.KH = d.KW = k
-    d.stride, d.pad_t, d.pad_l, d.OH, d.OW = stride, pad[0], pad[1], oh, ow
-    d.upsample2x, d.act, d.out_f32 = int(upsample), act, int(out_f32)
+    d.act, d.out_f32, d.out_scale = act, int(out_f32), out_scale
     d.n_split, d.t_rows = n_split, t_rows
-    d.k_chunk_major = int(pc.kcm and (c2 == 0 or c1 % 64 == 0))
-    assert not pc.kcm or d.k_chunk_major, "chunk-major weights need a 64-aligned concat boundary"
-    if wants_frag(pc, n, h, w_, c1, c2, stride, upsample, g) and pad == (1, 1):
-        d.w_frag = pc.frag().data_ptr()
     d.t_ld = yt.shape[-1] if yt is not None else 0
-    d.out_scale = out_scale
-    d.nbatch = g
-    if g > 1:
-        d.bs_x, d.bs_w, d.bs_bias, d.bs_y = c1 // g, (pc.cout // g) * pc.w.shape[1], pc.cout // g, pc.cout_out // g
-        d.bs_r = pc.cout_out // g
     stats = rstats = None
     if gn or rows:      # the consumer is a norm: plan the launch, then hand it the planes to fill (plain stores, no atomics)
         if gn:
@@ -250,32 +262,13 @@ def conv(x: torch.Tensor, pc: PackedConv, *, x2=None, residual=None, bias=None, 
 def conv_plan(x: torch.Tensor, pc: PackedConv, *, x2=None, stride=1, pad=None, upsample=False, gn=False, gn_ab=False,
               act=UR_ACT_NONE, residual=False, store=True) -> ConvPlan:
     """What `conv` would do for this (shape, weights) - used to decide whether the GroupNorm apply can ride in the conv."""
-    n, h, w_, c1 = x.shape
-    c2 = 0 if x2 is None else x2.shape[-1]
-    k, g = pc.k, pc.groups
-    pad = (k // 2, k // 2) if pad is None else pad
-    hin, win = (h * 2, w_ * 2) if upsample else (h, w_)
-    oh, ow = (hin + 2 * pad[0] - k) // stride + 1, (win + 2 * pad[1] - k) // stride + 1
-    d = ConvDesc()
-    d.dtype = _dt(x)
-    d.x, d.w, d.y = 16, 16, (16 if store else None)
-    d.x2 = 16 if c2 else None
+    d = _conv_desc(x, pc, x2, stride, pad, upsample, None, plan_only=True)
+    d.y = 16 if store else None
     d.residual = 16 if residual else None
     d.gn_part = 16 if gn else None
     d.gn_ab = 16 if gn_ab else None
-    ws = workspace(x.device)
-    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-    d.N, d.H, d.W = n, h, w_
-    d.C1, d.ldx, d.C2, d.ldx2 = (c1 // g if g > 1 else c1), c1, c2, c2
-    d.Cout, d.ldw, d.ldy, d.ldr = pc.cout // g, pc.w.shape[1], pc.cout_out, pc.cout_out if residual else 0
-    d.KH = d.KW = k
-    d.stride, d.pad_t, d.pad_l, d.OH, d.OW = stride, pad[0], pad[1], oh, ow
-    d.upsample2x, d.act, d.out_scale, d.nbatch = int(upsample), act, 1.0, g
-    d.k_chunk_major = int(pc.kcm and (c2 == 0 or c1 % 64 == 0))
-    if wants_frag(pc, n, h, w_, c1, c2, stride, upsample, g) and pad == (1, 1):
-        d.w_frag = 16
-    if g > 1:
-        d.bs_x, d.bs_w, d.bs_bias, d.bs_y, d.bs_r = c1 // g, (pc.cout // g) * pc.w.shape[1], pc.cout // g, pc.cout_out // g, pc.cout_out // g
+    d.ldr = pc.cout_out if residual else 0
+    d.act = act
     plan = ConvPlan()
     check(lib.ur_conv2d_plan(d, plan))
     return plan
