@@ -124,6 +124,22 @@ typedef struct ur_conv_plan {
 } ur_conv_plan;
 int ur_conv2d_plan(const ur_conv_desc* d, ur_conv_plan* plan);
 
+/* host-only query (no launch, no HIP call): which launcher runs `d` and how it splits the work, by the same workspace rule as
+ * the launch (d->workspace / d->workspace_bytes).  Fill d as for ur_conv2d_plan.  A grouped conv that runs one launch per group
+ * (group_loop) reports the launch of one group. */
+typedef struct ur_conv_launch_info {
+  int launcher;       /* index of the launcher: ur_conv_launcher_name(launcher) */
+  int splitk;         /* K splits (1: no split, no reduce pass) */
+  int nk_per_split;   /* 64-deep K tiles per split */
+  int reduce;         /* reduce pass after the splits: -1 none, 0 plain, 1 row-wise (LayerNorm statistics), 2 GroupNorm partials */
+  int reduce_ri;      /* reduce 2: 16 * reduce_ri output rows per block (4, 2 or 1); else 0 */
+  int gn_pass;        /* 1: the GroupNorm partials come from an extra pass over y (ur_conv_plan.gn_fused == 0) */
+  int group_loop;     /* 1: one halo launch per group on its channel slice */
+} ur_conv_launch_info;
+int ur_conv2d_plan_launch(const ur_conv_desc* d, ur_conv_launch_info* info);
+int ur_conv_launcher_count(void);
+const char* ur_conv_launcher_name(int i); /* static string, or NULL outside [0, ur_conv_launcher_count()) */
+
 /* Linear / 1x1 convolution with the epilogues of SURVEY.md 8(b): y[m, n] = act(x[m, :] . w[n, :] + bias[n]) (+ residual);
  * act in UR_ACT_* (GEGLU / GATE: w rows pre-interleaved, N = 2 * output columns).  Thin wrapper over ur_conv2d_nhwc. */
 int ur_gemm_bias_act(const void* x, const void* w, const float* bias, const void* residual, void* y, long long M, int N, int K,

@@ -1,9 +1,16 @@
 """CPU-side check of the conv / GEMM launch planning (csrc/igemm.hip dispatch_conv and the launchers' plan steps): ur_conv2d_plan on
 host-only descriptors (placeholder pointers, nothing runs), one shape per launcher.  The expected (row_stat_parts, gn_parts, gn_fused,
 prologue_ok) were recorded before planning was split from launching."""
+import math
+import os
+import re
+
 import pytest
 
+import conv_launcher_cases as LC
 from unirestore_amd import capi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 MiB = 1 << 20
 P = 16          # any non-null pointer: the plan reads no data
@@ -97,11 +104,118 @@ CASES = [
 VARIANTS = {"plain": {}, "gn": dict(gn_part=P), "gn_ab": dict(gn_ab=P, gn_part=P), "rows": dict(row_stats=P)}
 
 
+# launcher each CASES entry plans to, where its id is not already the launcher's name (the grouped conv: the launcher of each group's
+# launch, which needs >= 64 8 x 32 patch tiles for the halo kernel - a 64 x 64 map of one image has 16)
+LAUNCHER_OF = {"wstream_8x8_cpw2": "wstream_8x8", "v1_128x160_split": "v1_128x160", "grouped_halo": "v1_128x128"}
+
+
+def _launcher(d):
+    info = capi.ConvLaunchInfo()
+    rc = capi.lib.ur_conv2d_plan_launch(d, info)
+    assert rc == 0, capi.lib.ur_last_error()
+    return capi.launcher_names()[info.launcher], info
+
+
 @pytest.mark.parametrize("name,shape,expected", CASES, ids=[c[0] for c in CASES])
 @pytest.mark.parametrize("dtype", [capi.UR_DT_BF16, capi.UR_DT_F16])
 def test_plan_per_launcher(name, shape, expected, dtype):
     for (variant, extra), want in zip(VARIANTS.items(), expected):
         assert _plan(_desc(**shape, dtype=dtype, **extra)) == want, (name, variant)
+    assert _launcher(_desc(**shape, dtype=dtype))[0] == LAUNCHER_OF.get(name, name)
+
+
+def test_launcher_names_match_the_list():
+    names = capi.launcher_names()
+    assert len(names) == capi.lib.ur_conv_launcher_count() == len(set(names)) == 23
+    assert capi.lib.ur_conv_launcher_name(-1) is None and capi.lib.ur_conv_launcher_name(len(names)) is None
+    src = open(os.path.join(ROOT, "unirestore_amd", "csrc", "igemm_impl.h")).read()
+    body = src[src.index("#define UR_CONV_LAUNCHERS(X)"):]
+    body = body[:body.index("\n#define", 1)]
+    assert re.findall(r"X\((\w+)\)", body) == names
+
+
+def _plan_case(c, nbytes, dtype):
+    d = capi.ConvDesc()
+    ptrs = dict(LC.placeholders(c), workspace=LC.P if nbytes is not None else None)
+    LC.fill(d, c, ptrs, nbytes)
+    d.dtype = dtype
+    return _launcher(d)
+
+
+@pytest.mark.parametrize("dtype", [capi.UR_DT_BF16, capi.UR_DT_F16])
+def test_launcher_matrix_covers_every_launcher_and_path(dtype):
+    """The GPU parity matrix (tests/conv_launcher_cases.py) on the host: every case plans to the launcher it names at each of its
+    workspace sizes, the cases reach every launcher of UR_CONV_LAUNCHERS, and every split / reduce / statistics path occurs."""
+    names = capi.launcher_names()
+    hit, paths, moved = set(), set(), []
+    for c in LC.CASES:
+        _, full = _plan_case(c, LC.WS_FULL, dtype)
+        for label, nbytes in LC.ws_variants(c, full.splitk):
+            name, info = _plan_case(c, nbytes, dtype)
+            if name != LC.expected_launcher(c, label):
+                moved.append(f"{c['id']} [{label}]: {name}, expected {LC.expected_launcher(c, label)}")
+            hit.add(name)
+            if info.splitk > 1:
+                paths.add(("reduce", info.reduce, info.reduce_ri))
+            if info.gn_pass:
+                paths.add("gn_pass")
+            if info.group_loop:
+                paths.add("group_loop")
+            if label == "less" and 1 < info.splitk < full.splitk:
+                paths.add("workspace-limited split")
+            if label == "none":
+                assert info.splitk == 1, c["id"]
+    missing = sorted(set(names) - hit)
+    assert not missing and not moved, f"launchers no case reaches: {missing}; dispatch moved cases:\n" + "\n".join(moved)
+    assert hit == set(names)
+    want = {("reduce", 0, 0), ("reduce", 1, 0), ("reduce", 2, 4), ("reduce", 2, 2), ("reduce", 2, 1), "gn_pass", "group_loop",
+            "workspace-limited split"}
+    assert want <= paths, f"paths no case reaches: {want - paths}"
+
+
+@pytest.mark.parametrize("dt", ["bf16", "fp16"])
+def test_comparator_rejects_subtle_errors(dt):
+    """The per-element bound of tests/conv_reference.py accepts the fp64 reference after 16-bit rounding and rejects a ragged tile
+    corner set to 0, one 64-channel K chunk of one tap missing from one pixel, a halo tile edge read one column off, a NaN in a plane."""
+    import torch
+    import conv_reference as R
+    tdt = {"bf16": torch.bfloat16, "fp16": torch.float16}[dt]
+    g = torch.Generator().manual_seed(3)
+    N, H, W, C, Cout = 1, 8, 64, 128, 40                       # two 8 x 32 patches, two 64-channel chunks, a ragged 40-wide N
+    x = torch.randn(N, H, W, C, generator=g).to(tdt).double()
+    w = (torch.randn(Cout, 3, 3, C, generator=g) / math.sqrt(9 * C)).to(tdt).double()
+    K = 9 * C
+    acc = R.conv_nhwc(x, w, 1, (1, 1))
+    A = R.conv_nhwc(x.abs(), w.abs(), 1, (1, 1))
+    ref, Ao, eps = R.epilogue(acc, A)
+    bnd = R.bound(ref, Ao, eps, K, tdt)
+    y = ref.to(tdt).double()
+    assert R.compare(y, ref, bnd) < 1.0
+    bad = y.clone()                                            # (a) last ragged tile: largest element of columns 32..39 of the last rows
+    blk = ref[-32:, 32:].abs()
+    i = int(blk.argmax())
+    bad[ref.shape[0] - 32 + i // 8, 32 + i % 8] = 0
+    with pytest.raises(AssertionError):
+        R.compare(bad, ref, bnd)
+    pix = 3 * W + 17                                           # (b) one pixel without chunk 1 of tap (1, 1) (the centre tap)
+    part = x[0, 3, 17, 64:] @ w[:, 1, 1, 64:].t()
+    bad = y.clone()
+    bad[pix] = (ref[pix] - part).to(tdt).double()
+    with pytest.raises(AssertionError):
+        R.compare(bad, ref, bnd)
+    xs = x.clone()                                             # (c) the pixel at a patch edge (ow = 31) reads its input one column off
+    xs[:, :, 1:] = x[:, :, :-1]
+    shifted = R.conv_nhwc(xs, w, 1, (1, 1))
+    bad = y.clone()
+    bad[5 * W + 31] = shifted[5 * W + 31].to(tdt).double()
+    with pytest.raises(AssertionError):
+        R.compare(bad, ref, bnd)
+    yy = y.view(N, H * W, Cout).permute(0, 2, 1)               # (d) GroupNorm plane sums: exact sums pass, one NaN does not
+    s, q = yy.sum(-1), (yy * yy).sum(-1)
+    assert R.compare_sums(s, q, yy, H * W) < 1.0
+    s[0, 7] = float("nan")
+    with pytest.raises(AssertionError):
+        R.compare_sums(s, q, yy, H * W)
 
 
 def test_plan_refusals():

@@ -281,7 +281,9 @@ def test_conv3x3_weight_stream_8x8(ops, n, cin, cout, cat, feat):
         kw["gn"] = True
     pc = ops.pack_conv(wt, b, "cuda", c1=cin if cat else None)
     y = ops.conv(_nhwc(x), pc, x2=_nhwc(x2) if cat else None, **kw)
-    assert pc.w_frag is not None, "this shape must take the weight-streaming kernel"
+    from unirestore_amd import capi
+    launch = ops.conv_launch(_nhwc(x), pc, x2=_nhwc(x2) if cat else None, gn="gn" in f, act=kw.get("act", ops.UR_ACT_NONE), residual="res" in f)
+    assert capi.launcher_names()[launch.launcher] == "wstream_8x8", "this shape must take the weight-streaming kernel"
     y2 = ops.conv(_nhwc(x), pc, x2=_nhwc(x2) if cat else None, **kw)
     assert torch.equal(y, y2)                                  # fixed-order exchange + reduce: bit-deterministic
     got = _nchw(y).double()
@@ -454,18 +456,29 @@ def test_conv_fused_groupnorm_stats(ops, n, cin, cout, h, w, k):
     assert rel_l2(_nchw(out), ref) < TOL_BF16
 
 
-@pytest.mark.parametrize("n,cin,cout,h,w,ups,res", [(2, 64, 128, 16, 32, False, False), (1, 320, 320, 32, 32, False, True),
-                                                    (8, 128, 160, 8, 64, False, False), (2, 192, 256, 8, 16, True, True),
-                                                    (3, 256, 128, 8, 8, True, False), (8, 640, 1280, 8, 8, True, True)])   # 8x8 -> 16x16: whole-image tile, chunk-split
+# launcher each shape plans to (ops.conv_launch): the 8x32 patch kernels need >= 64 patch tiles, which smaller maps do not give
+_HALO_PATH = {(2, 64, 128, 16, 32, False, False): "v1_128x128", (1, 320, 320, 32, 32, False, True): "v1_128x160",
+              (8, 128, 160, 8, 64, False, False): "v1_128x160", (2, 192, 256, 8, 16, True, True): "v1_128x128",
+              (3, 256, 128, 8, 8, True, False): "himg_16x16", (8, 640, 1280, 8, 8, True, True): "himg_16x16",      # 8x8 -> 16x16: whole-image tile, chunk-split
+              (2, 64, 256, 64, 64, False, True): "halo_8x32_128", (2, 64, 320, 32, 32, True, False): "halo_8x32_160"}
+
+
+@pytest.mark.parametrize("n,cin,cout,h,w,ups,res", list(_HALO_PATH))
 def test_conv_halo_tile_path(ops, n, cin, cout, h, w, ups, res):
-    """3x3 / stride 1 / pad 1 shapes that take the LDS halo-tile kernels (8x32 output patches; whole 16x16 images), incl. fused upsample."""
+    """3x3 / stride 1 / pad 1 shapes around the LDS halo-tile kernels, incl. fused upsample: the 8x32 output patches (halo_8x32_128 /
+    _160, >= 64 patch tiles), whole 16x16 images (himg_16x16, the 8x8 -> 16x16 upsample among them) and the generic tiles that take
+    the smaller maps (fewer than 64 patch tiles).  Each shape asserts the launcher it plans to."""
+    from unirestore_amd import capi
     g = _gen(cin + cout + h)
     x = _rb(torch.randn(n, cin, h, w, generator=g)); wt = _rb(torch.randn(cout, cin, 3, 3, generator=g) / math.sqrt(cin * 9))
     b = torch.randn(cout, generator=g)
     xin = F.interpolate(x, scale_factor=2.0, mode="nearest") if ups else x
     ref = F.conv2d(xin, wt, b, padding=1)
     r = _rb(torch.randn(ref.shape, generator=g)) if res else None
-    y = ops.conv(_nhwc(x), ops.pack_conv(wt, b, "cuda"), upsample=ups, residual=None if r is None else _nhwc(r), gn=True)
+    pc = ops.pack_conv(wt, b, "cuda")
+    kernel = _HALO_PATH[(n, cin, cout, h, w, ups, res)]
+    assert capi.launcher_names()[ops.conv_launch(_nhwc(x), pc, upsample=ups, residual=res, gn=True).launcher] == kernel
+    y = ops.conv(_nhwc(x), pc, upsample=ups, residual=None if r is None else _nhwc(r), gn=True)
     ref = ref + r if res else ref
     assert rel_l2(_nchw(y), ref) < TOL_BF16
     st = ops.gn_of(y)[0].double().sum(1).cpu()          # partial planes [N][P][C][2] -> [N][C][2]
@@ -636,10 +649,17 @@ torch.save(outs, {out!r})
 def test_conv_halo_wave_specialised_equals_self_loading_kernel(ops, tmp_path):
     """The wave-specialised halo conv (8 compute waves + 1 loader wave, tap-crossing fragment pipeline, buffer-descriptor DMA) and the
     kernel whose waves load for themselves (UR_HALO_NOWS=1, read once per process: second process) accumulate in the same order:
-    outputs and GroupNorm partial planes must be BIT-identical, on full tiles, ragged Cout tiles, the fused upsample and both widths."""
+    outputs and GroupNorm partial planes must be BIT-identical, on full tiles, the fused upsample, the channel-chunk split and both
+    widths (each shape is asserted to plan to the 8 x 32 halo kernel it stands for)."""
     import os, subprocess, sys
+    from unirestore_amd import capi
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cases = [(2, 128, 320, 16, 64, False), (1, 192, 200, 8, 32, False), (2, 64, 256, 8, 16, True), (1, 320, 160, 24, 32, False)]
+    cases = [(2, 128, 256, 64, 64, False), (2, 64, 320, 64, 64, False), (2, 64, 256, 32, 32, True), (2, 256, 320, 64, 64, False)]
+    want = ["halo_8x32_128", "halo_8x32_160", "halo_8x32_128", "halo_8x32_160"]
+    for (n, cin, cout, h, w, ups), name in zip(cases, want):
+        x = torch.zeros(n, h, w, cin, dtype=DT, device="cuda")
+        pc = ops.pack_conv(torch.zeros(cout, cin, 3, 3), torch.zeros(cout), "cuda")
+        assert capi.launcher_names()[ops.conv_launch(x, pc, upsample=ups, gn=True).launcher] == name, (n, cin, cout, h, w, ups)
     dt = "fp16" if DT == torch.float16 else "bf16"
     res = []
     for tag, env in (("ws", {}), ("nows", {"UR_HALO_NOWS": "1"})):

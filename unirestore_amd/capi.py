@@ -47,6 +47,12 @@ class ConvPlan(C.Structure):
     _fields_ = [("row_stat_parts", C.c_int), ("gn_parts", C.c_int), ("gn_fused", C.c_int), ("prologue_ok", C.c_int)]
 
 
+class ConvLaunchInfo(C.Structure):
+    """Mirror of `ur_conv_launch_info`."""
+    _fields_ = [("launcher", C.c_int), ("splitk", C.c_int), ("nk_per_split", C.c_int), ("reduce", C.c_int), ("reduce_ri", C.c_int),
+                ("gn_pass", C.c_int), ("group_loop", C.c_int)]
+
+
 _P, _I, _F, _LL, _SZ = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_size_t
 
 # name -> (restype, argtypes); every symbol the header declares
@@ -55,6 +61,9 @@ SIGNATURES = {
     "ur_last_error": (C.c_char_p, []),
     "ur_conv2d_nhwc": (_I, [C.POINTER(ConvDesc), _P]),
     "ur_conv2d_plan": (_I, [C.POINTER(ConvDesc), C.POINTER(ConvPlan)]),
+    "ur_conv2d_plan_launch": (_I, [C.POINTER(ConvDesc), C.POINTER(ConvLaunchInfo)]),
+    "ur_conv_launcher_count": (_I, []),
+    "ur_conv_launcher_name": (C.c_char_p, [_I]),
     "ur_gemm_bias_act": (_I, [_P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _I, _I, _P, _SZ, _I, _P]),
     "ur_groupconv3x3_nhwc": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _SZ, _I, _P]),
     "ur_groupnorm_stats_parts": (_I, [_I, _I, _I]),
@@ -114,6 +123,18 @@ def _load():
 
 
 lib = _load()
+
+
+def launcher_names() -> list:
+    """Names of the conv / GEMM launchers, by index (ur_conv_launch_info.launcher)."""
+    return [lib.ur_conv_launcher_name(i).decode() for i in range(lib.ur_conv_launcher_count())]
+
+
+def plan_launch(d: ConvDesc) -> ConvLaunchInfo:
+    """ur_conv2d_plan_launch of a filled descriptor (host only); raises like `check`."""
+    info = ConvLaunchInfo()
+    check(lib.ur_conv2d_plan_launch(d, info))
+    return info
 
 
 class URError(RuntimeError):

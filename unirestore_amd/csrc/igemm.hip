@@ -127,8 +127,8 @@ ConvLaunch dispatch_conv(ConvK& k, bool pair, size_t ws_bytes) {
 
 }  // namespace
 
-// plan != nullptr: only plan the launch (ur_conv2d_plan), nothing runs
-static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, ur_conv_plan* plan) {
+// plan or info != nullptr: only plan the launch (ur_conv2d_plan / ur_conv2d_plan_launch), nothing runs
+static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, ur_conv_plan* plan, ur_conv_launch_info* info = nullptr) {
   UR_REQUIRE(d && d->x && d->w, "null x/w");
   UR_REQUIRE(d->KH == d->KW && (d->KH == 1 || d->KH == 3), "only 1x1 and 3x3 kernels");
   UR_REQUIRE(d->C1 > 0 && d->C1 % 8 == 0 && d->C2 % 8 == 0 && d->ldx % 8 == 0, "Cin/ldx must be multiples of 8");
@@ -185,11 +185,34 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, ur_conv_plan* pl
     fam = interned.emplace(buf, 0).first->first.c_str();
   }
   const ConvLaunch launch = dispatch_conv(k, pair, d->workspace_bytes);
+  // Grouped 3x3 convolutions whose groups are halo-kernel sized (chunk-major weights, >= 64 channels in, a multiple of 128 out):
+  // one halo launch per group on the channel slice instead of the batched generic kernel, which gathers 64-byte runs per pixel and
+  // tap (CFRM's AdaNAFV2.group_conv, densified to 128-channel blocks by the caller: 2.19 ms -> 4 x ~0.2 ms at 256 x 256 x 512)
+  const bool group_loop = k.nbatch > 1 && d->KH == 3 && k.kcm && k.stride == 1 && !pair && !k.gn_part && !k.row_stats && !k.ln_stats &&
+                          !k.yt && !k.gn_ab && !k.out_f32 && k.staged_ok_ && k.Cout % 128 == 0 && !k.bias_img && k.C2 == 0;
+  auto group_k = [&](int b) {      // the single-group problem of group b
+    ConvK kb = k;
+    kb.nbatch = 1;
+    kb.x = k.x + b * k.bs_x; kb.w = k.w + b * k.bs_w; kb.bias = k.bias ? k.bias + b * k.bs_bias : nullptr;
+    kb.res = k.res ? k.res + b * k.bs_r : nullptr;
+    kb.y = reinterpret_cast<uint16_t*>(k.y) + b * k.bs_y;
+    kb.bs_x = kb.bs_w = kb.bs_bias = kb.bs_y = kb.bs_r = 0;
+    return kb;
+  };
   if (plan) {      // row-stat planes: one per N tile, or the single one of a split-K reduce pass
     plan->row_stat_parts = d->row_stats ? (k.splitk > 1 ? 1 : k.tiles_n) : 0;
     plan->gn_parts = k.gn_parts; plan->gn_fused = k.gn_fused; plan->prologue_ok = launch.prologue_ok;
-    return UR_OK;
   }
+  if (info) {      // what runs: the launcher (per group, for the group loop), its split and reduce pass, the GroupNorm pass
+    ConvK kb = group_loop ? group_k(0) : k;
+    const ConvLaunch l = group_loop ? dispatch_conv(kb, pair, d->workspace_bytes) : launch;
+    info->launcher = l.id; info->splitk = kb.splitk; info->nk_per_split = kb.nk_per_split;
+    const ReducePlan r = kb.splitk > 1 ? plan_splitk_reduce(kb) : ReducePlan{-1, 0};
+    info->reduce = r.kind; info->reduce_ri = r.ri;
+    info->gn_pass = k.gn_part && !k.gn_fused && !group_loop;
+    info->group_loop = group_loop;
+  }
+  if (plan || info) return UR_OK;
   // statistics-only launch: only where the epilogue itself produces the partials
   if (!d->y && d->gn_part && (!k.gn_fused || k.splitk > 1))
     return ur::fail(UR_E_UNSUPPORTED, "ur_conv2d_nhwc: y == NULL needs a launch whose epilogue writes gn_part (see ur_conv2d_plan)");
@@ -197,18 +220,9 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, ur_conv_plan* pl
     return ur::fail(UR_E_UNSUPPORTED, "ur_conv2d_nhwc: gn_ab is not supported by this launch (see ur_conv2d_plan.prologue_ok)");
   ur::ProfScope prof(fam, flops, bytes, s);
   UR_REQUIRE(!(d->row_stats || d->ln_stats) || (k.staged_ok_ && k.nbatch == 1 && !d->yt == !d->yt), "row_stats / ln fusion need a bf16 staged output");
-  // Grouped 3x3 convolutions whose groups are halo-kernel sized (chunk-major weights, >= 64 channels in, a multiple of 128 out):
-  // one halo launch per group on the channel slice instead of the batched generic kernel, which gathers 64-byte runs per pixel and
-  // tap (CFRM's AdaNAFV2.group_conv, densified to 128-channel blocks by the caller: 2.19 ms -> 4 x ~0.2 ms at 256 x 256 x 512)
-  if (k.nbatch > 1 && d->KH == 3 && k.kcm && k.stride == 1 && !pair && !k.gn_part && !k.row_stats && !k.ln_stats && !k.yt && !k.gn_ab &&
-      !k.out_f32 && k.staged_ok_ && k.Cout % 128 == 0 && !k.bias_img && k.C2 == 0) {
+  if (group_loop) {
     for (int b = 0; b < d->nbatch; ++b) {
-      ConvK kb = k;
-      kb.nbatch = 1;
-      kb.x = k.x + b * k.bs_x; kb.w = k.w + b * k.bs_w; kb.bias = k.bias ? k.bias + b * k.bs_bias : nullptr;
-      kb.res = k.res ? k.res + b * k.bs_r : nullptr;
-      kb.y = reinterpret_cast<uint16_t*>(k.y) + b * k.bs_y;
-      kb.bs_x = kb.bs_w = kb.bs_bias = kb.bs_y = kb.bs_r = 0;
+      ConvK kb = group_k(b);
       const int rcb = dispatch_conv(kb, pair, d->workspace_bytes).launch(&kb, s);
       if (rcb != UR_OK) return rcb;
     }
@@ -234,6 +248,23 @@ extern "C" int ur_conv2d_plan(const ur_conv_desc* d, ur_conv_plan* plan) {
   if (!t.y && !t.yt && !t.gn_part) t.y = reinterpret_cast<void*>(16);    // any non-null value: only the plan is wanted
   return conv_impl(&t, nullptr, plan);
 }
+
+// Host-only plan of which launcher runs `d` and how (no kernel runs, no HIP call; the same workspace rule as the launch).
+extern "C" int ur_conv2d_plan_launch(const ur_conv_desc* d, ur_conv_launch_info* info) {
+  UR_REQUIRE(d && info, "null pointer");
+  ur_conv_desc t = *d;
+  if (!t.y && !t.yt && !t.gn_part) t.y = reinterpret_cast<void*>(16);    // any non-null value: only the plan is wanted
+  return conv_impl(&t, nullptr, nullptr, info);
+}
+
+// The launcher names, stringised from the list the launchers are declared from (they cannot drift apart).
+#define UR_LAUNCHER_NAME(name) #name,
+static const char* const kLauncherNames[] = {UR_CONV_LAUNCHERS(UR_LAUNCHER_NAME)};
+#undef UR_LAUNCHER_NAME
+static_assert(sizeof(kLauncherNames) / sizeof(kLauncherNames[0]) == UR_CONV_LAUNCHER_COUNT, "one name per launcher");
+
+extern "C" int ur_conv_launcher_count(void) { return UR_CONV_LAUNCHER_COUNT; }
+extern "C" const char* ur_conv_launcher_name(int i) { return i >= 0 && i < UR_CONV_LAUNCHER_COUNT ? kLauncherNames[i] : nullptr; }
 
 extern "C" int ur_gemm_bias_act(const void* x, const void* w, const float* bias, const void* residual, void* y, long long M, int N, int K,
                                 int ldx, int ldw, int ldy, int ldr, int act, float* workspace, size_t workspace_bytes, int dtype,

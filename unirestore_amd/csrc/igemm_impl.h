@@ -31,6 +31,7 @@ typedef uint32_t ig_u32x4 __attribute__((ext_vector_type(4)));
 struct ConvLaunch {
   int (*launch)(void* k, hipStream_t s);
   int prologue_ok;
+  int id;          // position of the launcher in UR_CONV_LAUNCHERS (ur_conv_launch_info.launcher)
 };
 
 namespace {
@@ -904,7 +905,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_gn_kernel(const ConvK p) {
 #define UR_LAUNCHER(name, ...)                                                                                   \
   ConvLaunch URK(name)(void* kp, size_t ws_bytes) {                                                              \
     return {[](void* k, hipStream_t s) { return __VA_ARGS__::launch(*static_cast<ConvK*>(k), s); },              \
-            __VA_ARGS__::plan(*static_cast<ConvK*>(kp), ws_bytes)};                                              \
+            __VA_ARGS__::plan(*static_cast<ConvK*>(kp), ws_bytes), UR_LAUNCHER_##name};                          \
   }
 // The launchers of the instantiation units (igemm_v1a/v1b/v2/halo/g1.hip, conv_wstream.hip); igemm.hip declares them from this list.
 #define UR_CONV_LAUNCHERS(X)                                                                                      \
@@ -912,6 +913,10 @@ __global__ __launch_bounds__(256) void splitk_reduce_gn_kernel(const ConvK p) {
   X(v2_256x32) X(v2_128x64) X(v2_256x160) X(v2_256x128) X(gemm_256x256) X(gemm_256x320_pair)                      \
   X(g1_128x128) X(g1_128x160) X(g1_128x64) X(g1_64x64) X(g1_64x64_deep) X(g1_128x64_deep)                         \
   X(halo_8x32_160) X(halo_8x32_128) X(halo_thin_32) X(himg_16x16) X(himg_8x8x4) X(wstream_8x8)
+// launcher index = position in the list (ConvLaunch::id; igemm.hip names them by stringising the same list)
+#define UR_LAUNCHER_ID(name) UR_LAUNCHER_##name,
+enum ConvLauncherId { UR_CONV_LAUNCHERS(UR_LAUNCHER_ID) UR_CONV_LAUNCHER_COUNT };
+#undef UR_LAUNCHER_ID
 #define UR_F16_SWITCH(k, ...)                  \
   do {                                         \
     constexpr bool F16 = UR_TU_F16 != 0;       \

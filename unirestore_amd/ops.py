@@ -274,6 +274,19 @@ def conv_plan(x: torch.Tensor, pc: PackedConv, *, x2=None, stride=1, pad=None, u
     return plan
 
 
+def conv_launch(x: torch.Tensor, pc: PackedConv, *, x2=None, stride=1, pad=None, upsample=False, gn=False, gn_ab=False,
+                act=UR_ACT_NONE, residual=False, store=True):
+    """Which launcher `conv` would run for this (shape, weights), and its split (capi.ConvLaunchInfo; name: capi.launcher_names())."""
+    d = _conv_desc(x, pc, x2, stride, pad, upsample, None, plan_only=True)
+    d.y = 16 if store else None
+    d.residual = 16 if residual else None
+    d.gn_part = 16 if gn else None
+    d.gn_ab = 16 if gn_ab else None
+    d.ldr = pc.cout_out if residual else 0
+    d.act = act
+    return capi.plan_launch(d)
+
+
 def pack_linear_ln(weight, bias, gamma, beta, eps, dev, *, pair=False) -> PackedConv:
     """Linear(LayerNorm(x)) folded for the LN-fused GEMM epilogue: w' = W*gamma (bf16), bias' = W.beta + b,
     ln_colsum[n] = sum_k bf16(w'[n,k]).  The kernel computes rstd*(w'.x - mean*ln_colsum) + bias'."""
