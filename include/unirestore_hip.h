@@ -264,6 +264,16 @@ int ur_linear_f32(const float* x, const float* w, const float* bias, float* y, i
                   int act, ur_stream_t stream);
 /* TFA prompt update (taskeditor.py:80-91): pooled [B][3][T*D] (filter, info, content), cond [B][T][D] -> upd */
 int ur_tfa_prompt_update(const float* pooled, const float* cond, float* upd, int B, int T, int D, ur_stream_t stream);
+/* Multi-task fan-out of ur_scale_channels (DiffUIE.forward_tasks): x [B,HW,C] is shared by K tasks, s fp32 [K*B][C] holds one scale
+   row per (task, image), y [K*B,HW,C] is task-major: y[k*B+b] = x[b] * s[k*B+b], rounded exactly as ur_scale_channels rounds it.
+   s == NULL replicates x K times (bit copies).  Each 16-byte vector of x is read once and written K times: (1 + K) tensors of
+   traffic instead of the 2K of K ur_scale_channels calls.  1 <= K <= 8.  No allocation, no synchronisation, no atomics. */
+int ur_scale_channels_fanout(const void* x, const float* s, void* y, int B, int K, int HW, int C, int dtype, ur_stream_t stream);
+/* Multi-task fan-out of ur_tfa_prompt_update: upd [K*B][T][D], row n = k*B+b reads pooled row n % B (pooled [B][3][T*D] is shared
+   by the tasks) and cond row n / B of a [K][T][D] prompt table (cond_per_row = 0) or row n of a [K*B][T][D] tensor
+   (cond_per_row = 1).  Same reduction order as ur_tfa_prompt_update: a row equals what that gives for the same inputs, bit for bit. */
+int ur_tfa_prompt_update_fanout(const float* pooled, const float* cond, float* upd, int B, int K, int T, int D, int cond_per_row,
+                                ur_stream_t stream);
 /* out[n][c] = a[n][c] * b[n][c / (C/G)]  (combine intra/inter group attention, cfrm.py:46-48) */
 int ur_vec_mul_group(const float* a, const float* b, float* out, int N, int C, int G, ur_stream_t stream);
 

@@ -87,10 +87,12 @@ SIGNATURES = {
     "ur_dwconv3x3_nhwc": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ur_avgpool_hw": (_I, [_P, _P, _I, _I, _I, _P, _I, _P]),
     "ur_scale_channels": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "ur_scale_channels_fanout": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ur_axpy_channels": (_I, [_P, _P, _P, _P, _LL, _I, _I, _P]),
     "ur_spade_modulate": (_I, [_P, _P, _I, _P, _P, _LL, _I, _I, _P]),
     "ur_linear_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ur_tfa_prompt_update": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "ur_tfa_prompt_update_fanout": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ur_vec_mul_group": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "ur_image_to_nhwc": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ur_nhwc_to_nchw_f32": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _F, _F, _I, _P]),

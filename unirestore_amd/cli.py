@@ -95,9 +95,16 @@ def resolve(cfg: dict, allow_16bit: bool = False) -> dict:
                 caller_args={k: init[k] for k in ("save_image", "eval_mode", "need_crop") if k in init}, data_args=dargs)
 
 
-def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_16bit=False, metrics_device="cpu") -> dict:
+def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_16bit=False, metrics_device="cpu", tasks=None) -> dict:
+    """tasks: a list of task names - every batch is restored once and decoded for each of them (DiffUIE.forward_tasks).  PSNR / SSIM
+    come from the "ir" output, so the list must hold "ir"; images_per_s counts input images."""
     import torch
     r = resolve(cfg, allow_16bit=allow_16bit)
+    if tasks is not None:
+        tasks = list(tasks)
+        if "ir" not in tasks:
+            raise ValueError(f"--tasks {','.join(tasks)}: PSNR / SSIM are computed on the 'ir' output; add 'ir' to the list "
+                             "(it is not added silently)")
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     if not torch.cuda.is_available():
         raise RuntimeError("no GPU visible: the restoration path runs on MI355X only (no CPU fallback)")
@@ -130,16 +137,17 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
             break
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        preds = lit.validation_step(batch, metrics=False)          # forward only inside the timed region
-        out = preds[-1]
+        preds = lit.validation_step(batch, metrics=False, tasks=tasks)          # forward only inside the timed region
+        by_task = preds[-1] if tasks is not None else {"ir": preds[-1]}
+        out = by_task["ir"]
         if world > 1:
             out = all_gather_images(out, sizes)
         torch.cuda.synchronize()
         if i >= 1:                                        # batch 0 captures the hipGraph: time from the second one
             secs += time.perf_counter() - t0
             n_img += out.shape[0]
-        finite = finite and bool(torch.isfinite(out).all())
-        lit.update_metrics(preds[-1], batch[1])           # this rank's shard; reduced over the ranks below (fp64 PSNR / SSIM: untimed)
+        finite = finite and bool(torch.isfinite(out).all()) and all(bool(torch.isfinite(v).all()) for v in by_task.values())
+        lit.update_metrics(by_task["ir"], batch[1])           # this rank's shard; reduced over the ranks below (fp64 PSNR / SSIM: untimed)
     if world > 1:                                         # the reference's metric states reduce with dist_reduce_fx="sum"
         # the totals are host floats (metrics_device "cpu") or 0-d fp64 device tensors ("gpu")
         tot = torch.stack([torch.as_tensor(v, dtype=torch.float64, device=dev)
@@ -148,6 +156,8 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
         lit.totals.update(psnr=float(tot[0]), ssim=float(tot[1]), images=int(tot[2]))
     res = dict(config=r["data_args"], dtype=r["dtype"], n_gpus=world, denoise_steps=r["model_kwargs"]["cnet"]["num_inference_steps"],
                images_per_s=(n_img / secs) if secs > 0 else None, output_finite=finite, **lit.metrics())
+    if tasks is not None:
+        res["tasks"] = tasks
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -164,13 +174,16 @@ def main(argv=None):
     ap.add_argument("--allow-16bit", action="store_true", help="run a `precision: 32` config in fp16 (fp32 accumulation) instead of refusing it")
     ap.add_argument("--metrics-device", choices=["cpu", "gpu"], default="cpu",
                     help="where PSNR / SSIM run: cpu = host fp64 (default), gpu = the HIP metric kernels (fp64, no per-batch host sync)")
+    ap.add_argument("--tasks", default=None, metavar="ir,cls,seg",
+                    help="restore every batch once and decode it for each of these tasks (forward_tasks); must hold 'ir', which feeds PSNR / SSIM")
     a = ap.parse_args(argv)
     cfg = load_config(a.config, a.set)
     if a.command == "print_config":
         print(yaml.safe_dump(cfg, sort_keys=False))
         print(json.dumps(resolve(cfg, allow_16bit=a.allow_16bit)))
         return 0
-    res = validate(cfg, hf_root=a.hf_root, max_batches=a.max_batches, allow_16bit=a.allow_16bit, metrics_device=a.metrics_device)
+    res = validate(cfg, hf_root=a.hf_root, max_batches=a.max_batches, allow_16bit=a.allow_16bit, metrics_device=a.metrics_device,
+                   tasks=[t for t in a.tasks.split(",") if t] if a.tasks is not None else None)
     if res is not None:
         print(json.dumps(res))
     return 0

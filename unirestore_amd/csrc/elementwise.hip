@@ -141,6 +141,41 @@ __global__ __launch_bounds__(256) void scale_channels_kernel(const uint16_t* __r
   }
 }
 
+// Multi-task fan-out of scale_channels_kernel: x [B,HW,C] is shared by K tasks, y [K*B,HW,C] is task-major (task k's image b is row
+// k*B+b).  One thread loads its 16-byte vector of x ONCE and writes the K scaled results (plain vector stores): (1 + K) tensors of HBM
+// traffic instead of 2K.  The product is the one of scale_channels_kernel (fp32 multiply, pack8t), so slice k equals
+// ur_scale_channels(x, s[k*B:(k+1)*B]) bit for bit.  s == nullptr: K bit copies of x.
+constexpr int FANOUT_MAX_K = 8;
+template <bool F16>
+__global__ __launch_bounds__(256) void scale_channels_fanout_kernel(const uint16_t* __restrict__ x, const float* __restrict__ s,
+                                                                    uint16_t* __restrict__ y, long long HWCV, int CV, long long totalv,
+                                                                    int B, int K) {
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < totalv; i += (long long)gridDim.x * 256) {
+    const uint4 raw = *reinterpret_cast<const uint4*>(x + i * 8);
+    if (!s) {
+#pragma unroll
+      for (int k = 0; k < FANOUT_MAX_K; ++k)
+        if (k < K) *reinterpret_cast<uint4*>(y + (k * totalv + i) * 8) = raw;
+      continue;
+    }
+    const int v = (int)(i % CV);
+    const long long b = i / HWCV;
+    float f[8];
+    unpack8t<F16>(raw, f);
+#pragma unroll
+    for (int k = 0; k < FANOUT_MAX_K; ++k) {
+      if (k < K) {
+        const float* sp = s + (((long long)k * B + b) * CV + v) * 8;
+        const float4 s0 = *reinterpret_cast<const float4*>(sp), s1 = *reinterpret_cast<const float4*>(sp + 4);
+        float g[8];
+        g[0] = f[0] * s0.x; g[1] = f[1] * s0.y; g[2] = f[2] * s0.z; g[3] = f[3] * s0.w;
+        g[4] = f[4] * s1.x; g[5] = f[5] * s1.y; g[6] = f[6] * s1.z; g[7] = f[7] * s1.w;
+        *reinterpret_cast<uint4*>(y + (k * totalv + i) * 8) = pack8t<F16>(g);
+      }
+    }
+  }
+}
+
 template <bool F16>
 __global__ __launch_bounds__(256) void axpy_channels_kernel(const uint16_t* __restrict__ a, const uint16_t* __restrict__ b,
                                                             const float* __restrict__ s, uint16_t* __restrict__ y, int CV,
@@ -238,6 +273,36 @@ __global__ __launch_bounds__(256) void tfa_prompt_kernel(const float* __restrict
   for (int d = t; d < D; d += 256) {
     const float f = expf(pf[d] - mf) / lf, iv = expf(pi[d] - mi) / li, c = tanhf(pc[d]);
     upd[(long long)bt * D + d] = f * cond[(long long)bt * D + d] + iv * c;
+  }
+}
+
+// Multi-task fan-out of tfa_prompt_kernel: block n*T+tt of K*B*T; `pooled` row n % B (shared by the tasks), `cond` row n / B of a
+// [K][T][D] prompt table (cond_per_row = 0) or row n (cond_per_row = 1).  The arithmetic and its order are tfa_prompt_kernel's.
+__global__ __launch_bounds__(256) void tfa_prompt_fanout_kernel(const float* __restrict__ pooled, const float* __restrict__ cond,
+                                                                float* __restrict__ upd, int B, int T, int D, int cond_per_row) {
+  __shared__ float red[16];
+  const int bt = blockIdx.x, n = bt / T, tt = bt - n * T, b = n % B, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const float* pf = pooled + ((long long)b * 3 + 0) * T * D + (long long)tt * D;
+  const float* pi = pooled + ((long long)b * 3 + 1) * T * D + (long long)tt * D;
+  const float* pc = pooled + ((long long)b * 3 + 2) * T * D + (long long)tt * D;
+  const float* cd = cond + ((long long)(cond_per_row ? n : n / B) * T + tt) * D;
+  float mf = -INFINITY, mi = -INFINITY;
+  for (int d = t; d < D; d += 256) { mf = fmaxf(mf, pf[d]); mi = fmaxf(mi, pi[d]); }
+  mf = wave_max(mf); mi = wave_max(mi);
+  if (lane == 0) { red[w] = mf; red[4 + w] = mi; }
+  __syncthreads();
+  mf = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  mi = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
+  float lf = 0.f, li = 0.f;
+  for (int d = t; d < D; d += 256) { lf += expf(pf[d] - mf); li += expf(pi[d] - mi); }
+  lf = wave_sum(lf); li = wave_sum(li);
+  if (lane == 0) { red[8 + w] = lf; red[12 + w] = li; }
+  __syncthreads();
+  lf = red[8] + red[9] + red[10] + red[11];
+  li = red[12] + red[13] + red[14] + red[15];
+  for (int d = t; d < D; d += 256) {
+    const float f = expf(pf[d] - mf) / lf, iv = expf(pi[d] - mi) / li, c = tanhf(pc[d]);
+    upd[(long long)bt * D + d] = f * cd[d] + iv * c;
   }
 }
 
@@ -512,6 +577,18 @@ int ur_scale_channels(const void* x, const float* sc, const void* residual, void
   return ur::check_launch("ur_scale_channels");
 }
 
+int ur_scale_channels_fanout(const void* x, const float* sc, void* y, int B, int K, int HW, int C, int dtype, ur_stream_t stream) {
+  UR_REQUIRE_DT(dtype);
+  UR_REQUIRE(x && y && B > 0 && HW > 0 && C > 0 && C % 8 == 0, "bad args");
+  UR_REQUIRE(K >= 1 && K <= FANOUT_MAX_K, "ur_scale_channels_fanout: 1 <= K <= 8");
+  hipStream_t s = (hipStream_t)stream;
+  const long long totalv = (long long)B * HW * (C / 8);
+  ur::ProfScope prof("elementwise", 0.0, 2.0 * (1.0 + K) * totalv * 8.0, s);
+  UR_DT_SWITCH(dtype, hipLaunchKernelGGL(scale_channels_fanout_kernel<F16>, dim3(nblocks(totalv)), dim3(256), 0, s, (const uint16_t*)x, sc,
+                     (uint16_t*)y, (long long)HW * (C / 8), C / 8, totalv, B, K));
+  return ur::check_launch("ur_scale_channels_fanout");
+}
+
 int ur_axpy_channels(const void* a, const void* b, const float* sc, void* y, long long rows, int C, int dtype, ur_stream_t stream) {
   UR_REQUIRE_DT(dtype);
   UR_REQUIRE(a && b && sc && y && C % 8 == 0, "bad args");
@@ -548,6 +625,14 @@ int ur_tfa_prompt_update(const float* pooled, const float* cond, float* upd, int
   UR_REQUIRE(pooled && cond && upd && B > 0 && T > 0 && D > 0, "bad args");
   hipLaunchKernelGGL(tfa_prompt_kernel, dim3(B * T), dim3(256), 0, (hipStream_t)stream, pooled, cond, upd, T, D);
   return ur::check_launch("ur_tfa_prompt_update");
+}
+
+int ur_tfa_prompt_update_fanout(const float* pooled, const float* cond, float* upd, int B, int K, int T, int D, int cond_per_row,
+                                ur_stream_t stream) {
+  UR_REQUIRE(pooled && cond && upd && B > 0 && K > 0 && T > 0 && D > 0 && (long long)B * K * T < (1ll << 31), "bad args");
+  hipLaunchKernelGGL(tfa_prompt_fanout_kernel, dim3(B * K * T), dim3(256), 0, (hipStream_t)stream, pooled, cond, upd, B, T, D,
+                     (int)(cond_per_row != 0));
+  return ur::check_launch("ur_tfa_prompt_update_fanout");
 }
 
 int ur_vec_mul_group(const float* a, const float* b, float* out, int N, int C, int G, ur_stream_t stream) {

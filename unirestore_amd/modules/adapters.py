@@ -265,9 +265,9 @@ class TaskFeatureAdapter(nn.Module):
             self.__dict__[key] = (ops.pack_conv(w1, b1, DEV), ops.pack_conv(w2, b2, DEV, groups=3))
         return self.__dict__[key]
 
-    def run(self, x, skip, condition):
-        """x [B,h,w,c_out], skip [B,h,w,c_skip] bf16 NHWC; condition fp32 [B,T,D] -> (x', cond' or None)."""
-        b, hh, ww, cs = skip.shape
+    def _pooled(self, skip):
+        """The three gate stacks on the skip feature alone -> pooled fp32 [B][3][T*D] (filter, info, content)."""
+        hh, ww, cs = skip.shape[1:]
         pc1, pc2 = self._fused()
         sn = ops.group_norm(skip, None, None, cs, 1e-5)                        # InstanceNorm2d (no affine); reuses fused sums
         h3 = ops.conv(sn, pc1, act=UR_ACT_GELU)
@@ -275,9 +275,13 @@ class TaskFeatureAdapter(nn.Module):
         # partial sums is written (no [B,h,w,3D] tensor); the finalize kernel adds them in a fixed order
         if ops.conv_plan(h3, pc2, gn=True, store=False).gn_fused:
             part, nparts = ops.conv(h3, pc2, gn=True, store=False)
-            pooled = ops.gn_finalize_planes(part, nparts, hh * ww)
-        else:
-            pooled = ops.avgpool(ops.conv(h3, pc2, gn=True))
+            return ops.gn_finalize_planes(part, nparts, hh * ww)
+        return ops.avgpool(ops.conv(h3, pc2, gn=True))
+
+    def run(self, x, skip, condition):
+        """x [B,h,w,c_out], skip [B,h,w,c_skip] bf16 NHWC; condition fp32 [B,T,D] -> (x', cond' or None)."""
+        b = skip.shape[0]
+        pooled = self._pooled(skip)
         upd = ops.tfa_prompt_update(pooled, condition.contiguous())
         wo, bo = self.out_gate["0"].dev_f32()
         o = ops.linear_f32(upd.view(b, -1), wo, bo, UR_ACT_TANH)               # [B, D]
@@ -288,6 +292,34 @@ class TaskFeatureAdapter(nn.Module):
         if not self.last_layer:
             wp, bp = self.prompt_trans["0"].dev_f32()
             new_cond = ops.linear_f32(upd.view(b * self.prompt_len, -1), wp, bp, UR_ACT_GELU).view(b, self.prompt_len, -1)
+        return x, new_cond
+
+    def run_shared(self, skip):
+        """The half of `run` no task enters: (pooled [B][3][T*D], t_gate1(skip)) - computed once per image for any number of tasks."""
+        return self._pooled(skip), ops.conv(skip, self.t_gate1.packed())
+
+    def run_tasks(self, x, skip, condition, n_tasks, x_shared, shared=None):
+        """`run` for n_tasks tasks of the same B images in one task-major batch (task k's image b is row k*B + b).
+        skip [B,h,w,c_skip] is shared.  x_shared=True (the first TFA level): x is [B,h,w,c_out], still shared, and condition is
+        the [n_tasks,T,D] prompt table; afterwards x is [n_tasks*B,...] and condition [n_tasks*B,T,D] (the previous level's cond').
+        shared: a `run_shared(skip)` result to reuse.  -> (x' [n_tasks*B,h,w,c_out], cond' [n_tasks*B,T,D'] or None).
+        Every conv is issued once; with n_tasks == 1 the launches have the shapes of `run`."""
+        b, k = skip.shape[0], n_tasks
+        pooled, g1 = shared if shared is not None else self.run_shared(skip)
+        upd = ops.tfa_prompt_update_fanout(pooled, condition.contiguous(), b, k, cond_per_row=not x_shared)
+        wo, bo = self.out_gate["0"].dev_f32()
+        o = ops.linear_f32(upd.view(k * b, -1), wo, bo, UR_ACT_TANH)           # [K*B, D]
+        hs = ops.scale_channels_fanout(g1, o, k)                               # g1 read once, K gated copies written
+        # the conv launchers take residual / second input per image: K-fold copies of the shared operands (one read, K stores)
+        skip_k = skip if k == 1 else ops.scale_channels_fanout(skip, None, k)
+        skip2 = ops.conv(hs, self.t_gate2.packed(), residual=skip_k)
+        if x_shared and k > 1:
+            x = ops.scale_channels_fanout(x, None, k)
+        x = ops.conv(x, self.conv_out.packed(), x2=skip2, residual=x, gn=True)
+        new_cond = None
+        if not self.last_layer:
+            wp, bp = self.prompt_trans["0"].dev_f32()
+            new_cond = ops.linear_f32(upd.view(k * b * self.prompt_len, -1), wp, bp, UR_ACT_GELU).view(k * b, self.prompt_len, -1)
         return x, new_cond
 
     def forward(self, x, skip, condition):

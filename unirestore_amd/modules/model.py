@@ -317,6 +317,84 @@ class SkipConnectedAutoEncoder(nn.Module):
             return ops.image_unpad_resize(h, dec.conv_out.out_channels, out_plan[0], out_plan[1], mul=0.5, add=0.5, quantize=out_plan[2])
         return ops.nhwc_to_nchw(h, c=dec.conv_out.out_channels, mul=0.5, add=0.5)             # (x+1)/2
 
+    # ---- multi-task decode: one shared decoder head, the task-dependent tail as one task-major batch ----------------------
+    def check_tasks(self, tasks):
+        """A non-empty list / tuple of distinct task names -> tuple (TypeError for a str, ValueError when empty or duplicated,
+        KeyError(name) for a name the task editor does not know - as `decode_run` / `forward` raise it)."""
+        if isinstance(tasks, str) or not isinstance(tasks, (list, tuple)):
+            raise TypeError(f"tasks must be a list or tuple of task names, got {type(tasks).__name__} {tasks!r}")
+        tasks = tuple(tasks)
+        if not tasks:
+            raise ValueError("tasks is empty: name at least one task")
+        if len(set(tasks)) != len(tasks):
+            raise ValueError(f"tasks holds duplicates: {list(tasks)}")
+        if self.tedit_dict:
+            for t in tasks:
+                if t not in self.task_list:
+                    raise KeyError(t)
+        return tasks
+
+    def _prompt_table(self, tasks):
+        """fp32 device [K][T][D] table of the tasks' prompts, made once per task tuple (not inside graph capture)."""
+        key = ("cache", "prompt_table", tasks)
+        if key not in self.__dict__:
+            prompts = self.vae.decoder.task_prompts
+            self.__dict__[key] = torch.stack([prompts[t].detach().float() for t in tasks]).to(DEV).contiguous()
+        return self.__dict__[key]
+
+    def fanout_extent(self, lh: int, lw: int):
+        """(out_h, out_w, widest_channels) for tiling.task_chunks: out_h x out_w x widest_channels elements cover one image's
+        largest conv input (H * W * ld) among the convs that run fanned out - TFA level i and up block i run at (lh, lw) * 2^i
+        on max(block in, block out, skip) channels - from the decoder's configuration and the latent size."""
+        dec = self.vae.decoder
+        last = len(dec.up_blocks) - 1
+        elems = 0
+        for i, blk in enumerate(dec.up_blocks):
+            c = max(blk.resnets[0].conv1.in_channels, blk.resnets[0].conv1.out_channels)
+            if i < last:
+                c = max(c, dec.task_editors[i].t_gate1.in_channels)
+            elems = max(elems, (lh << i) * (lw << i) * ops.round_up(c, 8))
+        oh, ow = lh << last, lw << last
+        return oh, ow, -(-elems // (oh * ow))
+
+    def decode_run_tasks(self, z_f32: torch.Tensor, res_samples, tasks, out_plan=None):
+        """`decode_run` for several tasks of the same latents -> {task: image}, insertion order = order of `tasks`.
+        post_quant_conv, conv_in, the mid block and every TFA's task-free half run once at B; the rest runs on a task-major
+        batch (task k's image b at row k*B + b), in as few chunks of tasks as the conv launcher's size limit allows."""
+        dec, lat = self.vae.decoder, self.vae.latent_channels
+        tasks = self.check_tasks(tasks)
+        zb = ops.f32_to_bf16(z_f32, lat, mul=1.0 / self.vae.config.scaling_factor)
+        h = ops.conv(ops.conv(zb, self.vae.post_quant_conv.packed()), dec.conv_in.packed(), gn=True)
+        h = dec.mid_block.run(h)
+
+        def tail(x):
+            x = ops.conv(dec.conv_norm_out.run(x, silu=True), dec.conv_out.packed(), out_f32=True)
+            if out_plan:
+                return ops.image_unpad_resize(x, dec.conv_out.out_channels, out_plan[0], out_plan[1], mul=0.5, add=0.5, quantize=out_plan[2])
+            return ops.nhwc_to_nchw(x, c=dec.conv_out.out_channels, mul=0.5, add=0.5)
+
+        if not self.tedit_dict:                                # stock decoder: the task is ignored - one decode, a tensor per name
+            for blk in dec.up_blocks:
+                h = blk.run(h)
+            img = tail(h)
+            return {t: (img if i == 0 else img.clone()) for i, t in enumerate(tasks)}
+        b = z_f32.shape[0]
+        table = self._prompt_table(tasks)
+        shared = [None] * len(dec.task_editors)               # per level (pooled, t_gate1(skip)): once, whatever the chunking
+        out = {}
+        for first, n in tiling.task_chunks(b, len(tasks), *self.fanout_extent(z_f32.shape[1], z_f32.shape[2])):
+            x, cond = h, table[first:first + n]
+            for i, blk in enumerate(dec.up_blocks[:-1]):
+                ed, skip = dec.task_editors[i], res_samples[-i - 1]
+                if shared[i] is None:
+                    shared[i] = ed.run_shared(skip)
+                x, cond = ed.run_tasks(x, skip, cond, n, x_shared=i == 0, shared=shared[i])
+                x = blk.run(x)
+            img = tail(dec.up_blocks[-1].run(x))
+            for j in range(n):
+                out[tasks[first + j]] = img[j * b:(j + 1) * b]
+        return out
+
     # ---- reference signatures ---------------------------------------------------------------------------------
     def encode(self, images, enable_fr: bool = False, noise=None):
         _use_dtype(self)
@@ -331,6 +409,12 @@ class SkipConnectedAutoEncoder(nn.Module):
         _use_dtype(self)
         z = ops.nchw_to_nhwc(latents.to(DEV)).float()
         return self.decode_run(z.contiguous(), [ops.nchw_to_nhwc(r.to(DEV)) for r in res_samples], task)
+
+    def decode_tasks(self, latents, res_samples, tasks):
+        """`decode` for a list of tasks -> {task: image}: the task-free part of the decoder runs once (decode_run_tasks)."""
+        _use_dtype(self)
+        z = ops.nchw_to_nhwc(latents.to(DEV)).float()
+        return self.decode_run_tasks(z.contiguous(), [ops.nchw_to_nhwc(r.to(DEV)) for r in res_samples], tasks)
 
     def forward(self, images, task: str):
         latents, res = self.encode(images, enable_fr=True)
@@ -495,8 +579,8 @@ class DiffUIE(nn.Module):
 
     # ---- the hot path ------------------------------------------------------------------------------------------------
     def _forward_device(self, images, task, n_vae, n_t, plan, quantize=False):
-        """images fp32 NCHW on device (original size); plan = resize_pad_plan(H, W).
-        Returns (preds NCHW fp32 at the original size, z0, zt) (NHWC fp32 latents)."""
+        """images fp32 NCHW on device (original size); plan = resize_pad_plan(H, W); task: a name, or a tuple of names
+        (forward_tasks: preds is then {task: images}).  Returns (preds NCHW fp32 at the original size, z0, zt) (NHWC fp32 latents)."""
         lat = self.ae.vae.latent_channels
         h, w, pad_h, pad_w = plan
         z0, z0b, mids = self.ae.encode_run(images, n_vae, enable_fr=self.fr_type is not None, plan=plan)
@@ -515,7 +599,8 @@ class DiffUIE(nn.Module):
                 ops.ddim_step_(zt, ztb, eps, lat, c_x, c_e)
                 if self.trace_zt is not None and not torch.cuda.is_current_stream_capturing():
                     self.trace_zt.append(ops.nhwc_to_nchw(zt, c=lat).cpu())      # parity instrumentation (eager runs only)
-        preds = self.ae.decode_run(zt, mids, task, out_plan=((h, w), tuple(images.shape[-2:]), quantize))
+        decode = self.ae.decode_run_tasks if isinstance(task, tuple) else self.ae.decode_run     # a tuple: forward_tasks
+        preds = decode(zt, mids, task, out_plan=((h, w), tuple(images.shape[-2:]), quantize))
         return preds, z0, zt
 
     def _denoise_tiled(self, z0, n_t, tp):
@@ -542,13 +627,8 @@ class DiffUIE(nn.Module):
                 self.trace_zt.append(ops.nhwc_to_nchw(zt, c=lat).cpu())
         return zt
 
-    @torch.no_grad()
-    def forward(self, images, task: str, noise=None, return_latents=False, quantize=False):
-        """noise = (eps_vae, eps_t999): the two RNG draws of the reference (autoencoder.py:152, unifie.py:87), NCHW fp32.
-        quantize=True additionally applies the evaluator's mul(255).round().clamp(0,255).div(255) (eval_image_restoration.py:71).
-        Resize / reflect pad / un-pad / resize back (unifie.py:124-134,164-168) run as HIP kernels inside the graph."""
-        if task not in self.ae.task_list and self.tedit:
-            raise KeyError(task)
+    def _run(self, images, task, noise, quantize):
+        """Shared body of forward / forward_tasks: device copies, resize / pad plan, the two noise draws, graph or eager run."""
         self._prepare()
         images = images.to(DEV).float().contiguous()
         org_h, org_w = images.shape[-2:]
@@ -562,15 +642,42 @@ class DiffUIE(nn.Module):
         if tuple(n_vae.shape) != (b, lat, lh, lw) or tuple(n_t.shape) != (b, lat, lh, lw):
             raise ValueError(f"noise must be two tensors of shape {(b, lat, lh, lw)}")
         if self.use_graph:
-            preds, z0, zt = self._graph_forward(images, task, n_vae, n_t, plan, quantize)
-        else:
-            preds, z0, zt = self._forward_device(images, task, n_vae, n_t, plan, quantize)
-        if self.dtype == torch.float16 and self.check_fp16_overflow and not bool(torch.isfinite(preds).all()):
+            return self._graph_forward(images, task, n_vae, n_t, plan, quantize)
+        return self._forward_device(images, task, n_vae, n_t, plan, quantize)
+
+    def _check_finite(self, preds):
+        if self.dtype == torch.float16 and self.check_fp16_overflow and not all(bool(torch.isfinite(p).all()) for p in preds):
             # fp16 conversions overflow to inf (csrc/common.h Act<true>::pack2); an inf becomes NaN in the next GroupNorm /
             # softmax and reaches the image.  Heavy-tailed activations (real SD-2.x weights can produce them) need bf16.
             raise FloatingPointError("fp16 activation overflow (|x| > 65504) somewhere in the forward: the restored image is not "
                                      "finite.  Run this model with dtype='bf16' (DiffUIE.set_dtype('bf16') / trainer.precision: bf16-mixed)")
+
+    @torch.no_grad()
+    def forward(self, images, task: str, noise=None, return_latents=False, quantize=False):
+        """noise = (eps_vae, eps_t999): the two RNG draws of the reference (autoencoder.py:152, unifie.py:87), NCHW fp32.
+        quantize=True additionally applies the evaluator's mul(255).round().clamp(0,255).div(255) (eval_image_restoration.py:71).
+        Resize / reflect pad / un-pad / resize back (unifie.py:124-134,164-168) run as HIP kernels inside the graph."""
+        if task not in self.ae.task_list and self.tedit:
+            raise KeyError(task)
+        preds, z0, zt = self._run(images, task, noise, quantize)
+        self._check_finite((preds,))
+        lat = self.ae.vae.latent_channels
         if return_latents:
+            return preds, ops.nhwc_to_nchw(z0, c=lat), ops.nhwc_to_nchw(zt, c=lat)
+        return preds
+
+    @torch.no_grad()
+    def forward_tasks(self, images, tasks, noise=None, return_latents=False, quantize=False):
+        """Restore once, decode for several tasks: {task: images} in the order of `tasks` (with return_latents: that dict, z0, zt -
+        ONE z0 and ONE zt, they are shared).  Encode, both noise draws, the Controller, every denoise step and the task-free
+        part of the decoder run once; only the decoder behind the first task adapter runs per task, as one task-major batch
+        (SkipConnectedAutoEncoder.decode_run_tasks).  noise / resize / pad / quantize / the fp16 check are those of `forward`;
+        with use_graph the call is one captured graph keyed by the task tuple."""
+        tasks = self.ae.check_tasks(tasks)
+        preds, z0, zt = self._run(images, tasks, noise, quantize)
+        self._check_finite(preds.values())
+        if return_latents:
+            lat = self.ae.vae.latent_channels
             return preds, ops.nhwc_to_nchw(z0, c=lat), ops.nhwc_to_nchw(zt, c=lat)
         return preds
 
@@ -604,7 +711,7 @@ class DiffUIE(nn.Module):
             torch.cuda.synchronize()
         # the graph's output tensors are overwritten by the next replay of this (shape, task) graph: hand the caller copies
         # (runner.forward keeps [enh_hq, enh_lq] of two same-shape calls; a copy is tiny next to a forward)
-        return tuple(o.clone() for o in outs)
+        return tuple({t: v.clone() for t, v in o.items()} if isinstance(o, dict) else o.clone() for o in outs)
 
     def predict_z0(self, latents, conditions, timesteps):
         """unifie.py:91-105 (training-side helper): per-sample timesteps via per-image bias rows."""

@@ -449,6 +449,24 @@ def scale_channels(x, s, residual=None):
     return out
 
 
+FANOUT_MAX_K = 8
+
+
+def scale_channels_fanout(x, s, k):
+    """Task fan-out of `scale_channels`: x [B,...,C] shared by k tasks, s fp32 [k*B, C] (or None: k copies of x) ->
+    [k*B,...,C], task-major (task j's image b is row j*B + b).  x is read once."""
+    b, c = x.shape[0], x.shape[-1]
+    if s is not None and (s.dtype != torch.float32 or tuple(s.shape) != (k * b, c) or not s.is_contiguous()):
+        raise ValueError(f"scale_channels_fanout: s must be a contiguous fp32 [{k * b}, {c}] tensor, got {s.dtype} {tuple(s.shape)}")
+    if not x.is_contiguous():
+        raise ValueError("scale_channels_fanout: x must be contiguous")
+    out = torch.empty((k * b, *x.shape[1:]), dtype=x.dtype, device=x.device)
+    for k0 in range(0, k, FANOUT_MAX_K):                   # the kernel keeps up to 8 results per thread in flight
+        check(lib.ur_scale_channels_fanout(x.data_ptr(), None if s is None else s[k0 * b:].data_ptr(), out[k0 * b:].data_ptr(), b,
+                                           min(FANOUT_MAX_K, k - k0), x.numel() // (b * c), c, _dt(x), _stream()))
+    return out
+
+
 def spade_modulate(n, gb, residual=None):
     """y = n * (1 + gamma) + beta (+ residual); gb [..., 2C] = gamma | beta (spade.py:69)."""
     c = n.shape[-1]
@@ -477,6 +495,19 @@ def tfa_prompt_update(pooled, cond):
     b, t, d = cond.shape
     upd = torch.empty_like(cond)
     check(lib.ur_tfa_prompt_update(pooled.data_ptr(), cond.data_ptr(), upd.data_ptr(), b, t, d, _stream()))
+    return upd
+
+
+def tfa_prompt_update_fanout(pooled, cond, b, k, cond_per_row):
+    """Task fan-out of `tfa_prompt_update`: pooled fp32 [b,3,T*D] shared by k tasks; cond fp32 [k,T,D] (one prompt per task,
+    cond_per_row=False) or [k*b,T,D] (cond_per_row=True) -> upd [k*b,T,D], row j*b + i from pooled row i."""
+    rows, t, d = cond.shape
+    if rows != (k * b if cond_per_row else k) or pooled.shape[0] != b or pooled.numel() != b * 3 * t * d:
+        raise ValueError(f"tfa_prompt_update_fanout: pooled {tuple(pooled.shape)} / cond {tuple(cond.shape)} do not fit b={b}, k={k}")
+    if not (pooled.is_contiguous() and cond.is_contiguous() and pooled.dtype == cond.dtype == torch.float32):
+        raise ValueError("tfa_prompt_update_fanout: pooled and cond must be contiguous fp32 tensors")
+    upd = torch.empty((k * b, t, d), dtype=torch.float32, device=cond.device)
+    check(lib.ur_tfa_prompt_update_fanout(pooled.data_ptr(), cond.data_ptr(), upd.data_ptr(), b, k, t, d, int(bool(cond_per_row)), _stream()))
     return upd
 
 

@@ -29,13 +29,23 @@ def forward(model, inputs: Sequence[torch.Tensor], task: str, quantize: bool = F
 
 
 @torch.inference_mode()
+def forward_tasks(model, inputs: Sequence[torch.Tensor], tasks: Sequence[str], quantize: bool = False) -> List[dict]:
+    """`forward` for several tasks: one model.forward_tasks per list item -> [{task: enh}, ...] (each item restored ONCE, decoded
+    per task)."""
+    return [model.forward_tasks(imgs, tasks, quantize=quantize) for imgs in inputs]
+
+
+@torch.inference_mode()
 def validation_step(model, lq: torch.Tensor, hq: torch.Tensor = None, task: str = "ir", need_crop: bool = True,
-                    eval_types: Sequence[str] = ("lq",)):
-    """Steps 1-2 of ImageRestorationEvaluator.validation_step: crop, restore, quantise to 8 bit.  Returns (preds, hq)."""
+                    eval_types: Sequence[str] = ("lq",), tasks: Sequence[str] = None):
+    """Steps 1-2 of ImageRestorationEvaluator.validation_step: crop, restore, quantise to 8 bit.  Returns (preds, hq).
+    tasks: restore with `forward_tasks` instead - preds is then a list of {task: images}."""
     if need_crop:
         lq = crop_tensor(lq) if "lq" in eval_types else lq
         hq = crop_tensor(hq) if (hq is not None and "hq" in eval_types) else hq
     inputs = ([hq] if "hq" in eval_types and hq is not None else []) + ([lq] if "lq" in eval_types else [])
+    if tasks is not None:
+        return forward_tasks(model, inputs, tasks, quantize=True), hq
     return forward(model, inputs, task, quantize=True), hq
 
 
@@ -98,8 +108,20 @@ class LitUniFIE:
     def forward(self, inputs: Sequence[torch.Tensor], task: str, quantize: bool = False) -> List[torch.Tensor]:
         return forward(self.model, inputs, task, quantize=quantize)
 
-    def validation_step(self, batch, eval_types: Sequence[str] = ("lq",), metrics: bool = True):
+    def forward_tasks(self, inputs: Sequence[torch.Tensor], tasks: Sequence[str], quantize: bool = False) -> List[dict]:
+        return forward_tasks(self.model, inputs, tasks, quantize=quantize)
+
+    def validation_step(self, batch, eval_types: Sequence[str] = ("lq",), metrics: bool = True, tasks: Sequence[str] = None):
+        """tasks (a list that holds "ir"): every input is restored once and decoded for each task (`forward_tasks`); the return
+        value is then a list of {task: images}, and PSNR / SSIM still come from the "ir" output."""
         lq, hq, _gt, _fname, _task = batch
+        if tasks is not None:
+            if "ir" not in tasks:
+                raise ValueError(f"tasks={list(tasks)}: PSNR / SSIM are computed on the 'ir' output - add 'ir' to the list")
+            outs, _ = validation_step(self.model, lq, hq, need_crop=self.need_crop, eval_types=eval_types, tasks=tasks)
+            if metrics and hq is not None:
+                self.update_metrics(outs[-1]["ir"], hq)
+            return outs
         # the IR evaluator always restores with the "ir" prompt (eval_image_restoration.py:70: self.forward(inputs, 'ir')), whatever
         # task tag the batch carries; task-driven decoding belongs to the downstream (MTL) evaluators, which are out of scope
         preds, hq_c = validation_step(self.model, lq, hq, task="ir", need_crop=self.need_crop, eval_types=eval_types)

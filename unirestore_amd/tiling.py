@@ -59,3 +59,28 @@ def latent_tile_plan(lh: int, lw: int, tile: int, stride: int):
         acc[y:y + th, x:x + tw] += w
     wn = np.stack([w / acc[y:y + th, x:x + tw] for y, x in origins])    # singly covered: w / w, exactly 1 (w >= e^-12.5 > 0)
     return origins, (th, tw), wn.astype(np.float32)
+
+
+# ---- multi-task decode (DiffUIE.forward_tasks): how many tasks one fanned-out decoder batch may hold ---------------------------
+# ur_conv2d_nhwc addresses its inputs with 32-bit element offsets and refuses N*H*W*ld >= 2^31 (csrc/igemm.hip)
+TASK_CHUNK_MAX_ELEMS = 1 << 31
+
+
+def task_chunks(n_images: int, n_tasks: int, out_h: int, out_w: int, widest_channels: int):
+    """Split `n_tasks` into the fewest, near-equal runs of consecutive tasks [(first_task, n), ...] whose fanned-out batch of
+    n * n_images images keeps the decoder's largest conv input below the launcher's limit:
+    n * n_images * out_h * out_w * widest_channels < TASK_CHUNK_MAX_ELEMS.  out_h * out_w * widest_channels stands for the largest
+    H*W*ld of one image over the convs that run fanned out.  Chunk sizes differ by at most one task.  A single task that does not
+    fit is returned as chunks of one (the launcher's own error then surfaces, as in a single-task forward)."""
+    if n_images < 1 or n_tasks < 1 or out_h < 1 or out_w < 1 or widest_channels < 1:
+        raise ValueError(f"task_chunks: positive sizes needed, got {(n_images, n_tasks, out_h, out_w, widest_channels)}")
+    per_task = n_images * out_h * out_w * widest_channels
+    most = max((TASK_CHUNK_MAX_ELEMS - 1) // per_task, 1)
+    n_chunks = -(-n_tasks // most)
+    base, rem = divmod(n_tasks, n_chunks)
+    out, first = [], 0
+    for i in range(n_chunks):
+        n = base + (1 if i < rem else 0)
+        out.append((first, n))
+        first += n
+    return out
