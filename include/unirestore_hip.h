@@ -295,6 +295,22 @@ int ur_image_resize_pad_nhwc(const float* img, void* y, int N, int C, int H, int
  * mul(255).round().clamp(0,255).div(255) -> out fp32 [N,C,OH,OW]. */
 int ur_image_unpad_resize_nchw(const void* x, int x_is_f32, float* out, int N, int C, int XH, int XW, int ld, int CH, int CW,
                                int OH, int OW, float mul, float add, int quantize, int dtype, ur_stream_t stream);
+/* Ragged 8-bit batch: N slots of one device buffer, slot n = one dense uint8 HWC [H_n, W_n, C] image at byte offset
+ * n * slot_bytes (slot_bytes >= CH * CW * C for the batch's canvas CH x CW; an image is never larger than its canvas), and a
+ * DEVICE table geom int32 [N][4] = (H_n, W_n, RH_n, RW_n): the image is resized to RH_n x RW_n and reflect-padded right / bottom
+ * to the canvas.  The geometry is read by the kernel, not passed as arguments, so one captured launch serves any images that
+ * fit the canvas.  A table row that does not fit (H > RH, RH > CH, padding >= RH, ...) is never followed.
+ * ingest: per image float(v) / 255.f (a true division), then exactly ur_image_resize_pad_nhwc (C = 3) -> y 16-bit [N,CH,CW,Cpad];
+ *         an image gives the same bits through either entry point.  A bad table row gives a zero image. */
+int ur_image_u8_ingest(const uint8_t* src, long long slot_bytes, const int* geom, void* y, int N, int CH, int CW, int Cpad, float mul,
+                       float add, int dtype, ur_stream_t stream);
+/* egress: per image exactly ur_image_unpad_resize_nchw(..., quantize = 1) - v*mul+add, crop [0:RH_n, 0:RW_n], bicubic to
+ *         H_n x W_n, rint(v*255) clamped to 0..255 - stored as the uint8 code value, HWC, into slot n of dst.  x NHWC (16-bit | fp32)
+ *         [N,XH,XW,ld], the canvas is XH x XW.  nonfinite int32 [N], zeroed by the caller before the launch: a non-finite sample
+ *         stores code 0 and sets nonfinite[n] = 1; a bad table row writes no pixel and sets nonfinite[n] = 2.
+ * Arguments are checked before any HIP call (UR_E_INVALID).  No allocation, no synchronisation, no atomics. */
+int ur_image_u8_egress(const void* x, int x_is_f32, uint8_t* dst, long long slot_bytes, const int* geom, int* nonfinite, int N, int C,
+                       int XH, int XW, int ld, float mul, float add, int dtype, ur_stream_t stream);
 /* z = (mean + exp(0.5*clamp(logvar,-30,20)) * noise) * scale; moments NHWC fp32 [M, ld] (mean | logvar) */
 int ur_vae_sample(const float* moments, int ld, const float* noise_nchw, float* z_nhwc, void* z_16, int N,
                   int HW, int Clat, int Cpad, float scale, int dtype, ur_stream_t stream);

@@ -1,4 +1,5 @@
-"""Config entry point: `python -m unirestore_amd.cli validate --config configs/<file>.yaml [--set a.b.c=value ...]`.
+"""Config entry point: `python -m unirestore_amd.cli validate --config configs/<file>.yaml [--set a.b.c=value ...]`, and
+`python -m unirestore_amd.cli restore --config CFG --input DIR_OR_LISTFILE --output DIR` for image files.
 
 Resolves a LightningCLI-style YAML (the key schema of the reference's configs/*.yaml: `seed_everything`, `trainer.{accelerator,
 devices,precision}`, `model.class_path` + `init_args.model_kwargs.{frenc,cnet,tedit}`, `data.class_path` + `init_args`;
@@ -24,6 +25,7 @@ MODEL_CLASSES = {
     "unirestore_amd.runner.LitUniFIE": "unirestore_amd.runner.LitUniFIE",
 }
 DATA_CLASSES = {"unirestore_amd.data.SyntheticImages": "unirestore_amd.data.SyntheticImages",
+                "unirestore_amd.data.ImageListFiles": "unirestore_amd.data.ImageListFiles",
                 "data.DatasetEngine": "unirestore_amd.data.SyntheticImages"}      # datasets are out of scope: synthetic stand-in
 PRECISIONS = {"bf16-mixed": "bf16", "bf16": "bf16", "bf16-true": "bf16", "16-mixed": "fp16", "16": "fp16", "16-true": "fp16",
               "fp16": "fp16"}
@@ -92,7 +94,8 @@ def resolve(cfg: dict, allow_16bit: bool = False) -> dict:
     devices = tr.get("devices", 1)
     n_dev = len(devices) if isinstance(devices, (list, tuple)) else (int(devices) if str(devices).isdigit() else 1)
     return dict(seed=cfg.get("seed_everything", 42), dtype=dtype, devices=n_dev, model_kwargs=mk,
-                caller_args={k: init[k] for k in ("save_image", "eval_mode", "need_crop") if k in init}, data_args=dargs)
+                caller_args={k: init[k] for k in ("save_image", "eval_mode", "need_crop") if k in init}, data_args=dargs,
+                data_class=DATA_CLASSES[dcp])
 
 
 def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_16bit=False, metrics_device="cpu", tasks=None) -> dict:
@@ -116,7 +119,7 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
         dist.init_process_group("nccl", device_id=dev)
     torch.manual_seed(r["seed"])
     from . import runner
-    from .data import SyntheticImages
+    from . import data as data_mod
     from .dist import all_gather_images, broadcast_weights_sharded, shard_range
     lit = runner.LitUniFIE(r["model_kwargs"], dtype=r["dtype"], hf_root=hf_root, metrics_device=metrics_device, **r["caller_args"])
     no_ckpt = not any((r["model_kwargs"].get(k) or {}).get("ckpt_path") for k in ("frenc", "cnet", "tedit")) and not hf_root
@@ -127,7 +130,7 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
     if world > 1:
         broadcast_weights_sharded(lit.model.to(dev), src=0)
     lit.model.refresh()
-    data = SyntheticImages(**r["data_args"])
+    data = getattr(data_mod, r["data_class"].rsplit(".", 1)[1])(**r["data_args"])
     if data.batch_size < world:
         raise ValueError(f"data batch_size {data.batch_size} < world size {world}: every rank needs at least one image per batch")
     sizes = [shard_range(data.batch_size, q, world)[1] - shard_range(data.batch_size, q, world)[0] for q in range(world)]
@@ -164,9 +167,137 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
     return res if rank == 0 else None
 
 
+def check_restore_args(r: dict, inp, output, task=None, tasks=None, batch=8):
+    """Everything about a `restore` call that can be wrong without looking at a GPU -> (input paths, a task name or a tuple
+    of names).  r = resolve(cfg).  Every message names the offending argument."""
+    from . import imageio
+    if task is not None and tasks is not None:
+        raise ValueError("--task and --tasks exclude each other: one output folder, or one sub-folder per task")
+    names = [t for t in tasks.split(",") if t] if isinstance(tasks, str) else (list(tasks) if tasks is not None else None)
+    if names is not None and (not names or len(set(names)) != len(names)):
+        raise ValueError(f"--tasks {tasks!r}: needs at least one task name, each once")
+    known = list((r["model_kwargs"].get("tedit") or {}).get("task") or [])
+    for t in (names if names is not None else [task or "ir"]):
+        if known and t not in known:
+            raise KeyError(f"--task{'s' if names is not None else ''}: unknown task {t!r}; the config's task editor knows {known}")
+    if int(batch) < 1:
+        raise ValueError(f"--batch {batch}: must be >= 1")
+    if not inp or not os.path.exists(inp):
+        raise FileNotFoundError(f"--input {inp!r}: no such folder or list file")
+    if not output:
+        raise ValueError("--output: a folder for the restored PNGs is required")
+    if os.path.isdir(inp) and os.path.realpath(inp) == os.path.realpath(output):
+        raise ValueError(f"--output {output!r} is the --input folder: the restored files would overwrite or join the inputs")
+    paths = imageio.list_inputs(inp)
+    if not paths:
+        raise ValueError(f"--input {inp!r}: no image file found (extensions PIL can read; a folder is not searched recursively)")
+    missing = [p for p in paths if not os.path.isfile(p)]
+    if missing:
+        raise FileNotFoundError(f"--input {inp!r}: {len(missing)} listed file(s) do not exist, first {missing[0]!r}")
+    stems = {}
+    for p in paths:
+        stem = os.path.splitext(os.path.basename(p))[0]
+        if stem in stems:
+            raise ValueError(f"--input {inp!r}: {stems[stem]!r} and {p!r} would both be written to {stem}.png")
+        stems[stem] = p
+    return paths, (tuple(names) if names is not None else (task or "ir"))
+
+
+def restore_noise(seed: int, index: int, n: int, canvas, latent_channels: int = 4):
+    """The two noise tensors of batch `index` of a restore plan: a host generator seeded from the config's seed_everything and
+    the batch's index in the plan of ALL ranks, so a rerun draws the same noise whatever the world size."""
+    import torch
+    g = torch.Generator().manual_seed(int(seed) * 1000003 + int(index))
+    shape = (n, latent_channels, canvas[0] // 8, canvas[1] // 8)
+    return torch.randn(shape, generator=g), torch.randn(shape, generator=g)
+
+
+def restore(cfg: dict, inp, output, task=None, tasks=None, batch=8, hf_root=None, allow_16bit=False, random_init=True,
+            model=None) -> dict:
+    """Restore image files: OUTPUT/<stem>.png (OUTPUT/<task>/<stem>.png with tasks), each the size of its input.  Files are
+    grouped by canvas (imageio.plan_batches) and every batch is one DiffUIE.forward_u8 call: uint8 in, uint8 out, one captured
+    graph per (batch size, canvas).  Under torch.distributed.run rank r restores batches r, r + world, ... of the same plan and
+    writes its own files; no collective runs inside the loop.  model: a ready DiffUIE to use instead of building the config's."""
+    import torch
+    r = resolve(cfg, allow_16bit=allow_16bit)
+    paths, which = check_restore_args(r, inp, output, task, tasks, batch)
+    from . import imageio
+    sizes = [hw for _, hw in imageio.scan(paths)]
+    rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
+    plan = imageio.plan_batches(sizes, int(batch), rank, world)
+    if not torch.cuda.is_available():
+        raise RuntimeError("no GPU visible: the restoration path runs on MI355X only (no CPU fallback)")
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    dist = None
+    if world > 1:
+        import torch.distributed as dist
+        dist.init_process_group("nccl", device_id=dev)
+    torch.manual_seed(r["seed"])
+    from . import runner
+    from .dist import broadcast_weights_sharded
+    lit = runner.LitUniFIE(r["model_kwargs"], dtype=r["dtype"], hf_root=hf_root, model=model)
+    no_ckpt = not any((r["model_kwargs"].get(k) or {}).get("ckpt_path") for k in ("frenc", "cnet", "tedit")) and not hf_root
+    if model is not None:
+        model.set_dtype(r["dtype"])
+    elif no_ckpt and random_init and rank == 0:             # no checkpoint reachable: seeded random weights of the architecture
+        from .init import init_random_
+        init_random_(lit.model, r["seed"], "cpu")
+    if world > 1:
+        broadcast_weights_sharded(lit.model.to(dev), src=0)
+    model = lit.model
+    model.refresh()
+    out_dirs = {t: os.path.join(output, t) for t in which} if isinstance(which, tuple) else {which: output}
+    for d in out_dirs.values():
+        os.makedirs(d, exist_ok=True)
+    captures_before, saves = model.graph_captures, []
+    n_img, n_timed, secs, finite = 0, 0, 0.0, True
+    t_all = time.perf_counter()
+    with imageio.io_pool() as pool:
+        for b, images in imageio.Prefetcher(plan, paths, pool):
+            noise = restore_noise(r["seed"], b.index, len(b.members), b.canvas, model.ae.vae.latent_channels)
+            torch.cuda.synchronize()
+            captures, t0 = model.graph_captures, time.perf_counter()
+            preds = model.forward_u8(images, which, noise=noise)
+            by_task = preds if isinstance(which, tuple) else {which: preds}
+            host = {t: [x.cpu() for x in v[:b.valid]] for t, v in by_task.items()}      # the repeats of a padded batch are dropped
+            dt = time.perf_counter() - t0
+            finite = finite and not any(model.u8_nonfinite())
+            if model.graph_captures == captures:          # a batch that captured its graph is not timed (validate: batch 0)
+                secs += dt
+                n_timed += b.valid
+            n_img += b.valid
+            while len(saves) > 4 * int(batch):            # bounded: encoding must not fall behind without limit
+                saves.pop(0).result()
+            for t, imgs in host.items():
+                for i, x in zip(b.members, imgs):
+                    stem = os.path.splitext(os.path.basename(paths[i]))[0]
+                    saves.append(pool.submit(imageio.save_u8, x, os.path.join(out_dirs[t], stem + ".png")))
+        for f in saves:
+            f.result()
+    total_s = time.perf_counter() - t_all
+    graphs = model.graph_captures - captures_before
+    counts = torch.tensor([n_img, n_timed, graphs, 0 if finite else 1], dtype=torch.float64, device=dev)
+    times = torch.tensor([secs, total_s], dtype=torch.float64, device=dev)
+    if world > 1:
+        dist.all_reduce(counts)
+        dist.all_reduce(times, op=dist.ReduceOp.MAX)
+    n_img, n_timed, graphs, bad = (int(v) for v in counts.tolist())
+    secs, total_s = times.tolist()
+    res = dict(images=n_img, input_sizes=len(set(sizes)), canvases=len({imageio.canvas_of(h, w) for h, w in sizes}),
+               graphs_captured=graphs, batch=int(batch), tasks=list(which) if isinstance(which, tuple) else [which],
+               dtype=r["dtype"], n_gpus=world, denoise_steps=r["model_kwargs"]["cnet"]["num_inference_steps"],
+               images_per_s=(n_timed / secs) if secs > 0 else None, images_timed=n_timed, seconds_total=total_s,
+               output_finite=not bad, output=output)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+    return res if rank == 0 else None
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m unirestore_amd.cli")
-    ap.add_argument("command", choices=["validate", "print_config"])
+    ap.add_argument("command", choices=["validate", "print_config", "restore"])
     ap.add_argument("--config", required=True)
     ap.add_argument("--set", action="append", default=[], metavar="a.b.c=value", help="override a config key")
     ap.add_argument("--hf-root", default=None, help="folder with unet/ and vae/ diffusion_pytorch_model.safetensors (sd-turbo)")
@@ -175,12 +306,22 @@ def main(argv=None):
     ap.add_argument("--metrics-device", choices=["cpu", "gpu"], default="cpu",
                     help="where PSNR / SSIM run: cpu = host fp64 (default), gpu = the HIP metric kernels (fp64, no per-batch host sync)")
     ap.add_argument("--tasks", default=None, metavar="ir,cls,seg",
-                    help="restore every batch once and decode it for each of these tasks (forward_tasks); must hold 'ir', which feeds PSNR / SSIM")
+                    help="restore every batch once and decode it for each of these tasks (forward_tasks); validate: must hold 'ir', which "
+                         "feeds PSNR / SSIM; restore: one sub-folder of --output per task")
+    ap.add_argument("--task", default=None, help="restore: the task to decode for (default ir)")
+    ap.add_argument("--input", default=None, help="restore: a folder of images, or a text file with one path (or `lq hq label`) per line")
+    ap.add_argument("--output", default=None, help="restore: folder for <stem>.png")
+    ap.add_argument("--batch", type=int, default=8, help="restore: images per forward (images of a batch share a canvas)")
     a = ap.parse_args(argv)
     cfg = load_config(a.config, a.set)
     if a.command == "print_config":
         print(yaml.safe_dump(cfg, sort_keys=False))
         print(json.dumps(resolve(cfg, allow_16bit=a.allow_16bit)))
+        return 0
+    if a.command == "restore":
+        res = restore(cfg, a.input, a.output, task=a.task, tasks=a.tasks, batch=a.batch, hf_root=a.hf_root, allow_16bit=a.allow_16bit)
+        if res is not None:
+            print(json.dumps(res))
         return 0
     res = validate(cfg, hf_root=a.hf_root, max_batches=a.max_batches, allow_16bit=a.allow_16bit, metrics_device=a.metrics_device,
                    tasks=[t for t in a.tasks.split(",") if t] if a.tasks is not None else None)

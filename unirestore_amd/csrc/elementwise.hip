@@ -355,6 +355,41 @@ __device__ __forceinline__ void cubic_taps(int dst, float scale, int in_size, in
   for (int j = 0; j < 4; ++j) idx[j] = max(min(i0 + j - 1, in_size - 1), 0);
 }
 
+// The tap / accumulate arithmetic of the two boundary directions, shared by the fp32-tensor kernels and the ragged 8-bit ones
+// (image_u8_ingest_kernel / image_u8_egress_kernel) so that both compile from the same expressions: an image gives the same bits
+// whichever kernel it goes through.  `at(a, b)` returns the source sample at tap row a, tap column b.
+__device__ __forceinline__ int reflect_index(int o, int size) { return o < size ? o : 2 * (size - 1) - o; }   // F.pad(mode="reflect")
+
+// sum_a wy[a] * (sum_b wx[b] * at(a, b)), written out with explicit fused multiply-adds and contraction off: which products of
+// such a sum the compiler fuses depends on the code around it (its vectoriser pairs lanes differently in each kernel), and a
+// differently fused product is a different fp32 result.  The pattern is the one image_resize_pad_kernel has always compiled to.
+template <class At>
+__device__ __forceinline__ float bicubic_in(const float wy[4], const float wx[4], At at) {
+#pragma clang fp contract(off)
+  float row[4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const float head = __builtin_fmaf(wx[2], at(a, 2), __builtin_fmaf(wx[0], at(a, 0), wx[1] * at(a, 1)));
+    row[a] = a < 3 ? head + wx[3] * at(a, 3) : __builtin_fmaf(wx[3], at(a, 3), head);
+  }
+  return __builtin_fmaf(wy[3], row[3], __builtin_fmaf(wy[2], row[2], __builtin_fmaf(wy[1], row[1], __builtin_fmaf(wy[0], row[0], 0.f))));
+}
+
+template <class At>
+__device__ __forceinline__ float bicubic_out(const float wy[4], const float wx[4], int taps, float mul, float add, At at) {
+  float v = 0.f;
+  for (int a = 0; a < taps; ++a) {
+    float rowv = 0.f;
+    for (int b = 0; b < taps; ++b) rowv += wx[b] * (at(a, b) * mul + add);
+    v += wy[a] * rowv;
+  }
+  return v;
+}
+
+// torch.round = half-to-even = rintf; the code value 0..255 as a float
+__device__ __forceinline__ float quantize_code(float v) { return fminf(fmaxf(rintf(v * 255.f), 0.f), 255.f); }
+__device__ __forceinline__ bool finite_sample(float v) { return fabsf(v) <= 3.0e38f; }
+
 // img [N,C,H,W] fp32 -> (bicubic to RH x RW) -> reflect pad right/bottom -> v*mul+add -> y bf16 [N,RH+PH,RW+PW,Cpad]
 template <bool F16>
 __global__ __launch_bounds__(256) void image_resize_pad_kernel(const float* __restrict__ img, uint16_t* __restrict__ y, int C,
@@ -367,7 +402,7 @@ __global__ __launch_bounds__(256) void image_resize_pad_kernel(const float* __re
     const int ox = (int)(i % OW);
     const long long r = i / OW;
     const int oy = (int)(r % OH), n = (int)(r / OH);
-    const int ry = oy < RH ? oy : 2 * (RH - 1) - oy, rx = ox < RW ? ox : 2 * (RW - 1) - ox;   // F.pad(mode="reflect")
+    const int ry = reflect_index(oy, RH), rx = reflect_index(ox, RW);
     const float* base = img + (long long)n * C * H * W;
     uint16_t* yo = y + i * Cpad;
     if (!resize) {
@@ -382,11 +417,7 @@ __global__ __launch_bounds__(256) void image_resize_pad_kernel(const float* __re
       float v = 0.f;
       if (c < C) {
         const float* pc = base + (long long)c * H * W;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-          const float* row = pc + (long long)iy[a] * W;
-          v += wy[a] * (wx[0] * row[ix[0]] + wx[1] * row[ix[1]] + wx[2] * row[ix[2]] + wx[3] * row[ix[3]]);
-        }
+        v = bicubic_in(wy, wx, [&](int a, int b) { return pc[(long long)iy[a] * W + ix[b]]; });
       }
       yo[c] = c < C ? f2h16<F16>(v * mul + add) : (uint16_t)0;
     }
@@ -410,21 +441,93 @@ __global__ __launch_bounds__(256) void image_unpad_resize_kernel(const void* __r
     if (resize) { cubic_taps(oy, sh, CH, iy, wy); cubic_taps(ox, sw, CW, ix, wx); }
     const long long nb = (long long)n * XH * XW;
     for (int c = 0; c < C; ++c) {
-      float v = 0.f;
-      const int taps = resize ? 4 : 1;
-      for (int a = 0; a < taps; ++a) {
-        float rowv = 0.f;
-        for (int b = 0; b < taps; ++b) {
-          const long long e = (nb + (long long)iy[a] * XW + ix[b]) * ld + c;
-          const float t = is_f32 ? reinterpret_cast<const float*>(x)[e] : Act<F16>::one(reinterpret_cast<const uint16_t*>(x)[e]);
-          rowv += wx[b] * (t * mul + add);
-        }
-        v += wy[a] * rowv;
-      }
-      // torch.round = half-to-even = rintf.  A non-finite value stays non-finite (torch.clamp propagates NaN; fmaxf would turn it into a
-      // black pixel and hide an fp16 overflow from DiffUIE.forward's finite check): NaN and +-inf both leave as NaN.
-      if (quantize) v = (fabsf(v) <= 3.0e38f) ? fminf(fmaxf(rintf(v * 255.f), 0.f), 255.f) / 255.f : __builtin_nanf("");
+      float v = bicubic_out(wy, wx, resize ? 4 : 1, mul, add, [&](int a, int b) {
+        const long long e = (nb + (long long)iy[a] * XW + ix[b]) * ld + c;
+        return is_f32 ? reinterpret_cast<const float*>(x)[e] : Act<F16>::one(reinterpret_cast<const uint16_t*>(x)[e]);
+      });
+      // A non-finite value stays non-finite (torch.clamp propagates NaN; fmaxf would turn it into a black pixel and hide an
+      // fp16 overflow from DiffUIE.forward's finite check): NaN and +-inf both leave as NaN.
+      if (quantize) v = finite_sample(v) ? quantize_code(v) / 255.f : __builtin_nanf("");
       out[(((long long)n * C + c) * OH + oy) * OW + ox] = v;
+    }
+  }
+}
+
+// ---- ragged 8-bit batch: slot n of `src` / `dst` holds one dense uint8 HWC [H_n, W_n, 3] image at n * slot_bytes;
+// geom int32 [N,4] = (H_n, W_n, RH_n, RW_n) in DEVICE memory, so that one captured launch serves any images that fit the canvas.
+// A row of geom that does not fit the canvas is never followed: ingest writes zeros, egress writes nothing but flag 2.
+__device__ __forceinline__ bool ragged_geom_ok(int H, int W, int RH, int RW, int CH, int CW) {
+  return H > 0 && W > 0 && H <= RH && W <= RW && RH <= CH && RW <= CW && CH - RH < RH && CW - RW < RW;
+}
+
+// u8 / 255 (a true division, = torch's u8.float() / 255) -> what image_resize_pad_kernel does -> y 16-bit [N,CH,CW,Cpad]
+template <bool F16>
+__global__ __launch_bounds__(256) void image_u8_ingest_kernel(const uint8_t* __restrict__ src, long long slot_bytes,
+                                                              const int* __restrict__ geom, uint16_t* __restrict__ y, int CH, int CW,
+                                                              int Cpad, float mul, float add, long long total) {
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int ox = (int)(i % CW);
+    const long long r = i / CW;
+    const int oy = (int)(r % CH), n = (int)(r / CH);
+    const int H = geom[4 * n], W = geom[4 * n + 1], RH = geom[4 * n + 2], RW = geom[4 * n + 3];
+    uint16_t* yo = y + i * Cpad;
+    if (!ragged_geom_ok(H, W, RH, RW, CH, CW)) {
+      for (int c = 0; c < Cpad; ++c) yo[c] = 0;
+      continue;
+    }
+    const bool resize = RH != H || RW != W;
+    const float sh = (float)H / RH, sw = (float)W / RW;
+    const int ry = reflect_index(oy, RH), rx = reflect_index(ox, RW);
+    const uint8_t* base = src + n * slot_bytes;
+    if (!resize) {
+      const uint8_t* px = base + ((long long)ry * W + rx) * 3;
+      for (int c = 0; c < Cpad; ++c) yo[c] = c < 3 ? f2h16<F16>((float)px[c] / 255.f * mul + add) : (uint16_t)0;
+      continue;
+    }
+    int iy[4], ix[4];
+    float wy[4], wx[4];
+    cubic_taps(ry, sh, H, iy, wy);
+    cubic_taps(rx, sw, W, ix, wx);
+    for (int c = 0; c < Cpad; ++c) {
+      float v = 0.f;
+      if (c < 3) v = bicubic_in(wy, wx, [&](int a, int b) { return (float)base[((long long)iy[a] * W + ix[b]) * 3 + c] / 255.f; });
+      yo[c] = c < 3 ? f2h16<F16>(v * mul + add) : (uint16_t)0;
+    }
+  }
+}
+
+// what image_unpad_resize_kernel does with quantize -> the code value as uint8 HWC into slot n.  One thread per CANVAS pixel
+// (the launch cannot know H_n x W_n); threads outside the image leave.  A non-finite sample stores code 0 and sets nonfinite[n].
+template <bool F16>
+__global__ __launch_bounds__(256) void image_u8_egress_kernel(const void* __restrict__ x, int is_f32, uint8_t* __restrict__ dst,
+                                                              long long slot_bytes, const int* __restrict__ geom,
+                                                              int* __restrict__ nonfinite, int C, int XH, int XW, int ld, float mul,
+                                                              float add, long long total) {
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int ox = (int)(i % XW);
+    const long long r = i / XW;
+    const int oy = (int)(r % XH), n = (int)(r / XH);
+    const int OH = geom[4 * n], OW = geom[4 * n + 1], CH = geom[4 * n + 2], CW = geom[4 * n + 3];
+    if (!ragged_geom_ok(OH, OW, CH, CW, XH, XW)) {
+      if (oy == 0 && ox == 0) nonfinite[n] = 2;
+      continue;
+    }
+    if (oy >= OH || ox >= OW) continue;
+    const bool resize = OH != CH || OW != CW;
+    const float sh = (float)CH / OH, sw = (float)CW / OW;
+    int iy[4] = {oy, 0, 0, 0}, ix[4] = {ox, 0, 0, 0};
+    float wy[4] = {1.f, 0.f, 0.f, 0.f}, wx[4] = {1.f, 0.f, 0.f, 0.f};
+    if (resize) { cubic_taps(oy, sh, CH, iy, wy); cubic_taps(ox, sw, CW, ix, wx); }
+    const long long nb = (long long)n * XH * XW;
+    uint8_t* px = dst + n * slot_bytes + ((long long)oy * OW + ox) * C;
+    for (int c = 0; c < C; ++c) {
+      const float v = bicubic_out(wy, wx, resize ? 4 : 1, mul, add, [&](int a, int b) {
+        const long long e = (nb + (long long)iy[a] * XW + ix[b]) * ld + c;
+        return is_f32 ? reinterpret_cast<const float*>(x)[e] : Act<F16>::one(reinterpret_cast<const uint16_t*>(x)[e]);
+      });
+      const bool ok = finite_sample(v);
+      if (!ok) nonfinite[n] = 1;
+      px[c] = ok ? (uint8_t)quantize_code(v) : (uint8_t)0;
     }
   }
 }
@@ -689,6 +792,30 @@ int ur_image_unpad_resize_nchw(const void* x, int x_is_f32, float* out, int N, i
   UR_DT_SWITCH(dtype, hipLaunchKernelGGL(image_unpad_resize_kernel<F16>, dim3(nblocks(total)), dim3(256), 0, (hipStream_t)stream, x, x_is_f32, out, C, XH, XW,
                      ld, CH, CW, OH, OW, mul, add, quantize, total));
   return ur::check_launch("ur_image_unpad_resize_nchw");
+}
+
+int ur_image_u8_ingest(const uint8_t* src, long long slot_bytes, const int* geom, void* y, int N, int CH, int CW, int Cpad, float mul,
+                       float add, int dtype, ur_stream_t stream) {
+  UR_REQUIRE_DT(dtype);
+  UR_REQUIRE(src && geom && y, "null pointer");
+  UR_REQUIRE(N > 0 && CH > 0 && CW > 0 && Cpad >= 3, "N, CH, CW must be positive and Cpad >= 3");
+  UR_REQUIRE(slot_bytes >= 3LL * CH * CW, "slot_bytes must hold a canvas-sized image (CH * CW * 3)");
+  const long long total = (long long)N * CH * CW;
+  UR_DT_SWITCH(dtype, hipLaunchKernelGGL(image_u8_ingest_kernel<F16>, dim3(nblocks(total)), dim3(256), 0, (hipStream_t)stream, src, slot_bytes, geom,
+                     (uint16_t*)y, CH, CW, Cpad, mul, add, total));
+  return ur::check_launch("ur_image_u8_ingest");
+}
+
+int ur_image_u8_egress(const void* x, int x_is_f32, uint8_t* dst, long long slot_bytes, const int* geom, int* nonfinite, int N, int C,
+                       int XH, int XW, int ld, float mul, float add, int dtype, ur_stream_t stream) {
+  UR_REQUIRE_DT(dtype);
+  UR_REQUIRE(x && dst && geom && nonfinite, "null pointer");
+  UR_REQUIRE(N > 0 && XH > 0 && XW > 0 && C > 0 && ld >= C, "N, C, XH, XW must be positive and ld >= C");
+  UR_REQUIRE(slot_bytes >= (long long)C * XH * XW, "slot_bytes must hold a canvas-sized image (XH * XW * C)");
+  const long long total = (long long)N * XH * XW;
+  UR_DT_SWITCH(dtype, hipLaunchKernelGGL(image_u8_egress_kernel<F16>, dim3(nblocks(total)), dim3(256), 0, (hipStream_t)stream, x, x_is_f32, dst,
+                     slot_bytes, geom, nonfinite, C, XH, XW, ld, mul, add, total));
+  return ur::check_launch("ur_image_u8_egress");
 }
 
 int ur_vae_sample(const float* moments, int ld, const float* noise_nchw, float* z_nhwc, void* z_16, int N, int HW,

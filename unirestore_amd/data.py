@@ -1,4 +1,5 @@
-"""Synthetic inputs for the config entry points (the reference's datasets / corruption pipeline are out of scope).
+"""Inputs for the config entry points: seeded synthetic images (the reference's corruption pipeline is out of scope) and
+`ImageListFiles`, real pairs from the reference's `lq hq label` list files.
 
 `SyntheticImages` yields the evaluator's batch tuple `(lq, hq, gt, fname, task)` (reference
 src/core/base/eval_image_restoration.py:56) from seeded random images: hq = torch.rand (what the reference's own smoke
@@ -47,3 +48,54 @@ class SyntheticImages:
             lq = torch.stack([degrade(hq[i], self.degradations[i % len(self.degradations)], g) for i in range(self.batch_size)])
             names = [f"syn_{b:04d}_{i:03d}" for i in range(lo, hi)]
             yield lq[lo:hi].to(device), hq[lo:hi].to(device), None, names, self.task
+
+
+class ImageListFiles:
+    """Real pairs for `validate` (`data.class_path: unirestore_amd.data.ImageListFiles`): a text file with one `lq hq [label]`
+    line per pair, paths relative to the list file's folder.  Yields the evaluator's tuple `(lq, hq, gt, fname, task)` with lq / hq
+    fp32 NCHW in [0, 1] (u8 / 255, the reference's ToDtype(scale=True)); pairs are grouped by shape, list order kept inside a
+    group, so every batch is one tensor (the evaluator's centre crop makes nearly everything 512 x 512)."""
+
+    def __init__(self, list_file: str, batch_size: int = 8, task: str = "ir", num_batches: int = None):
+        import os
+        self.list_file, self.batch_size, self.task, self.num_batches = list_file, int(batch_size), task, num_batches
+        base = os.path.dirname(os.path.abspath(list_file))
+        self.pairs = []
+        with open(list_file) as f:
+            for ln, line in enumerate(f, 1):
+                cols = line.split()
+                if not cols or cols[0].startswith("#"):
+                    continue
+                if len(cols) < 2:
+                    raise ValueError(f"{list_file}:{ln}: expected `lq hq [label]`, got {line.strip()!r}")
+                self.pairs.append(tuple(c if os.path.isabs(c) else os.path.join(base, c) for c in cols[:2]))
+        if not self.pairs:
+            raise ValueError(f"{list_file}: no `lq hq [label]` line")
+
+    def _plan(self):
+        from .imageio import scan
+        groups = {}
+        for i, (_, hw) in enumerate(scan(lq for lq, _ in self.pairs)):
+            groups.setdefault(hw, []).append(i)
+        cuts = [idx[s:s + self.batch_size] for idx in groups.values() for s in range(0, len(idx), self.batch_size)]
+        cuts.sort(key=lambda c: c[0])
+        return cuts[:self.num_batches]
+
+    def __len__(self):
+        return len(self._plan())
+
+    def batches(self, rank: int = 0, world: int = 1, device="cpu") -> Iterator[Tuple[torch.Tensor, torch.Tensor, None, List[str], str]]:
+        import os
+
+        from .imageio import load_u8
+        if world != 1:
+            raise ValueError("ImageListFiles does not shard a batch over ranks (batches of real files differ in size): run "
+                             "`validate` on one GPU, or restore the files with `cli restore`, which spreads batches over ranks")
+
+        def nchw(paths):
+            return torch.stack([load_u8(p).permute(2, 0, 1) for p in paths]).float().div(255).to(device)
+        for idx in self._plan():
+            lq, hq = nchw([self.pairs[i][0] for i in idx]), nchw([self.pairs[i][1] for i in idx])
+            if lq.shape != hq.shape:
+                raise ValueError(f"{self.list_file}: lq and hq of {self.pairs[idx[0]][0]!r}... differ in size: {tuple(lq.shape)} vs {tuple(hq.shape)}")
+            yield lq, hq, None, [os.path.splitext(os.path.basename(self.pairs[i][0]))[0] for i in idx], self.task

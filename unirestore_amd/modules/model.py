@@ -275,9 +275,13 @@ class SkipConnectedAutoEncoder(nn.Module):
     # ---- NHWC fast path -------------------------------------------------------------------------------------
     def encode_run(self, images_dev: torch.Tensor, noise_nchw: torch.Tensor, enable_fr: bool, plan=None):
         """images fp32 NCHW in [0,1] on device -> (z fp32 [B,h,w,8], z bf16, [3 NHWC bf16 skip features]).
-        plan = (resized_h, resized_w, pad_h, pad_w): DiffUIE.forward's bicubic resize + reflect pad run in the layout kernel."""
+        plan = (resized_h, resized_w, pad_h, pad_w): DiffUIE.forward's bicubic resize + reflect pad run in the layout kernel.
+        plan = a RaggedIO: images_dev is its uint8 slot buffer, the per-image geometry comes from its device table."""
         enc, lat = self.vae.encoder, self.vae.latent_channels
-        x0 = ops.image_resize_pad(images_dev, *plan) if plan else ops.nchw_to_nhwc(images_dev, image=True)   # x*2-1 fused
+        if isinstance(plan, RaggedIO):
+            x0 = plan.ingest(images_dev)
+        else:
+            x0 = ops.image_resize_pad(images_dev, *plan) if plan else ops.nchw_to_nhwc(images_dev, image=True)   # x*2-1 fused
         h = ops.conv(x0, enc.conv_in.packed(), gn=True)
         res = []
         for i, blk in enumerate(enc.down_blocks[:-1]):
@@ -292,7 +296,8 @@ class SkipConnectedAutoEncoder(nn.Module):
         return z, zb, res
 
     def decode_run(self, z_f32: torch.Tensor, res_samples, task: str, out_plan=None):
-        """out_plan = (crop_hw, out_hw, quantize): un-pad + bicubic resize back (+ 8-bit quantisation) in the layout kernel."""
+        """out_plan = (crop_hw, out_hw, quantize): un-pad + bicubic resize back (+ 8-bit quantisation) in the layout kernel.
+        out_plan = a RaggedIO: the same per image from its device table, the result is its uint8 slot buffer."""
         dec, lat = self.vae.decoder, self.vae.latent_channels
         if self.tedit_dict and task not in dec.task_prompts:
             raise KeyError(task)
@@ -313,6 +318,8 @@ class SkipConnectedAutoEncoder(nn.Module):
                 h = blk.run(h)
             h = dec.up_blocks[-1].run(h)
         h = ops.conv(dec.conv_norm_out.run(h, silu=True), dec.conv_out.packed(), out_f32=True)
+        if isinstance(out_plan, RaggedIO):
+            return out_plan.egress(h, dec.conv_out.out_channels)
         if out_plan:
             return ops.image_unpad_resize(h, dec.conv_out.out_channels, out_plan[0], out_plan[1], mul=0.5, add=0.5, quantize=out_plan[2])
         return ops.nhwc_to_nchw(h, c=dec.conv_out.out_channels, mul=0.5, add=0.5)             # (x+1)/2
@@ -360,7 +367,11 @@ class SkipConnectedAutoEncoder(nn.Module):
     def decode_run_tasks(self, z_f32: torch.Tensor, res_samples, tasks, out_plan=None):
         """`decode_run` for several tasks of the same latents -> {task: image}, insertion order = order of `tasks`.
         post_quant_conv, conv_in, the mid block and every TFA's task-free half run once at B; the rest runs on a task-major
-        batch (task k's image b at row k*B + b), in as few chunks of tasks as the conv launcher's size limit allows."""
+        batch (task k's image b at row k*B + b), in as few chunks of tasks as the conv launcher's size limit allows.
+        With a RaggedIO as out_plan (forward_u8) every chunk is ONE task: the conv launchers plan a batch of K*B differently from a
+        batch of B, so a fanned-out tail differs from the single-task decode in the last bits, and an 8-bit file must not depend
+        on which other tasks were asked for.  The head and the task-free halves still run once; the tail's cost is linear in K*B
+        either way (22.5 ms per task at B = 8, 512 x 512)."""
         dec, lat = self.vae.decoder, self.vae.latent_channels
         tasks = self.check_tasks(tasks)
         zb = ops.f32_to_bf16(z_f32, lat, mul=1.0 / self.vae.config.scaling_factor)
@@ -369,6 +380,8 @@ class SkipConnectedAutoEncoder(nn.Module):
 
         def tail(x):
             x = ops.conv(dec.conv_norm_out.run(x, silu=True), dec.conv_out.packed(), out_f32=True)
+            if isinstance(out_plan, RaggedIO):
+                return out_plan.egress(x, dec.conv_out.out_channels)
             if out_plan:
                 return ops.image_unpad_resize(x, dec.conv_out.out_channels, out_plan[0], out_plan[1], mul=0.5, add=0.5, quantize=out_plan[2])
             return ops.nhwc_to_nchw(x, c=dec.conv_out.out_channels, mul=0.5, add=0.5)
@@ -382,7 +395,9 @@ class SkipConnectedAutoEncoder(nn.Module):
         table = self._prompt_table(tasks)
         shared = [None] * len(dec.task_editors)               # per level (pooled, t_gate1(skip)): once, whatever the chunking
         out = {}
-        for first, n in tiling.task_chunks(b, len(tasks), *self.fanout_extent(z_f32.shape[1], z_f32.shape[2])):
+        chunks = [(k, 1) for k in range(len(tasks))] if isinstance(out_plan, RaggedIO) else \
+            tiling.task_chunks(b, len(tasks), *self.fanout_extent(z_f32.shape[1], z_f32.shape[2]))
+        for first, n in chunks:
             x, cond = h, table[first:first + n]
             for i, blk in enumerate(dec.up_blocks[:-1]):
                 ed, skip = dec.task_editors[i], res_samples[-i - 1]
@@ -421,6 +436,32 @@ class SkipConnectedAutoEncoder(nn.Module):
         return self.decode(latents, res, "ir")
 
 
+class RaggedIO:
+    """The ragged form of `encode_run`'s plan= and `decode_run` / `decode_run_tasks`' out_plan=: a batch of 8-bit images of
+    different sizes that share one canvas.  geom: device int32 [N, 4] rows (H, W, RH, RW); the boundary kernels read it at run
+    time, so a captured graph serves any images that fit the canvas.  `flags` collects one int32 [N] non-finite flag tensor per
+    egress launch (one launch per decoded task)."""
+
+    def __init__(self, geom: torch.Tensor, canvas):
+        self.geom, self.canvas = geom, (int(canvas[0]), int(canvas[1]))
+        self.flags = []
+
+    def ingest(self, slots):
+        return ops.image_u8_ingest(slots, self.geom, self.canvas, validate=False)        # x*2-1 fused, as image_resize_pad
+
+    def egress(self, x, c):
+        flags = torch.zeros(x.shape[0], dtype=torch.int32, device=x.device)      # zeroed in the graph, before the launch
+        out, _ = ops.image_u8_egress(x, c, self.geom, mul=0.5, add=0.5, nonfinite=flags, validate=False)
+        self.flags.append(flags)
+        return out
+
+
+def canvas_of(h: int, w: int):
+    """(CH, CW): the size the model sees for an h x w image - all that a captured graph depends on."""
+    rh, rw, ph, pw = resize_pad_plan(h, w)
+    return rh + ph, rw + pw
+
+
 def resize_pad_plan(h: int, w: int):
     """Integer shape arithmetic of unifie.py:121-134 -> (resized_h, resized_w, pad_h, pad_w)."""
     if h < 512 or w < 512:
@@ -447,6 +488,7 @@ class DiffUIE(nn.Module):
         self.trace_zt = None                   # parity instrumentation: a list collects zt after every DDIM step (eager runs only)
         self.check_fp16_overflow = True        # fp16 only: one isfinite reduction over the restored images per forward (+ a sync)
         self._graphs = {}
+        self.graph_captures = 0                # graphs captured so far (a graph evicted by UR_MAX_GRAPHS is captured again)
         if self.control_type:
             ccfg = controller_cfg or stablesr_config
             self.controller = Controller(**ccfg)
@@ -580,9 +622,10 @@ class DiffUIE(nn.Module):
     # ---- the hot path ------------------------------------------------------------------------------------------------
     def _forward_device(self, images, task, n_vae, n_t, plan, quantize=False):
         """images fp32 NCHW on device (original size); plan = resize_pad_plan(H, W); task: a name, or a tuple of names
-        (forward_tasks: preds is then {task: images}).  Returns (preds NCHW fp32 at the original size, z0, zt) (NHWC fp32 latents)."""
+        (forward_tasks: preds is then {task: images}).  Returns (preds NCHW fp32 at the original size, z0, zt) (NHWC fp32 latents).
+        forward_u8: images is the uint8 slot buffer and plan a RaggedIO; preds are then uint8 slot buffers."""
         lat = self.ae.vae.latent_channels
-        h, w, pad_h, pad_w = plan
+        out_plan = plan if isinstance(plan, RaggedIO) else (plan[:2], tuple(images.shape[-2:]), quantize)
         z0, z0b, mids = self.ae.encode_run(images, n_vae, enable_fr=self.fr_type is not None, plan=plan)
         zt = z0
         tp = self._tile_plan(z0.shape[1], z0.shape[2]) if self.control_type else None
@@ -600,7 +643,7 @@ class DiffUIE(nn.Module):
                 if self.trace_zt is not None and not torch.cuda.is_current_stream_capturing():
                     self.trace_zt.append(ops.nhwc_to_nchw(zt, c=lat).cpu())      # parity instrumentation (eager runs only)
         decode = self.ae.decode_run_tasks if isinstance(task, tuple) else self.ae.decode_run     # a tuple: forward_tasks
-        preds = decode(zt, mids, task, out_plan=((h, w), tuple(images.shape[-2:]), quantize))
+        preds = decode(zt, mids, task, out_plan=out_plan)
         return preds, z0, zt
 
     def _denoise_tiled(self, z0, n_t, tp):
@@ -645,8 +688,13 @@ class DiffUIE(nn.Module):
             return self._graph_forward(images, task, n_vae, n_t, plan, quantize)
         return self._forward_device(images, task, n_vae, n_t, plan, quantize)
 
-    def _check_finite(self, preds):
-        if self.dtype == torch.float16 and self.check_fp16_overflow and not all(bool(torch.isfinite(p).all()) for p in preds):
+    def _check_finite(self, preds, flags=None):
+        """preds: fp32 images, searched for a non-finite value; or flags: the int32 flag tensors of a RaggedIO (an 8-bit image
+        cannot carry a NaN) - one small device-to-host read."""
+        if self.dtype != torch.float16 or not self.check_fp16_overflow:
+            return
+        bad = any(torch.cat(flags).tolist()) if flags is not None else not all(bool(torch.isfinite(p).all()) for p in preds)
+        if bad:
             # fp16 conversions overflow to inf (csrc/common.h Act<true>::pack2); an inf becomes NaN in the next GroupNorm /
             # softmax and reaches the image.  Heavy-tailed activations (real SD-2.x weights can produce them) need bf16.
             raise FloatingPointError("fp16 activation overflow (|x| > 65504) somewhere in the forward: the restored image is not "
@@ -681,34 +729,121 @@ class DiffUIE(nn.Module):
             return preds, ops.nhwc_to_nchw(z0, c=lat), ops.nhwc_to_nchw(zt, c=lat)
         return preds
 
+    # ---- 8-bit images of different sizes that share a canvas: one graph per (N, canvas), uint8 in and out ------------------
+    @torch.no_grad()
+    def forward_u8(self, images, task, noise=None, return_latents=False):
+        """images: a sequence of uint8 [H_i, W_i, 3] tensors (host or device) with ONE canvas (`canvas_of`; ValueError otherwise)
+        -> a list of restored uint8 [H_i, W_i, 3] device tensors, or {task: list} when `task` is a list / tuple of names (the
+        body is then forward_tasks's, except that the task-dependent decoder tail runs task by task, so that every task's images equal
+        forward_u8(images, that task) bit for bit).  What `forward(u8 / 255, quantize=True) * 255` gives per image, but the sizes live in a
+        device table that every call refreshes, not in the captured launches: with use_graph, calls that share the number of
+        images and the canvas replay the same graph whatever the H_i x W_i.  noise = (eps_vae, eps_t999) [N, 4, CH/8, CW/8].
+        The fp16 check reads the egress kernel's per-image flags (one small device-to-host read)."""
+        multi = not isinstance(task, str)
+        if multi:
+            task = self.ae.check_tasks(task)
+        elif task not in self.ae.task_list and self.tedit:
+            raise KeyError(task)
+        images = list(images)
+        if not images:
+            raise ValueError("forward_u8: images is empty")
+        for i, t in enumerate(images):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.ndim != 3 or t.shape[2] != 3 or 0 in t.shape:
+                raise ValueError(f"forward_u8: image {i} must be a uint8 tensor [H, W, 3], got "
+                                 f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        sizes = [(int(t.shape[0]), int(t.shape[1])) for t in images]
+        canvases = [canvas_of(h, w) for h, w in sizes]
+        if len(set(canvases)) != 1:
+            raise ValueError("forward_u8: the images of a batch must share one canvas, got " +
+                             ", ".join(f"{h}x{w} -> {c[0]}x{c[1]}" for (h, w), c in zip(sizes, canvases)))
+        (ch, cw), n = canvases[0], len(images)
+        self._prepare()
+        lat = self.ae.vae.latent_channels
+        lh, lw = ch // 8, cw // 8
+        if noise is None:
+            noise = (torch.randn(n, lat, lh, lw, device=DEV), torch.randn(n, lat, lh, lw, device=DEV))
+        n_vae, n_t = (x.to(DEV).float().contiguous() for x in noise)
+        if tuple(n_vae.shape) != (n, lat, lh, lw) or tuple(n_t.shape) != (n, lat, lh, lw):
+            raise ValueError(f"noise must be two tensors of shape {(n, lat, lh, lw)}")
+        geom = ops.ragged_geometry([(h, w) + resize_pad_plan(h, w)[:2] for h, w in sizes], (ch, cw))
+        slots = self._stage_u8(images, ch * cw * 3)
+
+        def run(st):
+            io = RaggedIO(st["geom"], (ch, cw))
+            preds, z0, zt = self._forward_device(st["slots"], task, st["n_vae"], st["n_t"], io)
+            return preds, z0, zt, io.flags
+        inputs = dict(slots=slots, geom=geom, n_vae=n_vae, n_t=n_t)
+        if self.use_graph:
+            preds, z0, zt, flags = self._captured(("u8", n, ch, cw, task, self.dtype, self.latent_tiling), inputs, run)
+        else:
+            preds, z0, zt, flags = run({name: v.to(DEV) for name, v in inputs.items()})
+        self.__dict__["_u8_flags"] = (flags, n)
+        self._check_finite(None, flags)
+
+        def unpack(buf):           # copies: the slot buffer belongs to the graph
+            return [buf[i, :h * w * 3].reshape(h, w, 3).clone() for i, (h, w) in enumerate(sizes)]
+        preds = {t: unpack(v) for t, v in preds.items()} if multi else unpack(preds)
+        if return_latents:
+            return preds, ops.nhwc_to_nchw(z0, c=lat), ops.nhwc_to_nchw(zt, c=lat)
+        return preds
+
+    def u8_nonfinite(self):
+        """Per image of the last forward_u8 call: did the output of any task meet a non-finite sample (stored as code 0)?
+        One small device-to-host read; the flags belong to the graph, so ask before the next call."""
+        flags, n = self.__dict__["_u8_flags"]
+        return torch.stack(flags).ne(0).any(0).tolist()                       # one [N] tensor per decoded task
+
+    def _stage_u8(self, images, slot_bytes):
+        """The images packed into one uint8 [N, slot_bytes] slot buffer (image i dense at the start of row i): on the device when
+        every image is there, else in a pinned host buffer that is kept per size (its copy to the device is synchronous)."""
+        n = len(images)
+        if all(t.is_cuda for t in images):
+            stage = torch.empty((n, slot_bytes), dtype=torch.uint8, device=DEV)
+        else:
+            cache = self.__dict__.setdefault("_u8_stages", {})
+            if (n, slot_bytes) not in cache:
+                cache.clear()                                    # one staging buffer: a folder is restored canvas by canvas
+                cache[(n, slot_bytes)] = torch.empty((n, slot_bytes), dtype=torch.uint8, pin_memory=True)
+            stage = cache[(n, slot_bytes)]
+        for i, t in enumerate(images):
+            stage[i, :t.numel()].copy_(t.reshape(-1))
+        return stage
+
     # ---- hipGraph: the whole fixed-length forward (encode, N denoise steps, decode) is one captured graph --------------
-    def _graph_forward(self, images, task, n_vae, n_t, plan, quantize=False):
-        key = (tuple(images.shape), task, bool(quantize), self.dtype, self.latent_tiling)
+    def _captured(self, key, inputs, fn):
+        """Replay the graph `key` (captured on first use) of fn(static), static = device copies of the tensors in `inputs` that
+        every call refreshes -> fn's outputs, which the next replay of this graph overwrites."""
         g = self._graphs.get(key)
         if g is None:
-            static = dict(images=images.clone(), n_vae=n_vae.clone(), n_t=n_t.clone())
+            static = {k: v.to(DEV, copy=True) for k, v in inputs.items()}
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):                       # warm-up: packs weights, sizes workspaces, sets func attributes
-                self._forward_device(static["images"], task, static["n_vae"], static["n_t"], plan, quantize)
+                fn(static)
             torch.cuda.current_stream().wait_stream(s)
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):    # an RCCL watchdog thread may be alive
-                outs = self._forward_device(static["images"], task, static["n_vae"], static["n_t"], plan, quantize)
+                outs = fn(static)
+            self.graph_captures += 1
             max_graphs = int(os.environ.get("UR_MAX_GRAPHS", "8"))      # each captured shape keeps its own activation pool
             while len(self._graphs) >= max(max_graphs, 1):
                 self._graphs.pop(next(iter(self._graphs)))                # oldest first
             g = self._graphs[key] = (graph, static, outs)
         graph, static, outs = g
-        static["images"].copy_(images)
-        static["n_vae"].copy_(n_vae)
-        static["n_t"].copy_(n_t)
+        for k, v in inputs.items():
+            static[k].copy_(v)
         if os.environ.get("UR_DEBUG_SYNC"):
             torch.cuda.synchronize()
         graph.replay()
         if os.environ.get("UR_DEBUG_SYNC"):
             torch.cuda.synchronize()
+        return outs
+
+    def _graph_forward(self, images, task, n_vae, n_t, plan, quantize=False):
+        key = (tuple(images.shape), task, bool(quantize), self.dtype, self.latent_tiling)
+        outs = self._captured(key, dict(images=images, n_vae=n_vae, n_t=n_t),
+                              lambda st: self._forward_device(st["images"], task, st["n_vae"], st["n_t"], plan, quantize))
         # the graph's output tensors are overwritten by the next replay of this (shape, task) graph: hand the caller copies
         # (runner.forward keeps [enh_hq, enh_lq] of two same-shape calls; a copy is tiny next to a forward)
         return tuple({t: v.clone() for t, v in o.items()} if isinstance(o, dict) else o.clone() for o in outs)

@@ -547,6 +547,76 @@ def image_unpad_resize(x: torch.Tensor, c: int, crop_hw, out_hw, mul=1.0, add=0.
     return out
 
 
+def ragged_geometry(sizes, canvas):
+    """Host int32 [N,4] table (H, W, RH, RW) of a ragged 8-bit batch from [(H, W, RH, RW), ...] and the canvas (CH, CW); ValueError
+    for a row that does not fit the canvas (the kernels never follow such a row, they cannot report which)."""
+    ch, cw = int(canvas[0]), int(canvas[1])
+    rows = []
+    for n, row in enumerate(sizes):
+        h, w, rh, rw = (int(v) for v in row)
+        if not (0 < h <= rh <= ch and 0 < w <= rw <= cw and ch - rh < rh and cw - rw < rw):
+            raise ValueError(f"ragged geometry: image {n} (H, W, RH, RW) = {(h, w, rh, rw)} does not fit the canvas {(ch, cw)}: "
+                             "needs H <= RH <= CH, W <= RW <= CW and a reflect padding smaller than the resized image")
+        rows.append((h, w, rh, rw))
+    return torch.tensor(rows, dtype=torch.int32).reshape(-1, 4)
+
+
+def _check_ragged(name, slots, geom, n, canvas, validate):
+    dev = torch.device("cuda", torch.cuda.current_device())
+    ch, cw = int(canvas[0]), int(canvas[1])
+    if not isinstance(slots, torch.Tensor) or slots.dtype != torch.uint8 or slots.ndim != 2 or slots.shape[0] != n or n == 0:
+        raise ValueError(f"{name}: the slot buffer must be a uint8 tensor [N = {n}, slot_bytes], got "
+                         f"{getattr(slots, 'dtype', type(slots))} {tuple(getattr(slots, 'shape', ()))}")
+    if slots.shape[1] < ch * cw * 3:
+        raise ValueError(f"{name}: slot_bytes = {slots.shape[1]} is smaller than a canvas-sized image ({ch} * {cw} * 3)")
+    if not isinstance(geom, torch.Tensor) or geom.dtype != torch.int32 or tuple(geom.shape) != (n, 4):
+        raise ValueError(f"{name}: geom must be an int32 tensor [N = {n}, 4] of (H, W, RH, RW), got "
+                         f"{getattr(geom, 'dtype', type(geom))} {tuple(getattr(geom, 'shape', ()))}")
+    for what, t in (("slot buffer", slots), ("geom", geom)):
+        if t.device != dev:
+            raise ValueError(f"{name}: the {what} is on {t.device}, not on the current device {dev}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: the {what} must be contiguous")
+    if validate:
+        ragged_geometry(geom.tolist(), canvas)
+
+
+def image_u8_ingest(slots: torch.Tensor, geom: torch.Tensor, canvas, mul=2.0, add=-1.0, cpad=8, validate=True):
+    """Ragged 8-bit batch -> 16-bit NHWC [N, CH, CW, cpad]: per image u8 / 255, then what `image_resize_pad` does.  slots uint8
+    [N, slot_bytes] (image n dense HWC at the start of row n), geom device int32 [N,4] (H, W, RH, RW), canvas (CH, CW).
+    validate reads the table back (a sync) and raises for a row that does not fit; a caller that built the table with
+    `ragged_geometry` - or runs inside a graph capture, where a read-back is impossible - passes validate=False."""
+    n = int(slots.shape[0]) if isinstance(slots, torch.Tensor) and slots.ndim == 2 else 0
+    _check_ragged("image_u8_ingest", slots, geom, n, canvas, validate)
+    out = torch.empty((n, int(canvas[0]), int(canvas[1]), cpad), dtype=_act, device=slots.device)
+    check(lib.ur_image_u8_ingest(slots.data_ptr(), slots.shape[1], geom.data_ptr(), out.data_ptr(), n, int(canvas[0]), int(canvas[1]),
+                                 cpad, mul, add, _dt(), _stream()))
+    return out
+
+
+def image_u8_egress(x: torch.Tensor, c: int, geom: torch.Tensor, mul=1.0, add=0.0, out=None, nonfinite=None, validate=True):
+    """x NHWC (16-bit | fp32) [N, CH, CW, ld] -> ragged 8-bit batch: per image what `image_unpad_resize(..., quantize=True)` does,
+    stored as uint8 code values, HWC.  Returns (slots uint8 [N, CH*CW*c], nonfinite int32 [N]): flag n is 1 when image n met a
+    non-finite sample (stored as code 0).  `out` / `nonfinite` are written in place when given (nonfinite must come zeroed)."""
+    if not isinstance(x, torch.Tensor) or x.ndim != 4 or x.dtype not in (torch.float32, BF16, F16) or not x.is_contiguous():
+        raise ValueError(f"image_u8_egress: x must be a contiguous 4-d NHWC tensor (fp32 or 16-bit), got "
+                         f"{getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
+    n, xh, xw, ld = x.shape
+    if c != 3 or ld < c:
+        raise ValueError(f"image_u8_egress: c must be 3 (RGB) and at most ld = {ld}, got {c}")
+    if out is None:
+        out = torch.empty((n, xh * xw * c), dtype=torch.uint8, device=x.device)
+    _check_ragged("image_u8_egress", out, geom, n, (xh, xw), validate)
+    if nonfinite is None:
+        nonfinite = torch.zeros(n, dtype=torch.int32, device=x.device)
+    elif nonfinite.dtype != torch.int32 or tuple(nonfinite.shape) != (n,) or nonfinite.device != x.device or not nonfinite.is_contiguous():
+        raise ValueError(f"image_u8_egress: nonfinite must be a contiguous int32 tensor [{n}] on {x.device}")
+    check(lib.ur_image_u8_egress(x.data_ptr(), int(x.dtype == torch.float32), out.data_ptr(), out.shape[1], geom.data_ptr(),
+                                 nonfinite.data_ptr(), n, c, xh, xw, ld, mul, add, _dt() if x.dtype == torch.float32 else _dt(x),
+                                 _stream()))
+    return out, nonfinite
+
+
 def nhwc_to_nchw(x: torch.Tensor, c=None, mul=1.0, add=0.0):
     n, h, w_, ld = x.shape
     c = c or ld
