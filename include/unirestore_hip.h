@@ -211,6 +211,22 @@ size_t ur_attention_workspace_bytes(int B, int H, int Tq, int Tk, int D);
 int ur_attention_fwd_ws(const void* q, const void* k, const void* vt, void* o, int B, int H, int Tq, int Tk,
                         int D, int ldq, int ldk, int ldvt, int ldo, long long bs_q, long long bs_k, long long bs_vt,
                         long long bs_o, float scale, void* ws, size_t ws_bytes, int dtype, ur_stream_t stream);
+/* What ur_attention_fwd_ws would launch for these arguments: host only, no HIP call, nothing is read or written through the
+ * pointers (placeholders will do - their values matter only for the ping-pong kernel's alignment rule: q, k, vt 16-byte and o
+ * 8-byte aligned).  Same argument checks and return codes as the launch, which decides through the same function; honours
+ * UR_ATTN_NOPP (read once per process).  Kernels, by index: the 128-query kernel at d = 64 and at d = 128, the d = 512 kernel, the
+ * 256-query ping-pong kernel (d = 64, Tq and Tk multiples of 256, taken when its grid fills whole rounds of the CUs well enough). */
+typedef struct ur_attention_plan {
+  int kernel;      /* index for ur_attention_kernel_name(): 128-query d64, 128-query d128, d512, ping-pong */
+  int workgroups;  /* grid of the main launch */
+  int n_full;      /* ping-pong: whole (batch-head, query tile) work items; else 0 */
+  int n_split;     /* ping-pong: trailing tiles split in two key halves (0: none, no combine launch) */
+} ur_attention_plan;
+int ur_attention_plan_launch(const void* q, const void* k, const void* vt, void* o, int B, int H, int Tq, int Tk,
+                             int D, int ldq, int ldk, int ldvt, int ldo, long long bs_q, long long bs_k, long long bs_vt,
+                             long long bs_o, void* ws, size_t ws_bytes, ur_attention_plan* plan);
+int ur_attention_kernel_count(void);
+const char* ur_attention_kernel_name(int i); /* static string, or NULL outside [0, ur_attention_kernel_count()) */
 
 /* ---- token-stationary fused chains (csrc/tchain.hip) ----------------------------------------------
  * A wave keeps 32 tokens in registers through a whole chain of token-wise layers; the weights arrive as a pre-packed

@@ -133,6 +133,17 @@ def test_pp_attention_key_split_last_round(ops, dt):
                               c, t * 3 * c, t * 3 * c, c * t, t * c, 0.125, ops._dt(qkv), None)
     assert rc == 0
     torch.cuda.synchronize()
+    # what the two calls planned: the host-only query on the operands of the plain call.  ops.attention allocated q, k, V^T, o and
+    # its workspace itself; the plan depends on their alignment only (torch allocations are 16-byte aligned), so the workspace is a
+    # 16-byte aligned placeholder address here
+    from unirestore_amd import capi
+    nws = lib.ur_attention_workspace_bytes(b, heads, t, t, d)
+    geo = (qkv.data_ptr(), qkv[:, :, c:].data_ptr(), vt.data_ptr(), o_plain.data_ptr(), b, heads, t, t, d, 3 * c, 3 * c, t, c, t * 3 * c,
+           t * 3 * c, c * t, t * c)
+    split, plain = capi.attention_plan(*geo, 1 << 20, nws), capi.attention_plan(*geo, None, 0)
+    pp = capi.attention_kernel_names().index("attn_pp64")
+    assert (split.kernel, split.n_full, split.n_split, split.workgroups) == (pp, 512, 128, 768)
+    assert (plain.kernel, plain.n_full, plain.n_split, plain.workgroups) == (pp, 640, 0, 640)
     assert rel_l2(o_split.cpu(), ref) < TOL[dt] and rel_l2(o_plain.cpu(), ref) < TOL[dt]
     assert rel_l2(o_split.cpu(), o_plain.cpu()) < TOL[dt]
     head_rows = o_split[:, :, :].view(b * t, c)

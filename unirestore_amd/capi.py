@@ -53,6 +53,11 @@ class ConvLaunchInfo(C.Structure):
                 ("gn_pass", C.c_int), ("group_loop", C.c_int)]
 
 
+class AttentionPlan(C.Structure):
+    """Mirror of `ur_attention_plan`."""
+    _fields_ = [("kernel", C.c_int), ("workgroups", C.c_int), ("n_full", C.c_int), ("n_split", C.c_int)]
+
+
 _P, _I, _F, _LL, _SZ = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_size_t
 
 # name -> (restype, argtypes); every symbol the header declares
@@ -79,6 +84,9 @@ SIGNATURES = {
     "ur_attention_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _LL, _LL, _LL, _LL, _F, _I, _P]),
     "ur_attention_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "ur_attention_fwd_ws": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _LL, _LL, _LL, _LL, _F, _P, _SZ, _I, _P]),
+    "ur_attention_plan_launch": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _LL, _LL, _LL, _LL, _P, _SZ, C.POINTER(AttentionPlan)]),
+    "ur_attention_kernel_count": (_I, []),
+    "ur_attention_kernel_name": (C.c_char_p, [_I]),
     "ur_chain_tile_bytes": (_SZ, []),
     "ur_ff_geglu_fused": (_I, [_P, _P, _SZ, _P, _LL, _I, _I, _I, _I, _F, _I, _P]),
     "ur_transformer_head_fused": (_I, [_P, _P, _P, _SZ, _P, _P, _P, _P, _LL, _I, _I, _F, _I, _P]),
@@ -139,6 +147,18 @@ def plan_launch(d: ConvDesc) -> ConvLaunchInfo:
     info = ConvLaunchInfo()
     check(lib.ur_conv2d_plan_launch(d, info))
     return info
+
+
+def attention_kernel_names() -> list:
+    """Names of the attention kernels, by index (ur_attention_plan.kernel)."""
+    return [lib.ur_attention_kernel_name(i).decode() for i in range(lib.ur_attention_kernel_count())]
+
+
+def attention_plan(q, k, vt, o, B, H, Tq, Tk, D, ldq, ldk, ldvt, ldo, bs_q, bs_k, bs_vt, bs_o, ws, ws_bytes) -> AttentionPlan:
+    """ur_attention_plan_launch (host only; the pointers are integers and may be placeholders); raises like `check`."""
+    plan = AttentionPlan()
+    check(lib.ur_attention_plan_launch(q, k, vt, o, B, H, Tq, Tk, D, ldq, ldk, ldvt, ldo, bs_q, bs_k, bs_vt, bs_o, ws, ws_bytes, plan))
+    return plan
 
 
 class URError(RuntimeError):

@@ -246,8 +246,8 @@ int ur_attn_launch_bf16(const void* pp, int D, hipStream_t s);
 int ur_attn_launch_f16(const void* pp, int D, hipStream_t s);
 int ur_attn512_launch_bf16(const void* pp, hipStream_t s);
 int ur_attn512_launch_f16(const void* pp, hipStream_t s);
-int ur_attn_pp_launch_bf16(const void* pp, size_t ws_bytes, hipStream_t s);      // attention_pp.hip
-int ur_attn_pp_launch_f16(const void* pp, size_t ws_bytes, hipStream_t s);
+int ur_attn_pp_launch_bf16(const void* pp, int n_split, size_t ws_bytes, hipStream_t s);         // attention_pp.hip
+int ur_attn_pp_launch_f16(const void* pp, int n_split, size_t ws_bytes, hipStream_t s);
 
 int UR_ATTN_LAUNCH(const void* pp, int D, hipStream_t s) {
   const AttnP& p = *static_cast<const AttnP*>(pp);
@@ -272,26 +272,36 @@ extern "C" size_t ur_attention_workspace_bytes(int B, int H, int Tq, int Tk, int
   return B > 0 && H > 0 && Tq > 0 && Tk > 0 ? attn_pp_ws_bytes(attn_pp_split_tiles(B, H, Tq, Tk, D)) : 0;      // (attention_params.h: the one rule)
 }
 
-extern "C" int ur_attention_fwd_ws(const void* q, const void* k, const void* vt, void* o, int B, int H, int Tq, int Tk, int D,
-                                   int ldq, int ldk, int ldvt, int ldo, long long bs_q, long long bs_k, long long bs_vt,
-                                   long long bs_o, float scale, void* ws, size_t ws_bytes, int dtype, ur_stream_t stream) {
-  UR_REQUIRE(q && k && vt && o, "null pointer");
-  UR_REQUIRE(D == 64 || D == 128 || D == 512, "head dim must be 64, 128 or 512 (use the GEMM path otherwise)");
-  UR_REQUIRE_DT(dtype);
-  UR_REQUIRE(B > 0 && H > 0 && Tq > 0 && Tk > 0, "empty problem");
-  UR_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0 && ldvt >= Tk, "leading dims");
-  UR_REQUIRE(!ws || ((uintptr_t)ws & 15) == 0, "workspace must be 16-byte aligned");
-  AttnP p;
+namespace {
+enum { ATTN_Q128_D64, ATTN_Q128_D128, ATTN_D512, ATTN_PP64, ATTN_KERNEL_COUNT };
+const char* const kAttnKernelNames[ATTN_KERNEL_COUNT] = {"attn_q128_d64", "attn_q128_d128", "attn_d512", "attn_pp64"};
+
+#define ATTN_REQUIRE(cond, msg) \
+  do {                          \
+    if (!(cond)) return ur::fail(UR_E_INVALID, std::string(who) + ": " + (msg)); \
+  } while (0)
+
+// The ONE dispatch rule of the attention family: argument checks, kernel choice, grid and key split.  Host only, no HIP call -
+// ur_attention_fwd_ws launches what this returns and ur_attention_plan_launch reports it.  Fills p (all but scale_log2e) and plan.
+int attn_plan(const char* who, const void* q, const void* k, const void* vt, void* o, int B, int H, int Tq, int Tk, int D, int ldq, int ldk,
+              int ldvt, int ldo, long long bs_q, long long bs_k, long long bs_vt, long long bs_o, void* ws, size_t ws_bytes, AttnP& p,
+              ur_attention_plan& plan) {
+  ATTN_REQUIRE(q && k && vt && o, "null pointer");
+  ATTN_REQUIRE(D == 64 || D == 128 || D == 512, "head dim must be 64, 128 or 512 (use the GEMM path otherwise)");
+  ATTN_REQUIRE(B > 0 && H > 0 && Tq > 0 && Tk > 0, "empty problem");
+  ATTN_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0 && ldvt >= Tk, "leading dims");
+  ATTN_REQUIRE(!ws || ((uintptr_t)ws & 15) == 0, "workspace must be 16-byte aligned");
   p.q = (const uint16_t*)q; p.k = (const uint16_t*)k; p.vt = (const uint16_t*)vt; p.o = (uint16_t*)o;
   p.B = B; p.H = H; p.Tq = Tq; p.Tk = Tk; p.ldq = ldq; p.ldk = ldk; p.ldvt = ldvt; p.ldo = ldo;
   p.bs_q = bs_q; p.bs_k = bs_k; p.bs_vt = bs_vt; p.bs_o = bs_o;
-  p.scale_log2e = (float)((double)scale * 1.4426950408889634);      // (scale = ln 2 gives exactly 1: q arrives pre-scaled)
+  p.scale_log2e = 1.f;
   p.n_full = 0; p.ws = (float*)ws;
-  hipStream_t s = (hipStream_t)stream;
-  const double flops = 4.0 * B * H * (double)Tq * Tk * D;
-  const double bytes = 2.0 * B * H * ((double)Tq * D * 2 + (double)Tk * D * 2);
-  ur::ProfScope prof("attention", flops, bytes, s);
-  if (D == 512) return dtype == UR_DT_F16 ? ur_attn512_launch_f16(&p, s) : ur_attn512_launch_bf16(&p, s);     // attention512.hip
+  plan.n_full = plan.n_split = 0;
+  if (D == 512) {                                                                 // attention512.hip: 32 queries per workgroup
+    plan.kernel = ATTN_D512;
+    plan.workgroups = (Tq + 31) / 32 * B * H;
+    return UR_OK;
+  }
   // self-attention shapes: the ping-pong kernel (attention_pp.hip: 256 queries per workgroup, one workgroup per CU) when its
   // grid fills whole rounds of the 256 CUs well enough - counting a split last round (workspace given) as half a round.
   // 640 workgroups = 2.5 rounds: 203 us unsplit against 229 for the 128-query kernel below; 320 = 1.25 rounds unsplit: 42 against
@@ -302,10 +312,49 @@ extern "C" int ur_attention_fwd_ws(const void* q, const void* k, const void* vt,
     const long long rs = attn_pp_split_tiles(B, H, Tq, Tk, D);
     const long long r = ws && ws_bytes >= attn_pp_ws_bytes(rs) ? rs : 0;
     const double rounds = r ? (double)(wgs - r) / 256 + 0.5 : (double)((wgs + 255) / 256);
-    if (wgs <= 256 || wgs >= rounds * 256 * 0.75)
-      return dtype == UR_DT_F16 ? ur_attn_pp_launch_f16(&p, ws_bytes, s) : ur_attn_pp_launch_bf16(&p, ws_bytes, s);
+    if (wgs <= 256 || wgs >= rounds * 256 * 0.75) {
+      plan.kernel = ATTN_PP64;
+      plan.n_split = (int)r;
+      plan.n_full = p.n_full = (int)(wgs - r);
+      plan.workgroups = plan.n_full + 2 * plan.n_split;
+      return UR_OK;
+    }
   }
-  return dtype == UR_DT_F16 ? ur_attn_launch_f16(&p, D, s) : ur_attn_launch_bf16(&p, D, s);
+  plan.kernel = D == 64 ? ATTN_Q128_D64 : ATTN_Q128_D128;
+  plan.workgroups = (Tq + 127) / 128 * B * H;
+  return UR_OK;
+}
+}  // namespace
+
+extern "C" int ur_attention_kernel_count(void) { return ATTN_KERNEL_COUNT; }
+extern "C" const char* ur_attention_kernel_name(int i) { return i >= 0 && i < ATTN_KERNEL_COUNT ? kAttnKernelNames[i] : nullptr; }
+
+extern "C" int ur_attention_plan_launch(const void* q, const void* k, const void* vt, void* o, int B, int H, int Tq, int Tk, int D,
+                                        int ldq, int ldk, int ldvt, int ldo, long long bs_q, long long bs_k, long long bs_vt,
+                                        long long bs_o, void* ws, size_t ws_bytes, ur_attention_plan* plan) {
+  UR_REQUIRE(plan, "null plan");
+  AttnP p;
+  return attn_plan(__func__, q, k, vt, o, B, H, Tq, Tk, D, ldq, ldk, ldvt, ldo, bs_q, bs_k, bs_vt, bs_o, ws, ws_bytes, p, *plan);
+}
+
+extern "C" int ur_attention_fwd_ws(const void* q, const void* k, const void* vt, void* o, int B, int H, int Tq, int Tk, int D,
+                                   int ldq, int ldk, int ldvt, int ldo, long long bs_q, long long bs_k, long long bs_vt,
+                                   long long bs_o, float scale, void* ws, size_t ws_bytes, int dtype, ur_stream_t stream) {
+  UR_REQUIRE_DT(dtype);
+  AttnP p;
+  ur_attention_plan plan;
+  if (const int rc = attn_plan(__func__, q, k, vt, o, B, H, Tq, Tk, D, ldq, ldk, ldvt, ldo, bs_q, bs_k, bs_vt, bs_o, ws, ws_bytes, p, plan)) return rc;
+  p.scale_log2e = (float)((double)scale * 1.4426950408889634);      // (scale = ln 2 gives exactly 1: q arrives pre-scaled)
+  hipStream_t s = (hipStream_t)stream;
+  const double flops = 4.0 * B * H * (double)Tq * Tk * D;
+  const double bytes = 2.0 * B * H * ((double)Tq * D * 2 + (double)Tk * D * 2);
+  ur::ProfScope prof("attention", flops, bytes, s);
+  const bool f16 = dtype == UR_DT_F16;
+  switch (plan.kernel) {
+    case ATTN_D512: return f16 ? ur_attn512_launch_f16(&p, s) : ur_attn512_launch_bf16(&p, s);                    // attention512.hip
+    case ATTN_PP64: return f16 ? ur_attn_pp_launch_f16(&p, plan.n_split, ws_bytes, s) : ur_attn_pp_launch_bf16(&p, plan.n_split, ws_bytes, s);      // attention_pp.hip
+    default: return f16 ? ur_attn_launch_f16(&p, D, s) : ur_attn_launch_bf16(&p, D, s);
+  }
 }
 
 extern "C" int ur_attention_fwd(const void* q, const void* k, const void* vt, void* o, int B, int H, int Tq, int Tk, int D,

@@ -13,7 +13,9 @@ struct AttnP {
   float* ws;
 };
 
-// ONE rule for the ping-pong kernel's grid (used by ur_attention_workspace_bytes, the dispatcher's fill estimate and the launch):
+// ONE rule for the ping-pong kernel's key split, used by ur_attention_workspace_bytes (what to allocate) and by attn_plan
+// (attention.hip: the dispatcher, which also weighs the fill of the grid and the workspace it was given).  The launcher in
+// attention_pp.hip derives nothing: it takes n_full / n_split from attn_plan and only checks them against the shape and ws_bytes.
 // n = (Tq / 256) * B * H query tiles; when n = whole rounds of the 256 CUs + r with 0 < r <= 128, the last r tiles are split in two
 // key halves (2r <= 256 workgroups fill the last round) - if a workspace of attn_pp_ws_bytes(r) is there and Tk % 512 == 0.
 // Returns r (0: unsplit).

@@ -197,19 +197,15 @@ __global__ __launch_bounds__(256) void attn_pp_combine_kernel(const AttnP p, int
 // Workgroups per launch and how many of the trailing query tiles are split in two key halves.  One workgroup per CU: a grid of
 // n = whole rounds of 256 + r with 0 < r <= 128 leaves half of the chip idle for a whole tile time (B = 8, 5 heads, T = 4096:
 // 640 = 2.5 rounds); splitting the keys of those r tiles gives 2r <= 256 half-length workgroups that fill the last round.
-static void pp_plan(const AttnP& p, size_t ws_bytes, int& n_full, int& n_split) {
-  const long long n = (long long)(p.Tq / 256) * p.B * p.H, r = attn_pp_split_tiles(p.B, p.H, p.Tq, p.Tk, 64);      // (attention_params.h)
-  n_split = (r && p.ws && ws_bytes >= attn_pp_ws_bytes(r)) ? (int)r : 0;
-  n_full = (int)(n - n_split);
-}
-
-int UR_ATTN_PP_LAUNCH(const void* pp, size_t ws_bytes, hipStream_t s) {
-  AttnP p = *static_cast<const AttnP*>(pp);
+// The dispatcher's plan (attention.hip attn_plan, the one rule) decides both: p.n_full whole tiles, then n_split split ones.
+// This launcher derives nothing; it refuses a plan that does not cover the shape or that the ws_bytes at p.ws cannot hold.
+int UR_ATTN_PP_LAUNCH(const void* pp, int n_split, size_t ws_bytes, hipStream_t s) {
+  const AttnP& p = *static_cast<const AttnP*>(pp);
   // the asm loop has no tails and its buffer descriptors no range check: refuse what the dispatcher should never send
   if (!attn_pp_shape_ok(p, 64) || (p.ws && ((unsigned long long)p.ws & 15ull)))
     return ur::fail(UR_E_INVALID, "ping-pong attention: needs Tq, Tk multiples of 256 and 16-byte aligned q / k / v^T rows");
-  int n_split;
-  pp_plan(p, ws_bytes, p.n_full, n_split);
+  if (n_split < 0 || p.n_full + n_split != (long long)(p.Tq / 256) * p.B * p.H || (n_split && (!p.ws || p.Tk % 512 || ws_bytes < attn_pp_ws_bytes(n_split))))
+    return ur::fail(UR_E_INVALID, "ping-pong attention: plan does not match the shape");
 
   constexpr bool F16 = UR_TU_F16 != 0;
   dim3 grid(p.n_full + 2 * n_split), block(512);
