@@ -158,6 +158,9 @@ int ur_groupconv3x3_nhwc(const void* x, const void* w, const float* bias, void* 
  *      y = a*x + b == GroupNorm(x); fp64 sums in a fixed order;
  *   3. ur_groupnorm_apply_act (or ur_conv_desc.gn_ab: applied inside the consuming convolution).
  * G == C with gamma = beta = NULL gives InstanceNorm2d; mean_out gives AdaptiveAvgPool2d(1).
+ * Arguments are checked on the host before any arithmetic on them and before any launch: a null required pointer, a non-positive
+ * N / HW / rows / C / C1 / G (C2 when x2 / part2 is given), C % 8 != 0, C % G != 0 or an unknown dtype returns UR_E_INVALID
+ * (the size queries return UR_E_INVALID / the bytes of one partial).
  * Replaces: nn.GroupNorm(32,C)+SiLU in every ResnetBlock2D / conv_norm_out, Transformer2D / Attention
  *   pre-norms, AdaNAFV2.group_norm (cfrm.py:19), nn.InstanceNorm2d (taskeditor.py:31,40,49), nn.AdaptiveAvgPool2d(1).
  */
@@ -179,10 +182,11 @@ int ur_groupnorm_nhwc(const void* x, const void* x2, void* y, const float* gamma
                       int C1, int C2, int G, float eps, int silu, float* ws, float* ab, const float* pre1, int parts1,
                       const float* pre2, int parts2, int dtype, ur_stream_t stream);
 /* LayerNorm over the last dim of [rows, C] (nn.LayerNorm in BasicTransformerBlock; timm LayerNorm2d
- * in NAFBlock, nafnet_arch.py:97-98, which is LayerNorm-over-C in NHWC). */
+ * in NAFBlock, nafnet_arch.py:97-98, which is LayerNorm-over-C in NHWC).  0 < C <= 2048, C % 8 == 0; gamma / beta may be NULL. */
 int ur_layernorm_rows(const void* x, void* y, const float* gamma, const float* beta, long long rows, int C,
                       float eps, int dtype, ur_stream_t stream);
-/* softmax over rows of an fp32 [rows, cols] matrix -> 16-bit (upcast_softmax). */
+/* softmax over rows of an fp32 [rows, cols] matrix -> 16-bit (upcast_softmax): p [rows][ldp], ldp >= cols, columns [cols, ldp) are
+ * written as zeros. */
 int ur_softmax_rows_f32(const float* s, void* p, long long rows, int cols, int ldp, int dtype, ur_stream_t stream);
 
 /* ---- attention (flash-style, bf16 MFMA, fp32 softmax) ------------------------------------------
@@ -262,6 +266,8 @@ int ur_csce_fused(const void* x, const void* cond, const void* stream_w, size_t 
                   int tokens_per_image, int C, int Ccond, int dtype, ur_stream_t stream);
 
 /* ---- HBM-bound stencils / reductions / elementwise ---------------------------------------------*/
+/* Every entry point of this block returns UR_E_INVALID for a null required pointer, an empty tensor (non-positive N, H, W, HW,
+ * rows, M, B, T, D, C or G), C % 8 != 0 (16-bit tensors) or an unknown dtype - checked on the host before anything is launched. */
 /* depthwise 3x3 (pad 1) + bias, optional SimpleGate (out channels C/2): nafnet_arch.py:41-49,22-25 */
 int ur_dwconv3x3_nhwc(const void* x, const float* w9c, const float* bias, void* y, int N, int H, int W, int C,
                       int gate, int dtype, ur_stream_t stream);
@@ -291,6 +297,7 @@ int ur_scale_channels_fanout(const void* x, const float* s, void* y, int B, int 
 int ur_tfa_prompt_update_fanout(const float* pooled, const float* cond, float* upd, int B, int K, int T, int D, int cond_per_row,
                                 ur_stream_t stream);
 /* out[n][c] = a[n][c] * b[n][c / (C/G)]  (combine intra/inter group attention, cfrm.py:46-48) */
+/* G must divide C; N * C must fit an int */
 int ur_vec_mul_group(const float* a, const float* b, float* out, int N, int C, int G, ur_stream_t stream);
 
 /* ---- latent / image boundary --------------------------------------------------------------------*/

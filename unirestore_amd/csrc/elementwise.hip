@@ -653,6 +653,7 @@ int ur_dwconv3x3_nhwc(const void* x, const float* w9c, const float* bias, void* 
                       int dtype, ur_stream_t stream) {
   UR_REQUIRE_DT(dtype);
   UR_REQUIRE(x && w9c && bias && y, "null pointer");
+  UR_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0, "N, H, W, C must be positive");
   UR_REQUIRE(C % (gate ? 16 : 8) == 0, "C must be a multiple of 8 (16 with gate)");
   hipStream_t s = (hipStream_t)stream;
   const double elems = (double)N * H * W * C;
@@ -671,7 +672,7 @@ int ur_dwconv3x3_nhwc(const void* x, const float* w9c, const float* bias, void* 
 int ur_scale_channels(const void* x, const float* sc, const void* residual, void* y, int N, int HW, int C,
                       int dtype, ur_stream_t stream) {
   UR_REQUIRE_DT(dtype);
-  UR_REQUIRE(x && sc && y && C % 8 == 0, "bad args");
+  UR_REQUIRE(x && sc && y && N > 0 && HW > 0 && C > 0 && C % 8 == 0, "bad args");
   hipStream_t s = (hipStream_t)stream;
   const long long totalv = (long long)N * HW * (C / 8);
   ur::ProfScope prof("elementwise", 0.0, (residual ? 6.0 : 4.0) * totalv * 8.0, s);
@@ -694,7 +695,7 @@ int ur_scale_channels_fanout(const void* x, const float* sc, void* y, int B, int
 
 int ur_axpy_channels(const void* a, const void* b, const float* sc, void* y, long long rows, int C, int dtype, ur_stream_t stream) {
   UR_REQUIRE_DT(dtype);
-  UR_REQUIRE(a && b && sc && y && C % 8 == 0, "bad args");
+  UR_REQUIRE(a && b && sc && y && rows > 0 && C > 0 && C % 8 == 0, "bad args");
   hipStream_t s = (hipStream_t)stream;
   const long long totalv = rows * (C / 8);
   ur::ProfScope prof("elementwise", 0.0, 6.0 * totalv * 8.0, s);
@@ -706,7 +707,7 @@ int ur_axpy_channels(const void* a, const void* b, const float* sc, void* y, lon
 int ur_spade_modulate(const void* n, const void* gb, int ldgb, const void* residual, void* y, long long rows, int C,
                       int dtype, ur_stream_t stream) {
   UR_REQUIRE_DT(dtype);
-  UR_REQUIRE(n && gb && y && C % 8 == 0 && ldgb % 8 == 0 && ldgb >= 2 * C && rows > 0, "bad args");
+  UR_REQUIRE(n && gb && y && C > 0 && C % 8 == 0 && ldgb % 8 == 0 && ldgb >= 2 * C && rows > 0, "bad args");
   hipStream_t s = (hipStream_t)stream;
   const long long totalv = rows * (C / 8);
   ur::ProfScope prof("elementwise", 0.0, (residual ? 10.0 : 8.0) * totalv * 8.0, s);
@@ -739,7 +740,8 @@ int ur_tfa_prompt_update_fanout(const float* pooled, const float* cond, float* u
 }
 
 int ur_vec_mul_group(const float* a, const float* b, float* out, int N, int C, int G, ur_stream_t stream) {
-  UR_REQUIRE(a && b && out && C % G == 0, "bad args");
+  UR_REQUIRE(a && b && out && N > 0 && C > 0 && G > 0, "null pointer / N, C, G must be positive");      // G > 0 before C % G
+  UR_REQUIRE(C % G == 0 && (long long)N * C < (1ll << 31) - 256, "G must divide C and N * C must fit an int");
   hipLaunchKernelGGL(vec_mul_group_kernel, dim3((N * C + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, b, out, N, C, G);
   return ur::check_launch("ur_vec_mul_group");
 }

@@ -327,8 +327,8 @@ int ur_groupnorm_apply_act(const void* x, const void* x2, void* y, const float* 
                            int dtype, ur_stream_t stream) {
   UR_REQUIRE(x && y && ab && N > 0 && HW > 0, "null pointer / empty");
   UR_REQUIRE_DT(dtype);
+  UR_REQUIRE(C1 > 0 && C1 % 8 == 0 && (!x2 || (C2 > 0 && C2 % 8 == 0)), "C1 (and C2 with x2) must be positive multiples of 8");   // before gn_geom: 0 % 0
   const int C = C1 + (x2 ? C2 : 0);
-  UR_REQUIRE(C1 % 8 == 0 && (!x2 || C2 % 8 == 0), "C%8");
   hipStream_t s = (hipStream_t)stream;
   const char* fam = "groupnorm";
   static const bool prof_shapes = getenv("UR_PROF_SHAPES") != nullptr;
@@ -364,6 +364,11 @@ int ur_groupnorm_nhwc(const void* x, const void* x2, void* y, const float* gamma
                       int C1, int C2, int G, float eps, int silu, float* ws, float* ab, const float* pre1, int parts1,
                       const float* pre2, int parts2, int dtype, ur_stream_t stream) {
   UR_REQUIRE(x && y && ab, "null pointer");
+  UR_REQUIRE_DT(dtype);
+  // every shape check BEFORE gn_stats_parts (gn_geom divides by C / 8 and its divisors)
+  UR_REQUIRE(N > 0 && HW > 0 && C1 > 0 && C1 % 8 == 0 && (!x2 || (C2 > 0 && C2 % 8 == 0)), "N, HW, C1 (and C2 with x2) must be positive, C % 8 == 0");
+  UR_REQUIRE(G > 0 && (C1 + (x2 ? C2 : 0)) % G == 0, "G must be positive and divide C1 + C2");
+  UR_REQUIRE((!pre1 || parts1 > 0) && (!x2 || !pre2 || parts2 > 0), "producer-side partial planes need parts > 0");
   UR_REQUIRE((pre1 && (!x2 || pre2)) || ws, "a source without producer-side partials needs the ws scratch");
   // statistics pass only for sources whose producer left no partial plane (ws holds x's plane, then x2's)
   if (!pre1) {
@@ -386,7 +391,8 @@ int ur_groupnorm_nhwc(const void* x, const void* x2, void* y, const float* gamma
 
 /* mean over HW -> fp32 [N][C] (nn.AdaptiveAvgPool2d(1)): the statistics pass + a finalize with one group per channel */
 int ur_avgpool_hw(const void* x, float* out, int N, int HW, int C, float* ws, int dtype, ur_stream_t stream) {
-  UR_REQUIRE(x && out && ws && C % 8 == 0, "bad args");
+  UR_REQUIRE(x && out && ws && N > 0 && HW > 0 && C > 0 && C % 8 == 0, "bad args");
+  UR_REQUIRE_DT(dtype);
   int rc = ur_groupnorm_stats(x, ws, N, HW, C, dtype, stream);
   if (rc != UR_OK) return rc;
   return ur_groupnorm_finalize(ws, ur::gn_stats_parts(N, HW, C), C, nullptr, 0, 0, nullptr, nullptr, N, HW, C, 0.f, nullptr, out, stream);
@@ -395,7 +401,7 @@ int ur_avgpool_hw(const void* x, float* out, int N, int HW, int C, float* ws, in
 int ur_layernorm_rows(const void* x, void* y, const float* gamma, const float* beta, long long rows, int C, float eps,
                       int dtype, ur_stream_t stream) {
   UR_REQUIRE(x && y && rows > 0, "null pointer / empty");
-  UR_REQUIRE(C % 8 == 0 && C <= 2048, "C%8 and C<=2048");
+  UR_REQUIRE(C > 0 && C % 8 == 0 && C <= 2048, "C%8 and 0<C<=2048");
   UR_REQUIRE_DT(dtype);
   hipStream_t s = (hipStream_t)stream;
   ur::ProfScope prof("layernorm", 0.0, 4.0 * rows * (double)C, s);
@@ -415,6 +421,7 @@ int ur_layernorm_rows(const void* x, void* y, const float* gamma, const float* b
 
 int ur_softmax_rows_f32(const float* sm, void* p, long long rows, int cols, int ldp, int dtype, ur_stream_t stream) {
   UR_REQUIRE(sm && p && rows > 0 && cols > 0 && ldp >= cols, "bad args");
+  UR_REQUIRE_DT(dtype);
   hipStream_t s = (hipStream_t)stream;
   ur::ProfScope prof("softmax_rows", 0.0, rows * (double)cols * 6.0, s);
   UR_DT_SWITCH(dtype, hipLaunchKernelGGL(softmax_rows_kernel<F16>, dim3((unsigned)rows), dim3(256), 0, s, sm, (uint16_t*)p, cols, ldp));
