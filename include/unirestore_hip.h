@@ -301,6 +301,11 @@ int ur_tfa_prompt_update_fanout(const float* pooled, const float* cond, float* u
 int ur_vec_mul_group(const float* a, const float* b, float* out, int N, int C, int G, ur_stream_t stream);
 
 /* ---- latent / image boundary --------------------------------------------------------------------*/
+/* Every entry point of this block returns UR_E_INVALID for a null required pointer, an empty tensor (non-positive N, C, H, W, HW, M,
+ * T, th, tw, RH, RW, OH, OW, Clat), Cpad < C or < Clat, ld < C, ld < 2 * Clat (ur_vae_sample), ld_eps < Clat, Clat > 8 (blend), a reflect
+ * padding not smaller than the resized image, a crop window outside the input, a tile larger than the latent, slot_bytes smaller
+ * than a canvas-sized image or an unknown dtype - checked on the host before any arithmetic on the arguments and before anything is
+ * launched. */
 /* images NCHW fp32 in [0,1] -> NHWC 16-bit (x*2-1), channels padded with zeros to Cpad (autoencoder.py:149) */
 int ur_image_to_nhwc(const float* img, void* y, int N, int C, int H, int W, int Cpad, int dtype, ur_stream_t stream);
 /* NHWC fp32/16-bit [N,H,W,ld] first C channels -> NCHW fp32, out = x*mul+add (autoencoder.py:175) */
@@ -344,13 +349,15 @@ int ur_add_noise(const float* z0, const float* noise_nchw, float* zt, void* zt_1
 int ur_ddim_step(float* zt, const float* eps, int ld_eps, void* zt_16, long long M, int Clat, int Cpad,
                  float c_x, float c_e, int dtype, ur_stream_t stream);
 /* Tiled latent sampling (unirestore_amd/tiling.py).  Latents fp32 NHWC [N,LH,LW,Cpad]; tile batch [N*T,th,tw,.] with image n's
- * tile k at index n*T+k; origins device int [T][2] = (y0, x0), every tile inside the latent (others are skipped).
- * gather: tiles_16 <- 16-bit copy of each tile's window of z. */
+ * tile k at index n*T+k; origins device int [T][2] = (y0, x0), every tile inside the latent (others are skipped: a tile is valid when
+ * y0 >= 0, x0 >= 0, y0 + th <= LH and x0 + tw <= LW, by one test shared by both kernels).
+ * gather: tiles_16 <- 16-bit copy of each tile's window of z; the slots of a skipped tile are written as zeros. */
 int ur_latent_tiles_gather(const float* z, void* tiles_16, int N, int LH, int LW, int Cpad, int T, int th, int tw,
                            const int* origins, int dtype, ur_stream_t stream);
 /* Blended DDIM step, output-stationary per latent pixel p: eps(p) = sum_k wn[k](p) * eps_tiles_k(p) over the covering tiles in
  * ascending k (fp32), zt <- c_x*zt + c_e*eps, and the 16-bit zt into every covering tile slot of zt_tiles_16.  eps_tiles fp32
- * [N*T,th,tw,ld_eps], wn fp32 [T,th,tw] (normalised weights), Clat <= 8. */
+ * [N*T,th,tw,ld_eps], wn fp32 [T,th,tw] (normalised weights), Clat <= 8.  A skipped tile's eps and weights are not read and its slots
+ * are not written; a pixel that no valid tile covers gets c_x*zt. */
 int ur_latent_tiles_blend_ddim(float* zt, const float* eps_tiles, int ld_eps, void* zt_tiles_16, const float* wn, int N, int LH,
                                int LW, int Clat, int Cpad, int T, int th, int tw, const int* origins, float c_x, float c_e,
                                int dtype, ur_stream_t stream);

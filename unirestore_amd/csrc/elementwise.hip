@@ -586,7 +586,12 @@ __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restric
 }
 
 // ---- tiled latent sampling (unirestore_amd/tiling.py): tile gather + blended DDIM step ---------------------------------
-// origins: device int [T][2] = (y0, x0); a tile that would not lie inside the latent is skipped (gather writes zeros for it).
+// origins: device int [T][2] = (y0, x0); a tile that would not lie inside the latent on all four sides is skipped by both
+// kernels (gather writes zeros for it; blend neither reads its eps nor writes its slots).
+__device__ __forceinline__ bool tile_inside(int y0, int x0, int th, int tw, int LH, int LW) {
+  return y0 >= 0 && x0 >= 0 && y0 + th <= LH && x0 + tw <= LW;
+}
+
 template <bool F16>
 __global__ __launch_bounds__(256) void latent_tiles_gather_kernel(const float* __restrict__ z, uint16_t* __restrict__ tiles,
                                                                   int LH, int LW, int Cpad, int T, int th, int tw,
@@ -598,7 +603,7 @@ __global__ __launch_bounds__(256) void latent_tiles_gather_kernel(const float* _
     const long long nk = r / th;
     const int k = (int)(nk % T), n = (int)(nk / T);
     const int y0 = origins[2 * k], x0 = origins[2 * k + 1];
-    const bool ok = y0 >= 0 && x0 >= 0 && y0 + th <= LH && x0 + tw <= LW;
+    const bool ok = tile_inside(y0, x0, th, tw, LH, LW);
     const float* src = z + (((long long)n * LH + (y0 + y)) * LW + (x0 + x)) * Cpad;
     for (int c = 0; c < Cpad; ++c) tiles[i * Cpad + c] = ok ? f2h16<F16>(src[c]) : (uint16_t)0;
   }
@@ -622,7 +627,7 @@ __global__ __launch_bounds__(256) void latent_tiles_blend_ddim_kernel(float* __r
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int k = 0; k < T; ++k) {
       const int ty = y - origins[2 * k], tx = x - origins[2 * k + 1];
-      if (ty < 0 || tx < 0 || ty >= th || tx >= tw || origins[2 * k] + th > LH || origins[2 * k + 1] + tw > LW) continue;
+      if (ty < 0 || tx < 0 || ty >= th || tx >= tw || !tile_inside(origins[2 * k], origins[2 * k + 1], th, tw, LH, LW)) continue;
       const long long q = ((long long)k * th + ty) * tw + tx;
       const float w = wn[q];
       const float* e = eps + ((n * T) * th * tw + q) * ld_eps;
@@ -636,7 +641,7 @@ __global__ __launch_bounds__(256) void latent_tiles_blend_ddim_kernel(float* __r
     for (int c = 0; c < Cpad; ++c) zt[i * Cpad + c] = c < 8 ? v[c] : 0.f;
     for (int k = 0; k < T; ++k) {
       const int ty = y - origins[2 * k], tx = x - origins[2 * k + 1];
-      if (ty < 0 || tx < 0 || ty >= th || tx >= tw || origins[2 * k] + th > LH || origins[2 * k + 1] + tw > LW) continue;
+      if (ty < 0 || tx < 0 || ty >= th || tx >= tw || !tile_inside(origins[2 * k], origins[2 * k + 1], th, tw, LH, LW)) continue;
       uint16_t* d = tiles + ((n * T + k) * th * tw + (long long)ty * tw + tx) * Cpad;
       for (int c = 0; c < Cpad; ++c) d[c] = c < 8 ? f2h16<F16>(v[c]) : (uint16_t)0;
     }
@@ -748,7 +753,8 @@ int ur_vec_mul_group(const float* a, const float* b, float* out, int N, int C, i
 
 int ur_nchw_f32_to_nhwc(const float* x, void* y, int N, int C, int H, int W, int Cpad, int dtype, ur_stream_t stream) {
   UR_REQUIRE_DT(dtype);
-  UR_REQUIRE(x && y && Cpad >= C, "bad args");
+  UR_REQUIRE(x && y, "null pointer");
+  UR_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && Cpad >= C, "N, C, H, W must be positive and Cpad >= C");
   const long long total = (long long)N * H * W;
   UR_DT_SWITCH(dtype, hipLaunchKernelGGL(nchw_to_nhwc_kernel<F16>, dim3(nblocks(total)), dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)y, C,
                      (long long)H * W, Cpad, 1.f, 0.f, total));
@@ -757,7 +763,8 @@ int ur_nchw_f32_to_nhwc(const float* x, void* y, int N, int C, int H, int W, int
 
 int ur_image_to_nhwc(const float* img, void* y, int N, int C, int H, int W, int Cpad, int dtype, ur_stream_t stream) {
   UR_REQUIRE_DT(dtype);
-  UR_REQUIRE(img && y && Cpad >= C, "bad args");
+  UR_REQUIRE(img && y, "null pointer");
+  UR_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && Cpad >= C, "N, C, H, W must be positive and Cpad >= C");
   const long long total = (long long)N * H * W;
   UR_DT_SWITCH(dtype, hipLaunchKernelGGL(nchw_to_nhwc_kernel<F16>, dim3(nblocks(total)), dim3(256), 0, (hipStream_t)stream, img, (uint16_t*)y, C,
                      (long long)H * W, Cpad, 2.f, -1.f, total));
@@ -767,7 +774,8 @@ int ur_image_to_nhwc(const float* img, void* y, int N, int C, int H, int W, int 
 int ur_nhwc_to_nchw_f32(const void* x, int x_is_f32, float* out, int N, int C, int H, int W, int ld, float mul, float add,
                         int dtype, ur_stream_t stream) {
   UR_REQUIRE_DT(dtype);
-  UR_REQUIRE(x && out && ld >= C, "bad args");
+  UR_REQUIRE(x && out, "null pointer");
+  UR_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && ld >= C, "N, C, H, W must be positive and ld >= C");
   const long long total = (long long)N * H * W;
   UR_DT_SWITCH(dtype, hipLaunchKernelGGL(nhwc_to_nchw_kernel<F16>, dim3(nblocks(total)), dim3(256), 0, (hipStream_t)stream, x, x_is_f32, out, C,
                      (long long)H * W, ld, mul, add, total));
@@ -777,7 +785,8 @@ int ur_nhwc_to_nchw_f32(const void* x, int x_is_f32, float* out, int N, int C, i
 int ur_image_resize_pad_nhwc(const float* img, void* y, int N, int C, int H, int W, int RH, int RW, int PH, int PW, int Cpad,
                              float mul, float add, int dtype, ur_stream_t stream) {
   UR_REQUIRE_DT(dtype);
-  UR_REQUIRE(img && y && Cpad >= C && N > 0 && H > 0 && W > 0 && RH > 0 && RW > 0, "bad args");
+  UR_REQUIRE(img && y, "null pointer");
+  UR_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && RH > 0 && RW > 0 && Cpad >= C, "N, C, H, W, RH, RW must be positive and Cpad >= C");
   UR_REQUIRE(PH >= 0 && PW >= 0 && PH < RH && PW < RW, "reflect padding must be smaller than the image");
   const long long total = (long long)N * (RH + PH) * (RW + PW);
   UR_DT_SWITCH(dtype, hipLaunchKernelGGL(image_resize_pad_kernel<F16>, dim3(nblocks(total)), dim3(256), 0, (hipStream_t)stream, img, (uint16_t*)y, C, H, W,
@@ -788,7 +797,8 @@ int ur_image_resize_pad_nhwc(const float* img, void* y, int N, int C, int H, int
 int ur_image_unpad_resize_nchw(const void* x, int x_is_f32, float* out, int N, int C, int XH, int XW, int ld, int CH, int CW,
                                int OH, int OW, float mul, float add, int quantize, int dtype, ur_stream_t stream) {
   UR_REQUIRE_DT(dtype);
-  UR_REQUIRE(x && out && ld >= C && N > 0 && OH > 0 && OW > 0, "bad args");
+  UR_REQUIRE(x && out, "null pointer");
+  UR_REQUIRE(N > 0 && C > 0 && OH > 0 && OW > 0 && ld >= C, "N, C, OH, OW must be positive and ld >= C");
   UR_REQUIRE(CH > 0 && CW > 0 && CH <= XH && CW <= XW, "crop window must lie inside the input");
   const long long total = (long long)N * OH * OW;
   UR_DT_SWITCH(dtype, hipLaunchKernelGGL(image_unpad_resize_kernel<F16>, dim3(nblocks(total)), dim3(256), 0, (hipStream_t)stream, x, x_is_f32, out, C, XH, XW,
@@ -823,7 +833,9 @@ int ur_image_u8_egress(const void* x, int x_is_f32, uint8_t* dst, long long slot
 int ur_vae_sample(const float* moments, int ld, const float* noise_nchw, float* z_nhwc, void* z_16, int N, int HW,
                   int Clat, int Cpad, float scale, int dtype, ur_stream_t stream) {
   UR_REQUIRE_DT(dtype);
-  UR_REQUIRE(moments && noise_nchw && z_nhwc && z_16 && ld >= 2 * Clat && Cpad >= Clat, "bad args");
+  UR_REQUIRE(moments && noise_nchw && z_nhwc && z_16, "null pointer");
+  UR_REQUIRE(N > 0 && HW > 0 && Clat > 0, "N, HW, Clat must be positive");
+  UR_REQUIRE(ld >= 2 * Clat && Cpad >= Clat, "channels: ld >= 2 * Clat, Cpad >= Clat");
   const long long total = (long long)N * HW;
   UR_DT_SWITCH(dtype, hipLaunchKernelGGL(vae_sample_kernel<F16>, dim3(nblocks(total)), dim3(256), 0, (hipStream_t)stream, moments, ld, noise_nchw,
                      z_nhwc, (uint16_t*)z_16, (long long)HW, Clat, Cpad, scale, total));
@@ -834,6 +846,7 @@ int ur_add_noise(const float* z0, const float* noise_nchw, float* zt, void* zt_1
                  float sa, float sb, int dtype, ur_stream_t stream) {
   UR_REQUIRE_DT(dtype);
   UR_REQUIRE(z0 && noise_nchw && zt && zt_16, "null pointer");
+  UR_REQUIRE(N > 0 && HW > 0 && Clat > 0 && Cpad >= Clat, "N, HW, Clat must be positive and Cpad >= Clat");
   const long long total = (long long)N * HW;
   UR_DT_SWITCH(dtype, hipLaunchKernelGGL(add_noise_kernel<F16>, dim3(nblocks(total)), dim3(256), 0, (hipStream_t)stream, z0, noise_nchw, zt,
                      (uint16_t*)zt_16, (long long)HW, Clat, Cpad, sa, sb, total));
@@ -843,7 +856,9 @@ int ur_add_noise(const float* z0, const float* noise_nchw, float* zt, void* zt_1
 int ur_ddim_step(float* zt, const float* eps, int ld_eps, void* zt_16, long long M, int Clat, int Cpad, float c_x,
                  float c_e, int dtype, ur_stream_t stream) {
   UR_REQUIRE_DT(dtype);
-  UR_REQUIRE(zt && eps && zt_16 && ld_eps >= Clat, "bad args");
+  UR_REQUIRE(zt && eps && zt_16, "null pointer");
+  UR_REQUIRE(M > 0 && Clat > 0, "M, Clat must be positive");
+  UR_REQUIRE(Cpad >= Clat && ld_eps >= Clat, "channels: Cpad >= Clat, ld_eps >= Clat");
   UR_DT_SWITCH(dtype, hipLaunchKernelGGL(ddim_step_kernel<F16>, dim3(nblocks(M)), dim3(256), 0, (hipStream_t)stream, zt, eps, ld_eps,
                      (uint16_t*)zt_16, Clat, Cpad, c_x, c_e, M));
   return ur::check_launch("ur_ddim_step");
@@ -875,7 +890,8 @@ int ur_latent_tiles_blend_ddim(float* zt, const float* eps_tiles, int ld_eps, vo
 
 int ur_f32_to_bf16_scaled(const float* x, int ld, void* y, long long M, int C, int Cpad, float mul, int dtype, ur_stream_t stream) {
   UR_REQUIRE_DT(dtype);
-  UR_REQUIRE(x && y && ld >= C && Cpad >= C, "bad args");
+  UR_REQUIRE(x && y, "null pointer");
+  UR_REQUIRE(M > 0 && C > 0 && ld >= C && Cpad >= C, "M, C must be positive, ld >= C and Cpad >= C");
   UR_DT_SWITCH(dtype, hipLaunchKernelGGL(f32_to_bf16_kernel<F16>, dim3(nblocks(M)), dim3(256), 0, (hipStream_t)stream, x, ld, (uint16_t*)y, C, Cpad,
                      mul, M));
   return ur::check_launch("ur_f32_to_bf16_scaled");
