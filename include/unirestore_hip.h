@@ -375,6 +375,25 @@ int ur_image_metrics(const float* pred, const float* target, int N, int C, int H
                      double* psnr, double* ssim, void* ws, long long ws_bytes, ur_stream_t stream);
 long long ur_image_metrics_ws_size(int N, int C, int H, int W, int win);
 
+/* ---- colour correction of a restored image (between the decoder's conv_out and the egress kernels) ----------------------
+ * c fp32 NHWC [N,H,W,ld_c]: the restored image; src 16-bit NHWC [src_n,H,W,ld_s]: the image the encoder saw, image n is corrected
+ * against source n % src_n (a task-major K*B batch against B sources); out fp32 NHWC [N,H,W,ld_c], not c.  Channels 0..2 are RGB;
+ * channels [3, ld) of c and src are never used in arithmetic and those of out are written as zeros.
+ *   wavelet: out = c + L(src - c), L = B_16 B_8 B_4 B_2 B_1, B_r(v)[y,x] = sum over i,j in {-1,0,1} of k_i k_j v[clamp(y + i r), clamp(x + j r)],
+ *            k = (1/4, 1/2, 1/4), clamp to the image at every level (replicate border): the restored detail on the source's level-5
+ *            low band.  Two launches (the five vertical levels in LDS, then the five horizontal ones); out holds the value between.
+ *   adain:   out = (c - mu_c) * (sigma_s / sigma_c) + mu_s per image and channel over the H*W pixels, sigma = sqrt(unbiased variance
+ *            + 1e-5); fp64 fixed-order statistics, fp32 (a, b) and out = a*c + b.  ws: ur_color_fix_adain_ws_bytes(N, H, W) bytes,
+ *            8-byte aligned (that function returns 0 for a non-positive argument).
+ * UR_E_INVALID before any launch for a null pointer, N, src_n, H or W <= 0, N % src_n != 0, ld_c or ld_s < 3, an unknown dtype,
+ * out == c, for adain H*W < 2 or a workspace that is too small.  No allocation, no synchronisation, no atomics: the same inputs
+ * give the same bits. */
+int ur_color_fix_wavelet(const void* c_f32, int ld_c, const void* src_16, int ld_s, float* out, int N, int src_n, int H, int W, int dtype,
+                         ur_stream_t stream);
+int ur_color_fix_adain(const void* c_f32, int ld_c, const void* src_16, int ld_s, float* out, int N, int src_n, int H, int W, int dtype,
+                       void* ws, size_t ws_bytes, ur_stream_t stream);
+size_t ur_color_fix_adain_ws_bytes(int N, int H, int W);
+
 /* ---- live per-kernel-family timing (HIP events on the launch stream) ------------------------------*/
 int ur_profile_enable(int on);
 /* writes a JSON object {family: {launches, ms, flops, bytes}} into buf (host); synchronises the events */

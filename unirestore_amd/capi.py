@@ -117,6 +117,9 @@ SIGNATURES = {
     "ur_f32_to_bf16_scaled": (_I, [_P, _I, _P, _LL, _I, _I, _F, _I, _P]),
     "ur_image_metrics": (_I, [_P, _P, _I, _I, _I, _I, _I, C.c_double, _P, _P, _P, _LL, _P]),
     "ur_image_metrics_ws_size": (_LL, [_I, _I, _I, _I, _I]),
+    "ur_color_fix_wavelet": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
+    "ur_color_fix_adain": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
+    "ur_color_fix_adain_ws_bytes": (_SZ, [_I, _I, _I]),
     "ur_profile_enable": (_I, [_I]),
     "ur_profile_report": (_I, [C.c_char_p, _SZ]),
 }

@@ -48,6 +48,23 @@ def load_config(path: str, overrides=()) -> dict:
     return cfg
 
 
+COLOR_FIX_CHOICES = ("none", "wavelet", "adain")
+
+
+def apply_color_fix(cfg: dict, flag) -> dict:
+    """--color-fix {none,wavelet,adain} overrides the config's `cnet.color_fix` ("none" turns a configured fix off); flag None
+    leaves the config as it is.  Returns cfg."""
+    if flag is None:
+        return cfg
+    if flag not in COLOR_FIX_CHOICES:
+        raise ValueError(f"--color-fix {flag!r}: choose from {list(COLOR_FIX_CHOICES)}")
+    mk = cfg["model"].setdefault("init_args", {}).setdefault("model_kwargs", {})
+    if not mk.get("cnet"):
+        raise ValueError("--color-fix: the config has no model_kwargs.cnet section to carry cnet.color_fix")
+    mk["cnet"]["color_fix"] = None if flag == "none" else flag
+    return cfg
+
+
 def resolve(cfg: dict, allow_16bit: bool = False) -> dict:
     """Validate a config and reduce it to what the runner needs (raises ValueError / KeyError on unknown pieces)."""
     tr, mo, da = cfg.get("trainer", {}), cfg["model"], cfg.get("data", {})
@@ -82,6 +99,8 @@ def resolve(cfg: dict, allow_16bit: bool = False) -> dict:
         stride = int(cn["tile_stride"]) if cn.get("tile_stride") is not None else default_tile_stride(tile)
         check_tile_stride(tile, stride)
         mk["cnet"] = dict(cn, tile_size=tile, tile_stride=stride)
+    if cn.get("color_fix") is not None and cn["color_fix"] not in ("wavelet", "adain"):      # colour fix of the outputs (opt-in)
+        raise ValueError(f"cnet.color_fix={cn['color_fix']!r}: choose wavelet, adain or null")
     dcp = da.get("class_path", "unirestore_amd.data.SyntheticImages")
     if dcp not in DATA_CLASSES:
         raise KeyError(f"data.class_path {dcp!r} unknown: {sorted(DATA_CLASSES)}")
@@ -240,6 +259,7 @@ def restore(cfg: dict, inp, output, task=None, tasks=None, batch=8, hf_root=None
     no_ckpt = not any((r["model_kwargs"].get(k) or {}).get("ckpt_path") for k in ("frenc", "cnet", "tedit")) and not hf_root
     if model is not None:
         model.set_dtype(r["dtype"])
+        model.set_color_fix((r["model_kwargs"].get("cnet") or {}).get("color_fix"))
     elif no_ckpt and random_init and rank == 0:             # no checkpoint reachable: seeded random weights of the architecture
         from .init import init_random_
         init_random_(lit.model, r["seed"], "cpu")
@@ -311,9 +331,12 @@ def main(argv=None):
     ap.add_argument("--task", default=None, help="restore: the task to decode for (default ir)")
     ap.add_argument("--input", default=None, help="restore: a folder of images, or a text file with one path (or `lq hq label`) per line")
     ap.add_argument("--output", default=None, help="restore: folder for <stem>.png")
+    ap.add_argument("--color-fix", choices=list(COLOR_FIX_CHOICES), default=None,
+                    help="validate / restore: colour fix of the restored images against the inputs (DiffUIE.set_color_fix); overrides "
+                         "the config's cnet.color_fix, none turns it off")
     ap.add_argument("--batch", type=int, default=8, help="restore: images per forward (images of a batch share a canvas)")
     a = ap.parse_args(argv)
-    cfg = load_config(a.config, a.set)
+    cfg = apply_color_fix(load_config(a.config, a.set), a.color_fix)
     if a.command == "print_config":
         print(yaml.safe_dump(cfg, sort_keys=False))
         print(json.dumps(resolve(cfg, allow_16bit=a.allow_16bit)))

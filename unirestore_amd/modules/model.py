@@ -273,8 +273,9 @@ class SkipConnectedAutoEncoder(nn.Module):
             self.task_list, self.tedit_type = [], None
 
     # ---- NHWC fast path -------------------------------------------------------------------------------------
-    def encode_run(self, images_dev: torch.Tensor, noise_nchw: torch.Tensor, enable_fr: bool, plan=None):
-        """images fp32 NCHW in [0,1] on device -> (z fp32 [B,h,w,8], z bf16, [3 NHWC bf16 skip features]).
+    def encode_run(self, images_dev: torch.Tensor, noise_nchw: torch.Tensor, enable_fr: bool, plan=None, return_input=False):
+        """images fp32 NCHW in [0,1] on device -> (z fp32 [B,h,w,8], z bf16, [3 NHWC bf16 skip features]); with return_input
+        also x0, the 16-bit NHWC canvas in [-1, 1] that conv_in reads (the source of `decode_run`'s colour fix), as a fourth item.
         plan = (resized_h, resized_w, pad_h, pad_w): DiffUIE.forward's bicubic resize + reflect pad run in the layout kernel.
         plan = a RaggedIO: images_dev is its uint8 slot buffer, the per-image geometry comes from its device table."""
         enc, lat = self.vae.encoder, self.vae.latent_channels
@@ -293,11 +294,25 @@ class SkipConnectedAutoEncoder(nn.Module):
         h = ops.conv(enc.conv_norm_out.run(h, silu=True), enc.conv_out.packed())
         moments = ops.conv(h, self.vae.quant_conv.packed(), out_f32=True)
         z, zb = ops.vae_sample(moments, noise_nchw, lat, self.vae.config.scaling_factor)
-        return z, zb, res
+        return (z, zb, res, x0) if return_input else (z, zb, res)
 
-    def decode_run(self, z_f32: torch.Tensor, res_samples, task: str, out_plan=None):
+    def _egress(self, x, out_plan, color_src=None, color_fix=None):
+        """conv_out's fp32 NHWC canvas -> the caller's images: the colour fix against color_src (x0 of `encode_run`; a task-major
+        batch reads source n % B) when a source and a mode are given, then the boundary kernel that out_plan names."""
+        c = self.vae.decoder.conv_out.out_channels
+        if color_src is not None and color_fix is not None:
+            x = ops.color_fix(x, color_src, color_fix)
+        if isinstance(out_plan, RaggedIO):
+            return out_plan.egress(x, c)
+        if out_plan:
+            return ops.image_unpad_resize(x, c, out_plan[0], out_plan[1], mul=0.5, add=0.5, quantize=out_plan[2])
+        return ops.nhwc_to_nchw(x, c=c, mul=0.5, add=0.5)             # (x+1)/2
+
+    def decode_run(self, z_f32: torch.Tensor, res_samples, task: str, out_plan=None, color_src=None, color_fix=None):
         """out_plan = (crop_hw, out_hw, quantize): un-pad + bicubic resize back (+ 8-bit quantisation) in the layout kernel.
-        out_plan = a RaggedIO: the same per image from its device table, the result is its uint8 slot buffer."""
+        out_plan = a RaggedIO: the same per image from its device table, the result is its uint8 slot buffer.
+        color_src = x0 of `encode_run(return_input=True)` and color_fix = "wavelet" | "adain": ops.color_fix runs on conv_out's
+        output at canvas size, in front of whichever boundary kernel follows."""
         dec, lat = self.vae.decoder, self.vae.latent_channels
         if self.tedit_dict and task not in dec.task_prompts:
             raise KeyError(task)
@@ -318,11 +333,7 @@ class SkipConnectedAutoEncoder(nn.Module):
                 h = blk.run(h)
             h = dec.up_blocks[-1].run(h)
         h = ops.conv(dec.conv_norm_out.run(h, silu=True), dec.conv_out.packed(), out_f32=True)
-        if isinstance(out_plan, RaggedIO):
-            return out_plan.egress(h, dec.conv_out.out_channels)
-        if out_plan:
-            return ops.image_unpad_resize(h, dec.conv_out.out_channels, out_plan[0], out_plan[1], mul=0.5, add=0.5, quantize=out_plan[2])
-        return ops.nhwc_to_nchw(h, c=dec.conv_out.out_channels, mul=0.5, add=0.5)             # (x+1)/2
+        return self._egress(h, out_plan, color_src, color_fix)
 
     # ---- multi-task decode: one shared decoder head, the task-dependent tail as one task-major batch ----------------------
     def check_tasks(self, tasks):
@@ -364,14 +375,15 @@ class SkipConnectedAutoEncoder(nn.Module):
         oh, ow = lh << last, lw << last
         return oh, ow, -(-elems // (oh * ow))
 
-    def decode_run_tasks(self, z_f32: torch.Tensor, res_samples, tasks, out_plan=None):
+    def decode_run_tasks(self, z_f32: torch.Tensor, res_samples, tasks, out_plan=None, color_src=None, color_fix=None):
         """`decode_run` for several tasks of the same latents -> {task: image}, insertion order = order of `tasks`.
         post_quant_conv, conv_in, the mid block and every TFA's task-free half run once at B; the rest runs on a task-major
         batch (task k's image b at row k*B + b), in as few chunks of tasks as the conv launcher's size limit allows.
         With a RaggedIO as out_plan (forward_u8) every chunk is ONE task: the conv launchers plan a batch of K*B differently from a
         batch of B, so a fanned-out tail differs from the single-task decode in the last bits, and an 8-bit file must not depend
         on which other tasks were asked for.  The head and the task-free halves still run once; the tail's cost is linear in K*B
-        either way (22.5 ms per task at B = 8, 512 x 512)."""
+        either way (22.5 ms per task at B = 8, 512 x 512).
+        color_src / color_fix: as `decode_run`; every task is corrected against the same B sources."""
         dec, lat = self.vae.decoder, self.vae.latent_channels
         tasks = self.check_tasks(tasks)
         zb = ops.f32_to_bf16(z_f32, lat, mul=1.0 / self.vae.config.scaling_factor)
@@ -380,11 +392,7 @@ class SkipConnectedAutoEncoder(nn.Module):
 
         def tail(x):
             x = ops.conv(dec.conv_norm_out.run(x, silu=True), dec.conv_out.packed(), out_f32=True)
-            if isinstance(out_plan, RaggedIO):
-                return out_plan.egress(x, dec.conv_out.out_channels)
-            if out_plan:
-                return ops.image_unpad_resize(x, dec.conv_out.out_channels, out_plan[0], out_plan[1], mul=0.5, add=0.5, quantize=out_plan[2])
-            return ops.nhwc_to_nchw(x, c=dec.conv_out.out_channels, mul=0.5, add=0.5)
+            return self._egress(x, out_plan, color_src, color_fix)
 
         if not self.tedit_dict:                                # stock decoder: the task is ignored - one decode, a tensor per name
             for blk in dec.up_blocks:
@@ -503,6 +511,9 @@ class DiffUIE(nn.Module):
         if cnet and cnet.get("tile_size") is not None:
             tile = int(cnet["tile_size"])
             self.set_latent_tiling(tile, int(cnet.get("tile_stride") or tiling.default_tile_stride(tile)))
+        self.color_fix = None                  # "wavelet" | "adain": colour fix of the restored canvas against the input, or None
+        if cnet and cnet.get("color_fix") is not None:
+            self.set_color_fix(cnet["color_fix"])
         self._own_dtype()
         self._arm_load_hooks()
 
@@ -546,6 +557,20 @@ class DiffUIE(nn.Module):
             self.latent_tiling = (int(tile), int(stride))
         self._graphs.clear()
         return self
+
+    def set_color_fix(self, mode):
+        """Colour correction of the restored images against the input (off by default): "wavelet" keeps the restored detail and
+        takes the level-5 a-trous low band from the input, "adain" matches per-channel mean and standard deviation
+        (ops.color_fix).  It runs at canvas size between the decoder's conv_out and the boundary kernel, in forward, forward_tasks
+        (every task against the same input) and forward_u8, eager and captured.  set_color_fix(None) turns it off; anything else
+        is a ValueError.  Captured graphs are dropped."""
+        self.color_fix = ops.check_color_fix_mode(mode)
+        self._graphs.clear()
+        return self
+
+    def _fix_key(self):
+        """The colour fix's part of every graph key: the mode behind the key's other fields, nothing while the fix is off."""
+        return () if self.color_fix is None else (self.color_fix,)
 
     def _tile_plan(self, lh, lw):
         """(T, (th, tw), device origins int32 [T,2], device wn fp32 [T,th,tw]) of the current tiling for an lh x lw latent, or
@@ -626,7 +651,11 @@ class DiffUIE(nn.Module):
         forward_u8: images is the uint8 slot buffer and plan a RaggedIO; preds are then uint8 slot buffers."""
         lat = self.ae.vae.latent_channels
         out_plan = plan if isinstance(plan, RaggedIO) else (plan[:2], tuple(images.shape[-2:]), quantize)
-        z0, z0b, mids = self.ae.encode_run(images, n_vae, enable_fr=self.fr_type is not None, plan=plan)
+        x0 = None
+        if self.color_fix is None:
+            z0, z0b, mids = self.ae.encode_run(images, n_vae, enable_fr=self.fr_type is not None, plan=plan)
+        else:
+            z0, z0b, mids, x0 = self.ae.encode_run(images, n_vae, enable_fr=self.fr_type is not None, plan=plan, return_input=True)
         zt = z0
         tp = self._tile_plan(z0.shape[1], z0.shape[2]) if self.control_type else None
         if tp is not None:
@@ -643,7 +672,8 @@ class DiffUIE(nn.Module):
                 if self.trace_zt is not None and not torch.cuda.is_current_stream_capturing():
                     self.trace_zt.append(ops.nhwc_to_nchw(zt, c=lat).cpu())      # parity instrumentation (eager runs only)
         decode = self.ae.decode_run_tasks if isinstance(task, tuple) else self.ae.decode_run     # a tuple: forward_tasks
-        preds = decode(zt, mids, task, out_plan=out_plan)
+        preds = decode(zt, mids, task, out_plan=out_plan) if x0 is None else \
+            decode(zt, mids, task, out_plan=out_plan, color_src=x0, color_fix=self.color_fix)
         return preds, z0, zt
 
     def _denoise_tiled(self, z0, n_t, tp):
@@ -774,7 +804,7 @@ class DiffUIE(nn.Module):
             return preds, z0, zt, io.flags
         inputs = dict(slots=slots, geom=geom, n_vae=n_vae, n_t=n_t)
         if self.use_graph:
-            preds, z0, zt, flags = self._captured(("u8", n, ch, cw, task, self.dtype, self.latent_tiling), inputs, run)
+            preds, z0, zt, flags = self._captured(("u8", n, ch, cw, task, self.dtype, self.latent_tiling) + self._fix_key(), inputs, run)
         else:
             preds, z0, zt, flags = run({name: v.to(DEV) for name, v in inputs.items()})
         self.__dict__["_u8_flags"] = (flags, n)
@@ -841,7 +871,7 @@ class DiffUIE(nn.Module):
         return outs
 
     def _graph_forward(self, images, task, n_vae, n_t, plan, quantize=False):
-        key = (tuple(images.shape), task, bool(quantize), self.dtype, self.latent_tiling)
+        key = (tuple(images.shape), task, bool(quantize), self.dtype, self.latent_tiling) + self._fix_key()
         outs = self._captured(key, dict(images=images, n_vae=n_vae, n_t=n_t),
                               lambda st: self._forward_device(st["images"], task, st["n_vae"], st["n_t"], plan, quantize))
         # the graph's output tensors are overwritten by the next replay of this (shape, task) graph: hand the caller copies

@@ -617,6 +617,57 @@ def image_u8_egress(x: torch.Tensor, c: int, geom: torch.Tensor, mul=1.0, add=0.
     return out, nonfinite
 
 
+COLOR_FIX_MODES = ("wavelet", "adain")
+
+
+def check_color_fix_mode(mode):
+    """None (off) or one of COLOR_FIX_MODES -> the mode; ValueError for anything else."""
+    if mode is not None and mode not in COLOR_FIX_MODES:
+        raise ValueError(f"color fix mode must be None, 'wavelet' or 'adain', got {mode!r}")
+    return mode
+
+
+def color_fix(c: torch.Tensor, src: torch.Tensor, mode: str, src_n=None):
+    """Colour correction of restored images against the images the encoder saw, in the decoder's domain (about [-1, 1]):
+    c fp32 NHWC [N, H, W, ld_c] (the conv_out output), src 16-bit NHWC [>= src_n, H, W, ld_s] (x0), image n is corrected against
+    source n % src_n (src_n defaults to src.shape[0] and must divide N).  mode "wavelet": c + L(src - c), the restored detail on the
+    source's level-5 a-trous low band; "adain": c's per-channel mean / standard deviation replaced by the source's.
+    -> fp32 NHWC [N, H, W, ld_c], RGB in channels 0..2 and zeros behind them."""
+    if mode not in COLOR_FIX_MODES:
+        raise ValueError(f"color_fix: mode must be 'wavelet' or 'adain', got {mode!r}")
+    if not isinstance(c, torch.Tensor) or c.ndim != 4 or c.dtype != torch.float32 or not c.is_contiguous():
+        raise ValueError(f"color_fix: c must be a contiguous 4-d fp32 NHWC tensor, got {getattr(c, 'dtype', type(c))} "
+                         f"{tuple(getattr(c, 'shape', ()))}")
+    if not isinstance(src, torch.Tensor) or src.ndim != 4 or src.dtype not in (BF16, F16) or not src.is_contiguous():
+        raise ValueError(f"color_fix: src must be a contiguous 4-d 16-bit NHWC tensor, got {getattr(src, 'dtype', type(src))} "
+                         f"{tuple(getattr(src, 'shape', ()))}")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    for name, t in (("c", c), ("src", src)):
+        if t.device != dev:
+            raise ValueError(f"color_fix: {name} is on {t.device}, not on the current device {dev}")
+    n, h, w_, ld_c = c.shape
+    src_n = int(src.shape[0] if src_n is None else src_n)
+    if tuple(src.shape[1:3]) != (h, w_):
+        raise ValueError(f"color_fix: c is {h} x {w_} but src is {src.shape[1]} x {src.shape[2]}: both live on one canvas")
+    if not 1 <= src_n <= src.shape[0] or n % src_n:
+        raise ValueError(f"color_fix: src_n = {src_n} must be in [1, {src.shape[0]}] and divide N = {n}")
+    if ld_c < 3 or src.shape[3] < 3:
+        raise ValueError(f"color_fix: both tensors need at least 3 channels (RGB), got ld_c = {ld_c}, ld_s = {src.shape[3]}")
+    if n == 0 or h == 0 or w_ == 0:
+        raise ValueError(f"color_fix: empty tensor {tuple(c.shape)}")
+    out = torch.empty_like(c)
+    if mode == "wavelet":
+        check(lib.ur_color_fix_wavelet(c.data_ptr(), ld_c, src.data_ptr(), src.shape[3], out.data_ptr(), n, src_n, h, w_, _dt(src), _stream()))
+    else:
+        if h * w_ < 2:
+            raise ValueError("color_fix: adain needs at least 2 pixels per image (unbiased variance)")
+        ws_bytes = lib.ur_color_fix_adain_ws_bytes(n, h, w_)
+        ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+        check(lib.ur_color_fix_adain(c.data_ptr(), ld_c, src.data_ptr(), src.shape[3], out.data_ptr(), n, src_n, h, w_, _dt(src),
+                                     ws.data_ptr(), ws_bytes, _stream()))
+    return out
+
+
 def nhwc_to_nchw(x: torch.Tensor, c=None, mul=1.0, add=0.0):
     n, h, w_, ld = x.shape
     c = c or ld
