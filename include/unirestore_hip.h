@@ -364,6 +364,23 @@ int ur_latent_tiles_blend_ddim(float* zt, const float* eps_tiles, int ld_eps, vo
 /* y_16[M][Cpad] = x_f32[M][ld] * mul (latents / scaling_factor before post_quant_conv) */
 int ur_f32_to_bf16_scaled(const float* x, int ld, void* y, long long M, int C, int Cpad, float mul, int dtype, ur_stream_t stream);
 
+/* ---- counter-based noise keyed per image (the forward's two draws when seeds are given) -------------------------------------
+ * out[n][e] for image n (key row n), draw `draw` (0 = the VAE posterior draw, 1 = the t=999 draw) and element e of the image's
+ * `count` elements (for a [C,H,W] latent in NCHW order e = (c*H + y)*W + x):
+ *   Philox4x32-10, multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85;
+ *   key = (keys[n][0], keys[n][1]) = (seed_n & 0xffffffff, seed_n >> 32) of the image's unsigned 64-bit seed;
+ *   counter = (e >> 2, draw, 0, 0); element e takes output word e & 3.
+ *   kind 1: out uint32 = that word.
+ *   kind 0: out fp32 = a standard normal by Box-Muller on the word pairs (0,1) and (2,3): u = ((word >> 9) + 0.5) * 2^-23 (exact in
+ *           fp32, inside [2^-24, 1 - 2^-24], so the logarithm never sees 0), r = sqrt(-2 ln u_a), theta = 2 pi u_b, the even word
+ *           gives r cos(theta), the odd word r sin(theta); fp32 arithmetic with the precise logf / sqrtf / sincosf, never the fast
+ *           intrinsics.  |value| <= sqrt(48 ln 2) ~ 5.77; within 1e-5 of the same formula in fp64.
+ * keys: DEVICE uint32 [N][2], read by the kernel (never baked into its arguments: one captured graph serves every seed).  One thread
+ * per counter, a 16-byte store where the address allows it, 4-byte stores for the count % 4 tail and an `out` off 16 bytes (out must
+ * be 4-byte aligned).  One launch; no allocation, no synchronisation, no atomics.  UR_E_INVALID before any launch for a null
+ * pointer, N <= 0, count <= 0, count > 2^34 or an unknown kind. */
+int ur_keyed_noise(const uint32_t* keys, uint32_t draw, void* out, int N, long long count, int kind, ur_stream_t stream);
+
 /* ---- full-reference image metrics (evaluator side; the GPU counterpart of runner.psnr_per_image / runner.ssim) ----------
  * Full-reference metrics per image (skimage semantics, fp64 accumulation, fixed-order reductions): pred / target fp32 NCHW
  * [N,C,H,W] contiguous; psnr / ssim fp64 [N]; ws fp64 workspace of ur_image_metrics_ws_size(...) bytes.

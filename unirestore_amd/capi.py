@@ -115,6 +115,7 @@ SIGNATURES = {
     "ur_latent_tiles_gather": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "ur_latent_tiles_blend_ddim": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _F, _F, _I, _P]),
     "ur_f32_to_bf16_scaled": (_I, [_P, _I, _P, _LL, _I, _I, _F, _I, _P]),
+    "ur_keyed_noise": (_I, [_P, C.c_uint32, _P, _I, _LL, _I, _P]),
     "ur_image_metrics": (_I, [_P, _P, _I, _I, _I, _I, _I, C.c_double, _P, _P, _P, _LL, _P]),
     "ur_image_metrics_ws_size": (_LL, [_I, _I, _I, _I, _I]),
     "ur_color_fix_wavelet": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),

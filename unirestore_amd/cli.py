@@ -222,6 +222,44 @@ def check_restore_args(r: dict, inp, output, task=None, tasks=None, batch=8):
     return paths, (tuple(names) if names is not None else (task or "ir"))
 
 
+NOISE_MODES = ("batch", "image")
+
+
+def image_seed(seed: int, stem: str, sample: int = 0) -> int:
+    """The 64-bit noise seed of sample `sample` of the input named `stem` under the config's seed_everything (--noise image): a
+    pure function of the three, so a file's noise does not depend on the other files, their order, --batch or the world size."""
+    import hashlib
+    return int.from_bytes(hashlib.sha256(f"{seed}\0{stem}\0{sample}".encode()).digest()[:8], "little")
+
+
+def check_noise_args(noise="batch", samples=1):
+    """--noise / --samples of a `restore` call -> (noise mode, K); ValueError names the offending argument."""
+    if noise not in NOISE_MODES:
+        raise ValueError(f"--noise {noise!r}: choose from {list(NOISE_MODES)}")
+    if isinstance(samples, bool) or not isinstance(samples, int) or samples < 1:
+        raise ValueError(f"--samples {samples!r}: must be an integer >= 1")
+    if samples > 1 and noise != "image":
+        raise ValueError(f"--samples {samples} needs --noise image: with --noise batch a file's noise belongs to its batch, "
+                         "so its samples cannot be told apart")
+    return noise, samples
+
+
+def plan_samples(paths, samples=1):
+    """Every input K times, consecutively: [(path, stem, k)] in the order the batches are planned in."""
+    return [(p, os.path.splitext(os.path.basename(p))[0], k) for p in paths for k in range(samples)]
+
+
+def output_name(stem: str, sample: int, samples: int) -> str:
+    """<stem>.png for one sample per input, <stem>.s<k>.png for several."""
+    return f"{stem}.png" if samples == 1 else f"{stem}.s{sample}.png"
+
+
+def batch_seeds(seed: int, units, members):
+    """The seeds of a batch's slots under --noise image: units = plan_samples(...), members = the batch's indices into it.  A slot
+    that a padded batch repeats carries the repeated image's seed."""
+    return [image_seed(seed, units[i][1], units[i][2]) for i in members]
+
+
 def restore_noise(seed: int, index: int, n: int, canvas, latent_channels: int = 4):
     """The two noise tensors of batch `index` of a restore plan: a host generator seeded from the config's seed_everything and
     the batch's index in the plan of ALL ranks, so a rerun draws the same noise whatever the world size."""
@@ -232,16 +270,22 @@ def restore_noise(seed: int, index: int, n: int, canvas, latent_channels: int = 
 
 
 def restore(cfg: dict, inp, output, task=None, tasks=None, batch=8, hf_root=None, allow_16bit=False, random_init=True,
-            model=None) -> dict:
+            model=None, noise="batch", samples=1) -> dict:
     """Restore image files: OUTPUT/<stem>.png (OUTPUT/<task>/<stem>.png with tasks), each the size of its input.  Files are
     grouped by canvas (imageio.plan_batches) and every batch is one DiffUIE.forward_u8 call: uint8 in, uint8 out, one captured
     graph per (batch size, canvas).  Under torch.distributed.run rank r restores batches r, r + world, ... of the same plan and
-    writes its own files; no collective runs inside the loop.  model: a ready DiffUIE to use instead of building the config's."""
+    writes its own files; no collective runs inside the loop.  model: a ready DiffUIE to use instead of building the config's.
+    noise "batch": one host draw per batch (restore_noise), a file's noise depends on its batch and slot.  noise "image": every
+    file's noise is generated on the device from image_seed(seed_everything, stem, k) alone; samples = K then restores every
+    input K times (k = 0..K-1) into <stem>.s<k>.png."""
     import torch
+    noise, samples = check_noise_args(noise, samples)
     r = resolve(cfg, allow_16bit=allow_16bit)
     paths, which = check_restore_args(r, inp, output, task, tasks, batch)
     from . import imageio
-    sizes = [hw for _, hw in imageio.scan(paths)]
+    sizes = [hw for _, hw in imageio.scan(paths) for _k in range(samples)]
+    units = plan_samples(paths, samples)                   # what the plan's indices mean: (path, stem, sample)
+    paths = [u[0] for u in units]
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     plan = imageio.plan_batches(sizes, int(batch), rank, world)
     if not torch.cuda.is_available():
@@ -275,10 +319,13 @@ def restore(cfg: dict, inp, output, task=None, tasks=None, batch=8, hf_root=None
     t_all = time.perf_counter()
     with imageio.io_pool() as pool:
         for b, images in imageio.Prefetcher(plan, paths, pool):
-            noise = restore_noise(r["seed"], b.index, len(b.members), b.canvas, model.ae.vae.latent_channels)
+            if noise == "image":                            # a repeated slot of a padded batch carries the repeated image's seed
+                draws = dict(seeds=batch_seeds(r["seed"], units, b.members))
+            else:
+                draws = dict(noise=restore_noise(r["seed"], b.index, len(b.members), b.canvas, model.ae.vae.latent_channels))
             torch.cuda.synchronize()
             captures, t0 = model.graph_captures, time.perf_counter()
-            preds = model.forward_u8(images, which, noise=noise)
+            preds = model.forward_u8(images, which, **draws)
             by_task = preds if isinstance(which, tuple) else {which: preds}
             host = {t: [x.cpu() for x in v[:b.valid]] for t, v in by_task.items()}      # the repeats of a padded batch are dropped
             dt = time.perf_counter() - t0
@@ -291,8 +338,8 @@ def restore(cfg: dict, inp, output, task=None, tasks=None, batch=8, hf_root=None
                 saves.pop(0).result()
             for t, imgs in host.items():
                 for i, x in zip(b.members, imgs):
-                    stem = os.path.splitext(os.path.basename(paths[i]))[0]
-                    saves.append(pool.submit(imageio.save_u8, x, os.path.join(out_dirs[t], stem + ".png")))
+                    name = output_name(units[i][1], units[i][2], samples)
+                    saves.append(pool.submit(imageio.save_u8, x, os.path.join(out_dirs[t], name)))
         for f in saves:
             f.result()
     total_s = time.perf_counter() - t_all
@@ -308,7 +355,7 @@ def restore(cfg: dict, inp, output, task=None, tasks=None, batch=8, hf_root=None
                graphs_captured=graphs, batch=int(batch), tasks=list(which) if isinstance(which, tuple) else [which],
                dtype=r["dtype"], n_gpus=world, denoise_steps=r["model_kwargs"]["cnet"]["num_inference_steps"],
                images_per_s=(n_timed / secs) if secs > 0 else None, images_timed=n_timed, seconds_total=total_s,
-               output_finite=not bad, output=output)
+               output_finite=not bad, output=output, noise=noise, samples=samples)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -335,14 +382,25 @@ def main(argv=None):
                     help="validate / restore: colour fix of the restored images against the inputs (DiffUIE.set_color_fix); overrides "
                          "the config's cnet.color_fix, none turns it off")
     ap.add_argument("--batch", type=int, default=8, help="restore: images per forward (images of a batch share a canvas)")
+    ap.add_argument("--noise", choices=list(NOISE_MODES), default="batch",
+                    help="restore: batch = one host draw per batch (a file's noise depends on its batch and slot); image = every file's "
+                         "noise is generated on the GPU from (seed_everything, file stem, sample) alone")
+    ap.add_argument("--samples", type=int, default=1, metavar="K",
+                    help="restore: K restorations of every input, written as <stem>.s<k>.png (K > 1 needs --noise image)")
     a = ap.parse_args(argv)
+    if a.command == "restore":
+        try:
+            check_noise_args(a.noise, a.samples)
+        except ValueError as e:
+            ap.error(str(e))
     cfg = apply_color_fix(load_config(a.config, a.set), a.color_fix)
     if a.command == "print_config":
         print(yaml.safe_dump(cfg, sort_keys=False))
         print(json.dumps(resolve(cfg, allow_16bit=a.allow_16bit)))
         return 0
     if a.command == "restore":
-        res = restore(cfg, a.input, a.output, task=a.task, tasks=a.tasks, batch=a.batch, hf_root=a.hf_root, allow_16bit=a.allow_16bit)
+        res = restore(cfg, a.input, a.output, task=a.task, tasks=a.tasks, batch=a.batch, hf_root=a.hf_root, allow_16bit=a.allow_16bit,
+                      noise=a.noise, samples=a.samples)
         if res is not None:
             print(json.dumps(res))
         return 0

@@ -572,6 +572,11 @@ class DiffUIE(nn.Module):
         """The colour fix's part of every graph key: the mode behind the key's other fields, nothing while the fix is off."""
         return () if self.color_fix is None else (self.color_fix,)
 
+    @staticmethod
+    def _seeded_key(keys):
+        """The seeds' part of every graph key: a seeded graph generates its noise and has no noise inputs; nothing without seeds."""
+        return () if keys is None else ("seeded",)
+
     def _tile_plan(self, lh, lw):
         """(T, (th, tw), device origins int32 [T,2], device wn fp32 [T,th,tw]) of the current tiling for an lh x lw latent, or
         None when tiling is off or one tile covers the latent.  Cached: captured graphs hold the device tensors' addresses."""
@@ -645,11 +650,17 @@ class DiffUIE(nn.Module):
         return torch.cat(outs, 0), noise, torch.as_tensor(ts)
 
     # ---- the hot path ------------------------------------------------------------------------------------------------
-    def _forward_device(self, images, task, n_vae, n_t, plan, quantize=False):
+    def _forward_device(self, images, task, n_vae, n_t, plan, quantize=False, keys=None):
         """images fp32 NCHW on device (original size); plan = resize_pad_plan(H, W); task: a name, or a tuple of names
         (forward_tasks: preds is then {task: images}).  Returns (preds NCHW fp32 at the original size, z0, zt) (NHWC fp32 latents).
-        forward_u8: images is the uint8 slot buffer and plan a RaggedIO; preds are then uint8 slot buffers."""
+        forward_u8: images is the uint8 slot buffer and plan a RaggedIO; preds are then uint8 slot buffers.
+        keys: the device key table of a seeded call (n_vae / n_t are then None): both draws are generated here, at canvas latent
+        size, from the table's current content."""
         lat = self.ae.vae.latent_channels
+        if keys is not None:
+            ch, cw = plan.canvas if isinstance(plan, RaggedIO) else (plan[0] + plan[2], plan[1] + plan[3])
+            n_vae = ops.keyed_noise(keys, 0, (lat, ch // 8, cw // 8))
+            n_t = ops.keyed_noise(keys, 1, (lat, ch // 8, cw // 8))
         out_plan = plan if isinstance(plan, RaggedIO) else (plan[:2], tuple(images.shape[-2:]), quantize)
         x0 = None
         if self.color_fix is None:
@@ -700,8 +711,22 @@ class DiffUIE(nn.Module):
                 self.trace_zt.append(ops.nhwc_to_nchw(zt, c=lat).cpu())
         return zt
 
-    def _run(self, images, task, noise, quantize):
+    @staticmethod
+    def _seed_keys(seeds, noise, n):
+        """The host key table of a call's `seeds` (one int in [0, 2^64) per image), or None without seeds; ValueError for seeds
+        next to noise, a wrong count or a seed out of range."""
+        if seeds is None:
+            return None
+        if noise is not None:
+            raise ValueError("seeds and noise exclude each other: the noise is either given or generated from the seeds")
+        seeds = list(seeds)
+        if len(seeds) != n:
+            raise ValueError(f"seeds: {len(seeds)} given for {n} image(s); one per image is needed")
+        return ops.noise_keys(seeds)
+
+    def _run(self, images, task, noise, quantize, seeds=None):
         """Shared body of forward / forward_tasks: device copies, resize / pad plan, the two noise draws, graph or eager run."""
+        keys = self._seed_keys(seeds, noise, images.shape[0])
         self._prepare()
         images = images.to(DEV).float().contiguous()
         org_h, org_w = images.shape[-2:]
@@ -709,6 +734,10 @@ class DiffUIE(nn.Module):
         h, w, pad_h, pad_w = plan
         b, lat = images.shape[0], self.ae.vae.latent_channels
         lh, lw = (h + pad_h) // 8, (w + pad_w) // 8
+        if keys is not None:                     # seeded: the key table is the only noise input, the draws happen on the device
+            if self.use_graph:
+                return self._graph_forward(images, task, None, None, plan, quantize, keys=keys)
+            return self._forward_device(images, task, None, None, plan, quantize, keys=keys.to(DEV))
         if noise is None:
             noise = (torch.randn(b, lat, lh, lw, device=DEV), torch.randn(b, lat, lh, lw, device=DEV))
         n_vae, n_t = (n.to(DEV).float().contiguous() for n in noise)
@@ -731,13 +760,16 @@ class DiffUIE(nn.Module):
                                      "finite.  Run this model with dtype='bf16' (DiffUIE.set_dtype('bf16') / trainer.precision: bf16-mixed)")
 
     @torch.no_grad()
-    def forward(self, images, task: str, noise=None, return_latents=False, quantize=False):
+    def forward(self, images, task: str, noise=None, return_latents=False, quantize=False, seeds=None):
         """noise = (eps_vae, eps_t999): the two RNG draws of the reference (autoencoder.py:152, unifie.py:87), NCHW fp32.
+        seeds = one int in [0, 2^64) per image, instead of noise: both draws are then generated on the device inside the forward
+        by `ops.keyed_noise` (draw 0, draw 1), so image n's noise depends on seeds[n] alone - not on the batch it sits in, its
+        slot or the global generator - and calls with other seeds replay the same graph.
         quantize=True additionally applies the evaluator's mul(255).round().clamp(0,255).div(255) (eval_image_restoration.py:71).
         Resize / reflect pad / un-pad / resize back (unifie.py:124-134,164-168) run as HIP kernels inside the graph."""
         if task not in self.ae.task_list and self.tedit:
             raise KeyError(task)
-        preds, z0, zt = self._run(images, task, noise, quantize)
+        preds, z0, zt = self._run(images, task, noise, quantize, seeds)
         self._check_finite((preds,))
         lat = self.ae.vae.latent_channels
         if return_latents:
@@ -745,14 +777,14 @@ class DiffUIE(nn.Module):
         return preds
 
     @torch.no_grad()
-    def forward_tasks(self, images, tasks, noise=None, return_latents=False, quantize=False):
+    def forward_tasks(self, images, tasks, noise=None, return_latents=False, quantize=False, seeds=None):
         """Restore once, decode for several tasks: {task: images} in the order of `tasks` (with return_latents: that dict, z0, zt -
         ONE z0 and ONE zt, they are shared).  Encode, both noise draws, the Controller, every denoise step and the task-free
         part of the decoder run once; only the decoder behind the first task adapter runs per task, as one task-major batch
-        (SkipConnectedAutoEncoder.decode_run_tasks).  noise / resize / pad / quantize / the fp16 check are those of `forward`;
+        (SkipConnectedAutoEncoder.decode_run_tasks).  noise / seeds / resize / pad / quantize / the fp16 check are those of `forward`;
         with use_graph the call is one captured graph keyed by the task tuple."""
         tasks = self.ae.check_tasks(tasks)
-        preds, z0, zt = self._run(images, tasks, noise, quantize)
+        preds, z0, zt = self._run(images, tasks, noise, quantize, seeds)
         self._check_finite(preds.values())
         if return_latents:
             lat = self.ae.vae.latent_channels
@@ -761,13 +793,14 @@ class DiffUIE(nn.Module):
 
     # ---- 8-bit images of different sizes that share a canvas: one graph per (N, canvas), uint8 in and out ------------------
     @torch.no_grad()
-    def forward_u8(self, images, task, noise=None, return_latents=False):
+    def forward_u8(self, images, task, noise=None, return_latents=False, seeds=None):
         """images: a sequence of uint8 [H_i, W_i, 3] tensors (host or device) with ONE canvas (`canvas_of`; ValueError otherwise)
         -> a list of restored uint8 [H_i, W_i, 3] device tensors, or {task: list} when `task` is a list / tuple of names (the
         body is then forward_tasks's, except that the task-dependent decoder tail runs task by task, so that every task's images equal
         forward_u8(images, that task) bit for bit).  What `forward(u8 / 255, quantize=True) * 255` gives per image, but the sizes live in a
         device table that every call refreshes, not in the captured launches: with use_graph, calls that share the number of
-        images and the canvas replay the same graph whatever the H_i x W_i.  noise = (eps_vae, eps_t999) [N, 4, CH/8, CW/8].
+        images and the canvas replay the same graph whatever the H_i x W_i.  noise = (eps_vae, eps_t999) [N, 4, CH/8, CW/8], or
+        seeds = one int per image as in `forward` (the key table is refreshed per call like the size table).
         The fp16 check reads the egress kernel's per-image flags (one small device-to-host read)."""
         multi = not isinstance(task, str)
         if multi:
@@ -787,24 +820,29 @@ class DiffUIE(nn.Module):
             raise ValueError("forward_u8: the images of a batch must share one canvas, got " +
                              ", ".join(f"{h}x{w} -> {c[0]}x{c[1]}" for (h, w), c in zip(sizes, canvases)))
         (ch, cw), n = canvases[0], len(images)
+        keys = self._seed_keys(seeds, noise, n)
         self._prepare()
         lat = self.ae.vae.latent_channels
         lh, lw = ch // 8, cw // 8
-        if noise is None:
-            noise = (torch.randn(n, lat, lh, lw, device=DEV), torch.randn(n, lat, lh, lw, device=DEV))
-        n_vae, n_t = (x.to(DEV).float().contiguous() for x in noise)
-        if tuple(n_vae.shape) != (n, lat, lh, lw) or tuple(n_t.shape) != (n, lat, lh, lw):
-            raise ValueError(f"noise must be two tensors of shape {(n, lat, lh, lw)}")
         geom = ops.ragged_geometry([(h, w) + resize_pad_plan(h, w)[:2] for h, w in sizes], (ch, cw))
-        slots = self._stage_u8(images, ch * cw * 3)
+        if keys is not None:                     # seeded: the key table is the only noise input, the draws happen on the device
+            inputs = dict(geom=geom, keys=keys)
+        else:
+            if noise is None:
+                noise = (torch.randn(n, lat, lh, lw, device=DEV), torch.randn(n, lat, lh, lw, device=DEV))
+            n_vae, n_t = (x.to(DEV).float().contiguous() for x in noise)
+            if tuple(n_vae.shape) != (n, lat, lh, lw) or tuple(n_t.shape) != (n, lat, lh, lw):
+                raise ValueError(f"noise must be two tensors of shape {(n, lat, lh, lw)}")
+            inputs = dict(geom=geom, n_vae=n_vae, n_t=n_t)
+        inputs = dict(slots=self._stage_u8(images, ch * cw * 3), **inputs)
 
         def run(st):
             io = RaggedIO(st["geom"], (ch, cw))
-            preds, z0, zt = self._forward_device(st["slots"], task, st["n_vae"], st["n_t"], io)
+            preds, z0, zt = self._forward_device(st["slots"], task, st.get("n_vae"), st.get("n_t"), io, keys=st.get("keys"))
             return preds, z0, zt, io.flags
-        inputs = dict(slots=slots, geom=geom, n_vae=n_vae, n_t=n_t)
         if self.use_graph:
-            preds, z0, zt, flags = self._captured(("u8", n, ch, cw, task, self.dtype, self.latent_tiling) + self._fix_key(), inputs, run)
+            key = ("u8", n, ch, cw, task, self.dtype, self.latent_tiling) + self._fix_key() + self._seeded_key(keys)
+            preds, z0, zt, flags = self._captured(key, inputs, run)
         else:
             preds, z0, zt, flags = run({name: v.to(DEV) for name, v in inputs.items()})
         self.__dict__["_u8_flags"] = (flags, n)
@@ -870,10 +908,12 @@ class DiffUIE(nn.Module):
             torch.cuda.synchronize()
         return outs
 
-    def _graph_forward(self, images, task, n_vae, n_t, plan, quantize=False):
-        key = (tuple(images.shape), task, bool(quantize), self.dtype, self.latent_tiling) + self._fix_key()
-        outs = self._captured(key, dict(images=images, n_vae=n_vae, n_t=n_t),
-                              lambda st: self._forward_device(st["images"], task, st["n_vae"], st["n_t"], plan, quantize))
+    def _graph_forward(self, images, task, n_vae, n_t, plan, quantize=False, keys=None):
+        key = (tuple(images.shape), task, bool(quantize), self.dtype, self.latent_tiling) + self._fix_key() + self._seeded_key(keys)
+        inputs = dict(images=images, n_vae=n_vae, n_t=n_t) if keys is None else dict(images=images, keys=keys)
+        outs = self._captured(key, inputs,
+                              lambda st: self._forward_device(st["images"], task, st.get("n_vae"), st.get("n_t"), plan, quantize,
+                                                              keys=st.get("keys")))
         # the graph's output tensors are overwritten by the next replay of this (shape, task) graph: hand the caller copies
         # (runner.forward keeps [enh_hq, enh_lq] of two same-shape calls; a copy is tiny next to a forward)
         return tuple({t: v.clone() for t, v in o.items()} if isinstance(o, dict) else o.clone() for o in outs)

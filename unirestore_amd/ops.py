@@ -693,6 +693,56 @@ def add_noise(z0, noise_nchw, clat, sa, sb):
     return zt, zb
 
 
+def noise_keys(seeds):
+    """Per-image seeds (ints in [0, 2^64)) -> the host int32 [N,2] key table of `keyed_noise`: row n holds (seed_n & 0xffffffff,
+    seed_n >> 32) as two's-complement words.  ValueError for an empty sequence, a non-integer or a seed outside the range."""
+    rows = []
+    for n, sd in enumerate(seeds):
+        if isinstance(sd, bool) or not hasattr(sd, "__index__"):
+            raise ValueError(f"noise_keys: seed {n} must be an integer, got {sd!r}")
+        sd = sd.__index__()
+        if not 0 <= sd < 1 << 64:
+            raise ValueError(f"noise_keys: seed {n} = {sd} is outside [0, 2^64)")
+        rows.append([w - (1 << 32) if w >= 1 << 31 else w for w in (sd & 0xffffffff, sd >> 32)])
+    if not rows:
+        raise ValueError("noise_keys: needs at least one seed")
+    return torch.tensor(rows, dtype=torch.int32).reshape(-1, 2)
+
+
+NOISE_KINDS = {"normal": (0, torch.float32), "bits": (1, torch.int32)}
+
+
+def keyed_noise(keys_dev: torch.Tensor, draw: int, shape, kind="normal", out=None):
+    """Counter-based noise keyed per image (Philox4x32-10, csrc/noise.hip; the specification is ur_keyed_noise's comment in the
+    header): keys_dev device int32 / uint32 [N,2] (`noise_keys(seeds)` on the device), draw 0 (the VAE posterior draw) or 1 (the
+    t=999 draw) or any other uint32, shape = (C, H, W) -> [N,C,H,W] on the device: fp32 standard normals for kind "normal", int32
+    holding the raw words for "bits".  Image n's values depend on (key n, draw, element) only - not on N or on n.  The keys are
+    read by the kernel, so a captured launch follows later changes of the table.  out: a contiguous tensor of the result's
+    dtype and element count to write instead of a new one (4-byte aligned; any offset)."""
+    if kind not in NOISE_KINDS:
+        raise ValueError(f"keyed_noise: kind must be 'normal' or 'bits', got {kind!r}")
+    code, dtype = NOISE_KINDS[kind]
+    if not isinstance(keys_dev, torch.Tensor) or keys_dev.dtype not in (torch.int32, torch.uint32) or keys_dev.ndim != 2 or \
+            keys_dev.shape[1] != 2 or keys_dev.shape[0] == 0 or not keys_dev.is_contiguous():
+        raise ValueError(f"keyed_noise: keys must be a contiguous int32 / uint32 tensor [N, 2], got "
+                         f"{getattr(keys_dev, 'dtype', type(keys_dev))} {tuple(getattr(keys_dev, 'shape', ()))}")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if keys_dev.device != dev:
+        raise ValueError(f"keyed_noise: the keys are on {keys_dev.device}, not on the current device {dev}")
+    if len(shape) != 3 or any(int(v) < 1 for v in shape):
+        raise ValueError(f"keyed_noise: shape must be (C, H, W) with positive extents, got {tuple(shape)}")
+    if not 0 <= int(draw) < 1 << 32:
+        raise ValueError(f"keyed_noise: draw = {draw} is outside [0, 2^32)")
+    n, (c, h, w_) = keys_dev.shape[0], (int(v) for v in shape)
+    if out is None:
+        out = torch.empty((n, c, h, w_), dtype=dtype, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.dtype != dtype or out.numel() != n * c * h * w_ or out.device != dev or \
+            not out.is_contiguous():
+        raise ValueError(f"keyed_noise: out must be a contiguous {dtype} tensor of {n * c * h * w_} elements on {dev}")
+    check(lib.ur_keyed_noise(keys_dev.data_ptr(), int(draw), out.data_ptr(), n, c * h * w_, code, _stream()))
+    return out.view(n, c, h, w_)
+
+
 def ddim_step_(zt, zt_bf16, eps_f32, clat, c_x, c_e):
     cp = zt.shape[-1]
     check(lib.ur_ddim_step(zt.data_ptr(), eps_f32.data_ptr(), eps_f32.shape[-1], zt_bf16.data_ptr(), zt.numel() // cp, clat, cp,
