@@ -411,6 +411,62 @@ int ur_color_fix_adain(const void* c_f32, int ld_c, const void* src_16, int ld_s
                        void* ws, size_t ws_bytes, ur_stream_t stream);
 size_t ur_color_fix_adain_ws_bytes(int N, int H, int W);
 
+/* ---- corruptions of 8-bit images (ImageNet-C semantics; the planner is unirestore_amd/corrupt.py) ---------------------------
+ * x u8 [N,H,W,3] contiguous HWC on the device, H and W >= 32, N*H*W*3 < 2^31; out of the same shape, not x: u8 for out_kind 0,
+ * fp32 for out_kind 1.  Every primitive computes a value v in fp32 on the 0-255 scale; out_kind 1 stores clamp(v, 0, 255),
+ * out_kind 0 the floor of that (truncation, as numpy's cast to uint8).  keys: DEVICE uint32 [N][2] as for ur_keyed_noise; element e
+ * of a field takes word e & 3 of the Philox counter (e >> 2, draw, 0, 0) under image n's key, uniforms and normals as
+ * ur_keyed_noise's; for the image fields e = (y*W + x)*3 + ch.  All tables are DEVICE memory and read by the kernels.
+ *   ur_corrupt_noise  mode 0 gaussian: v = x + c*n (draw 16, c = 255 sigma);  mode 1 speckle: v = x + x*(c*n) (draw 17, c = sigma);
+ *       mode 2 impulse: u1 = uniform of draw 18, u2 of draw 19; u1 < c flips the element to 255 if u2 < 0.5 else to 0, any other
+ *       element keeps x (c = amount);  mode 3 shot: k = the number of j in [0, 128) with table[x][j] <= (word of draw 20) >> 8, at
+ *       most 127, v = (k*255)/c (one correctly rounded division; table uint32 [256][128], row x = floor(2^24 CDF) of Poisson(x*c/255)).
+ *   ur_corrupt_filter_sep  v = sum_k taps[k+r] * t[clamp(x+k)], t = sum_k taps[k+r] * x[clamp(y+k)] (rows first, k ascending, fp32
+ *       accumulation, replicate border); taps fp32 [2*radius+1]; ws holds t.
+ *   ur_corrupt_taps  v = sum over t (ascending) of w_t * x[b(y + ty_t)][b(x + tx_t)] per channel; taps int32 [n_taps][3] = (tx, ty,
+ *       the fp32 bits of w), or [N][n_taps][3] with per_image 1; b = replicate (border 0) or reflect-101 (border 1; an index still
+ *       outside after one reflection is clamped).  A tap of weight 0 adds nothing: pad shorter lists with (0, 0, 0.0f).
+ *   ur_corrupt_zoom  v = (x + sum of the layers) / (n_layers + 1); layers int32 [n_layers][6] = (top, left, ch, cw, oh, ow): the crop
+ *       [top, top+ch) x [left, left+cw) resampled bilinearly to oh x ow, of which the top-left H x W is used (a pixel beyond oh x ow
+ *       gets nothing from that layer).  Output index o reads position o*(in-1)/(out-1): the cell by integer division, the fraction
+ *       (remainder)/(out-1) in fp32; value a + fy*(b - a) with a, b = p0 + fx*(p1 - p0) on the two rows.
+ *   ur_corrupt_color  mode 0 contrast: v = (x - mean_c)*a + mean_c, mean_c = the image's exact integer channel sum / (H*W), divided in
+ *       fp64 and rounded to fp32;  mode 1 brightness / mode 2 saturate: V = max(r,g,b), delta = V - min, S = delta/V (0 for delta 0),
+ *       hue h6 in [0, 6) = 4 + (r-g)/delta if b is the maximum, else 2 + (b-r)/delta if g is, else (g-b)/delta (+6 if negative), 0 for
+ *       delta 0; mode 1: V = clamp(V + a, 0, 255), mode 2: S = clamp(S*a + b, 0, 1); back with i = floor(h6), f = h6 - i,
+ *       p = V(1-S), q = V(1-fS), t = V(1-(1-f)S): (V,t,p) (q,V,p) (p,V,t) (p,q,V) (t,p,V) (V,p,q) for i = 0..5.
+ *   ur_corrupt_pixelate  box tables int32 [small][2] = (first, count) of the source range an output index of the reduced image
+ *       averages, the mean rounded half up to u8: the horizontal pass first (into ws), then the vertical one; ymap [H] / xmap [W]
+ *       = the reduced image's row / column a full-size pixel copies.  Integers throughout.
+ *   ur_corrupt_fog  a diamond-square map of M x M fp32 cells per image, M = the power of two >= max(H, W, 32): cell (0,0) = 0; for
+ *       step = M, M/2, .., 2 with wibble = fp32(100 / decay^level) (fp64 on the host): the centre of every step x step square =
+ *       ((c00 + c10) + (c01 + c11))/4 + r, then the midpoint of its top edge = ((centre + the centre above) + (corner + the corner
+ *       to the right))/4 + r and of its left edge = ((centre + the centre to the left) + (corner + the corner below))/4 + r,
+ *       neighbours wrapping around; r = wibble*(wibble*(2u - 1)), u = the uniform of element y*M + x of draw 21.  Then
+ *       v = (x + c*(map[y][x] - min)/(max - min)) * (m/(m + c)), min / max over the whole map, m = the image's largest byte,
+ *       c = 255 * the reference's constant.
+ * ws: the matching _ws_bytes function's size (0 for a non-positive argument), 8-byte aligned.  UR_E_INVALID before any HIP call
+ * for a null pointer, N <= 0, H or W < 32, an image of 2^31 elements or more, out == x, an unknown mode / border / out_kind, a
+ * misaligned fp32 out, table or workspace, a table size out of range or a workspace that is too small.  No allocation, no
+ * synchronisation, no atomics: the same inputs give the same bits. */
+int ur_corrupt_noise(const uint8_t* x, const uint32_t* keys, void* out, int N, int H, int W, int mode, float c, const uint32_t* table,
+                     int out_kind, ur_stream_t stream);
+int ur_corrupt_filter_sep(const uint8_t* x, const float* taps, int radius, void* out, int N, int H, int W, void* ws, size_t ws_bytes,
+                          int out_kind, ur_stream_t stream);
+size_t ur_corrupt_filter_sep_ws_bytes(int N, int H, int W);
+int ur_corrupt_taps(const uint8_t* x, const int32_t* taps, int n_taps, int per_image, int border, void* out, int N, int H, int W,
+                    int out_kind, ur_stream_t stream);
+int ur_corrupt_zoom(const uint8_t* x, const int32_t* layers, int n_layers, void* out, int N, int H, int W, int out_kind, ur_stream_t stream);
+int ur_corrupt_color(const uint8_t* x, void* out, int N, int H, int W, int mode, float a, float b, void* ws, size_t ws_bytes, int out_kind,
+                     ur_stream_t stream);
+size_t ur_corrupt_color_ws_bytes(int N, int H, int W);
+int ur_corrupt_pixelate(const uint8_t* x, void* out, int N, int H, int W, int small_h, int small_w, const int32_t* hbox, const int32_t* vbox,
+                        const int32_t* ymap, const int32_t* xmap, void* ws, size_t ws_bytes, int out_kind, ur_stream_t stream);
+size_t ur_corrupt_pixelate_ws_bytes(int N, int H, int small_w);
+int ur_corrupt_fog(const uint8_t* x, const uint32_t* keys, void* out, int N, int H, int W, float c, double decay, void* ws, size_t ws_bytes,
+                   int out_kind, ur_stream_t stream);
+size_t ur_corrupt_fog_ws_bytes(int N, int H, int W);
+
 /* ---- live per-kernel-family timing (HIP events on the launch stream) ------------------------------*/
 int ur_profile_enable(int on);
 /* writes a JSON object {family: {launches, ms, flops, bytes}} into buf (host); synchronises the events */

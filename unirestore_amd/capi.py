@@ -121,6 +121,17 @@ SIGNATURES = {
     "ur_color_fix_wavelet": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "ur_color_fix_adain": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "ur_color_fix_adain_ws_bytes": (_SZ, [_I, _I, _I]),
+    "ur_corrupt_noise": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _I, _P]),
+    "ur_corrupt_filter_sep": (_I, [_P, _P, _I, _P, _I, _I, _I, _P, _SZ, _I, _P]),
+    "ur_corrupt_filter_sep_ws_bytes": (_SZ, [_I, _I, _I]),
+    "ur_corrupt_taps": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P]),
+    "ur_corrupt_zoom": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P]),
+    "ur_corrupt_color": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _P, _SZ, _I, _P]),
+    "ur_corrupt_color_ws_bytes": (_SZ, [_I, _I, _I]),
+    "ur_corrupt_pixelate": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _SZ, _I, _P]),
+    "ur_corrupt_pixelate_ws_bytes": (_SZ, [_I, _I, _I]),
+    "ur_corrupt_fog": (_I, [_P, _P, _P, _I, _I, _I, _F, C.c_double, _P, _SZ, _I, _P]),
+    "ur_corrupt_fog_ws_bytes": (_SZ, [_I, _I, _I]),
     "ur_profile_enable": (_I, [_I]),
     "ur_profile_report": (_I, [C.c_char_p, _SZ]),
 }

@@ -1,5 +1,7 @@
 """Config entry point: `python -m unirestore_amd.cli validate --config configs/<file>.yaml [--set a.b.c=value ...]`, and
-`python -m unirestore_amd.cli restore --config CFG --input DIR_OR_LISTFILE --output DIR` for image files.
+`python -m unirestore_amd.cli restore --config CFG --input DIR_OR_LISTFILE --output DIR` for image files;
+`python -m unirestore_amd.cli corrupt --input DIR_OR_LISTFILE --output DIR --corruptions NAMES_OR_SUBSET` writes corrupted copies of
+clean images (no config).
 
 Resolves a LightningCLI-style YAML (the key schema of the reference's configs/*.yaml: `seed_everything`, `trainer.{accelerator,
 devices,precision}`, `model.class_path` + `init_args.model_kwargs.{frenc,cnet,tedit}`, `data.class_path` + `init_args`;
@@ -26,6 +28,7 @@ MODEL_CLASSES = {
 }
 DATA_CLASSES = {"unirestore_amd.data.SyntheticImages": "unirestore_amd.data.SyntheticImages",
                 "unirestore_amd.data.ImageListFiles": "unirestore_amd.data.ImageListFiles",
+                "unirestore_amd.data.CorruptedImageFiles": "unirestore_amd.data.CorruptedImageFiles",
                 "data.DatasetEngine": "unirestore_amd.data.SyntheticImages"}      # datasets are out of scope: synthetic stand-in
 PRECISIONS = {"bf16-mixed": "bf16", "bf16": "bf16", "bf16-true": "bf16", "16-mixed": "fp16", "16": "fp16", "16-true": "fp16",
               "fp16": "fp16"}
@@ -117,9 +120,12 @@ def resolve(cfg: dict, allow_16bit: bool = False) -> dict:
                 data_class=DATA_CLASSES[dcp])
 
 
-def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_16bit=False, metrics_device="cpu", tasks=None) -> dict:
+def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_16bit=False, metrics_device="cpu", tasks=None,
+             model=None) -> dict:
     """tasks: a list of task names - every batch is restored once and decoded for each of them (DiffUIE.forward_tasks).  PSNR / SSIM
-    come from the "ir" output, so the list must hold "ir"; images_per_s counts input images."""
+    come from the "ir" output, so the list must hold "ir"; images_per_s counts input images.  model: a ready DiffUIE to use instead
+    of building the config's.  With data.CorruptedImageFiles the result also holds by_corruption ("fog/3" -> psnr, ssim, images)
+    and skipped (the subset members that are not built)."""
     import torch
     r = resolve(cfg, allow_16bit=allow_16bit)
     if tasks is not None:
@@ -140,9 +146,13 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
     from . import runner
     from . import data as data_mod
     from .dist import all_gather_images, broadcast_weights_sharded, shard_range
-    lit = runner.LitUniFIE(r["model_kwargs"], dtype=r["dtype"], hf_root=hf_root, metrics_device=metrics_device, **r["caller_args"])
+    lit = runner.LitUniFIE(r["model_kwargs"], dtype=r["dtype"], hf_root=hf_root, metrics_device=metrics_device, model=model,
+                           **r["caller_args"])
     no_ckpt = not any((r["model_kwargs"].get(k) or {}).get("ckpt_path") for k in ("frenc", "cnet", "tedit")) and not hf_root
-    if no_ckpt and random_init:                           # no checkpoint reachable: seeded random weights of the architecture
+    if model is not None:
+        model.set_dtype(r["dtype"])
+        model.set_color_fix((r["model_kwargs"].get("cnet") or {}).get("color_fix"))
+    elif no_ckpt and random_init:                         # no checkpoint reachable: seeded random weights of the architecture
         from .init import init_random_
         if rank == 0:
             init_random_(lit.model, r["seed"], "cpu")
@@ -154,6 +164,7 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
         raise ValueError(f"data batch_size {data.batch_size} < world size {world}: every rank needs at least one image per batch")
     sizes = [shard_range(data.batch_size, q, world)[1] - shard_range(data.batch_size, q, world)[0] for q in range(world)]
     n_img, secs, finite = 0, 0.0, True
+    by_corruption = {} if isinstance(data, data_mod.CorruptedImageFiles) else None      # "fog/3" -> metric sums of its batches
     for i, batch in enumerate(data.batches(rank, world, dev)):
         if max_batches is not None and i >= max_batches:
             break
@@ -169,7 +180,12 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
             secs += time.perf_counter() - t0
             n_img += out.shape[0]
         finite = finite and bool(torch.isfinite(out).all()) and all(bool(torch.isfinite(v).all()) for v in by_task.values())
+        before = dict(lit.totals)
         lit.update_metrics(by_task["ir"], batch[1])           # this rank's shard; reduced over the ranks below (fp64 PSNR / SSIM: untimed)
+        if by_corruption is not None:                     # the batch is homogeneous: its increment of the totals belongs to one key
+            acc = by_corruption.setdefault("%s/%d" % data.last, dict(psnr=0.0, ssim=0.0, images=0))
+            for k in acc:
+                acc[k] = acc[k] + (lit.totals[k] - before[k])
     if world > 1:                                         # the reference's metric states reduce with dist_reduce_fx="sum"
         # the totals are host floats (metrics_device "cpu") or 0-d fp64 device tensors ("gpu")
         tot = torch.stack([torch.as_tensor(v, dtype=torch.float64, device=dev)
@@ -180,6 +196,10 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
                images_per_s=(n_img / secs) if secs > 0 else None, output_finite=finite, **lit.metrics())
     if tasks is not None:
         res["tasks"] = tasks
+    if by_corruption is not None:
+        res["by_corruption"] = {k: dict(psnr=float(v["psnr"]) / v["images"], ssim=float(v["ssim"]) / v["images"], images=int(v["images"]))
+                                for k, v in by_corruption.items()}
+        res["skipped"] = list(data.skipped)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -362,10 +382,78 @@ def restore(cfg: dict, inp, output, task=None, tasks=None, batch=8, hf_root=None
     return res if rank == 0 else None
 
 
+def check_corrupt_args(inp, output, corruptions, severity=3, batch=8):
+    """Everything about a `corrupt` call that can be wrong without looking at a GPU -> (clean image paths, corruption names, an
+    integer severity or "mixed").  Every message names the offending argument."""
+    from . import corrupt as cr
+    if not corruptions:
+        raise ValueError("--corruptions: name at least one corruption or subset (" + ", ".join(sorted(cr.SUBSETS)) + ")")
+    try:
+        names = cr.expand(corruptions)
+    except ValueError as e:
+        raise ValueError(f"--corruptions {corruptions!r}: {e}") from None
+    if "clean" in names:
+        raise ValueError("--corruptions: 'clean' writes nothing new; name corruptions only")
+    if str(severity) != "mixed":
+        if str(severity) not in ("1", "2", "3", "4", "5"):
+            raise ValueError(f"--severity {severity!r}: choose 1..5 or mixed")
+        severity = int(severity)
+    if int(batch) < 1:
+        raise ValueError(f"--batch {batch}: must be >= 1")
+    if not inp or not os.path.exists(inp):
+        raise FileNotFoundError(f"--input {inp!r}: no such folder or list file")
+    if not output:
+        raise ValueError("--output: a folder for the corrupted PNGs is required")
+    if os.path.isdir(inp) and os.path.realpath(inp) == os.path.realpath(output):
+        raise ValueError(f"--output {output!r} is the --input folder")
+    try:
+        paths = cr.check_inputs(inp)
+    except ValueError as e:
+        raise ValueError(f"--input {e}") from None
+    return paths, names, severity
+
+
+def corrupt_files(inp, output, corruptions, severity=3, seed=42, batch=8) -> dict:
+    """Corrupt clean image files on the GPU: OUTPUT/<name>_<severity>/<stem>.png for every named corruption and input, and
+    OUTPUT/<name>_<severity>/pairs.txt with one `lq hq` line per file (what data.ImageListFiles and the reference's list datasets
+    read).  A file's bytes depend on (seed, stem, name, severity) alone - not on the other files, their order or --batch."""
+    import torch
+    paths, names, severity = check_corrupt_args(inp, output, corruptions, severity, batch)
+    from . import corrupt as cr
+    from . import imageio
+    if not torch.cuda.is_available():
+        raise RuntimeError("no GPU visible: the corruptions run on MI355X only (no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    sizes = [hw for _, hw in imageio.scan(paths)]
+    stems = [cr.stem_of(p) for p in paths]
+    sevs = [cr.draw_severity(seed, st) if severity == "mixed" else severity for st in stems]
+    groups = {}
+    for i, (hw, sev) in enumerate(zip(sizes, sevs)):
+        groups.setdefault((hw, sev), []).append(i)
+    t0, folders = time.perf_counter(), {}
+    for name in names:
+        for (hw, sev), idx in groups.items():
+            folder = os.path.join(output, f"{name}_{sev}")
+            os.makedirs(folder, exist_ok=True)
+            for s in range(0, len(idx), int(batch)):
+                cut = idx[s:s + int(batch)]
+                hq = torch.stack([imageio.load_u8(paths[i]) for i in cut]).to(dev)
+                lq = cr.corrupt(hq, name, sev, seed, [stems[i] for i in cut]).cpu()
+                for i, img in zip(cut, lq):
+                    imageio.save_u8(img, os.path.join(folder, stems[i] + ".png"))
+            folders.setdefault(folder, []).extend(idx)
+    for folder, idx in folders.items():
+        with open(os.path.join(folder, "pairs.txt"), "w") as f:
+            for i in sorted(idx):
+                f.write(f"{stems[i]}.png {os.path.abspath(paths[i])}\n")
+    return dict(images=len(paths), corruptions=names, skipped=cr.skipped(corruptions), severity=severity, seed=seed,
+                folders=sorted(os.path.basename(d) for d in folders), output=output, seconds_total=time.perf_counter() - t0)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m unirestore_amd.cli")
-    ap.add_argument("command", choices=["validate", "print_config", "restore"])
-    ap.add_argument("--config", required=True)
+    ap.add_argument("command", choices=["validate", "print_config", "restore", "corrupt"])
+    ap.add_argument("--config", default=None, help="validate / print_config / restore: the YAML config (required there)")
     ap.add_argument("--set", action="append", default=[], metavar="a.b.c=value", help="override a config key")
     ap.add_argument("--hf-root", default=None, help="folder with unet/ and vae/ diffusion_pytorch_model.safetensors (sd-turbo)")
     ap.add_argument("--max-batches", type=int, default=None)
@@ -387,7 +475,20 @@ def main(argv=None):
                          "noise is generated on the GPU from (seed_everything, file stem, sample) alone")
     ap.add_argument("--samples", type=int, default=1, metavar="K",
                     help="restore: K restorations of every input, written as <stem>.s<k>.png (K > 1 needs --noise image)")
+    ap.add_argument("--corruptions", default=None, metavar="fog,motion_blur|SUBSET",
+                    help="corrupt: corruption names and / or subsets (common, validation, all, noise, blur, weather, digital)")
+    ap.add_argument("--severity", default="3", help="corrupt: 1..5, or mixed for the reference's per-image draw")
+    ap.add_argument("--seed", type=int, default=42, help="corrupt: with a file's stem, the seed of all its randomness")
     a = ap.parse_args(argv)
+    if a.command == "corrupt":
+        try:
+            check_corrupt_args(a.input, a.output, a.corruptions, a.severity, a.batch)
+        except (ValueError, FileNotFoundError, NotImplementedError) as e:
+            ap.error(str(e))
+        print(json.dumps(corrupt_files(a.input, a.output, a.corruptions, a.severity, a.seed, a.batch)))
+        return 0
+    if a.config is None:
+        ap.error("the following arguments are required: --config")
     if a.command == "restore":
         try:
             check_noise_args(a.noise, a.samples)

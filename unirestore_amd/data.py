@@ -1,5 +1,5 @@
-"""Inputs for the config entry points: seeded synthetic images (the reference's corruption pipeline is out of scope) and
-`ImageListFiles`, real pairs from the reference's `lq hq label` list files.
+"""Inputs for the config entry points: seeded synthetic images, `ImageListFiles`, real pairs from the reference's `lq hq label`
+list files, and `CorruptedImageFiles`, clean images corrupted on the GPU (unirestore_amd.corrupt).
 
 `SyntheticImages` yields the evaluator's batch tuple `(lq, hq, gt, fname, task)` (reference
 src/core/base/eval_image_restoration.py:56) from seeded random images: hq = torch.rand (what the reference's own smoke
@@ -99,3 +99,52 @@ class ImageListFiles:
             if lq.shape != hq.shape:
                 raise ValueError(f"{self.list_file}: lq and hq of {self.pairs[idx[0]][0]!r}... differ in size: {tuple(lq.shape)} vs {tuple(hq.shape)}")
             yield lq, hq, None, [os.path.splitext(os.path.basename(self.pairs[i][0]))[0] for i in idx], self.task
+
+
+class CorruptedImageFiles:
+    """Clean images corrupted on the GPU for `validate` (`data.class_path: unirestore_amd.data.CorruptedImageFiles`): `source` is a
+    folder, a list file of clean images or an `lq hq [label]` list, of which only the hq column is read.  `corruptions` is a subset
+    name (unirestore_amd.corrupt.SUBSETS), a name, or a comma-separated string / list of names ("clean" only when it is named);
+    `severity` an integer 1..5 or "mixed", the reference's per-image draw.  Every image's corruption, severity and randomness come
+    from sha256 of (seed, file stem) alone.  Images are grouped by (shape, corruption, severity), so a batch is homogeneous; hq is
+    uploaded as u8 and corrupted there.  Yields `(lq, hq, None, names, task)` with fp32 NCHW tensors in [0, 1]; `last` holds the
+    (corruption, severity) of the batch just yielded and `skipped` the subset members that are not built."""
+
+    def __init__(self, source: str, corruptions="common", severity=3, batch_size: int = 8, task: str = "ir", seed: int = 42,
+                 num_batches: int = None):
+        from . import corrupt
+        self.source, self.batch_size, self.task, self.seed, self.num_batches = source, int(batch_size), task, int(seed), num_batches
+        if self.batch_size < 1:
+            raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+        self.names, self.skipped = corrupt.expand(corruptions), corrupt.skipped(corruptions)
+        self.severity = severity if severity == "mixed" else corrupt.check_severity(severity)
+        self.paths = corrupt.check_inputs(source)
+        self.last = None
+
+    def _plan(self):
+        from . import corrupt
+        from .imageio import scan
+        sizes = [hw for _, hw in scan(self.paths)]
+        return corrupt.plan_files(self.paths, sizes, self.names, self.severity, self.seed, self.batch_size)[:self.num_batches]
+
+    def __len__(self):
+        return len(self._plan())
+
+    def batches(self, rank: int = 0, world: int = 1, device="cpu") -> Iterator[Tuple[torch.Tensor, torch.Tensor, None, List[str], str]]:
+        from . import corrupt
+        from .imageio import load_u8
+        if world != 1:
+            raise ValueError("CorruptedImageFiles does not shard a batch over ranks (batches of real files differ in size): run "
+                             "`validate` on one GPU")
+        # u8 / 255 as the host computes it, the values ImageListFiles yields for the same bytes (a device division by a scalar may
+        # multiply by the reciprocal and differ in the last bit)
+        unit = (torch.arange(256, dtype=torch.float32) / 255).to(device)
+
+        def nchw(t):
+            return unit.index_select(0, t.permute(0, 3, 1, 2).reshape(-1).int()).view(t.shape[0], 3, t.shape[1], t.shape[2])
+        for name, sev, idx in self._plan():
+            stems = [corrupt.stem_of(self.paths[i]) for i in idx]
+            hq = torch.stack([load_u8(self.paths[i]) for i in idx]).to(device)
+            lq = corrupt.corrupt(hq, name, sev, self.seed, stems)
+            self.last = (name, sev)
+            yield nchw(lq), nchw(hq), None, stems, self.task

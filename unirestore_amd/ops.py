@@ -743,6 +743,126 @@ def keyed_noise(keys_dev: torch.Tensor, draw: int, shape, kind="normal", out=Non
     return out.view(n, c, h, w_)
 
 
+# ---- corruptions of u8 images (csrc/corrupt.hip; the specification is the ur_corrupt_* comment in the header; the planner that
+# builds the tables is unirestore_amd.corrupt) ----------------------------------------------------------------------------------
+def check_u8_images(who: str, x):
+    """x must be a contiguous uint8 [N, H, W, 3] tensor on the current device with N >= 1 and H, W >= 32."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.ndim != 4 or x.shape[3] != 3 or not x.is_contiguous():
+        raise ValueError(f"{who}: images must be a contiguous uint8 tensor [N, H, W, 3], got {getattr(x, 'dtype', type(x))} "
+                         f"{tuple(getattr(x, 'shape', ()))}")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if x.device != dev:
+        raise ValueError(f"{who}: the images are on {x.device}, not on the current device {dev}")
+    if x.shape[0] < 1 or x.shape[1] < 32 or x.shape[2] < 32:
+        raise ValueError(f"{who}: needs N >= 1 and H, W >= 32, got {tuple(x.shape)}")
+
+
+def _corrupt_table(who: str, t, dtype, numel=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.device.type != "cuda" or \
+            (numel is not None and t.numel() != numel) or t.numel() == 0:
+        raise ValueError(f"{who}: expected a contiguous device {dtype} table" + (f" of {numel} elements" if numel is not None else "") +
+                         f", got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    return t
+
+
+def _corrupt_out(x, out_kind):
+    if out_kind not in (0, 1):
+        raise ValueError(f"out_kind must be 0 (uint8) or 1 (fp32 before the floor), got {out_kind!r}")
+    return torch.empty(x.shape, dtype=torch.float32 if out_kind else torch.uint8, device=x.device)
+
+
+def _corrupt_ws(x, nbytes):
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=x.device), nbytes
+
+
+def corrupt_noise(x, keys_dev, mode: int, c: float, table=None, out_kind=0):
+    """Keyed pointwise noise: mode 0 gaussian (c = 255 sigma), 1 speckle (c = sigma), 2 impulse (c = amount), 3 shot (c = the
+    reference's constant; table = the int32 view of corrupt.poisson_table(c) on the device).  keys_dev as for `keyed_noise`."""
+    check_u8_images("corrupt_noise", x)
+    n, h, w_, _ = x.shape
+    _corrupt_table("corrupt_noise: keys", keys_dev, torch.int32, 2 * n)
+    if mode == 3:
+        _corrupt_table("corrupt_noise: table", table, torch.int32, 256 * 128)
+    out = _corrupt_out(x, out_kind)
+    check(lib.ur_corrupt_noise(x.data_ptr(), keys_dev.data_ptr(), out.data_ptr(), n, h, w_, int(mode), float(c), _ptr(table), out_kind, _stream()))
+    return out
+
+
+def corrupt_filter_sep(x, taps, out_kind=0):
+    """Separable filter with a replicate border: taps = device fp32 [2 r + 1], applied along the rows, then along the columns."""
+    check_u8_images("corrupt_filter_sep", x)
+    _corrupt_table("corrupt_filter_sep: taps", taps, torch.float32)
+    if taps.numel() % 2 != 1:
+        raise ValueError(f"corrupt_filter_sep: needs an odd number of taps, got {taps.numel()}")
+    n, h, w_, _ = x.shape
+    out = _corrupt_out(x, out_kind)
+    ws, nbytes = _corrupt_ws(x, lib.ur_corrupt_filter_sep_ws_bytes(n, h, w_))
+    check(lib.ur_corrupt_filter_sep(x.data_ptr(), taps.data_ptr(), taps.numel() // 2, out.data_ptr(), n, h, w_, ws.data_ptr(), nbytes, out_kind,
+                                    _stream()))
+    return out
+
+
+def corrupt_taps(x, taps, border=0, out_kind=0):
+    """Tap-list sum: taps = device int32 [T, 3] (one list) or [N, T, 3] (one per image) of (tx, ty, fp32 bits of the weight)
+    (corrupt.pack_taps); border 0 = replicate, 1 = reflect-101."""
+    check_u8_images("corrupt_taps", x)
+    _corrupt_table("corrupt_taps: taps", taps, torch.int32)
+    n, h, w_, _ = x.shape
+    if taps.shape[-1] != 3 or taps.ndim not in (2, 3) or (taps.ndim == 3 and taps.shape[0] != n):
+        raise ValueError(f"corrupt_taps: taps must be [T, 3] or [{n}, T, 3], got {tuple(taps.shape)}")
+    out = _corrupt_out(x, out_kind)
+    check(lib.ur_corrupt_taps(x.data_ptr(), taps.data_ptr(), taps.shape[-2], int(taps.ndim == 3), int(border), out.data_ptr(), n, h, w_, out_kind,
+                              _stream()))
+    return out
+
+
+def corrupt_zoom(x, layers, out_kind=0):
+    """(x + the bilinear zoom layers) / (K + 1): layers = device int32 [K, 6] (corrupt.zoom_layers)."""
+    check_u8_images("corrupt_zoom", x)
+    _corrupt_table("corrupt_zoom: layers", layers, torch.int32)
+    if layers.ndim != 2 or layers.shape[1] != 6:
+        raise ValueError(f"corrupt_zoom: layers must be [K, 6], got {tuple(layers.shape)}")
+    n, h, w_, _ = x.shape
+    out = _corrupt_out(x, out_kind)
+    check(lib.ur_corrupt_zoom(x.data_ptr(), layers.data_ptr(), layers.shape[0], out.data_ptr(), n, h, w_, out_kind, _stream()))
+    return out
+
+
+def corrupt_color(x, mode: int, a: float, b: float = 0.0, out_kind=0):
+    """mode 0 contrast (a = the factor), 1 brightness (V + a, a on the 0-255 scale), 2 saturate (S * a + b)."""
+    check_u8_images("corrupt_color", x)
+    n, h, w_, _ = x.shape
+    out = _corrupt_out(x, out_kind)
+    ws, nbytes = _corrupt_ws(x, lib.ur_corrupt_color_ws_bytes(n, h, w_))
+    check(lib.ur_corrupt_color(x.data_ptr(), out.data_ptr(), n, h, w_, int(mode), float(a), float(b), ws.data_ptr(), nbytes, out_kind, _stream()))
+    return out
+
+
+def corrupt_pixelate(x, small_h: int, small_w: int, hbox, vbox, ymap, xmap, out_kind=0):
+    """Box reduction to small_h x small_w and nearest-neighbour enlargement by the device int32 tables of corrupt.pixelate_tables."""
+    check_u8_images("corrupt_pixelate", x)
+    n, h, w_, _ = x.shape
+    for name, t, numel in (("hbox", hbox, 2 * small_w), ("vbox", vbox, 2 * small_h), ("ymap", ymap, h), ("xmap", xmap, w_)):
+        _corrupt_table(f"corrupt_pixelate: {name}", t, torch.int32, numel)
+    out = _corrupt_out(x, out_kind)
+    ws, nbytes = _corrupt_ws(x, lib.ur_corrupt_pixelate_ws_bytes(n, h, small_w))
+    check(lib.ur_corrupt_pixelate(x.data_ptr(), out.data_ptr(), n, h, w_, int(small_h), int(small_w), hbox.data_ptr(), vbox.data_ptr(),
+                                  ymap.data_ptr(), xmap.data_ptr(), ws.data_ptr(), nbytes, out_kind, _stream()))
+    return out
+
+
+def corrupt_fog(x, keys_dev, c: float, decay: float, out_kind=0):
+    """Fog: a keyed diamond-square map per image blended into it; c = 255 * the reference's constant, decay = its wibble decay."""
+    check_u8_images("corrupt_fog", x)
+    n, h, w_, _ = x.shape
+    _corrupt_table("corrupt_fog: keys", keys_dev, torch.int32, 2 * n)
+    out = _corrupt_out(x, out_kind)
+    ws, nbytes = _corrupt_ws(x, lib.ur_corrupt_fog_ws_bytes(n, h, w_))
+    check(lib.ur_corrupt_fog(x.data_ptr(), keys_dev.data_ptr(), out.data_ptr(), n, h, w_, float(c), float(decay), ws.data_ptr(), nbytes, out_kind,
+                             _stream()))
+    return out
+
+
 def ddim_step_(zt, zt_bf16, eps_f32, clat, c_x, c_e):
     cp = zt.shape[-1]
     check(lib.ur_ddim_step(zt.data_ptr(), eps_f32.data_ptr(), eps_f32.shape[-1], zt_bf16.data_ptr(), zt.numel() // cp, clat, cp,
