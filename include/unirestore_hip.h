@@ -467,6 +467,51 @@ int ur_corrupt_fog(const uint8_t* x, const uint32_t* keys, void* out, int N, int
                    int out_kind, ur_stream_t stream);
 size_t ur_corrupt_fog_ws_bytes(int N, int H, int W);
 
+/* ---- JPEG compression as a degradation: the bytes a baseline JPEG decodes to (the planner is unirestore_amd/jpeg.py) ---------
+ * x u8 [N,H,W,3] contiguous HWC RGB on the device, H and W >= 16; out of the same shape, not x.  quality 1..100; subsampling 0
+ * (4:4:4) or 2 (4:2:0), Pillow's codes.  out = what Pillow (libjpeg-turbo) reads back from save(quality, subsampling), byte for
+ * byte: only the lossy steps are computed, the entropy coder is lossless and absent.  Everything is int32, >> is the arithmetic
+ * shift, D(v, n) = (v + (1 << (n-1))) >> n.
+ *   tables   the Annex-K luminance and chrominance tables in natural order, entry = clamp((base*s + 50)/100, 1, 255), s = 5000/quality
+ *            (integer division) for quality < 50, else 200 - 2*quality; built once per call on the host.
+ *   colour   Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + (128<<16) + 32767) >> 16,
+ *            Cr = (32768 R - 27439 G - 5329 B + (128<<16) + 32767) >> 16.
+ *   planes   Y is padded by edge replication to multiples of 8 in both directions; for 4:4:4 so are Cb and Cr.  For 4:2:0 with
+ *            ch = ceil(H/2), cw = ceil(W/2) and chb, cwb their round-ups to 8: the full-size chroma is edge-replicated to 2*ch rows
+ *            and 2*cwb columns, reduced with (a00 + a01 + a10 + a11 + bias) >> 2, bias 1 for even output columns and 2 for odd, and
+ *            the reduced plane is then edge-replicated downwards from ch to chb rows (rows beyond ch copy the last reduced row).
+ *   block    per 8 x 8 block: subtract 128; the forward "islow" DCT (CONST_BITS 13, PASS1_BITS 2), rows then columns, on
+ *            t0..t3 = d0+d7, d1+d6, d2+d5, d3+d4, t4..t7 = d3-d4, d2-d5, d1-d6, d0-d7, t10, t13 = t0 +- t3, t11, t12 = t1 +- t2:
+ *              o0, o4 = t10 +- t11;  e = 4433 (t12 + t13): o2 = e + 6270 t13, o6 = e - 15137 t12;
+ *              z5 = 9633 (t4+t5+t6+t7), z1 = -7373 (t4+t7), z2 = -20995 (t5+t6), z3 = -16069 (t4+t6) + z5, z4 = -3196 (t5+t7) + z5:
+ *              o7 = 2446 t4 + z1 + z3, o5 = 16819 t5 + z2 + z4, o3 = 25172 t6 + z2 + z3, o1 = 12299 t7 + z1 + z4;
+ *            pass 1 stores o0, o4 shifted left by 2 and the others as D(., 11), pass 2 stores D(o0, 2), D(o4, 2) and the others as
+ *            D(., 15): 8 times the DCT.  Quantise with d = q << 3, rounding half away from zero: sign(c) * ((|c| + (d >> 1)) / d);
+ *            dequantise with coef * q.  The inverse "islow" DCT, columns with D(., 11) then rows with D(., 18):
+ *              e = 4433 (c2 + c6), e2 = e - 15137 c6, e3 = e + 6270 c2, e0, e1 = (c0 +- c4) << 13, t10, t13 = e0 +- e3, t11, t12 = e1 +- e2;
+ *              z5 = 9633 (c7+c5+c3+c1), z1 = -7373 (c7+c1), z2 = -20995 (c5+c3), z3 = -16069 (c7+c3) + z5, z4 = -3196 (c5+c1) + z5,
+ *              a0 = 2446 c7 + z1 + z3, a1 = 16819 c5 + z2 + z4, a2 = 25172 c3 + z2 + z3, a3 = 12299 c1 + z1 + z4;
+ *              outputs 0..7 = t10 + a3, t11 + a2, t12 + a1, t13 + a0, t13 - a0, t12 - a1, t11 - a2, t10 - a3;
+ *            add 128 and clamp to 0..255 (libjpeg-turbo's SIMD path saturates; plain libjpeg's table wraps).
+ *   decode   Y cropped to H x W, chroma to ch x cw.  4:2:0 "fancy" upsampling: the two output rows of a chroma row are
+ *            v = 3*this + above and 3*this + below, then the even output column is (3 v + v_left + 8) >> 4 and the odd one
+ *            (3 v + v_right + 7) >> 4, neighbours edge-replicated inside ch x cw; cropped to H x W.
+ *            R = Y + ((91881 (Cr-128) + 32768) >> 16), G = Y + ((-22554 (Cb-128) - 46802 (Cr-128) + 32768) >> 16),
+ *            B = Y + ((116130 (Cb-128) + 32768) >> 16), each clamped to 0..255.
+ *   ranges   no int32 product overflows.  The forward DCT's output is 8 times an orthonormal transform of 64 samples in
+ *            [-128, 127], so |c| <= 8 * 8 * 128 = 2^13 up to rounding; a pass-1 value is below 4 * 8 sqrt(2) * 128 = 5793, a t4..t7 of
+ *            pass 2 below T = 11586, and the crudest bound of an odd output, every term at its maximum with one sign,
+ *            (25172 + 2*20995 + 2*16069 + 4*9633) T = 1.6e9, is below 2^31; the even outputs are smaller.  The inverse sees |coef * q| <= |c|/8 + q/2 < 2^11, the range jidctint.c is written for.  The quantiser's division
+ *            is a multiply-high by m = ceil(2^32 / d): with n = |c| + (d >> 1) < 2^14 and m d - 2^32 < d <= 2040, n (m d - 2^32) <
+ *            2^32, which makes floor(n m / 2^32) = floor(n / d) for every n.
+ * ws: ur_jpeg_roundtrip_ws_bytes(N, H, W, subsampling) bytes (the padded u8 planes; 0 for a non-positive argument or an unknown
+ * subsampling), 8-byte aligned; nothing in it is read before this call has written it.  UR_E_INVALID before any HIP call for a null
+ * pointer, N <= 0, H or W < 16, N*(H+7)*(W+7)*3 >= 2^31, quality outside 1..100, a subsampling other than 0 and 2, out == x, a
+ * misaligned workspace or one that is too small.  No allocation, no synchronisation, no atomics: the same inputs give the same bits. */
+int ur_jpeg_roundtrip(const uint8_t* x, uint8_t* out, int N, int H, int W, int quality, int subsampling, void* ws, size_t ws_bytes,
+                      ur_stream_t stream);
+size_t ur_jpeg_roundtrip_ws_bytes(int N, int H, int W, int subsampling);
+
 /* ---- live per-kernel-family timing (HIP events on the launch stream) ------------------------------*/
 int ur_profile_enable(int on);
 /* writes a JSON object {family: {launches, ms, flops, bytes}} into buf (host); synchronises the events */

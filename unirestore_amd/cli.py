@@ -1,7 +1,8 @@
 """Config entry point: `python -m unirestore_amd.cli validate --config configs/<file>.yaml [--set a.b.c=value ...]`, and
 `python -m unirestore_amd.cli restore --config CFG --input DIR_OR_LISTFILE --output DIR` for image files;
 `python -m unirestore_amd.cli corrupt --input DIR_OR_LISTFILE --output DIR --corruptions NAMES_OR_SUBSET` writes corrupted copies of
-clean images (no config).
+clean images (no config); `python -m unirestore_amd.cli jpeg --input DIR_OR_LISTFILE --output DIR --quality 10,25,s3` writes what their
+JPEGs of those qualities decode to (no config).
 
 Resolves a LightningCLI-style YAML (the key schema of the reference's configs/*.yaml: `seed_everything`, `trainer.{accelerator,
 devices,precision}`, `model.class_path` + `init_args.model_kwargs.{frenc,cnet,tedit}`, `data.class_path` + `init_args`;
@@ -29,6 +30,7 @@ MODEL_CLASSES = {
 DATA_CLASSES = {"unirestore_amd.data.SyntheticImages": "unirestore_amd.data.SyntheticImages",
                 "unirestore_amd.data.ImageListFiles": "unirestore_amd.data.ImageListFiles",
                 "unirestore_amd.data.CorruptedImageFiles": "unirestore_amd.data.CorruptedImageFiles",
+                "unirestore_amd.data.JpegImageFiles": "unirestore_amd.data.JpegImageFiles",
                 "data.DatasetEngine": "unirestore_amd.data.SyntheticImages"}      # datasets are out of scope: synthetic stand-in
 PRECISIONS = {"bf16-mixed": "bf16", "bf16": "bf16", "bf16-true": "bf16", "16-mixed": "fp16", "16": "fp16", "16-true": "fp16",
               "fp16": "fp16"}
@@ -125,7 +127,7 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
     """tasks: a list of task names - every batch is restored once and decoded for each of them (DiffUIE.forward_tasks).  PSNR / SSIM
     come from the "ir" output, so the list must hold "ir"; images_per_s counts input images.  model: a ready DiffUIE to use instead
     of building the config's.  With data.CorruptedImageFiles the result also holds by_corruption ("fog/3" -> psnr, ssim, images)
-    and skipped (the subset members that are not built)."""
+    and skipped (the subset members that are not built); with data.JpegImageFiles it holds by_corruption ("jpeg/10", the quality)."""
     import torch
     r = resolve(cfg, allow_16bit=allow_16bit)
     if tasks is not None:
@@ -164,7 +166,8 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
         raise ValueError(f"data batch_size {data.batch_size} < world size {world}: every rank needs at least one image per batch")
     sizes = [shard_range(data.batch_size, q, world)[1] - shard_range(data.batch_size, q, world)[0] for q in range(world)]
     n_img, secs, finite = 0, 0.0, True
-    by_corruption = {} if isinstance(data, data_mod.CorruptedImageFiles) else None      # "fog/3" -> metric sums of its batches
+    # "fog/3" (data.JpegImageFiles: "jpeg/10", the quality) -> metric sums of its batches
+    by_corruption = {} if isinstance(data, (data_mod.CorruptedImageFiles, data_mod.JpegImageFiles)) else None
     for i, batch in enumerate(data.batches(rank, world, dev)):
         if max_batches is not None and i >= max_batches:
             break
@@ -199,7 +202,8 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
     if by_corruption is not None:
         res["by_corruption"] = {k: dict(psnr=float(v["psnr"]) / v["images"], ssim=float(v["ssim"]) / v["images"], images=int(v["images"]))
                                 for k, v in by_corruption.items()}
-        res["skipped"] = list(data.skipped)
+        if isinstance(data, data_mod.CorruptedImageFiles):
+            res["skipped"] = list(data.skipped)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -450,9 +454,77 @@ def corrupt_files(inp, output, corruptions, severity=3, seed=42, batch=8) -> dic
                 folders=sorted(os.path.basename(d) for d in folders), output=output, seconds_total=time.perf_counter() - t0)
 
 
+def check_jpeg_args(inp, output, quality, subsampling="4:2:0", batch=8):
+    """Everything about a `jpeg` call that can be wrong without looking at a GPU -> (clean image paths, the qualities as integers,
+    each once, the subsampling code).  Every message names the offending argument."""
+    from . import corrupt as cr
+    from . import jpeg
+    specs = [s for s in str(quality).split(",") if s.strip()] if quality is not None else []
+    if not specs:
+        raise ValueError("--quality: name at least one quality (1..100, or s1..s5 for the reference's severities), e.g. 10,25,s3")
+    qualities = []
+    for s in specs:
+        try:
+            q = jpeg.quality_of(s)
+        except ValueError as e:
+            raise ValueError(f"--quality {quality!r}: {e}") from None
+        if q not in qualities:
+            qualities.append(q)
+    try:
+        code = jpeg.subsampling_code(subsampling)
+    except ValueError as e:
+        raise ValueError(f"--subsampling: {e}") from None
+    if int(batch) < 1:
+        raise ValueError(f"--batch {batch}: must be >= 1")
+    if not inp or not os.path.exists(inp):
+        raise FileNotFoundError(f"--input {inp!r}: no such folder or list file")
+    if not output:
+        raise ValueError("--output: a folder for the compressed images' PNGs is required")
+    if os.path.isdir(inp) and os.path.realpath(inp) == os.path.realpath(output):
+        raise ValueError(f"--output {output!r} is the --input folder")
+    try:
+        paths = cr.check_inputs(inp)
+    except ValueError as e:
+        raise ValueError(f"--input {e}") from None
+    return paths, qualities, code
+
+
+def jpeg_files(inp, output, quality, subsampling="4:2:0", batch=8) -> dict:
+    """JPEG-compress clean image files on the GPU: OUTPUT/jpeg_q<Q>/<stem>.png (the decoded bytes, stored losslessly) for every
+    quality and input, and OUTPUT/jpeg_q<Q>/pairs.txt with one `lq hq` line per file (what data.ImageListFiles reads).  A file's
+    bytes depend on (the clean file, quality, subsampling) alone - there is no seed."""
+    import torch
+    paths, qualities, code = check_jpeg_args(inp, output, quality, subsampling, batch)
+    from . import corrupt as cr
+    from . import imageio, jpeg
+    if not torch.cuda.is_available():
+        raise RuntimeError("no GPU visible: the JPEG round trip runs on MI355X only (no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    sizes = [hw for _, hw in imageio.scan(paths)]
+    small = [p for p, hw in zip(paths, sizes) if min(hw) < jpeg.MIN_SIDE]
+    if small:
+        raise ValueError(f"--input: {len(small)} image(s) smaller than {jpeg.MIN_SIDE} x {jpeg.MIN_SIDE}, first {small[0]!r}")
+    stems = [cr.stem_of(p) for p in paths]
+    t0, folders = time.perf_counter(), []
+    for q in qualities:
+        folder = os.path.join(output, f"jpeg_q{q}")
+        os.makedirs(folder, exist_ok=True)
+        for _, cut in jpeg.plan_files(sizes, [q], int(batch)):
+            hq = torch.stack([imageio.load_u8(paths[i]) for i in cut]).to(dev)
+            lq = jpeg.roundtrip(hq, q, code).cpu()
+            for i, img in zip(cut, lq):
+                imageio.save_u8(img, os.path.join(folder, stems[i] + ".png"))
+        with open(os.path.join(folder, "pairs.txt"), "w") as f:
+            for i in range(len(paths)):
+                f.write(f"{stems[i]}.png {os.path.abspath(paths[i])}\n")
+        folders.append(os.path.basename(folder))
+    return dict(images=len(paths), qualities=qualities, subsampling={2: "4:2:0", 0: "4:4:4"}[code], folders=folders, output=output,
+                seconds_total=time.perf_counter() - t0)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m unirestore_amd.cli")
-    ap.add_argument("command", choices=["validate", "print_config", "restore", "corrupt"])
+    ap.add_argument("command", choices=["validate", "print_config", "restore", "corrupt", "jpeg"])
     ap.add_argument("--config", default=None, help="validate / print_config / restore: the YAML config (required there)")
     ap.add_argument("--set", action="append", default=[], metavar="a.b.c=value", help="override a config key")
     ap.add_argument("--hf-root", default=None, help="folder with unet/ and vae/ diffusion_pytorch_model.safetensors (sd-turbo)")
@@ -479,7 +551,16 @@ def main(argv=None):
                     help="corrupt: corruption names and / or subsets (common, validation, all, noise, blur, weather, digital)")
     ap.add_argument("--severity", default="3", help="corrupt: 1..5, or mixed for the reference's per-image draw")
     ap.add_argument("--seed", type=int, default=42, help="corrupt: with a file's stem, the seed of all its randomness")
+    ap.add_argument("--quality", default=None, metavar="10,25,s3", help="jpeg: qualities 1..100 and / or s1..s5 (the reference's severities)")
+    ap.add_argument("--subsampling", default="4:2:0", help="jpeg: 4:2:0 (Pillow's and the reference's default) or 4:4:4")
     a = ap.parse_args(argv)
+    if a.command == "jpeg":
+        try:
+            check_jpeg_args(a.input, a.output, a.quality, a.subsampling, a.batch)
+        except (ValueError, FileNotFoundError) as e:
+            ap.error(str(e))
+        print(json.dumps(jpeg_files(a.input, a.output, a.quality, a.subsampling, a.batch)))
+        return 0
     if a.command == "corrupt":
         try:
             check_corrupt_args(a.input, a.output, a.corruptions, a.severity, a.batch)

@@ -59,7 +59,8 @@ def motion_angle(seed: int, stem: str) -> float:
 
 def check_name(name: str) -> str:
     if name in UNBUILT:
-        raise NotImplementedError(f"corruption {name!r} is not built (built: {', '.join(NAMES)})")
+        hint = "; JPEG compression is a module of its own: unirestore_amd.jpeg.roundtrip, `cli jpeg`" if name == "jpeg_compression" else ""
+        raise NotImplementedError(f"corruption {name!r} is not built (built: {', '.join(NAMES)}){hint}")
     if name not in NAMES:
         raise ValueError(f"unknown corruption {name!r}: choose from {', '.join(NAMES)}")
     return name

@@ -1,5 +1,6 @@
 """Inputs for the config entry points: seeded synthetic images, `ImageListFiles`, real pairs from the reference's `lq hq label`
-list files, and `CorruptedImageFiles`, clean images corrupted on the GPU (unirestore_amd.corrupt).
+list files, `CorruptedImageFiles`, clean images corrupted on the GPU (unirestore_amd.corrupt), and `JpegImageFiles`, clean images
+JPEG-compressed on the GPU at a list of qualities (unirestore_amd.jpeg).
 
 `SyntheticImages` yields the evaluator's batch tuple `(lq, hq, gt, fname, task)` (reference
 src/core/base/eval_image_restoration.py:56) from seeded random images: hq = torch.rand (what the reference's own smoke
@@ -148,3 +149,54 @@ class CorruptedImageFiles:
             lq = corrupt.corrupt(hq, name, sev, self.seed, stems)
             self.last = (name, sev)
             yield nchw(lq), nchw(hq), None, stems, self.task
+
+
+class JpegImageFiles:
+    """Clean images JPEG-compressed on the GPU for `validate` (`data.class_path: unirestore_amd.data.JpegImageFiles`): `source` is
+    read as CorruptedImageFiles reads it (a folder, a list file of clean images, or the hq column of an `lq hq [label]` list).
+    `quality` is one quality or a list of them (unirestore_amd.jpeg.quality_of: integers 1..100 or "s1".."s5"); EVERY image is
+    taken at EVERY listed quality.  Images are grouped by (shape, quality), uploaded as u8 and compressed there (4:2:0, Pillow's
+    and the reference's default).  Yields `(lq, hq, None, names, task)` with fp32 NCHW tensors in [0, 1], the values
+    ImageListFiles yields for the same bytes; `last` holds ("jpeg", quality) of the batch just yielded."""
+
+    def __init__(self, source: str, quality=(10, 25, 50), batch_size: int = 8, task: str = "ir", num_batches: int = None):
+        from . import corrupt, jpeg
+        self.source, self.batch_size, self.task, self.num_batches = source, int(batch_size), task, num_batches
+        if self.batch_size < 1:
+            raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+        specs = [s for s in quality.split(",") if s] if isinstance(quality, str) else \
+            list(quality) if isinstance(quality, (list, tuple)) else [quality]
+        self.qualities = []
+        for s in specs:
+            q = jpeg.quality_of(s)
+            if q not in self.qualities:
+                self.qualities.append(q)
+        if not self.qualities:
+            raise ValueError("quality: name at least one quality")
+        self.paths = corrupt.check_inputs(source)
+        self.last = None
+
+    def _plan(self):
+        from . import jpeg
+        from .imageio import scan
+        sizes = [hw for _, hw in scan(self.paths)]
+        return jpeg.plan_files(sizes, self.qualities, self.batch_size)[:self.num_batches]
+
+    def __len__(self):
+        return len(self._plan())
+
+    def batches(self, rank: int = 0, world: int = 1, device="cpu") -> Iterator[Tuple[torch.Tensor, torch.Tensor, None, List[str], str]]:
+        from . import corrupt, jpeg
+        from .imageio import load_u8
+        if world != 1:
+            raise ValueError("JpegImageFiles does not shard a batch over ranks (batches of real files differ in size): run "
+                             "`validate` on one GPU")
+        unit = (torch.arange(256, dtype=torch.float32) / 255).to(device)          # u8 / 255 as the host computes it (CorruptedImageFiles)
+
+        def nchw(t):
+            return unit.index_select(0, t.permute(0, 3, 1, 2).reshape(-1).int()).view(t.shape[0], 3, t.shape[1], t.shape[2])
+        for q, idx in self._plan():
+            hq = torch.stack([load_u8(self.paths[i]) for i in idx]).to(device)
+            lq = jpeg.roundtrip(hq, q)
+            self.last = ("jpeg", q)
+            yield nchw(lq), nchw(hq), None, [corrupt.stem_of(self.paths[i]) for i in idx], self.task

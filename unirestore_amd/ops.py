@@ -745,16 +745,16 @@ def keyed_noise(keys_dev: torch.Tensor, draw: int, shape, kind="normal", out=Non
 
 # ---- corruptions of u8 images (csrc/corrupt.hip; the specification is the ur_corrupt_* comment in the header; the planner that
 # builds the tables is unirestore_amd.corrupt) ----------------------------------------------------------------------------------
-def check_u8_images(who: str, x):
-    """x must be a contiguous uint8 [N, H, W, 3] tensor on the current device with N >= 1 and H, W >= 32."""
+def check_u8_images(who: str, x, min_side: int = 32):
+    """x must be a contiguous uint8 [N, H, W, 3] tensor on the current device with N >= 1 and H, W >= min_side."""
     if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.ndim != 4 or x.shape[3] != 3 or not x.is_contiguous():
         raise ValueError(f"{who}: images must be a contiguous uint8 tensor [N, H, W, 3], got {getattr(x, 'dtype', type(x))} "
                          f"{tuple(getattr(x, 'shape', ()))}")
     dev = torch.device("cuda", torch.cuda.current_device())
     if x.device != dev:
         raise ValueError(f"{who}: the images are on {x.device}, not on the current device {dev}")
-    if x.shape[0] < 1 or x.shape[1] < 32 or x.shape[2] < 32:
-        raise ValueError(f"{who}: needs N >= 1 and H, W >= 32, got {tuple(x.shape)}")
+    if x.shape[0] < 1 or x.shape[1] < min_side or x.shape[2] < min_side:
+        raise ValueError(f"{who}: needs N >= 1 and H, W >= {min_side}, got {tuple(x.shape)}")
 
 
 def _corrupt_table(who: str, t, dtype, numel=None):
@@ -860,6 +860,25 @@ def corrupt_fog(x, keys_dev, c: float, decay: float, out_kind=0):
     ws, nbytes = _corrupt_ws(x, lib.ur_corrupt_fog_ws_bytes(n, h, w_))
     check(lib.ur_corrupt_fog(x.data_ptr(), keys_dev.data_ptr(), out.data_ptr(), n, h, w_, float(c), float(decay), ws.data_ptr(), nbytes, out_kind,
                              _stream()))
+    return out
+
+
+# ---- JPEG compression as a degradation (csrc/jpeg.hip; the specification is the ur_jpeg_roundtrip comment in the header; the
+# planner is unirestore_amd.jpeg) ----------------------------------------------------------------------------------------------
+def jpeg_roundtrip(x, quality: int, subsampling: int = 2, out=None):
+    """The bytes a baseline JPEG of x (device uint8 [N, H, W, 3], H, W >= 16) decodes to: quality 1..100, subsampling 0 (4:4:4) or
+    2 (4:2:0), Pillow's codes.  out: a contiguous uint8 tensor of x's shape on x's device, not x (default: a new one)."""
+    check_u8_images("jpeg_roundtrip", x, min_side=16)
+    if subsampling not in (0, 2):
+        raise ValueError(f"jpeg_roundtrip: subsampling must be 0 (4:4:4) or 2 (4:2:0), got {subsampling!r}")
+    n, h, w_, _ = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.shape != x.shape or out.device != x.device or \
+            not out.is_contiguous():
+        raise ValueError(f"jpeg_roundtrip: out must be a contiguous uint8 tensor {tuple(x.shape)} on {x.device}")
+    ws, nbytes = _corrupt_ws(x, lib.ur_jpeg_roundtrip_ws_bytes(n, h, w_, int(subsampling)))
+    check(lib.ur_jpeg_roundtrip(x.data_ptr(), out.data_ptr(), n, h, w_, int(quality), int(subsampling), ws.data_ptr(), nbytes, _stream()))
     return out
 
 
