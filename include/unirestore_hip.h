@@ -512,6 +512,35 @@ int ur_jpeg_roundtrip(const uint8_t* x, uint8_t* out, int N, int H, int W, int q
                       ur_stream_t stream);
 size_t ur_jpeg_roundtrip_ws_bytes(int N, int H, int W, int subsampling);
 
+/* ---- antialiased resize of 8-bit images: the bytes torch's CPU interpolate(uint8, antialias=True) gives, which is what
+ * torchvision v2's resize of a uint8 tensor runs (the planner is unirestore_amd/resize.py) ---------------------------------------
+ * x u8 [N,H,W,3] contiguous HWC on the device -> out u8 [N,oh,ow,3], not x; H, W, oh and ow >= 2.  Two 1-D passes: ALONG THE WIDTH
+ * FIRST, into a u8 intermediate [N,H,ow,3] in ws, then along the height.  A pass whose input and output length are equal is
+ * skipped; with both equal out is a copy of x.  The kernels know no filter: the caller builds, per axis n_in -> n_out, in fp64 on
+ * the host, and hands over as DEVICE int32 tables
+ *   bounds [n_out][2] = (xmin, xsize) and weights [n_out][K], with K and one precision p for the whole axis:
+ *     scale = n_in / n_out; isz = 2 (bilinear) or 4 (bicubic); support = isz/2 * scale if scale >= 1 else isz/2;
+ *     inv = 1/scale if scale >= 1 else 1; K = ceil(support)*2 + 1.  For output index i: c = scale*(i + 0.5),
+ *     xmin = max(int(c - support + 0.5), 0), xsize = min(int(c + support + 0.5), n_in) - xmin,
+ *     w_j = f((j + xmin - c + 0.5) * inv) for j < xsize, divided by their sum (added in ascending j); the other slots are 0.
+ *     f(t) = 1 - |t| below 1 (bilinear); the Keys cubic with a = -0.5 (bicubic): ((a+2)|t| - (a+3)) t^2 + 1 below 1,
+ *     (((|t| - 5)|t| + 8)|t| - 4) a below 2; 0 beyond.
+ *     p = the smallest of 0..21 with int(0.5 + wmax * 2^(p+1)) >= 2^15, wmax the largest weight of the axis, else 22;
+ *     W_j = int(0.5 + w_j * 2^p), or int(-0.5 + w_j * 2^p) for a negative w_j (both truncate towards zero).
+ *   out byte = clamp((2^(p-1) + sum_j W_j * src[xmin + j]) >> p, 0, 255): int32 accumulation, arithmetic shift.
+ * The rounded weights of a row need not sum to 2^p, so a constant image does not always come back constant: that is the target.
+ * The float path (interpolate(float).round()) and Pillow's BILINEAR are different functions and differ by one in some bytes.
+ * A table row with xmin < 0, xsize < 0, xsize > K or xmin + xsize > n_in is read as xsize = 0: no kernel reads outside x, the
+ * tables or ws.  The tables of a skipped pass are not read but must still be given.
+ * ws: ur_resize_u8_ws_bytes(N, H, W, oh, ow) bytes (the intermediate, rounded up to 8; 0 for a non-positive argument), 8-byte
+ * aligned; nothing in it is read before this call has written it.  UR_E_INVALID before any HIP call for a null pointer, N <= 0, a
+ * side below 2, N*H*W*3, N*oh*ow*3 or N*H*ow*3 >= 2^31, K outside 1..65536, p outside 1..22, out == x, a misaligned table or
+ * workspace, or a workspace that is too small.  No allocation, no synchronisation, no atomics: the same inputs give the same
+ * bits. */
+int ur_resize_u8(const uint8_t* x, uint8_t* out, int N, int H, int W, int oh, int ow, const int32_t* xbounds, const int32_t* xweights, int xK,
+                 int xp, const int32_t* ybounds, const int32_t* yweights, int yK, int yp, void* ws, size_t ws_bytes, ur_stream_t stream);
+size_t ur_resize_u8_ws_bytes(int N, int H, int W, int oh, int ow);
+
 /* ---- live per-kernel-family timing (HIP events on the launch stream) ------------------------------*/
 int ur_profile_enable(int on);
 /* writes a JSON object {family: {launches, ms, flops, bytes}} into buf (host); synchronises the events */

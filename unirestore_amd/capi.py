@@ -134,6 +134,8 @@ SIGNATURES = {
     "ur_corrupt_fog_ws_bytes": (_SZ, [_I, _I, _I]),
     "ur_jpeg_roundtrip": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "ur_jpeg_roundtrip_ws_bytes": (_SZ, [_I, _I, _I, _I]),
+    "ur_resize_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _SZ, _P]),
+    "ur_resize_u8_ws_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "ur_profile_enable": (_I, [_I]),
     "ur_profile_report": (_I, [C.c_char_p, _SZ]),
 }

@@ -127,7 +127,8 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
     """tasks: a list of task names - every batch is restored once and decoded for each of them (DiffUIE.forward_tasks).  PSNR / SSIM
     come from the "ir" output, so the list must hold "ir"; images_per_s counts input images.  model: a ready DiffUIE to use instead
     of building the config's.  With data.CorruptedImageFiles the result also holds by_corruption ("fog/3" -> psnr, ssim, images)
-    and skipped (the subset members that are not built); with data.JpegImageFiles it holds by_corruption ("jpeg/10", the quality)."""
+    and skipped (the subset members that are not built); with data.JpegImageFiles it holds by_corruption ("jpeg/10", the quality);
+    with either, resize = [lo, hi] when the data's resize-down / resize-back wrapper is on."""
     import torch
     r = resolve(cfg, allow_16bit=allow_16bit)
     if tasks is not None:
@@ -204,6 +205,8 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
                                 for k, v in by_corruption.items()}
         if isinstance(data, data_mod.CorruptedImageFiles):
             res["skipped"] = list(data.skipped)
+        if data.resize is not None:
+            res["resize"] = list(data.resize)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -386,10 +389,22 @@ def restore(cfg: dict, inp, output, task=None, tasks=None, batch=8, hf_root=None
     return res if rank == 0 else None
 
 
-def check_corrupt_args(inp, output, corruptions, severity=3, batch=8):
+def check_resize_arg(resize, minimum: int):
+    """--resize LO,HI (or a pair of integers, or None) -> (lo, hi) or None; the message names --resize."""
+    from . import resize as rz
+    if resize is None:
+        return None
+    try:
+        return rz.check_range(resize, minimum)
+    except ValueError as e:
+        raise ValueError(f"--{e}") from None
+
+
+def check_corrupt_args(inp, output, corruptions, severity=3, batch=8, resize=None):
     """Everything about a `corrupt` call that can be wrong without looking at a GPU -> (clean image paths, corruption names, an
-    integer severity or "mixed").  Every message names the offending argument."""
+    integer severity or "mixed").  Every message names the offending argument.  resize: None, "LO,HI" or (lo, hi), checked only."""
     from . import corrupt as cr
+    check_resize_arg(resize, 32)
     if not corruptions:
         raise ValueError("--corruptions: name at least one corruption or subset (" + ", ".join(sorted(cr.SUBSETS)) + ")")
     try:
@@ -417,12 +432,15 @@ def check_corrupt_args(inp, output, corruptions, severity=3, batch=8):
     return paths, names, severity
 
 
-def corrupt_files(inp, output, corruptions, severity=3, seed=42, batch=8) -> dict:
+def corrupt_files(inp, output, corruptions, severity=3, seed=42, batch=8, resize=None) -> dict:
     """Corrupt clean image files on the GPU: OUTPUT/<name>_<severity>/<stem>.png for every named corruption and input, and
     OUTPUT/<name>_<severity>/pairs.txt with one `lq hq` line per file (what data.ImageListFiles and the reference's list datasets
-    read).  A file's bytes depend on (seed, stem, name, severity) alone - not on the other files, their order or --batch."""
+    read).  A file's bytes depend on (seed, stem, name, severity) alone - not on the other files, their order or --batch.
+    resize = "LO,HI" or (lo, hi): every file is corrupted inside the resize-down / resize-back wrapper (corrupt.degrade), its short
+    edge drawn from [lo, hi) by (seed, stem); the folders and pairs.txt are what they are without it."""
     import torch
-    paths, names, severity = check_corrupt_args(inp, output, corruptions, severity, batch)
+    paths, names, severity = check_corrupt_args(inp, output, corruptions, severity, batch, resize)
+    resize = check_resize_arg(resize, 32)
     from . import corrupt as cr
     from . import imageio
     if not torch.cuda.is_available():
@@ -442,7 +460,7 @@ def corrupt_files(inp, output, corruptions, severity=3, seed=42, batch=8) -> dic
             for s in range(0, len(idx), int(batch)):
                 cut = idx[s:s + int(batch)]
                 hq = torch.stack([imageio.load_u8(paths[i]) for i in cut]).to(dev)
-                lq = cr.corrupt(hq, name, sev, seed, [stems[i] for i in cut]).cpu()
+                lq = cr.degrade(hq, name, sev, seed, [stems[i] for i in cut], resize).cpu()
                 for i, img in zip(cut, lq):
                     imageio.save_u8(img, os.path.join(folder, stems[i] + ".png"))
             folders.setdefault(folder, []).extend(idx)
@@ -451,14 +469,16 @@ def corrupt_files(inp, output, corruptions, severity=3, seed=42, batch=8) -> dic
             for i in sorted(idx):
                 f.write(f"{stems[i]}.png {os.path.abspath(paths[i])}\n")
     return dict(images=len(paths), corruptions=names, skipped=cr.skipped(corruptions), severity=severity, seed=seed,
-                folders=sorted(os.path.basename(d) for d in folders), output=output, seconds_total=time.perf_counter() - t0)
+                folders=sorted(os.path.basename(d) for d in folders), output=output, seconds_total=time.perf_counter() - t0,
+                **({"resize": list(resize)} if resize is not None else {}))
 
 
-def check_jpeg_args(inp, output, quality, subsampling="4:2:0", batch=8):
+def check_jpeg_args(inp, output, quality, subsampling="4:2:0", batch=8, resize=None):
     """Everything about a `jpeg` call that can be wrong without looking at a GPU -> (clean image paths, the qualities as integers,
-    each once, the subsampling code).  Every message names the offending argument."""
+    each once, the subsampling code).  Every message names the offending argument.  resize: None, "LO,HI" or (lo, hi), checked only."""
     from . import corrupt as cr
     from . import jpeg
+    check_resize_arg(resize, jpeg.MIN_SIDE)
     specs = [s for s in str(quality).split(",") if s.strip()] if quality is not None else []
     if not specs:
         raise ValueError("--quality: name at least one quality (1..100, or s1..s5 for the reference's severities), e.g. 10,25,s3")
@@ -489,14 +509,17 @@ def check_jpeg_args(inp, output, quality, subsampling="4:2:0", batch=8):
     return paths, qualities, code
 
 
-def jpeg_files(inp, output, quality, subsampling="4:2:0", batch=8) -> dict:
+def jpeg_files(inp, output, quality, subsampling="4:2:0", batch=8, resize=None, seed=42) -> dict:
     """JPEG-compress clean image files on the GPU: OUTPUT/jpeg_q<Q>/<stem>.png (the decoded bytes, stored losslessly) for every
     quality and input, and OUTPUT/jpeg_q<Q>/pairs.txt with one `lq hq` line per file (what data.ImageListFiles reads).  A file's
-    bytes depend on (the clean file, quality, subsampling) alone - there is no seed."""
+    bytes depend on (the clean file, quality, subsampling) alone - there is no seed - unless resize = "LO,HI" or (lo, hi) puts the
+    round trip inside the resize-down / resize-back wrapper (jpeg.degrade): the short edge is then drawn from [lo, hi) by
+    (seed, stem)."""
     import torch
-    paths, qualities, code = check_jpeg_args(inp, output, quality, subsampling, batch)
+    paths, qualities, code = check_jpeg_args(inp, output, quality, subsampling, batch, resize)
     from . import corrupt as cr
     from . import imageio, jpeg
+    resize = check_resize_arg(resize, jpeg.MIN_SIDE)
     if not torch.cuda.is_available():
         raise RuntimeError("no GPU visible: the JPEG round trip runs on MI355X only (no CPU fallback)")
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -511,7 +534,7 @@ def jpeg_files(inp, output, quality, subsampling="4:2:0", batch=8) -> dict:
         os.makedirs(folder, exist_ok=True)
         for _, cut in jpeg.plan_files(sizes, [q], int(batch)):
             hq = torch.stack([imageio.load_u8(paths[i]) for i in cut]).to(dev)
-            lq = jpeg.roundtrip(hq, q, code).cpu()
+            lq = jpeg.degrade(hq, q, seed, [stems[i] for i in cut], resize, code).cpu()
             for i, img in zip(cut, lq):
                 imageio.save_u8(img, os.path.join(folder, stems[i] + ".png"))
         with open(os.path.join(folder, "pairs.txt"), "w") as f:
@@ -519,7 +542,7 @@ def jpeg_files(inp, output, quality, subsampling="4:2:0", batch=8) -> dict:
                 f.write(f"{stems[i]}.png {os.path.abspath(paths[i])}\n")
         folders.append(os.path.basename(folder))
     return dict(images=len(paths), qualities=qualities, subsampling={2: "4:2:0", 0: "4:4:4"}[code], folders=folders, output=output,
-                seconds_total=time.perf_counter() - t0)
+                seconds_total=time.perf_counter() - t0, **({"resize": list(resize), "seed": seed} if resize is not None else {}))
 
 
 def main(argv=None):
@@ -550,23 +573,26 @@ def main(argv=None):
     ap.add_argument("--corruptions", default=None, metavar="fog,motion_blur|SUBSET",
                     help="corrupt: corruption names and / or subsets (common, validation, all, noise, blur, weather, digital)")
     ap.add_argument("--severity", default="3", help="corrupt: 1..5, or mixed for the reference's per-image draw")
-    ap.add_argument("--seed", type=int, default=42, help="corrupt: with a file's stem, the seed of all its randomness")
+    ap.add_argument("--seed", type=int, default=42, help="corrupt: with a file's stem, the seed of all its randomness; jpeg: of the --resize draw")
+    ap.add_argument("--resize", default=None, metavar="LO,HI",
+                    help="corrupt / jpeg: degrade inside the reference's wrapper - resize every image so that its short edge is an integer "
+                         "drawn from [LO, HI) by (seed, stem), degrade at that size, resize back (the reference draws from [128, 512))")
     ap.add_argument("--quality", default=None, metavar="10,25,s3", help="jpeg: qualities 1..100 and / or s1..s5 (the reference's severities)")
     ap.add_argument("--subsampling", default="4:2:0", help="jpeg: 4:2:0 (Pillow's and the reference's default) or 4:4:4")
     a = ap.parse_args(argv)
     if a.command == "jpeg":
         try:
-            check_jpeg_args(a.input, a.output, a.quality, a.subsampling, a.batch)
+            check_jpeg_args(a.input, a.output, a.quality, a.subsampling, a.batch, a.resize)
         except (ValueError, FileNotFoundError) as e:
             ap.error(str(e))
-        print(json.dumps(jpeg_files(a.input, a.output, a.quality, a.subsampling, a.batch)))
+        print(json.dumps(jpeg_files(a.input, a.output, a.quality, a.subsampling, a.batch, a.resize, a.seed)))
         return 0
     if a.command == "corrupt":
         try:
-            check_corrupt_args(a.input, a.output, a.corruptions, a.severity, a.batch)
+            check_corrupt_args(a.input, a.output, a.corruptions, a.severity, a.batch, a.resize)
         except (ValueError, FileNotFoundError, NotImplementedError) as e:
             ap.error(str(e))
-        print(json.dumps(corrupt_files(a.input, a.output, a.corruptions, a.severity, a.seed, a.batch)))
+        print(json.dumps(corrupt_files(a.input, a.output, a.corruptions, a.severity, a.seed, a.batch, a.resize)))
         return 0
     if a.config is None:
         ap.error("the following arguments are required: --config")

@@ -5,7 +5,8 @@ The names, severity constants and subsets are the reference's (src/data/corrupti
 names raise NotImplementedError.  This module is the planner: it builds the small tables a corruption needs on the host in fp64
 (Gaussian taps, the defocus disk, motion taps, zoom layers, the Poisson table, the pixelate tables) and launches the primitives of
 `ops`.  An image's randomness is a pure function of (seed, stem): `corruption_seed` keys the device draws, `motion_angle` is the one
-host scalar.  The reference's resize-down / resize-back wrapper around the corruption is not part of this.
+host scalar.  `corrupt` works at the size it is given; `degrade` is `corrupt` inside the reference's resize-down / resize-back
+wrapper (unirestore_amd.resize.around) when a short-edge range is given, and `corrupt` itself when none is.
 """
 import hashlib
 import math
@@ -287,6 +288,28 @@ def corrupt(images_u8, name: str, severity: int, seeds, stems=None, out_kind: in
         sh, sw, hbox, vbox, ymap, xmap = pixelate_tables(h, w, c)
         return ops.corrupt_pixelate(images_u8, sh, sw, table(hbox), table(vbox), table(ymap), table(xmap), out_kind)
     return ops.corrupt_fog(images_u8, keys(), 255.0 * c[0], c[1], out_kind)      # fog
+
+
+def degrade(images_u8, name: str, severity: int, seeds, stems=None, resize=None):
+    """`corrupt` as the reference degrades an image (IRCorruptDataset._degrade_image).  resize None: `corrupt` itself.  resize =
+    (lo, hi), lo >= 32: image n is resized so that its short edge is resize.draw_short_edge(seeds[n], stems[n], lo, hi)
+    (torchvision's rule for a one-element size, antialiased bilinear on the bytes), corrupted at that size under its own seed and
+    stem, and resized back: uint8 of the input's shape.  "clean" returns the input unresized, as the reference does."""
+    if resize is None or name == "clean":
+        return corrupt(images_u8, name, severity, seeds, stems)
+    from . import ops
+    from . import resize as rz
+    lo, hi = rz.check_range(resize, 32)
+    check_name(name)
+    check_severity(severity)
+    ops.check_u8_images("degrade", images_u8)
+    n, h, w, _ = images_u8.shape
+    seeds = [seeds] * n if hasattr(seeds, "__index__") else list(seeds)
+    stems = [""] * n if stems is None else list(stems)
+    if len(seeds) != n or len(stems) != n:
+        raise ValueError(f"degrade: {n} images but {len(seeds)} seeds and {len(stems)} stems")
+    sizes = [rz.short_edge_size(h, w, rz.draw_short_edge(s, t, lo, hi)) for s, t in zip(seeds, stems)]
+    return rz.around(images_u8, sizes, lambda batch, idx: corrupt(batch, name, severity, [seeds[i] for i in idx], [stems[i] for i in idx]))
 
 
 # ------------------------------------------------------------------------------------------ files

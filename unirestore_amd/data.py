@@ -109,11 +109,15 @@ class CorruptedImageFiles:
     `severity` an integer 1..5 or "mixed", the reference's per-image draw.  Every image's corruption, severity and randomness come
     from sha256 of (seed, file stem) alone.  Images are grouped by (shape, corruption, severity), so a batch is homogeneous; hq is
     uploaded as u8 and corrupted there.  Yields `(lq, hq, None, names, task)` with fp32 NCHW tensors in [0, 1]; `last` holds the
-    (corruption, severity) of the batch just yielded and `skipped` the subset members that are not built."""
+    (corruption, severity) of the batch just yielded and `skipped` the subset members that are not built.  `resize` = [lo, hi]
+    (lo >= 32) turns on the reference's resize-down / resize-back wrapper (corrupt.degrade): every image's short edge is drawn
+    from [lo, hi) by (seed, stem) as well, lq keeps hq's shape; the reference's own range is [resolution // 4, resolution)."""
 
     def __init__(self, source: str, corruptions="common", severity=3, batch_size: int = 8, task: str = "ir", seed: int = 42,
-                 num_batches: int = None):
+                 num_batches: int = None, resize=None):
         from . import corrupt
+        from . import resize as rz
+        self.resize = None if resize is None else rz.check_range(resize, 32)
         self.source, self.batch_size, self.task, self.seed, self.num_batches = source, int(batch_size), task, int(seed), num_batches
         if self.batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
@@ -146,7 +150,7 @@ class CorruptedImageFiles:
         for name, sev, idx in self._plan():
             stems = [corrupt.stem_of(self.paths[i]) for i in idx]
             hq = torch.stack([load_u8(self.paths[i]) for i in idx]).to(device)
-            lq = corrupt.corrupt(hq, name, sev, self.seed, stems)
+            lq = corrupt.degrade(hq, name, sev, self.seed, stems, self.resize)
             self.last = (name, sev)
             yield nchw(lq), nchw(hq), None, stems, self.task
 
@@ -157,10 +161,15 @@ class JpegImageFiles:
     `quality` is one quality or a list of them (unirestore_amd.jpeg.quality_of: integers 1..100 or "s1".."s5"); EVERY image is
     taken at EVERY listed quality.  Images are grouped by (shape, quality), uploaded as u8 and compressed there (4:2:0, Pillow's
     and the reference's default).  Yields `(lq, hq, None, names, task)` with fp32 NCHW tensors in [0, 1], the values
-    ImageListFiles yields for the same bytes; `last` holds ("jpeg", quality) of the batch just yielded."""
+    ImageListFiles yields for the same bytes; `last` holds ("jpeg", quality) of the batch just yielded.  `resize` = [lo, hi]
+    (lo >= 16) turns on the reference's resize-down / resize-back wrapper (jpeg.degrade): every image's short edge is drawn from
+    [lo, hi) by (`seed`, stem), the only use of `seed`; lq keeps hq's shape."""
 
-    def __init__(self, source: str, quality=(10, 25, 50), batch_size: int = 8, task: str = "ir", num_batches: int = None):
+    def __init__(self, source: str, quality=(10, 25, 50), batch_size: int = 8, task: str = "ir", num_batches: int = None, resize=None,
+                 seed: int = 42):
         from . import corrupt, jpeg
+        from . import resize as rz
+        self.resize, self.seed = None if resize is None else rz.check_range(resize, jpeg.MIN_SIDE), int(seed)
         self.source, self.batch_size, self.task, self.num_batches = source, int(batch_size), task, num_batches
         if self.batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
@@ -197,6 +206,7 @@ class JpegImageFiles:
             return unit.index_select(0, t.permute(0, 3, 1, 2).reshape(-1).int()).view(t.shape[0], 3, t.shape[1], t.shape[2])
         for q, idx in self._plan():
             hq = torch.stack([load_u8(self.paths[i]) for i in idx]).to(device)
-            lq = jpeg.roundtrip(hq, q)
+            stems = [corrupt.stem_of(self.paths[i]) for i in idx]
+            lq = jpeg.degrade(hq, q, self.seed, stems, self.resize)
             self.last = ("jpeg", q)
-            yield nchw(lq), nchw(hq), None, [corrupt.stem_of(self.paths[i]) for i in idx], self.task
+            yield nchw(lq), nchw(hq), None, stems, self.task

@@ -4,6 +4,8 @@ ur_jpeg_roundtrip comment of include/unirestore_hip.h, the derivation notes are 
 `roundtrip` returns the bytes Pillow reads back from `save(buf, "JPEG", quality=q)`, which is the reference's `jpeg_compression`
 (src/data/corruption), without writing a JPEG: only the lossy steps change pixels.  A quality is an integer 1..100 or one of the
 reference's five severities by name ("s1".."s5").  There is no randomness: the result depends on (image, quality, subsampling).
+`degrade` is `roundtrip` inside the reference's resize-down / resize-back wrapper (unirestore_amd.resize), whose short edge is drawn
+from (seed, stem).
 `unirestore_amd.corrupt` still lists jpeg_compression as unbuilt; this module is its sibling, not a member of corrupt.NAMES.
 """
 import numpy as np
@@ -65,6 +67,26 @@ def roundtrip(images_u8, quality, subsampling="4:2:0"):
     if len(shape) == 4 and (shape[1] < MIN_SIDE or shape[2] < MIN_SIDE):
         raise ValueError(f"jpeg.roundtrip: H and W must be >= {MIN_SIDE} (one 4:2:0 MCU), got {shape[1]} x {shape[2]}")
     return ops.jpeg_roundtrip(images_u8, q, code)
+
+
+def degrade(images_u8, quality, seeds, stems, resize, subsampling="4:2:0"):
+    """`roundtrip` inside the reference's resize-down / resize-back wrapper (unirestore_amd.resize.around), as corrupt.degrade is
+    for the corruptions.  resize None: `roundtrip` itself (seeds and stems are not looked at).  resize = (lo, hi), lo >= MIN_SIDE:
+    image n's short edge is resize.draw_short_edge(seeds[n], stems[n], lo, hi).  -> uint8 of the input's shape."""
+    if resize is None:
+        return roundtrip(images_u8, quality, subsampling)
+    from . import ops
+    from . import resize as rz
+    lo, hi = rz.check_range(resize, MIN_SIDE)
+    q, code = quality_of(quality), subsampling_code(subsampling)
+    ops.check_u8_images("jpeg.degrade", images_u8, min_side=rz.MIN_SIDE)
+    n, h, w, _ = images_u8.shape
+    seeds = [seeds] * n if hasattr(seeds, "__index__") else list(seeds)
+    stems = [""] * n if stems is None else list(stems)
+    if len(seeds) != n or len(stems) != n:
+        raise ValueError(f"jpeg.degrade: {n} images but {len(seeds)} seeds and {len(stems)} stems")
+    sizes = [rz.short_edge_size(h, w, rz.draw_short_edge(s, t, lo, hi)) for s, t in zip(seeds, stems)]
+    return rz.around(images_u8, sizes, lambda batch, idx: roundtrip(batch, q, code))
 
 
 def plan_files(sizes, qualities, batch_size: int):

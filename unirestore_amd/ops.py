@@ -882,6 +882,40 @@ def jpeg_roundtrip(x, quality: int, subsampling: int = 2, out=None):
     return out
 
 
+# ---- antialiased resize of u8 images (csrc/resize.hip; the specification is the ur_resize_u8 comment in the header; the planner
+# that builds the tables is unirestore_amd.resize) -----------------------------------------------------------------------------
+def resize_u8(x, size, xaxis, yaxis, out=None):
+    """x: device uint8 [N, H, W, 3] (H, W >= 2) -> uint8 [N, oh, ow, 3], size = (oh, ow), both >= 2.  xaxis / yaxis = (bounds, weights,
+    K, p) of the width / height axis: device int32 tables [n_out, 2] and [n_out, K] (resize.axis_tables, uploaded).  out: a
+    contiguous uint8 tensor [N, oh, ow, 3] on x's device, not x (default: a new one)."""
+    check_u8_images("resize_u8", x, min_side=2)
+    n, h, w_, _ = x.shape
+    if not isinstance(size, (tuple, list)) or len(size) != 2 or any(isinstance(s, bool) or not hasattr(s, "__index__") for s in size) or \
+            min(int(s) for s in size) < 2:
+        raise ValueError(f"resize_u8: size must be two integers (oh, ow), both >= 2, got {size!r}")
+    oh, ow = int(size[0]), int(size[1])
+    for who, axis, n_out in (("width", xaxis, ow), ("height", yaxis, oh)):
+        if not isinstance(axis, (tuple, list)) or len(axis) != 4:
+            raise ValueError(f"resize_u8: the {who} axis must be (bounds, weights, K, p)")
+        bounds, weights, k, p = axis
+        if isinstance(k, bool) or not hasattr(k, "__index__") or not 1 <= int(k) <= 65536:
+            raise ValueError(f"resize_u8: {who} K must be an integer in [1, 65536], got {k!r}")
+        if isinstance(p, bool) or not hasattr(p, "__index__") or not 1 <= int(p) <= 22:
+            raise ValueError(f"resize_u8: {who} p must be an integer in [1, 22], got {p!r}")
+        _corrupt_table(f"resize_u8: {who} bounds", bounds, torch.int32, 2 * n_out)
+        _corrupt_table(f"resize_u8: {who} weights", weights, torch.int32, int(k) * n_out)
+    shape = (n, oh, ow, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != x.device or \
+            not out.is_contiguous() or out.data_ptr() == x.data_ptr():
+        raise ValueError(f"resize_u8: out must be a contiguous uint8 tensor {shape} on {x.device}, not the input")
+    ws, nbytes = _corrupt_ws(x, lib.ur_resize_u8_ws_bytes(n, h, w_, oh, ow))
+    check(lib.ur_resize_u8(x.data_ptr(), out.data_ptr(), n, h, w_, oh, ow, xaxis[0].data_ptr(), xaxis[1].data_ptr(), int(xaxis[2]), int(xaxis[3]),
+                           yaxis[0].data_ptr(), yaxis[1].data_ptr(), int(yaxis[2]), int(yaxis[3]), ws.data_ptr(), nbytes, _stream()))
+    return out
+
+
 def ddim_step_(zt, zt_bf16, eps_f32, clat, c_x, c_e):
     cp = zt.shape[-1]
     check(lib.ur_ddim_step(zt.data_ptr(), eps_f32.data_ptr(), eps_f32.shape[-1], zt_bf16.data_ptr(), zt.numel() // cp, clat, cp,
