@@ -541,6 +541,52 @@ int ur_resize_u8(const uint8_t* x, uint8_t* out, int N, int H, int W, int oh, in
                  int xp, const int32_t* ybounds, const int32_t* yweights, int yK, int yp, void* ws, size_t ws_bytes, ur_stream_t stream);
 size_t ur_resize_u8_ws_bytes(int N, int H, int W, int oh, int ow);
 
+/* ---- glass blur, snow and elastic transform: the corruptions that work on float fields between the u8 ends (the planner is
+ * unirestore_amd/distort.py; siblings of ur_corrupt_*, whose conventions hold: x u8 [N,H,W,3] HWC on the device, H and W >= 32,
+ * N*H*W*3 < 2^31, fp32 values v on the 0-255 scale, out_kind 1 stores clamp(v, 0, 255) as fp32 and out_kind 0 its floor as u8, keys
+ * DEVICE uint32 [N][2], uniforms and normals as ur_keyed_noise's) -----------------------------------------------------------------
+ * Element e = y*W + x of a per-pixel field [H][W] takes word e & 3 of the Philox counter (e >> 2, draw, 0, 0) under image n's key.
+ * Draw numbers: 32..37 glass_blur (iteration i: 32 + 2i for dy, 33 + 2i for dx), 40 snow, 48 / 49 elastic_transform (dy / dx);
+ * 0, 1 and 16..21 are taken by ur_keyed_noise's callers and ur_corrupt_*.
+ *   glass_blur = ur_corrupt_filter_sep (out_kind 0) -> `iterations` times ur_distort_shuffle -> ur_corrupt_filter_sep.
+ *   ur_distort_shuffle  one iteration, u8 -> u8, integers throughout: a pixel with delta <= y < H - delta and delta <= x < W - delta
+ *       becomes the whole pixel x[y + dy][x + dx], dy = ((word of `draw` * 2 delta) >> 32) - delta (a 64-bit product), dx the same
+ *       from draw + 1: independent integers in [-delta, delta); every other pixel is copied.  delta in 1..4; out != x.
+ *   snow = ur_distort_snow_layer -> ur_distort_snow.
+ *   ur_distort_snow_layer  field fp32 [N][oh][ow]: layer[y][x] = loc + scale*n, n = the normal of element y*W + x of draw 40; the crop
+ *       [top, top+ch) x [left, left+cw) of the layer is resampled bilinearly to oh x ow exactly as a layer of ur_corrupt_zoom is
+ *       (position o*(in-1)/(out-1): the cell by integer division, the fraction (remainder)/(out-1) in fp32, a + fy*(b - a) with
+ *       a, b = p0 + fx*(p1 - p0)); a value < thr becomes 0, every other one is clamped to [0, 1].  The normals are drawn at the four
+ *       source cells; nothing else is stored.  oh >= H, ow >= W, both <= 32768, N*oh*ow < 2^31, scale > 0.
+ *   ur_distort_snow  s = sum over t (ascending) of w_t * field[clamp(y + ty_t)][clamp(x + tx_t)] (replicate border of the oh x ow
+ *       field; taps int32 [N][n_taps][3] = (tx, ty, the fp32 bits of w) per image, n_taps in 1..64, pad a shorter list with
+ *       weight-0 taps), L[y][x] = rint(255*s) (round half to even) as u8 for y < H, x < W, held in ws; then, in a second launch so
+ *       that all of L is written before any of it is read, per channel
+ *         v = (keep*x + (1 - keep)*max(x, 1.5*g + 127.5)) + (L[y][x] + L[H-1-y][W-1-x]),  g = 0.299 R + 0.587 G + 0.114 B,
+ *       keep in [0, 1], N <= 65535.  ws: ur_distort_snow_ws_bytes(N, H, W).
+ *   elastic_transform = ur_distort_field -> ur_distort_warp.
+ *   ur_distort_field  field fp32 [N][2][H][W], plane 0 = dy (draw 48), plane 1 = dx (draw 49): f = m*(2u - 1), u = the uniform of
+ *       element y*W + x; t = sum_k taps_y[k+ry] * f[r(y+k)][x], then field = alpha * sum_k taps_x[k+rx] * t[y][r(x+k)] (k ascending,
+ *       fp32), r = the half-sample-symmetric reflection (d c b a | a b c d, periodic).  taps fp32 [2*radius+1], radii in 0..255,
+ *       m >= 0.  ws: ur_distort_field_ws_bytes(N, H, W); field is not ws.
+ *   ur_distort_warp  per channel the bilinear sample of x at (py, px) = (y + field[n][0][y][x], x + field[n][1][y][x]), each sum
+ *       rounded once to fp32 and limited to +-1e6: i = floor(p), f = p - i, rows r(iy), r(iy + 1) and columns r(ix), r(ix + 1) with
+ *       the same reflection r, value a + fy*(b - a), a, b = p0 + fx*(p1 - p0).  A field of zeros returns x.
+ * UR_E_INVALID before any HIP call for a null pointer, N <= 0, H or W < 32, an image of 2^31 elements or more, out == x, an unknown
+ * out_kind, a misaligned fp32 array, table or workspace, a size, radius, delta or constant out of the ranges above, or a workspace
+ * that is too small; the _ws_bytes functions return 0 for a non-positive argument.  Workspaces are 8-byte aligned and nothing in
+ * them is read before the call has written it.  No allocation, no synchronisation, no atomics: the same inputs give the same bits. */
+int ur_distort_shuffle(const uint8_t* x, const uint32_t* keys, uint8_t* out, int N, int H, int W, int delta, uint32_t draw, ur_stream_t stream);
+int ur_distort_snow_layer(const uint32_t* keys, float* field, int N, int H, int W, int top, int left, int ch, int cw, int oh, int ow, float loc,
+                          float scale, float thr, ur_stream_t stream);
+int ur_distort_snow(const uint8_t* x, const float* field, const int32_t* taps, int n_taps, void* out, int N, int H, int W, int oh, int ow,
+                    float keep, void* ws, size_t ws_bytes, int out_kind, ur_stream_t stream);
+size_t ur_distort_snow_ws_bytes(int N, int H, int W);
+int ur_distort_field(const uint32_t* keys, const float* taps_y, int ry, const float* taps_x, int rx, float* field, int N, int H, int W, float m,
+                     float alpha, void* ws, size_t ws_bytes, ur_stream_t stream);
+size_t ur_distort_field_ws_bytes(int N, int H, int W);
+int ur_distort_warp(const uint8_t* x, const float* field, void* out, int N, int H, int W, int out_kind, ur_stream_t stream);
+
 /* ---- live per-kernel-family timing (HIP events on the launch stream) ------------------------------*/
 int ur_profile_enable(int on);
 /* writes a JSON object {family: {launches, ms, flops, bytes}} into buf (host); synchronises the events */

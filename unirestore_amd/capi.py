@@ -136,6 +136,13 @@ SIGNATURES = {
     "ur_jpeg_roundtrip_ws_bytes": (_SZ, [_I, _I, _I, _I]),
     "ur_resize_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _SZ, _P]),
     "ur_resize_u8_ws_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "ur_distort_shuffle": (_I, [_P, _P, _P, _I, _I, _I, _I, C.c_uint32, _P]),
+    "ur_distort_snow_layer": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F, _P]),
+    "ur_distort_snow": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _P, _SZ, _I, _P]),
+    "ur_distort_snow_ws_bytes": (_SZ, [_I, _I, _I]),
+    "ur_distort_field": (_I, [_P, _P, _I, _P, _I, _P, _I, _I, _I, _F, _F, _P, _SZ, _P]),
+    "ur_distort_field_ws_bytes": (_SZ, [_I, _I, _I]),
+    "ur_distort_warp": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "ur_profile_enable": (_I, [_I]),
     "ur_profile_report": (_I, [C.c_char_p, _SZ]),
 }

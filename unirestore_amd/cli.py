@@ -2,7 +2,8 @@
 `python -m unirestore_amd.cli restore --config CFG --input DIR_OR_LISTFILE --output DIR` for image files;
 `python -m unirestore_amd.cli corrupt --input DIR_OR_LISTFILE --output DIR --corruptions NAMES_OR_SUBSET` writes corrupted copies of
 clean images (no config); `python -m unirestore_amd.cli jpeg --input DIR_OR_LISTFILE --output DIR --quality 10,25,s3` writes what their
-JPEGs of those qualities decode to (no config).
+JPEGs of those qualities decode to (no config); `python -m unirestore_amd.cli distort --input DIR_OR_LISTFILE --output DIR --corruptions
+glass_blur,snow|all` is `corrupt` for glass blur, snow and elastic transform (unirestore_amd.distort).
 
 Resolves a LightningCLI-style YAML (the key schema of the reference's configs/*.yaml: `seed_everything`, `trainer.{accelerator,
 devices,precision}`, `model.class_path` + `init_args.model_kwargs.{frenc,cnet,tedit}`, `data.class_path` + `init_args`;
@@ -31,6 +32,7 @@ DATA_CLASSES = {"unirestore_amd.data.SyntheticImages": "unirestore_amd.data.Synt
                 "unirestore_amd.data.ImageListFiles": "unirestore_amd.data.ImageListFiles",
                 "unirestore_amd.data.CorruptedImageFiles": "unirestore_amd.data.CorruptedImageFiles",
                 "unirestore_amd.data.JpegImageFiles": "unirestore_amd.data.JpegImageFiles",
+                "unirestore_amd.data.DistortedImageFiles": "unirestore_amd.data.DistortedImageFiles",
                 "data.DatasetEngine": "unirestore_amd.data.SyntheticImages"}      # datasets are out of scope: synthetic stand-in
 PRECISIONS = {"bf16-mixed": "bf16", "bf16": "bf16", "bf16-true": "bf16", "16-mixed": "fp16", "16": "fp16", "16-true": "fp16",
               "fp16": "fp16"}
@@ -126,7 +128,7 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
              model=None) -> dict:
     """tasks: a list of task names - every batch is restored once and decoded for each of them (DiffUIE.forward_tasks).  PSNR / SSIM
     come from the "ir" output, so the list must hold "ir"; images_per_s counts input images.  model: a ready DiffUIE to use instead
-    of building the config's.  With data.CorruptedImageFiles the result also holds by_corruption ("fog/3" -> psnr, ssim, images)
+    of building the config's.  With data.CorruptedImageFiles (and data.DistortedImageFiles: "snow/3") the result also holds by_corruption ("fog/3" -> psnr, ssim, images)
     and skipped (the subset members that are not built); with data.JpegImageFiles it holds by_corruption ("jpeg/10", the quality);
     with either, resize = [lo, hi] when the data's resize-down / resize-back wrapper is on."""
     import torch
@@ -168,7 +170,7 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
     sizes = [shard_range(data.batch_size, q, world)[1] - shard_range(data.batch_size, q, world)[0] for q in range(world)]
     n_img, secs, finite = 0, 0.0, True
     # "fog/3" (data.JpegImageFiles: "jpeg/10", the quality) -> metric sums of its batches
-    by_corruption = {} if isinstance(data, (data_mod.CorruptedImageFiles, data_mod.JpegImageFiles)) else None
+    by_corruption = {} if isinstance(data, (data_mod.CorruptedImageFiles, data_mod.JpegImageFiles, data_mod.DistortedImageFiles)) else None
     for i, batch in enumerate(data.batches(rank, world, dev)):
         if max_batches is not None and i >= max_batches:
             break
@@ -400,6 +402,38 @@ def check_resize_arg(resize, minimum: int):
         raise ValueError(f"--{e}") from None
 
 
+def _write_degraded(degrade, paths, names, severity, seed, batch, resize, output):
+    """OUTPUT/<name>_<severity>/<stem>.png and pairs.txt for every name and path through degrade(hq, name, severity, seed, stems,
+    resize) (corrupt.degrade or distort.degrade) -> (the folders written, seconds)."""
+    import torch
+    from . import corrupt as cr
+    from . import imageio
+    dev = torch.device("cuda", torch.cuda.current_device())
+    sizes = [hw for _, hw in imageio.scan(paths)]
+    stems = [cr.stem_of(p) for p in paths]
+    sevs = [cr.draw_severity(seed, st) if severity == "mixed" else severity for st in stems]
+    groups = {}
+    for i, (hw, sev) in enumerate(zip(sizes, sevs)):
+        groups.setdefault((hw, sev), []).append(i)
+    t0, folders = time.perf_counter(), {}
+    for name in names:
+        for (hw, sev), idx in groups.items():
+            folder = os.path.join(output, f"{name}_{sev}")
+            os.makedirs(folder, exist_ok=True)
+            for s in range(0, len(idx), int(batch)):
+                cut = idx[s:s + int(batch)]
+                hq = torch.stack([imageio.load_u8(paths[i]) for i in cut]).to(dev)
+                lq = degrade(hq, name, sev, seed, [stems[i] for i in cut], resize).cpu()
+                for i, img in zip(cut, lq):
+                    imageio.save_u8(img, os.path.join(folder, stems[i] + ".png"))
+            folders.setdefault(folder, []).extend(idx)
+    for folder, idx in folders.items():
+        with open(os.path.join(folder, "pairs.txt"), "w") as f:
+            for i in sorted(idx):
+                f.write(f"{stems[i]}.png {os.path.abspath(paths[i])}\n")
+    return sorted(os.path.basename(d) for d in folders), time.perf_counter() - t0
+
+
 def check_corrupt_args(inp, output, corruptions, severity=3, batch=8, resize=None):
     """Everything about a `corrupt` call that can be wrong without looking at a GPU -> (clean image paths, corruption names, an
     integer severity or "mixed").  Every message names the offending argument.  resize: None, "LO,HI" or (lo, hi), checked only."""
@@ -442,35 +476,55 @@ def corrupt_files(inp, output, corruptions, severity=3, seed=42, batch=8, resize
     paths, names, severity = check_corrupt_args(inp, output, corruptions, severity, batch, resize)
     resize = check_resize_arg(resize, 32)
     from . import corrupt as cr
-    from . import imageio
     if not torch.cuda.is_available():
         raise RuntimeError("no GPU visible: the corruptions run on MI355X only (no CPU fallback)")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    sizes = [hw for _, hw in imageio.scan(paths)]
-    stems = [cr.stem_of(p) for p in paths]
-    sevs = [cr.draw_severity(seed, st) if severity == "mixed" else severity for st in stems]
-    groups = {}
-    for i, (hw, sev) in enumerate(zip(sizes, sevs)):
-        groups.setdefault((hw, sev), []).append(i)
-    t0, folders = time.perf_counter(), {}
-    for name in names:
-        for (hw, sev), idx in groups.items():
-            folder = os.path.join(output, f"{name}_{sev}")
-            os.makedirs(folder, exist_ok=True)
-            for s in range(0, len(idx), int(batch)):
-                cut = idx[s:s + int(batch)]
-                hq = torch.stack([imageio.load_u8(paths[i]) for i in cut]).to(dev)
-                lq = cr.degrade(hq, name, sev, seed, [stems[i] for i in cut], resize).cpu()
-                for i, img in zip(cut, lq):
-                    imageio.save_u8(img, os.path.join(folder, stems[i] + ".png"))
-            folders.setdefault(folder, []).extend(idx)
-    for folder, idx in folders.items():
-        with open(os.path.join(folder, "pairs.txt"), "w") as f:
-            for i in sorted(idx):
-                f.write(f"{stems[i]}.png {os.path.abspath(paths[i])}\n")
+    folders, seconds = _write_degraded(cr.degrade, paths, names, severity, seed, batch, resize, output)
     return dict(images=len(paths), corruptions=names, skipped=cr.skipped(corruptions), severity=severity, seed=seed,
-                folders=sorted(os.path.basename(d) for d in folders), output=output, seconds_total=time.perf_counter() - t0,
-                **({"resize": list(resize)} if resize is not None else {}))
+                folders=folders, output=output, seconds_total=seconds, **({"resize": list(resize)} if resize is not None else {}))
+
+
+def check_distort_args(inp, output, corruptions, severity=3, batch=8, resize=None):
+    """`check_corrupt_args` for a `distort` call: the names are unirestore_amd.distort's (glass_blur, snow, elastic_transform, all)."""
+    from . import corrupt as cr
+    from . import distort as ds
+    check_resize_arg(resize, 32)
+    if not corruptions:
+        raise ValueError("--corruptions: name at least one of " + ", ".join(ds.NAMES) + " or all")
+    try:
+        names = ds.expand(corruptions)
+    except ValueError as e:
+        raise ValueError(f"--corruptions {corruptions!r}: {e}") from None
+    if str(severity) != "mixed":
+        if str(severity) not in ("1", "2", "3", "4", "5"):
+            raise ValueError(f"--severity {severity!r}: choose 1..5 or mixed")
+        severity = int(severity)
+    if int(batch) < 1:
+        raise ValueError(f"--batch {batch}: must be >= 1")
+    if not inp or not os.path.exists(inp):
+        raise FileNotFoundError(f"--input {inp!r}: no such folder or list file")
+    if not output:
+        raise ValueError("--output: a folder for the corrupted PNGs is required")
+    if os.path.isdir(inp) and os.path.realpath(inp) == os.path.realpath(output):
+        raise ValueError(f"--output {output!r} is the --input folder")
+    try:
+        paths = cr.check_inputs(inp)
+    except ValueError as e:
+        raise ValueError(f"--input {e}") from None
+    return paths, names, severity
+
+
+def distort_files(inp, output, corruptions, severity=3, seed=42, batch=8, resize=None) -> dict:
+    """`corrupt_files` for glass_blur, snow and elastic_transform (unirestore_amd.distort): the same folders, pairs.txt and result,
+    a file's bytes depending on (seed, stem, name, severity) alone."""
+    import torch
+    paths, names, severity = check_distort_args(inp, output, corruptions, severity, batch, resize)
+    resize = check_resize_arg(resize, 32)
+    from . import distort as ds
+    if not torch.cuda.is_available():
+        raise RuntimeError("no GPU visible: the corruptions run on MI355X only (no CPU fallback)")
+    folders, seconds = _write_degraded(ds.degrade, paths, names, severity, seed, batch, resize, output)
+    return dict(images=len(paths), corruptions=names, skipped=[], severity=severity, seed=seed, folders=folders, output=output,
+                seconds_total=seconds, **({"resize": list(resize)} if resize is not None else {}))
 
 
 def check_jpeg_args(inp, output, quality, subsampling="4:2:0", batch=8, resize=None):
@@ -547,7 +601,7 @@ def jpeg_files(inp, output, quality, subsampling="4:2:0", batch=8, resize=None, 
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m unirestore_amd.cli")
-    ap.add_argument("command", choices=["validate", "print_config", "restore", "corrupt", "jpeg"])
+    ap.add_argument("command", choices=["validate", "print_config", "restore", "corrupt", "jpeg", "distort"])
     ap.add_argument("--config", default=None, help="validate / print_config / restore: the YAML config (required there)")
     ap.add_argument("--set", action="append", default=[], metavar="a.b.c=value", help="override a config key")
     ap.add_argument("--hf-root", default=None, help="folder with unet/ and vae/ diffusion_pytorch_model.safetensors (sd-turbo)")
@@ -571,11 +625,12 @@ def main(argv=None):
     ap.add_argument("--samples", type=int, default=1, metavar="K",
                     help="restore: K restorations of every input, written as <stem>.s<k>.png (K > 1 needs --noise image)")
     ap.add_argument("--corruptions", default=None, metavar="fog,motion_blur|SUBSET",
-                    help="corrupt: corruption names and / or subsets (common, validation, all, noise, blur, weather, digital)")
-    ap.add_argument("--severity", default="3", help="corrupt: 1..5, or mixed for the reference's per-image draw")
-    ap.add_argument("--seed", type=int, default=42, help="corrupt: with a file's stem, the seed of all its randomness; jpeg: of the --resize draw")
+                    help="corrupt: corruption names and / or subsets (common, validation, all, noise, blur, weather, digital); "
+                         "distort: glass_blur, snow, elastic_transform or all")
+    ap.add_argument("--severity", default="3", help="corrupt / distort: 1..5, or mixed for the reference's per-image draw")
+    ap.add_argument("--seed", type=int, default=42, help="corrupt / distort: with a file's stem, the seed of all its randomness; jpeg: of the --resize draw")
     ap.add_argument("--resize", default=None, metavar="LO,HI",
-                    help="corrupt / jpeg: degrade inside the reference's wrapper - resize every image so that its short edge is an integer "
+                    help="corrupt / distort / jpeg: degrade inside the reference's wrapper - resize every image so that its short edge is an integer "
                          "drawn from [LO, HI) by (seed, stem), degrade at that size, resize back (the reference draws from [128, 512))")
     ap.add_argument("--quality", default=None, metavar="10,25,s3", help="jpeg: qualities 1..100 and / or s1..s5 (the reference's severities)")
     ap.add_argument("--subsampling", default="4:2:0", help="jpeg: 4:2:0 (Pillow's and the reference's default) or 4:4:4")
@@ -586,6 +641,13 @@ def main(argv=None):
         except (ValueError, FileNotFoundError) as e:
             ap.error(str(e))
         print(json.dumps(jpeg_files(a.input, a.output, a.quality, a.subsampling, a.batch, a.resize, a.seed)))
+        return 0
+    if a.command == "distort":
+        try:
+            check_distort_args(a.input, a.output, a.corruptions, a.severity, a.batch, a.resize)
+        except (ValueError, FileNotFoundError, NotImplementedError) as e:
+            ap.error(str(e))
+        print(json.dumps(distort_files(a.input, a.output, a.corruptions, a.severity, a.seed, a.batch, a.resize)))
         return 0
     if a.command == "corrupt":
         try:

@@ -60,7 +60,8 @@ def motion_angle(seed: int, stem: str) -> float:
 
 def check_name(name: str) -> str:
     if name in UNBUILT:
-        hint = "; JPEG compression is a module of its own: unirestore_amd.jpeg.roundtrip, `cli jpeg`" if name == "jpeg_compression" else ""
+        hint = "; JPEG compression is a module of its own: unirestore_amd.jpeg.roundtrip, `cli jpeg`" if name == "jpeg_compression" else \
+            "; it is built in a module of its own: unirestore_amd.distort.distort, `cli distort`" if name in ("glass_blur", "snow", "elastic_transform") else ""
         raise NotImplementedError(f"corruption {name!r} is not built (built: {', '.join(NAMES)}){hint}")
     if name not in NAMES:
         raise ValueError(f"unknown corruption {name!r}: choose from {', '.join(NAMES)}")

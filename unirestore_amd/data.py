@@ -1,6 +1,7 @@
 """Inputs for the config entry points: seeded synthetic images, `ImageListFiles`, real pairs from the reference's `lq hq label`
 list files, `CorruptedImageFiles`, clean images corrupted on the GPU (unirestore_amd.corrupt), and `JpegImageFiles`, clean images
-JPEG-compressed on the GPU at a list of qualities (unirestore_amd.jpeg).
+JPEG-compressed on the GPU at a list of qualities (unirestore_amd.jpeg), and `DistortedImageFiles`, CorruptedImageFiles for glass blur,
+snow and elastic transform (unirestore_amd.distort).
 
 `SyntheticImages` yields the evaluator's batch tuple `(lq, hq, gt, fname, task)` (reference
 src/core/base/eval_image_restoration.py:56) from seeded random images: hq = torch.rand (what the reference's own smoke
@@ -113,15 +114,20 @@ class CorruptedImageFiles:
     (lo >= 32) turns on the reference's resize-down / resize-back wrapper (corrupt.degrade): every image's short edge is drawn
     from [lo, hi) by (seed, stem) as well, lq keeps hq's shape; the reference's own range is [resolution // 4, resolution)."""
 
+    _module = "corrupt"                            # the planner whose expand / degrade this class uses (DistortedImageFiles: distort)
+
     def __init__(self, source: str, corruptions="common", severity=3, batch_size: int = 8, task: str = "ir", seed: int = 42,
                  num_batches: int = None, resize=None):
+        import importlib
         from . import corrupt
         from . import resize as rz
+        self._planner = importlib.import_module(f"{__package__}.{self._module}")
         self.resize = None if resize is None else rz.check_range(resize, 32)
         self.source, self.batch_size, self.task, self.seed, self.num_batches = source, int(batch_size), task, int(seed), num_batches
         if self.batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
-        self.names, self.skipped = corrupt.expand(corruptions), corrupt.skipped(corruptions)
+        self.names = self._planner.expand(corruptions)
+        self.skipped = corrupt.skipped(corruptions) if self._planner is corrupt else []
         self.severity = severity if severity == "mixed" else corrupt.check_severity(severity)
         self.paths = corrupt.check_inputs(source)
         self.last = None
@@ -150,9 +156,21 @@ class CorruptedImageFiles:
         for name, sev, idx in self._plan():
             stems = [corrupt.stem_of(self.paths[i]) for i in idx]
             hq = torch.stack([load_u8(self.paths[i]) for i in idx]).to(device)
-            lq = corrupt.degrade(hq, name, sev, self.seed, stems, self.resize)
+            lq = self._planner.degrade(hq, name, sev, self.seed, stems, self.resize)
             self.last = (name, sev)
             yield nchw(lq), nchw(hq), None, stems, self.task
+
+
+class DistortedImageFiles(CorruptedImageFiles):
+    """CorruptedImageFiles for glass blur, snow and elastic transform (unirestore_amd.distort; `data.class_path:
+    unirestore_amd.data.DistortedImageFiles`): `corruptions` is "all", a name, or a comma-separated string / list of names of
+    distort.NAMES; everything else - `source`, `severity`, `seed`, `resize`, the grouping, what is yielded and `last` - is the base
+    class's, with distort.degrade in the place of corrupt.degrade.  `skipped` is empty: a name that is not built is refused."""
+    _module = "distort"
+
+    def __init__(self, source: str, corruptions="all", severity=3, batch_size: int = 8, task: str = "ir", seed: int = 42,
+                 num_batches: int = None, resize=None):
+        super().__init__(source, corruptions, severity, batch_size, task, seed, num_batches, resize)
 
 
 class JpegImageFiles:

@@ -916,6 +916,96 @@ def resize_u8(x, size, xaxis, yaxis, out=None):
     return out
 
 
+# ---- glass blur, snow and elastic transform (csrc/distort.hip; the specification is the ur_distort_* comment in the header; the
+# planner is unirestore_amd.distort) --------------------------------------------------------------------------------------------
+def _distort_field(who: str, f, shape, dev):
+    if not isinstance(f, torch.Tensor) or f.dtype != torch.float32 or tuple(f.shape) != tuple(shape) or not f.is_contiguous() or f.device != dev:
+        raise ValueError(f"{who}: the field must be a contiguous fp32 tensor {tuple(shape)} on {dev}, got "
+                         f"{getattr(f, 'dtype', type(f))} {tuple(getattr(f, 'shape', ()))}")
+    return f
+
+
+def _distort_shape(who: str, n, h, w_):
+    if any(isinstance(v, bool) or not hasattr(v, "__index__") for v in (n, h, w_)) or n < 1 or h < 32 or w_ < 32:
+        raise ValueError(f"{who}: needs integers N >= 1 and H, W >= 32, got {(n, h, w_)!r}")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def distort_shuffle(x, keys_dev, delta: int, draw: int):
+    """One iteration of glass blur's local shuffle, u8 -> u8: every interior pixel takes the pixel at (y + dy, x + dx), dy / dx
+    keyed integers in [-delta, delta) of draws `draw` / `draw + 1`; delta in 1..4."""
+    check_u8_images("distort_shuffle", x)
+    n, h, w_, _ = x.shape
+    _corrupt_table("distort_shuffle: keys", keys_dev, torch.int32, 2 * n)
+    if isinstance(delta, bool) or not hasattr(delta, "__index__") or not 1 <= delta <= 4:
+        raise ValueError(f"distort_shuffle: delta must be an integer in [1, 4], got {delta!r}")
+    if isinstance(draw, bool) or not hasattr(draw, "__index__") or not 0 <= draw < (1 << 32) - 1:
+        raise ValueError(f"distort_shuffle: draw = {draw!r} must be an integer in [0, 2^32 - 1)")
+    out = torch.empty_like(x)
+    check(lib.ur_distort_shuffle(x.data_ptr(), keys_dev.data_ptr(), out.data_ptr(), n, h, w_, int(delta), int(draw), _stream()))
+    return out
+
+
+def distort_snow_layer(keys_dev, n: int, h: int, w_: int, geometry, loc: float, scale: float, thr: float):
+    """The snow layer fp32 [N, oh, ow]: the keyed normal field loc + scale n of an H x W image, its crop geometry = (top, left, ch,
+    cw, oh, ow) (distort.snow_geometry) enlarged bilinearly to oh x ow, values < thr zeroed, the rest clamped to [0, 1]."""
+    dev = _distort_shape("distort_snow_layer", n, h, w_)
+    _corrupt_table("distort_snow_layer: keys", keys_dev, torch.int32, 2 * n)
+    if len(geometry) != 6 or any(isinstance(v, bool) or not hasattr(v, "__index__") for v in geometry):
+        raise ValueError(f"distort_snow_layer: geometry must be six integers (top, left, ch, cw, oh, ow), got {geometry!r}")
+    top, left, ch, cw, oh, ow = (int(v) for v in geometry)
+    if oh < h or ow < w_:
+        raise ValueError(f"distort_snow_layer: the enlarged layer {oh} x {ow} must cover the image {h} x {w_}")
+    field = torch.empty((n, oh, ow), dtype=torch.float32, device=dev)
+    check(lib.ur_distort_snow_layer(keys_dev.data_ptr(), field.data_ptr(), n, h, w_, top, left, ch, cw, oh, ow, float(loc), float(scale),
+                                    float(thr), _stream()))
+    return field
+
+
+def distort_snow(x, field, taps, keep: float, out_kind=0):
+    """Snow from its layer: the motion blur of `field` fp32 [N, oh, ow] by the per-image tap lists int32 [N, T, 3]
+    (corrupt.pack_taps), rounded to bytes, added to the whitened image with its own 180-degree rotation."""
+    check_u8_images("distort_snow", x)
+    n, h, w_, _ = x.shape
+    if not isinstance(field, torch.Tensor) or field.ndim != 3 or field.shape[1] < h or field.shape[2] < w_:
+        raise ValueError(f"distort_snow: the field must be fp32 [{n}, oh >= {h}, ow >= {w_}], got {tuple(getattr(field, 'shape', ()))}")
+    _distort_field("distort_snow", field, (n, field.shape[1], field.shape[2]), x.device)
+    _corrupt_table("distort_snow: taps", taps, torch.int32)
+    if taps.ndim != 3 or taps.shape[0] != n or taps.shape[2] != 3 or taps.shape[1] > 64:
+        raise ValueError(f"distort_snow: taps must be [{n}, T <= 64, 3], got {tuple(taps.shape)}")
+    out = _corrupt_out(x, out_kind)
+    ws, nbytes = _corrupt_ws(x, lib.ur_distort_snow_ws_bytes(n, h, w_))
+    check(lib.ur_distort_snow(x.data_ptr(), field.data_ptr(), taps.data_ptr(), taps.shape[1], out.data_ptr(), n, h, w_, field.shape[1],
+                              field.shape[2], float(keep), ws.data_ptr(), nbytes, out_kind, _stream()))
+    return out
+
+
+def distort_field(keys_dev, n: int, h: int, w_: int, taps_y, taps_x, m: float, alpha: float):
+    """The elastic displacement field fp32 [N, 2, H, W] (dy, dx): keyed uniforms m (2u - 1) smoothed by the separable filter taps_y
+    (along the rows' axis) / taps_x (device fp32, odd lengths) with a reflect border, times alpha."""
+    dev = _distort_shape("distort_field", n, h, w_)
+    _corrupt_table("distort_field: keys", keys_dev, torch.int32, 2 * n)
+    for name, t in (("taps_y", taps_y), ("taps_x", taps_x)):
+        _corrupt_table(f"distort_field: {name}", t, torch.float32)
+        if t.numel() % 2 != 1:
+            raise ValueError(f"distort_field: {name} needs an odd number of taps, got {t.numel()}")
+    field = torch.empty((n, 2, h, w_), dtype=torch.float32, device=dev)
+    ws, nbytes = _corrupt_ws(field, lib.ur_distort_field_ws_bytes(n, h, w_))
+    check(lib.ur_distort_field(keys_dev.data_ptr(), taps_y.data_ptr(), taps_y.numel() // 2, taps_x.data_ptr(), taps_x.numel() // 2,
+                               field.data_ptr(), n, h, w_, float(m), float(alpha), ws.data_ptr(), nbytes, _stream()))
+    return field
+
+
+def distort_warp(x, field, out_kind=0):
+    """x sampled bilinearly at (y + field[n, 0], x + field[n, 1]), indices reflected at the edges (map_coordinates' "reflect")."""
+    check_u8_images("distort_warp", x)
+    n, h, w_, _ = x.shape
+    _distort_field("distort_warp", field, (n, 2, h, w_), x.device)
+    out = _corrupt_out(x, out_kind)
+    check(lib.ur_distort_warp(x.data_ptr(), field.data_ptr(), out.data_ptr(), n, h, w_, out_kind, _stream()))
+    return out
+
+
 def ddim_step_(zt, zt_bf16, eps_f32, clat, c_x, c_e):
     cp = zt.shape[-1]
     check(lib.ur_ddim_step(zt.data_ptr(), eps_f32.data_ptr(), eps_f32.shape[-1], zt_bf16.data_ptr(), zt.numel() // cp, clat, cp,
