@@ -141,6 +141,23 @@ def test_check_range():
         rz.check_range("15,96", 16)
 
 
+def test_per_image_and_the_sizes_the_wrapper_draws():
+    assert rz.per_image("who", 3, 7, None) == ([7, 7, 7], ["", "", ""])
+    assert rz.per_image("who", 2, np.int64(7), ("a", "b")) == ([7, 7], ["a", "b"])
+    seeds, stems = [5, 6, 7], ["p", "q", "r"]
+    assert rz.per_image("who", 3, seeds, stems) == (seeds, stems) and rz.per_image("who", 3, iter(seeds), iter(stems)) == (seeds, stems)
+    for bad in ((3, [5, 6], stems), (3, seeds, ["p", "q"]), (2, seeds, None), (3, 5, ["p"]), (1, [], None)):
+        with pytest.raises(ValueError, match=r"jpeg\.degrade: \d images but \d seeds and \d stems"):
+            rz.per_image("jpeg.degrade", *bad)
+    # what `inside` hands to `around`: every image's own draw, whatever the batch around it
+    for h, w in ((40, 32), (32, 48)):
+        sizes = rz.drawn_sizes(h, w, seeds, stems, 32, 40)
+        assert sizes == [rz.short_edge_size(h, w, rz.draw_short_edge(s, t, 32, 40)) for s, t in zip(seeds, stems)]
+        assert all(min(s) == rz.draw_short_edge(sd, st, 32, 40) for s, sd, st in zip(sizes, seeds, stems)) and len(set(sizes)) == 3
+        assert rz.drawn_sizes(h, w, seeds[1:2], stems[1:2], 32, 40) == sizes[1:2]
+    assert rz.drawn_sizes(40, 32, seeds, stems, 32, 40)[2] == (40, 32)                            # a draw of the short side: no resize
+
+
 def test_c_abi_refuses_wrong_arguments_before_the_gpu():
     from unirestore_amd import capi
     size = capi.lib.ur_resize_u8_ws_bytes

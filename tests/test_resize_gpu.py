@@ -1,5 +1,5 @@
 """The resize kernels (csrc/resize.hip) against the numpy restatement of resize_reference.py, byte for byte, and the layers above them
-(ops.resize_u8, resize.resize_u8, resize.around, corrupt.degrade, jpeg.degrade, the two datasets, cli.validate, cli corrupt / jpeg).
+(ops.resize_u8, resize.resize_u8, resize.around, corrupt.degrade, distort.degrade, jpeg.degrade, the two datasets, cli.validate, cli corrupt / jpeg).
 The cases are resize_cases.py; test_resize_cpu.py holds the restatement against torch's CPU kernel.  Every launch goes through the C
 ABI on guarded buffers: guards, the input and the tables untouched, and a second launch into a dirtied output and a dirtied
 workspace bit-identical (nothing in the workspace is read before it is written)."""
@@ -207,6 +207,30 @@ def test_jpeg_degrade_equals_the_composition_by_hand():
     assert got.shape == dev.shape and torch.equal(got.cpu(), want), int((got.cpu() != want).sum())
     assert torch.equal(jpeg.degrade(dev[1:2].contiguous(), "25", seeds[1:2], stems[1:2], (16, 96), "4:2:0"), got[1:2])
     assert not torch.equal(jpeg.degrade(dev, 25, seeds, stems, (16, 96), "4:4:4"), got)
+
+
+@pytest.mark.parametrize("name", ("glass_blur", "snow", "elastic_transform"))
+def test_distort_degrade_equals_the_composition_by_hand(name):
+    """Both sides run the same resize and distortion kernels on the same bytes: equal, not close.  40 x 32 with [32, 40) is the
+    smallest shape with all three situations in one batch: a draw equal to the short side (both resizes are copies), a draw above
+    it (a real resize: 32 is the smallest side distort takes, so it enlarges), and groups of different resized shapes."""
+    from unirestore_amd import distort as ds
+    from unirestore_amd import resize as rz
+    dev = torch.randint(0, 256, (3, 40, 32, 3), generator=torch.Generator().manual_seed(31), dtype=torch.uint8).cuda()
+    seeds, stems = [5, 6, 7], ["p", "q", "r"]                                        # these draw the short edges 38, 39 and 32
+    edges = [rz.draw_short_edge(s, t, 32, 40) for s, t in zip(seeds, stems)]
+    assert edges[2] == 32 and len(set(edges)) == 3, edges
+    got = ds.degrade(dev, name, 3, seeds, stems, resize=(32, 40))
+    want = []
+    for i, e in enumerate(edges):
+        small = rz.resize_u8(dev[i:i + 1].contiguous(), rz.short_edge_size(40, 32, e))
+        assert (e > 32) == (small.shape != dev[i:i + 1].shape)
+        want.append(rz.resize_u8(ds.distort(small, name, 3, seeds[i:i + 1], stems[i:i + 1]), (40, 32)))
+    want = torch.cat(want)
+    assert got.dtype == torch.uint8 and got.shape == dev.shape and got.is_contiguous()
+    assert torch.equal(got, want), (name, int((got != want).sum()))
+    assert torch.equal(got[2:3], ds.distort(dev[2:3].contiguous(), name, 3, seeds[2:], stems[2:]))   # the copies change nothing
+    assert torch.equal(ds.degrade(dev, name, 3, seeds, stems), ds.distort(dev, name, 3, seeds, stems))   # resize=None: distort itself
 
 
 SIZES = [("a0", (96, 128)), ("a1", (64, 80)), ("b0", (96, 128)), ("a2", (64, 80)), ("a3", (96, 128))]

@@ -1,9 +1,9 @@
 """Config entry point: `python -m unirestore_amd.cli validate --config configs/<file>.yaml [--set a.b.c=value ...]`, and
-`python -m unirestore_amd.cli restore --config CFG --input DIR_OR_LISTFILE --output DIR` for image files;
-`python -m unirestore_amd.cli corrupt --input DIR_OR_LISTFILE --output DIR --corruptions NAMES_OR_SUBSET` writes corrupted copies of
-clean images (no config); `python -m unirestore_amd.cli jpeg --input DIR_OR_LISTFILE --output DIR --quality 10,25,s3` writes what their
-JPEGs of those qualities decode to (no config); `python -m unirestore_amd.cli distort --input DIR_OR_LISTFILE --output DIR --corruptions
-glass_blur,snow|all` is `corrupt` for glass blur, snow and elastic transform (unirestore_amd.distort).
+`python -m unirestore_amd.cli restore --config CFG --input DIR_OR_LISTFILE --output DIR` for image files.  Three commands take no
+config and write degraded copies of clean images, `python -m unirestore_amd.cli COMMAND --input DIR_OR_LISTFILE --output DIR` with
+`corrupt --corruptions NAMES_OR_SUBSET` (unirestore_amd.corrupt), `distort --corruptions glass_blur,snow|all` (glass blur, snow and
+elastic transform: unirestore_amd.distort) or `jpeg --quality 10,25,s3` (what the images' JPEGs of those qualities decode to):
+one argument check (`_check_file_args`), one writer (`_write_degraded`) and one dispatch in `main` serve all three.
 
 Resolves a LightningCLI-style YAML (the key schema of the reference's configs/*.yaml: `seed_everything`, `trainer.{accelerator,
 devices,precision}`, `model.class_path` + `init_args.model_kwargs.{frenc,cnet,tedit}`, `data.class_path` + `init_args`;
@@ -124,6 +124,42 @@ def resolve(cfg: dict, allow_16bit: bool = False) -> dict:
                 data_class=DATA_CLASSES[dcp])
 
 
+def _ranks():
+    """(rank, world size, local rank) of this process under torch.distributed.run; (0, 1, 0) without it."""
+    return int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
+
+
+def _start(r: dict, hf_root, random_init, model, **caller_args):
+    """What `validate` and `restore` do before their loops: this rank's device, the process group, the caller with the config's
+    model (or `model`), seeded random weights on rank 0 when no checkpoint is reachable, the weights broadcast, `refresh`.
+    r = resolve(cfg) -> (rank, world, device, torch.distributed or None, the LitUniFIE)."""
+    import torch
+    rank, world, local = _ranks()
+    if not torch.cuda.is_available():
+        raise RuntimeError("no GPU visible: the restoration path runs on MI355X only (no CPU fallback)")
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    dist = None
+    if world > 1:
+        import torch.distributed as dist
+        dist.init_process_group("nccl", device_id=dev)
+    torch.manual_seed(r["seed"])
+    from . import runner
+    from .dist import broadcast_weights_sharded
+    lit = runner.LitUniFIE(r["model_kwargs"], dtype=r["dtype"], hf_root=hf_root, model=model, **caller_args)
+    no_ckpt = not any((r["model_kwargs"].get(k) or {}).get("ckpt_path") for k in ("frenc", "cnet", "tedit")) and not hf_root
+    if model is not None:
+        model.set_dtype(r["dtype"])
+        model.set_color_fix((r["model_kwargs"].get("cnet") or {}).get("color_fix"))
+    elif no_ckpt and random_init and rank == 0:             # no checkpoint reachable: seeded random weights of the architecture
+        from .init import init_random_
+        init_random_(lit.model, r["seed"], "cpu")
+    if world > 1:
+        broadcast_weights_sharded(lit.model.to(dev), src=0)
+    lit.model.refresh()
+    return rank, world, dev, dist, lit
+
+
 def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_16bit=False, metrics_device="cpu", tasks=None,
              model=None) -> dict:
     """tasks: a list of task names - every batch is restored once and decoded for each of them (DiffUIE.forward_tasks).  PSNR / SSIM
@@ -138,39 +174,17 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
         if "ir" not in tasks:
             raise ValueError(f"--tasks {','.join(tasks)}: PSNR / SSIM are computed on the 'ir' output; add 'ir' to the list "
                              "(it is not added silently)")
-    rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
-    if not torch.cuda.is_available():
-        raise RuntimeError("no GPU visible: the restoration path runs on MI355X only (no CPU fallback)")
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-    dist = None
-    if world > 1:
-        import torch.distributed as dist
-        dist.init_process_group("nccl", device_id=dev)
-    torch.manual_seed(r["seed"])
-    from . import runner
     from . import data as data_mod
-    from .dist import all_gather_images, broadcast_weights_sharded, shard_range
-    lit = runner.LitUniFIE(r["model_kwargs"], dtype=r["dtype"], hf_root=hf_root, metrics_device=metrics_device, model=model,
-                           **r["caller_args"])
-    no_ckpt = not any((r["model_kwargs"].get(k) or {}).get("ckpt_path") for k in ("frenc", "cnet", "tedit")) and not hf_root
-    if model is not None:
-        model.set_dtype(r["dtype"])
-        model.set_color_fix((r["model_kwargs"].get("cnet") or {}).get("color_fix"))
-    elif no_ckpt and random_init:                         # no checkpoint reachable: seeded random weights of the architecture
-        from .init import init_random_
-        if rank == 0:
-            init_random_(lit.model, r["seed"], "cpu")
-    if world > 1:
-        broadcast_weights_sharded(lit.model.to(dev), src=0)
-    lit.model.refresh()
+    from .dist import all_gather_images, shard_range
+    rank, world, dev, dist, lit = _start(r, hf_root, random_init, model, metrics_device=metrics_device, **r["caller_args"])
     data = getattr(data_mod, r["data_class"].rsplit(".", 1)[1])(**r["data_args"])
     if data.batch_size < world:
         raise ValueError(f"data batch_size {data.batch_size} < world size {world}: every rank needs at least one image per batch")
     sizes = [shard_range(data.batch_size, q, world)[1] - shard_range(data.batch_size, q, world)[0] for q in range(world)]
     n_img, secs, finite = 0, 0.0, True
-    # "fog/3" (data.JpegImageFiles: "jpeg/10", the quality) -> metric sums of its batches
-    by_corruption = {} if isinstance(data, (data_mod.CorruptedImageFiles, data_mod.JpegImageFiles, data_mod.DistortedImageFiles)) else None
+    # a dataset of files degraded on the GPU says what its last batch was: "fog/3" (data.JpegImageFiles: "jpeg/10", the quality)
+    # -> metric sums of its batches
+    by_corruption = {} if hasattr(data, "last") else None
     for i, batch in enumerate(data.batches(rank, world, dev)):
         if max_batches is not None and i >= max_batches:
             break
@@ -205,7 +219,7 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
     if by_corruption is not None:
         res["by_corruption"] = {k: dict(psnr=float(v["psnr"]) / v["images"], ssim=float(v["ssim"]) / v["images"], images=int(v["images"]))
                                 for k, v in by_corruption.items()}
-        if isinstance(data, data_mod.CorruptedImageFiles):
+        if hasattr(data, "skipped"):
             res["skipped"] = list(data.skipped)
         if data.resize is not None:
             res["resize"] = list(data.resize)
@@ -315,31 +329,10 @@ def restore(cfg: dict, inp, output, task=None, tasks=None, batch=8, hf_root=None
     sizes = [hw for _, hw in imageio.scan(paths) for _k in range(samples)]
     units = plan_samples(paths, samples)                   # what the plan's indices mean: (path, stem, sample)
     paths = [u[0] for u in units]
-    rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
+    rank, world, _ = _ranks()
     plan = imageio.plan_batches(sizes, int(batch), rank, world)
-    if not torch.cuda.is_available():
-        raise RuntimeError("no GPU visible: the restoration path runs on MI355X only (no CPU fallback)")
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-    dist = None
-    if world > 1:
-        import torch.distributed as dist
-        dist.init_process_group("nccl", device_id=dev)
-    torch.manual_seed(r["seed"])
-    from . import runner
-    from .dist import broadcast_weights_sharded
-    lit = runner.LitUniFIE(r["model_kwargs"], dtype=r["dtype"], hf_root=hf_root, model=model)
-    no_ckpt = not any((r["model_kwargs"].get(k) or {}).get("ckpt_path") for k in ("frenc", "cnet", "tedit")) and not hf_root
-    if model is not None:
-        model.set_dtype(r["dtype"])
-        model.set_color_fix((r["model_kwargs"].get("cnet") or {}).get("color_fix"))
-    elif no_ckpt and random_init and rank == 0:             # no checkpoint reachable: seeded random weights of the architecture
-        from .init import init_random_
-        init_random_(lit.model, r["seed"], "cpu")
-    if world > 1:
-        broadcast_weights_sharded(lit.model.to(dev), src=0)
+    rank, world, dev, dist, lit = _start(r, hf_root, random_init, model)
     model = lit.model
-    model.refresh()
     out_dirs = {t: os.path.join(output, t) for t in which} if isinstance(which, tuple) else {which: output}
     for d in out_dirs.values():
         os.makedirs(d, exist_ok=True)
@@ -402,68 +395,110 @@ def check_resize_arg(resize, minimum: int):
         raise ValueError(f"--{e}") from None
 
 
-def _write_degraded(degrade, paths, names, severity, seed, batch, resize, output):
-    """OUTPUT/<name>_<severity>/<stem>.png and pairs.txt for every name and path through degrade(hq, name, severity, seed, stems,
-    resize) (corrupt.degrade or distort.degrade) -> (the folders written, seconds)."""
+def _check_file_args(inp, output, batch, what: str):
+    """What the corrupt, distort and jpeg commands check alike: --batch, --input and --output, a folder for `what` -> the clean
+    image paths.  Every message names the offending argument."""
+    from . import corrupt as cr
+    if int(batch) < 1:
+        raise ValueError(f"--batch {batch}: must be >= 1")
+    if not inp or not os.path.exists(inp):
+        raise FileNotFoundError(f"--input {inp!r}: no such folder or list file")
+    if not output:
+        raise ValueError(f"--output: a folder for the {what} is required")
+    if os.path.isdir(inp) and os.path.realpath(inp) == os.path.realpath(output):
+        raise ValueError(f"--output {output!r} is the --input folder")
+    try:
+        return cr.check_inputs(inp)
+    except ValueError as e:
+        raise ValueError(f"--input {e}") from None
+
+
+def _check_severity_arg(severity):
+    """--severity -> an integer 1..5 or "mixed" as it was given."""
+    if str(severity) == "mixed":
+        return severity
+    if str(severity) not in ("1", "2", "3", "4", "5"):
+        raise ValueError(f"--severity {severity!r}: choose 1..5 or mixed")
+    return int(severity)
+
+
+def _write_degraded(degrade, paths, sizes, jobs, batch, output):
+    """OUTPUT/<folder>/<stem>.png and OUTPUT/<folder>/pairs.txt (one `lq hq` line per file, in input order).  jobs[i] lists what
+    becomes of paths[i], of size sizes[i], as (folder name, key) pairs, equally many for every file; the files are grouped by
+    (shape, folder, key), the groups cut into batches, and a batch is degrade(hq, key, stems).  -> (the folder names in the
+    order they were begun, seconds)."""
     import torch
     from . import corrupt as cr
     from . import imageio
     dev = torch.device("cuda", torch.cuda.current_device())
-    sizes = [hw for _, hw in imageio.scan(paths)]
     stems = [cr.stem_of(p) for p in paths]
-    sevs = [cr.draw_severity(seed, st) if severity == "mixed" else severity for st in stems]
     groups = {}
-    for i, (hw, sev) in enumerate(zip(sizes, sevs)):
-        groups.setdefault((hw, sev), []).append(i)
+    for k in range(len(jobs[0])):                         # job by job, a job's groups in the order of their first file
+        for i, hw in enumerate(sizes):
+            groups.setdefault((hw, *jobs[i][k]), []).append(i)
     t0, folders = time.perf_counter(), {}
-    for name in names:
-        for (hw, sev), idx in groups.items():
-            folder = os.path.join(output, f"{name}_{sev}")
-            os.makedirs(folder, exist_ok=True)
-            for s in range(0, len(idx), int(batch)):
-                cut = idx[s:s + int(batch)]
-                hq = torch.stack([imageio.load_u8(paths[i]) for i in cut]).to(dev)
-                lq = degrade(hq, name, sev, seed, [stems[i] for i in cut], resize).cpu()
-                for i, img in zip(cut, lq):
-                    imageio.save_u8(img, os.path.join(folder, stems[i] + ".png"))
-            folders.setdefault(folder, []).extend(idx)
+    for (_, name, key), idx in groups.items():
+        folder = os.path.join(output, name)
+        os.makedirs(folder, exist_ok=True)
+        for s in range(0, len(idx), int(batch)):
+            cut = idx[s:s + int(batch)]
+            hq = torch.stack([imageio.load_u8(paths[i]) for i in cut]).to(dev)
+            lq = degrade(hq, key, [stems[i] for i in cut]).cpu()
+            for i, img in zip(cut, lq):
+                imageio.save_u8(img, os.path.join(folder, stems[i] + ".png"))
+        folders.setdefault(folder, []).extend(idx)
     for folder, idx in folders.items():
         with open(os.path.join(folder, "pairs.txt"), "w") as f:
             for i in sorted(idx):
                 f.write(f"{stems[i]}.png {os.path.abspath(paths[i])}\n")
-    return sorted(os.path.basename(d) for d in folders), time.perf_counter() - t0
+    return [os.path.basename(d) for d in folders], time.perf_counter() - t0
+
+
+def _check_corruption_args(planner, hint, inp, output, corruptions, severity, batch, resize):
+    """`check_corrupt_args` / `check_distort_args`: planner is unirestore_amd.corrupt or .distort, hint what --corruptions may name."""
+    check_resize_arg(resize, 32)
+    if not corruptions:
+        raise ValueError("--corruptions: name at least one " + hint)
+    try:
+        names = planner.expand(corruptions)
+    except ValueError as e:
+        raise ValueError(f"--corruptions {corruptions!r}: {e}") from None
+    if "clean" in names:                                  # (corrupt only: distort.expand knows no such name)
+        raise ValueError("--corruptions: 'clean' writes nothing new; name corruptions only")
+    severity = _check_severity_arg(severity)
+    return _check_file_args(inp, output, batch, "corrupted PNGs"), names, severity
 
 
 def check_corrupt_args(inp, output, corruptions, severity=3, batch=8, resize=None):
     """Everything about a `corrupt` call that can be wrong without looking at a GPU -> (clean image paths, corruption names, an
     integer severity or "mixed").  Every message names the offending argument.  resize: None, "LO,HI" or (lo, hi), checked only."""
     from . import corrupt as cr
-    check_resize_arg(resize, 32)
-    if not corruptions:
-        raise ValueError("--corruptions: name at least one corruption or subset (" + ", ".join(sorted(cr.SUBSETS)) + ")")
-    try:
-        names = cr.expand(corruptions)
-    except ValueError as e:
-        raise ValueError(f"--corruptions {corruptions!r}: {e}") from None
-    if "clean" in names:
-        raise ValueError("--corruptions: 'clean' writes nothing new; name corruptions only")
-    if str(severity) != "mixed":
-        if str(severity) not in ("1", "2", "3", "4", "5"):
-            raise ValueError(f"--severity {severity!r}: choose 1..5 or mixed")
-        severity = int(severity)
-    if int(batch) < 1:
-        raise ValueError(f"--batch {batch}: must be >= 1")
-    if not inp or not os.path.exists(inp):
-        raise FileNotFoundError(f"--input {inp!r}: no such folder or list file")
-    if not output:
-        raise ValueError("--output: a folder for the corrupted PNGs is required")
-    if os.path.isdir(inp) and os.path.realpath(inp) == os.path.realpath(output):
-        raise ValueError(f"--output {output!r} is the --input folder")
-    try:
-        paths = cr.check_inputs(inp)
-    except ValueError as e:
-        raise ValueError(f"--input {e}") from None
-    return paths, names, severity
+    return _check_corruption_args(cr, "corruption or subset (" + ", ".join(sorted(cr.SUBSETS)) + ")", inp, output, corruptions, severity,
+                                  batch, resize)
+
+
+def check_distort_args(inp, output, corruptions, severity=3, batch=8, resize=None):
+    """`check_corrupt_args` for a `distort` call: the names are unirestore_amd.distort's (glass_blur, snow, elastic_transform, all)."""
+    from . import distort as ds
+    return _check_corruption_args(ds, "of " + ", ".join(ds.NAMES) + " or all", inp, output, corruptions, severity, batch, resize)
+
+
+def _corruption_files(check, degrade, skipped, inp, output, corruptions, severity, seed, batch, resize):
+    """`corrupt_files` / `distort_files`: check is the command's argument check, degrade corrupt.degrade or distort.degrade,
+    skipped(corruptions) the subset members that are not built."""
+    import torch
+    from . import corrupt as cr
+    from . import imageio
+    paths, names, severity = check(inp, output, corruptions, severity, batch, resize)
+    resize = check_resize_arg(resize, 32)
+    if not torch.cuda.is_available():
+        raise RuntimeError("no GPU visible: the corruptions run on MI355X only (no CPU fallback)")
+    sevs = [cr.draw_severity(seed, cr.stem_of(p)) if severity == "mixed" else severity for p in paths]
+    folders, seconds = _write_degraded(lambda hq, key, stems: degrade(hq, *key, seed, stems, resize), paths,
+                                       [hw for _, hw in imageio.scan(paths)],
+                                       [[(f"{name}_{sev}", (name, sev)) for name in names] for sev in sevs], batch, output)
+    return dict(images=len(paths), corruptions=names, skipped=skipped(corruptions), severity=severity, seed=seed, folders=sorted(folders),
+                output=output, seconds_total=seconds, **({"resize": list(resize)} if resize is not None else {}))
 
 
 def corrupt_files(inp, output, corruptions, severity=3, seed=42, batch=8, resize=None) -> dict:
@@ -472,65 +507,20 @@ def corrupt_files(inp, output, corruptions, severity=3, seed=42, batch=8, resize
     read).  A file's bytes depend on (seed, stem, name, severity) alone - not on the other files, their order or --batch.
     resize = "LO,HI" or (lo, hi): every file is corrupted inside the resize-down / resize-back wrapper (corrupt.degrade), its short
     edge drawn from [lo, hi) by (seed, stem); the folders and pairs.txt are what they are without it."""
-    import torch
-    paths, names, severity = check_corrupt_args(inp, output, corruptions, severity, batch, resize)
-    resize = check_resize_arg(resize, 32)
     from . import corrupt as cr
-    if not torch.cuda.is_available():
-        raise RuntimeError("no GPU visible: the corruptions run on MI355X only (no CPU fallback)")
-    folders, seconds = _write_degraded(cr.degrade, paths, names, severity, seed, batch, resize, output)
-    return dict(images=len(paths), corruptions=names, skipped=cr.skipped(corruptions), severity=severity, seed=seed,
-                folders=folders, output=output, seconds_total=seconds, **({"resize": list(resize)} if resize is not None else {}))
-
-
-def check_distort_args(inp, output, corruptions, severity=3, batch=8, resize=None):
-    """`check_corrupt_args` for a `distort` call: the names are unirestore_amd.distort's (glass_blur, snow, elastic_transform, all)."""
-    from . import corrupt as cr
-    from . import distort as ds
-    check_resize_arg(resize, 32)
-    if not corruptions:
-        raise ValueError("--corruptions: name at least one of " + ", ".join(ds.NAMES) + " or all")
-    try:
-        names = ds.expand(corruptions)
-    except ValueError as e:
-        raise ValueError(f"--corruptions {corruptions!r}: {e}") from None
-    if str(severity) != "mixed":
-        if str(severity) not in ("1", "2", "3", "4", "5"):
-            raise ValueError(f"--severity {severity!r}: choose 1..5 or mixed")
-        severity = int(severity)
-    if int(batch) < 1:
-        raise ValueError(f"--batch {batch}: must be >= 1")
-    if not inp or not os.path.exists(inp):
-        raise FileNotFoundError(f"--input {inp!r}: no such folder or list file")
-    if not output:
-        raise ValueError("--output: a folder for the corrupted PNGs is required")
-    if os.path.isdir(inp) and os.path.realpath(inp) == os.path.realpath(output):
-        raise ValueError(f"--output {output!r} is the --input folder")
-    try:
-        paths = cr.check_inputs(inp)
-    except ValueError as e:
-        raise ValueError(f"--input {e}") from None
-    return paths, names, severity
+    return _corruption_files(check_corrupt_args, cr.degrade, cr.skipped, inp, output, corruptions, severity, seed, batch, resize)
 
 
 def distort_files(inp, output, corruptions, severity=3, seed=42, batch=8, resize=None) -> dict:
     """`corrupt_files` for glass_blur, snow and elastic_transform (unirestore_amd.distort): the same folders, pairs.txt and result,
     a file's bytes depending on (seed, stem, name, severity) alone."""
-    import torch
-    paths, names, severity = check_distort_args(inp, output, corruptions, severity, batch, resize)
-    resize = check_resize_arg(resize, 32)
     from . import distort as ds
-    if not torch.cuda.is_available():
-        raise RuntimeError("no GPU visible: the corruptions run on MI355X only (no CPU fallback)")
-    folders, seconds = _write_degraded(ds.degrade, paths, names, severity, seed, batch, resize, output)
-    return dict(images=len(paths), corruptions=names, skipped=[], severity=severity, seed=seed, folders=folders, output=output,
-                seconds_total=seconds, **({"resize": list(resize)} if resize is not None else {}))
+    return _corruption_files(check_distort_args, ds.degrade, lambda c: [], inp, output, corruptions, severity, seed, batch, resize)
 
 
 def check_jpeg_args(inp, output, quality, subsampling="4:2:0", batch=8, resize=None):
     """Everything about a `jpeg` call that can be wrong without looking at a GPU -> (clean image paths, the qualities as integers,
     each once, the subsampling code).  Every message names the offending argument.  resize: None, "LO,HI" or (lo, hi), checked only."""
-    from . import corrupt as cr
     from . import jpeg
     check_resize_arg(resize, jpeg.MIN_SIDE)
     specs = [s for s in str(quality).split(",") if s.strip()] if quality is not None else []
@@ -548,19 +538,7 @@ def check_jpeg_args(inp, output, quality, subsampling="4:2:0", batch=8, resize=N
         code = jpeg.subsampling_code(subsampling)
     except ValueError as e:
         raise ValueError(f"--subsampling: {e}") from None
-    if int(batch) < 1:
-        raise ValueError(f"--batch {batch}: must be >= 1")
-    if not inp or not os.path.exists(inp):
-        raise FileNotFoundError(f"--input {inp!r}: no such folder or list file")
-    if not output:
-        raise ValueError("--output: a folder for the compressed images' PNGs is required")
-    if os.path.isdir(inp) and os.path.realpath(inp) == os.path.realpath(output):
-        raise ValueError(f"--output {output!r} is the --input folder")
-    try:
-        paths = cr.check_inputs(inp)
-    except ValueError as e:
-        raise ValueError(f"--input {e}") from None
-    return paths, qualities, code
+    return _check_file_args(inp, output, batch, "compressed images' PNGs"), qualities, code
 
 
 def jpeg_files(inp, output, quality, subsampling="4:2:0", batch=8, resize=None, seed=42) -> dict:
@@ -571,32 +549,24 @@ def jpeg_files(inp, output, quality, subsampling="4:2:0", batch=8, resize=None, 
     (seed, stem)."""
     import torch
     paths, qualities, code = check_jpeg_args(inp, output, quality, subsampling, batch, resize)
-    from . import corrupt as cr
     from . import imageio, jpeg
     resize = check_resize_arg(resize, jpeg.MIN_SIDE)
     if not torch.cuda.is_available():
         raise RuntimeError("no GPU visible: the JPEG round trip runs on MI355X only (no CPU fallback)")
-    dev = torch.device("cuda", torch.cuda.current_device())
     sizes = [hw for _, hw in imageio.scan(paths)]
     small = [p for p, hw in zip(paths, sizes) if min(hw) < jpeg.MIN_SIDE]
     if small:
         raise ValueError(f"--input: {len(small)} image(s) smaller than {jpeg.MIN_SIDE} x {jpeg.MIN_SIDE}, first {small[0]!r}")
-    stems = [cr.stem_of(p) for p in paths]
-    t0, folders = time.perf_counter(), []
-    for q in qualities:
-        folder = os.path.join(output, f"jpeg_q{q}")
-        os.makedirs(folder, exist_ok=True)
-        for _, cut in jpeg.plan_files(sizes, [q], int(batch)):
-            hq = torch.stack([imageio.load_u8(paths[i]) for i in cut]).to(dev)
-            lq = jpeg.degrade(hq, q, seed, [stems[i] for i in cut], resize, code).cpu()
-            for i, img in zip(cut, lq):
-                imageio.save_u8(img, os.path.join(folder, stems[i] + ".png"))
-        with open(os.path.join(folder, "pairs.txt"), "w") as f:
-            for i in range(len(paths)):
-                f.write(f"{stems[i]}.png {os.path.abspath(paths[i])}\n")
-        folders.append(os.path.basename(folder))
+    folders, seconds = _write_degraded(lambda hq, q, stems: jpeg.degrade(hq, q, seed, stems, resize, code), paths, sizes,
+                                       [[(f"jpeg_q{q}", q) for q in qualities]] * len(paths), batch, output)
     return dict(images=len(paths), qualities=qualities, subsampling={2: "4:2:0", 0: "4:4:4"}[code], folders=folders, output=output,
-                seconds_total=time.perf_counter() - t0, **({"resize": list(resize), "seed": seed} if resize is not None else {}))
+                seconds_total=seconds, **({"resize": list(resize), "seed": seed} if resize is not None else {}))
+
+
+# the commands that write degraded copies of clean files: (the argument check, the command, what the check may raise)
+FILE_COMMANDS = {"corrupt": (check_corrupt_args, corrupt_files, (ValueError, FileNotFoundError, NotImplementedError)),
+                 "distort": (check_distort_args, distort_files, (ValueError, FileNotFoundError, NotImplementedError)),
+                 "jpeg": (check_jpeg_args, jpeg_files, (ValueError, FileNotFoundError))}
 
 
 def main(argv=None):
@@ -635,26 +605,16 @@ def main(argv=None):
     ap.add_argument("--quality", default=None, metavar="10,25,s3", help="jpeg: qualities 1..100 and / or s1..s5 (the reference's severities)")
     ap.add_argument("--subsampling", default="4:2:0", help="jpeg: 4:2:0 (Pillow's and the reference's default) or 4:4:4")
     a = ap.parse_args(argv)
-    if a.command == "jpeg":
+    if a.command in FILE_COMMANDS:
+        check, run, errors = FILE_COMMANDS[a.command]
+        kw = dict(inp=a.input, output=a.output, batch=a.batch, resize=a.resize)
+        kw.update(dict(quality=a.quality, subsampling=a.subsampling) if a.command == "jpeg" else
+                  dict(corruptions=a.corruptions, severity=a.severity))
         try:
-            check_jpeg_args(a.input, a.output, a.quality, a.subsampling, a.batch, a.resize)
-        except (ValueError, FileNotFoundError) as e:
+            check(**kw)
+        except errors as e:
             ap.error(str(e))
-        print(json.dumps(jpeg_files(a.input, a.output, a.quality, a.subsampling, a.batch, a.resize, a.seed)))
-        return 0
-    if a.command == "distort":
-        try:
-            check_distort_args(a.input, a.output, a.corruptions, a.severity, a.batch, a.resize)
-        except (ValueError, FileNotFoundError, NotImplementedError) as e:
-            ap.error(str(e))
-        print(json.dumps(distort_files(a.input, a.output, a.corruptions, a.severity, a.seed, a.batch, a.resize)))
-        return 0
-    if a.command == "corrupt":
-        try:
-            check_corrupt_args(a.input, a.output, a.corruptions, a.severity, a.batch, a.resize)
-        except (ValueError, FileNotFoundError, NotImplementedError) as e:
-            ap.error(str(e))
-        print(json.dumps(corrupt_files(a.input, a.output, a.corruptions, a.severity, a.seed, a.batch, a.resize)))
+        print(json.dumps(run(seed=a.seed, **kw)))
         return 0
     if a.config is None:
         ap.error("the following arguments are required: --config")

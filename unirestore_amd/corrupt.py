@@ -6,7 +6,7 @@ names raise NotImplementedError.  This module is the planner: it builds the smal
 (Gaussian taps, the defocus disk, motion taps, zoom layers, the Poisson table, the pixelate tables) and launches the primitives of
 `ops`.  An image's randomness is a pure function of (seed, stem): `corruption_seed` keys the device draws, `motion_angle` is the one
 host scalar.  `corrupt` works at the size it is given; `degrade` is `corrupt` inside the reference's resize-down / resize-back
-wrapper (unirestore_amd.resize.around) when a short-edge range is given, and `corrupt` itself when none is.
+wrapper (unirestore_amd.resize.inside) when a short-edge range is given, and `corrupt` itself when none is.
 """
 import hashlib
 import math
@@ -247,16 +247,14 @@ def corrupt(images_u8, name: str, severity: int, seeds, stems=None, out_kind: in
     import torch
 
     from . import ops
+    from .resize import per_image
     if name == "clean":
         return images_u8.float() if out_kind else images_u8.clone()
     check_name(name)
     sev = check_severity(severity)
     ops.check_u8_images("corrupt", images_u8)
     n, h, w, _ = images_u8.shape
-    seeds = [seeds] * n if hasattr(seeds, "__index__") else list(seeds)
-    stems = [""] * n if stems is None else list(stems)
-    if len(seeds) != n or len(stems) != n:
-        raise ValueError(f"corrupt: {n} images but {len(seeds)} seeds and {len(stems)} stems")
+    seeds, stems = per_image("corrupt", n, seeds, stems)
     dev = images_u8.device
     c = SEVERITY[name][sev - 1]
 
@@ -298,19 +296,10 @@ def degrade(images_u8, name: str, severity: int, seeds, stems=None, resize=None)
     stem, and resized back: uint8 of the input's shape.  "clean" returns the input unresized, as the reference does."""
     if resize is None or name == "clean":
         return corrupt(images_u8, name, severity, seeds, stems)
-    from . import ops
     from . import resize as rz
-    lo, hi = rz.check_range(resize, 32)
     check_name(name)
     check_severity(severity)
-    ops.check_u8_images("degrade", images_u8)
-    n, h, w, _ = images_u8.shape
-    seeds = [seeds] * n if hasattr(seeds, "__index__") else list(seeds)
-    stems = [""] * n if stems is None else list(stems)
-    if len(seeds) != n or len(stems) != n:
-        raise ValueError(f"degrade: {n} images but {len(seeds)} seeds and {len(stems)} stems")
-    sizes = [rz.short_edge_size(h, w, rz.draw_short_edge(s, t, lo, hi)) for s, t in zip(seeds, stems)]
-    return rz.around(images_u8, sizes, lambda batch, idx: corrupt(batch, name, severity, [seeds[i] for i in idx], [stems[i] for i in idx]))
+    return rz.inside(images_u8, seeds, stems, resize, lambda batch, s, t: corrupt(batch, name, severity, s, t), 32, "degrade")
 
 
 # ------------------------------------------------------------------------------------------ files

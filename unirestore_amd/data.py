@@ -1,7 +1,8 @@
 """Inputs for the config entry points: seeded synthetic images, `ImageListFiles`, real pairs from the reference's `lq hq label`
 list files, `CorruptedImageFiles`, clean images corrupted on the GPU (unirestore_amd.corrupt), and `JpegImageFiles`, clean images
 JPEG-compressed on the GPU at a list of qualities (unirestore_amd.jpeg), and `DistortedImageFiles`, CorruptedImageFiles for glass blur,
-snow and elastic transform (unirestore_amd.distort).
+snow and elastic transform (unirestore_amd.distort).  The last three share `_DegradedImageFiles`: the constructor checks and the load /
+degrade / yield loop are written once there.
 
 `SyntheticImages` yields the evaluator's batch tuple `(lq, hq, gt, fname, task)` (reference
 src/core/base/eval_image_restoration.py:56) from seeded random images: hq = torch.rand (what the reference's own smoke
@@ -11,6 +12,8 @@ test feeds, src/modules/diffuie/autoencoder.py:209), lq = hq under one of three 
 from typing import Iterator, List, Sequence, Tuple
 
 import torch
+
+from . import corrupt, distort, jpeg
 
 DEGRADATIONS = ("noise", "haze", "lowlight")
 
@@ -103,7 +106,42 @@ class ImageListFiles:
             yield lq, hq, None, [os.path.splitext(os.path.basename(self.pairs[i][0]))[0] for i in idx], self.task
 
 
-class CorruptedImageFiles:
+class _DegradedImageFiles:
+    """Clean image files degraded on the GPU, what the three datasets below share: the common constructor arguments, the plan's
+    length and the loop over it.  A subclass gives `_plan()` -> the batches, each a tuple that ends in the batch's file indices,
+    and `_degrade(hq, stems, *what)` -> (lq, label): `what` is the rest of that tuple, `label` what `last` holds after the batch."""
+
+    def __init__(self, source, batch_size, task, seed, num_batches, resize, min_side):
+        from . import resize as rz
+        self.resize = None if resize is None else rz.check_range(resize, min_side)
+        self.source, self.batch_size, self.task, self.seed, self.num_batches = source, int(batch_size), task, int(seed), num_batches
+        if self.batch_size < 1:
+            raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+        self.paths = corrupt.check_inputs(source)
+        self.last = None
+
+    def __len__(self):
+        return len(self._plan())
+
+    def batches(self, rank: int = 0, world: int = 1, device="cpu") -> Iterator[Tuple[torch.Tensor, torch.Tensor, None, List[str], str]]:
+        from .imageio import load_u8
+        if world != 1:
+            raise ValueError(f"{type(self).__name__} does not shard a batch over ranks (batches of real files differ in size): run "
+                             "`validate` on one GPU")
+        # u8 / 255 as the host computes it, the values ImageListFiles yields for the same bytes (a device division by a scalar may
+        # multiply by the reciprocal and differ in the last bit)
+        unit = (torch.arange(256, dtype=torch.float32) / 255).to(device)
+
+        def nchw(t):
+            return unit.index_select(0, t.permute(0, 3, 1, 2).reshape(-1).int()).view(t.shape[0], 3, t.shape[1], t.shape[2])
+        for *what, idx in self._plan():
+            stems = [corrupt.stem_of(self.paths[i]) for i in idx]
+            hq = torch.stack([load_u8(self.paths[i]) for i in idx]).to(device)
+            lq, self.last = self._degrade(hq, stems, *what)
+            yield nchw(lq), nchw(hq), None, stems, self.task
+
+
+class CorruptedImageFiles(_DegradedImageFiles):
     """Clean images corrupted on the GPU for `validate` (`data.class_path: unirestore_amd.data.CorruptedImageFiles`): `source` is a
     folder, a list file of clean images or an `lq hq [label]` list, of which only the hq column is read.  `corruptions` is a subset
     name (unirestore_amd.corrupt.SUBSETS), a name, or a comma-separated string / list of names ("clean" only when it is named);
@@ -114,51 +152,22 @@ class CorruptedImageFiles:
     (lo >= 32) turns on the reference's resize-down / resize-back wrapper (corrupt.degrade): every image's short edge is drawn
     from [lo, hi) by (seed, stem) as well, lq keeps hq's shape; the reference's own range is [resolution // 4, resolution)."""
 
-    _module = "corrupt"                            # the planner whose expand / degrade this class uses (DistortedImageFiles: distort)
+    _planner = corrupt                             # the module whose expand / degrade this class uses (DistortedImageFiles: distort)
 
     def __init__(self, source: str, corruptions="common", severity=3, batch_size: int = 8, task: str = "ir", seed: int = 42,
                  num_batches: int = None, resize=None):
-        import importlib
-        from . import corrupt
-        from . import resize as rz
-        self._planner = importlib.import_module(f"{__package__}.{self._module}")
-        self.resize = None if resize is None else rz.check_range(resize, 32)
-        self.source, self.batch_size, self.task, self.seed, self.num_batches = source, int(batch_size), task, int(seed), num_batches
-        if self.batch_size < 1:
-            raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+        super().__init__(source, batch_size, task, seed, num_batches, resize, 32)
         self.names = self._planner.expand(corruptions)
-        self.skipped = corrupt.skipped(corruptions) if self._planner is corrupt else []
+        self.skipped = corrupt.skipped(corruptions)
         self.severity = severity if severity == "mixed" else corrupt.check_severity(severity)
-        self.paths = corrupt.check_inputs(source)
-        self.last = None
 
     def _plan(self):
-        from . import corrupt
         from .imageio import scan
         sizes = [hw for _, hw in scan(self.paths)]
         return corrupt.plan_files(self.paths, sizes, self.names, self.severity, self.seed, self.batch_size)[:self.num_batches]
 
-    def __len__(self):
-        return len(self._plan())
-
-    def batches(self, rank: int = 0, world: int = 1, device="cpu") -> Iterator[Tuple[torch.Tensor, torch.Tensor, None, List[str], str]]:
-        from . import corrupt
-        from .imageio import load_u8
-        if world != 1:
-            raise ValueError("CorruptedImageFiles does not shard a batch over ranks (batches of real files differ in size): run "
-                             "`validate` on one GPU")
-        # u8 / 255 as the host computes it, the values ImageListFiles yields for the same bytes (a device division by a scalar may
-        # multiply by the reciprocal and differ in the last bit)
-        unit = (torch.arange(256, dtype=torch.float32) / 255).to(device)
-
-        def nchw(t):
-            return unit.index_select(0, t.permute(0, 3, 1, 2).reshape(-1).int()).view(t.shape[0], 3, t.shape[1], t.shape[2])
-        for name, sev, idx in self._plan():
-            stems = [corrupt.stem_of(self.paths[i]) for i in idx]
-            hq = torch.stack([load_u8(self.paths[i]) for i in idx]).to(device)
-            lq = self._planner.degrade(hq, name, sev, self.seed, stems, self.resize)
-            self.last = (name, sev)
-            yield nchw(lq), nchw(hq), None, stems, self.task
+    def _degrade(self, hq, stems, name, sev):
+        return self._planner.degrade(hq, name, sev, self.seed, stems, self.resize), (name, sev)
 
 
 class DistortedImageFiles(CorruptedImageFiles):
@@ -166,14 +175,15 @@ class DistortedImageFiles(CorruptedImageFiles):
     unirestore_amd.data.DistortedImageFiles`): `corruptions` is "all", a name, or a comma-separated string / list of names of
     distort.NAMES; everything else - `source`, `severity`, `seed`, `resize`, the grouping, what is yielded and `last` - is the base
     class's, with distort.degrade in the place of corrupt.degrade.  `skipped` is empty: a name that is not built is refused."""
-    _module = "distort"
+    _planner = distort
 
     def __init__(self, source: str, corruptions="all", severity=3, batch_size: int = 8, task: str = "ir", seed: int = 42,
                  num_batches: int = None, resize=None):
         super().__init__(source, corruptions, severity, batch_size, task, seed, num_batches, resize)
+        self.skipped = []
 
 
-class JpegImageFiles:
+class JpegImageFiles(_DegradedImageFiles):
     """Clean images JPEG-compressed on the GPU for `validate` (`data.class_path: unirestore_amd.data.JpegImageFiles`): `source` is
     read as CorruptedImageFiles reads it (a folder, a list file of clean images, or the hq column of an `lq hq [label]` list).
     `quality` is one quality or a list of them (unirestore_amd.jpeg.quality_of: integers 1..100 or "s1".."s5"); EVERY image is
@@ -185,12 +195,7 @@ class JpegImageFiles:
 
     def __init__(self, source: str, quality=(10, 25, 50), batch_size: int = 8, task: str = "ir", num_batches: int = None, resize=None,
                  seed: int = 42):
-        from . import corrupt, jpeg
-        from . import resize as rz
-        self.resize, self.seed = None if resize is None else rz.check_range(resize, jpeg.MIN_SIDE), int(seed)
-        self.source, self.batch_size, self.task, self.num_batches = source, int(batch_size), task, num_batches
-        if self.batch_size < 1:
-            raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+        super().__init__(source, batch_size, task, seed, num_batches, resize, jpeg.MIN_SIDE)
         specs = [s for s in quality.split(",") if s] if isinstance(quality, str) else \
             list(quality) if isinstance(quality, (list, tuple)) else [quality]
         self.qualities = []
@@ -200,31 +205,11 @@ class JpegImageFiles:
                 self.qualities.append(q)
         if not self.qualities:
             raise ValueError("quality: name at least one quality")
-        self.paths = corrupt.check_inputs(source)
-        self.last = None
 
     def _plan(self):
-        from . import jpeg
         from .imageio import scan
         sizes = [hw for _, hw in scan(self.paths)]
         return jpeg.plan_files(sizes, self.qualities, self.batch_size)[:self.num_batches]
 
-    def __len__(self):
-        return len(self._plan())
-
-    def batches(self, rank: int = 0, world: int = 1, device="cpu") -> Iterator[Tuple[torch.Tensor, torch.Tensor, None, List[str], str]]:
-        from . import corrupt, jpeg
-        from .imageio import load_u8
-        if world != 1:
-            raise ValueError("JpegImageFiles does not shard a batch over ranks (batches of real files differ in size): run "
-                             "`validate` on one GPU")
-        unit = (torch.arange(256, dtype=torch.float32) / 255).to(device)          # u8 / 255 as the host computes it (CorruptedImageFiles)
-
-        def nchw(t):
-            return unit.index_select(0, t.permute(0, 3, 1, 2).reshape(-1).int()).view(t.shape[0], 3, t.shape[1], t.shape[2])
-        for q, idx in self._plan():
-            hq = torch.stack([load_u8(self.paths[i]) for i in idx]).to(device)
-            stems = [corrupt.stem_of(self.paths[i]) for i in idx]
-            lq = jpeg.degrade(hq, q, self.seed, stems, self.resize)
-            self.last = ("jpeg", q)
-            yield nchw(lq), nchw(hq), None, stems, self.task
+    def _degrade(self, hq, stems, q):
+        return jpeg.degrade(hq, q, self.seed, stems, self.resize), ("jpeg", q)

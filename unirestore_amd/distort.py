@@ -10,7 +10,7 @@ randomness is a pure function of (seed, stem): corrupt.corruption_seed keys the 
                      the whitened image and the layer's own rotation (ur_distort_snow)
   elastic_transform  two smoothed keyed uniform fields (ur_distort_field) -> bilinear warp (ur_distort_warp)
 `distort` works at the size it is given; `degrade` is `distort` inside the reference's resize-down / resize-back wrapper
-(unirestore_amd.resize.around).  Of the reference's names only frost and spatter stay unbuilt (DESIGN.md 6t says why).
+(unirestore_amd.resize.inside).  Of the reference's names only frost and spatter stay unbuilt (DESIGN.md 6t says why).
 """
 import numpy as np
 
@@ -77,23 +77,7 @@ def elastic_taps(h: int, w: int):
     return tuple(out)
 
 
-def choose(seed: int, stem: str, names, severity):
-    """The (corruption, severity) of one image from sha256 of (seed, stem) alone, as corrupt.choose."""
-    return _cr.choose(seed, stem, names, severity)
-
-
-def plan_files(paths, sizes, names, severity, seed: int, batch_size: int):
-    """corrupt.plan_files: every file's (corruption, severity) from `choose`, grouped by (shape, corruption, severity)."""
-    return _cr.plan_files(paths, sizes, names, severity, seed, batch_size)
-
-
-def _per_image(who, images_u8, seeds, stems):
-    n = images_u8.shape[0]
-    seeds = [seeds] * n if hasattr(seeds, "__index__") else list(seeds)
-    stems = [""] * n if stems is None else list(stems)
-    if len(seeds) != n or len(stems) != n:
-        raise ValueError(f"{who}: {n} images but {len(seeds)} seeds and {len(stems)} stems")
-    return seeds, stems
+choose = _cr.choose                                # the (corruption, severity) of one image, as corrupt draws it
 
 
 def distort(images_u8, name: str, severity: int, seeds, stems=None, out_kind: int = 0):
@@ -104,11 +88,12 @@ def distort(images_u8, name: str, severity: int, seeds, stems=None, out_kind: in
     import torch
 
     from . import ops
+    from .resize import per_image
     check_name(name)
     sev = check_severity(severity)
     ops.check_u8_images("distort", images_u8)
     n, h, w, _ = images_u8.shape
-    seeds, stems = _per_image("distort", images_u8, seeds, stems)
+    seeds, stems = per_image("distort", n, seeds, stems)
     dev = images_u8.device
     c = SEVERITY[name][sev - 1]
 
@@ -142,13 +127,7 @@ def degrade(images_u8, name: str, severity: int, seeds, stems=None, resize=None)
     size under its own seed and stem, and resizes it back: uint8 of the input's shape."""
     if resize is None:
         return distort(images_u8, name, severity, seeds, stems)
-    from . import ops
     from . import resize as rz
-    lo, hi = rz.check_range(resize, 32)
     check_name(name)
     check_severity(severity)
-    ops.check_u8_images("degrade", images_u8)
-    n, h, w, _ = images_u8.shape
-    seeds, stems = _per_image("degrade", images_u8, seeds, stems)
-    sizes = [rz.short_edge_size(h, w, rz.draw_short_edge(s, t, lo, hi)) for s, t in zip(seeds, stems)]
-    return rz.around(images_u8, sizes, lambda batch, idx: distort(batch, name, severity, [seeds[i] for i in idx], [stems[i] for i in idx]))
+    return rz.inside(images_u8, seeds, stems, resize, lambda batch, s, t: distort(batch, name, severity, s, t), 32, "degrade")

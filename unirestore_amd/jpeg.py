@@ -70,23 +70,14 @@ def roundtrip(images_u8, quality, subsampling="4:2:0"):
 
 
 def degrade(images_u8, quality, seeds, stems, resize, subsampling="4:2:0"):
-    """`roundtrip` inside the reference's resize-down / resize-back wrapper (unirestore_amd.resize.around), as corrupt.degrade is
+    """`roundtrip` inside the reference's resize-down / resize-back wrapper (unirestore_amd.resize.inside), as corrupt.degrade is
     for the corruptions.  resize None: `roundtrip` itself (seeds and stems are not looked at).  resize = (lo, hi), lo >= MIN_SIDE:
     image n's short edge is resize.draw_short_edge(seeds[n], stems[n], lo, hi).  -> uint8 of the input's shape."""
     if resize is None:
         return roundtrip(images_u8, quality, subsampling)
-    from . import ops
     from . import resize as rz
-    lo, hi = rz.check_range(resize, MIN_SIDE)
     q, code = quality_of(quality), subsampling_code(subsampling)
-    ops.check_u8_images("jpeg.degrade", images_u8, min_side=rz.MIN_SIDE)
-    n, h, w, _ = images_u8.shape
-    seeds = [seeds] * n if hasattr(seeds, "__index__") else list(seeds)
-    stems = [""] * n if stems is None else list(stems)
-    if len(seeds) != n or len(stems) != n:
-        raise ValueError(f"jpeg.degrade: {n} images but {len(seeds)} seeds and {len(stems)} stems")
-    sizes = [rz.short_edge_size(h, w, rz.draw_short_edge(s, t, lo, hi)) for s, t in zip(seeds, stems)]
-    return rz.around(images_u8, sizes, lambda batch, idx: roundtrip(batch, q, code))
+    return rz.inside(images_u8, seeds, stems, resize, lambda batch, s, t: roundtrip(batch, q, code), MIN_SIDE, "jpeg.degrade", rz.MIN_SIDE)
 
 
 def plan_files(sizes, qualities, batch_size: int):

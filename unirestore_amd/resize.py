@@ -5,8 +5,8 @@ include/unirestore_hip.h, the notes are DESIGN.md 6s), and the reference's resiz
 `TF.resize` runs on the uint8 tensor `read_image` returns and so what the reference's IRCorruptDataset._degrade_image calls twice
 per image (src/data/dataset_ir.py).  This module is the planner: per axis it builds the (xmin, xsize) table and the fixed-point
 weights on the host in fp64 (`axis_tables`); the two kernels only apply tables, so bilinear and bicubic are the same kernels.
-`around` is the wrapper itself; `corrupt.degrade` and `jpeg.degrade` put a degradation inside it.  An image's short edge is a pure
-function of (seed, stem): `draw_short_edge`.
+`around` is the wrapper itself; `inside` is the one body of `corrupt.degrade`, `distort.degrade` and `jpeg.degrade`, which put a
+degradation inside it.  An image's short edge is a pure function of (seed, stem): `draw_short_edge`.
 """
 import hashlib
 from functools import lru_cache
@@ -115,6 +115,33 @@ def draw_short_edge(seed: int, stem: str, lo: int, hi: int) -> int:
         raise ValueError(f"draw_short_edge: empty range [{lo}, {hi})")
     h = int.from_bytes(hashlib.sha256(f"{seed}\0corrupt\0{stem}\0resize".encode()).digest()[:8], "little")
     return lo + min(int((h >> 11) * 2.0 ** -53 * (hi - lo)), hi - lo - 1)
+
+
+def per_image(who: str, n: int, seeds, stems):
+    """One integer seed -> n of it, stems None -> n empty names; lists pass through.  -> (seeds, stems), both of length n."""
+    seeds = [seeds] * n if hasattr(seeds, "__index__") else list(seeds)
+    stems = [""] * n if stems is None else list(stems)
+    if len(seeds) != n or len(stems) != n:
+        raise ValueError(f"{who}: {n} images but {len(seeds)} seeds and {len(stems)} stems")
+    return seeds, stems
+
+
+def drawn_sizes(h: int, w: int, seeds, stems, lo: int, hi: int) -> list:
+    """The resized (oh, ow) of every H x W image of a batch: its short edge drawn from [lo, hi) by its own (seed, stem)."""
+    return [short_edge_size(h, w, draw_short_edge(s, t, lo, hi)) for s, t in zip(seeds, stems)]
+
+
+def inside(images_u8, seeds, stems, resize, fn, minimum: int, who: str, min_side: int = 32):
+    """A degradation inside the wrapper: resize = (lo, hi) with lo >= minimum, images of H, W >= min_side; image n is resized to
+    its drawn size (`drawn_sizes`), fn(batch, seeds, stems) -> uint8 of batch's shape degrades every group of equal resized shape
+    under its members' own seeds and stems, and `around` resizes the results back.  -> uint8 of the input's shape."""
+    from . import ops
+    lo, hi = check_range(resize, minimum)
+    ops.check_u8_images(who, images_u8, min_side=min_side)
+    n, h, w, _ = images_u8.shape
+    seeds, stems = per_image(who, n, seeds, stems)
+    return around(images_u8, drawn_sizes(h, w, seeds, stems, lo, hi),
+                  lambda batch, idx: fn(batch, [seeds[i] for i in idx], [stems[i] for i in idx]))
 
 
 def around(images_u8, sizes, fn, mode: str = "bilinear"):
