@@ -392,6 +392,37 @@ int ur_image_metrics(const float* pred, const float* target, int N, int C, int H
                      double* psnr, double* ssim, void* ws, long long ws_bytes, ur_stream_t stream);
 long long ur_image_metrics_ws_size(int N, int C, int H, int W, int win);
 
+/* ---- LPIPS (AlexNet features, v0.1 linear layers), exact fp32 (evaluator side) ----------------------------------------------
+ * The perceptual distance of the reference's LPIPS(net_type="alex", normalize=True): both images go through AlexNet's five
+ * convolutions as ONE batch of 2N (predictions first), every ReLU output is a tap; per tap and pixel the features are
+ * unit-normalised over channels (f / (sqrt(sum f^2) + 1e-10)), the squared difference is weighted per channel, averaged over
+ * the pixels, and the five taps are added.  All kernels are fp32 on NHWC activations (the convolution on the fp32-input MFMA,
+ * a k-ordered fma chain), use no atomics and sum in a fixed order: the same inputs give the same bits, eagerly and in a graph.
+ * Every function checks its arguments before any HIP call (UR_E_INVALID).
+ *
+ * ur_lpips_prep: x fp32 NCHW [N,3,H,W] in [0,1] -> y fp32 NHWC [N,H,W,3] = ((2x - 1) - shift_c) / scale_c, shift = (-.030, -.088,
+ *   -.188), scale = (.458, .448, .450).  C must be 3, H and W >= 31 (the smallest input whose fifth tap has a pixel).
+ * ur_conv2d_f32: y[N,OH,OW,Cout] = act(conv(x[N,H,W,Cin], w) + bias), OH = (H + 2 pad - KH) / stride + 1, zero padding, relu 0 / 1.
+ *   w is the host's repack [Kpad][Cout_pad] of the OIHW filter: row k = (kh * KW + kw) * Cin + cin, column cout, zero-filled up to
+ *   the sizes ur_conv2d_f32_wpack_dims gives (K to a multiple of 16, Cout to a multiple of 64), 16-byte aligned.  The
+ *   activations are read as they are: padding, the K tail and the M tail cost no copy.  bias fp32 [Cout].
+ * ur_maxpool2d_f32: 3x3 window, stride 2, no padding, floor mode: x [N,H,W,C] -> y [N,(H-3)/2+1,(W-3)/2+1,C].
+ * ur_lpips_layer: feat [2N][P][C] (one tap; images 0..N-1 predictions, N..2N-1 targets), lin fp32 [C] ->
+ *   part fp64 [N][ur_lpips_layer_parts(P)]: partial sums over pixels of sum_c lin_c (u_c^pred - u_c^tgt)^2.
+ * ur_lpips_finish: ws holds the five taps' partials one after the other (tap t of an H x W input has ur_lpips_tap_hw pixels, its
+ *   block starts where tap t-1's N * parts doubles end; ur_lpips_ws_size bytes in all) -> out fp64 [N] = sum over taps, in tap
+ *   order, of (sum of the tap's partials in ascending order) / pixels. */
+int ur_lpips_prep(const float* x, float* y, int N, int C, int H, int W, ur_stream_t stream);
+int ur_conv2d_f32_wpack_dims(int Cin, int Cout, int KH, int KW, int* kpad, int* cout_pad);
+int ur_conv2d_f32(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int KH, int KW,
+                  int stride, int pad, int relu, ur_stream_t stream);
+int ur_maxpool2d_f32(const float* x, float* y, int N, int H, int W, int C, ur_stream_t stream);
+int ur_lpips_tap_hw(int H, int W, int tap, int* oh, int* ow);
+long long ur_lpips_layer_parts(long long P);
+int ur_lpips_layer(const float* feat, const float* lin, int N, int P, int C, double* part, long long part_bytes, ur_stream_t stream);
+long long ur_lpips_ws_size(int N, int H, int W);
+int ur_lpips_finish(const void* ws, long long ws_bytes, int N, int H, int W, double* out, ur_stream_t stream);
+
 /* ---- colour correction of a restored image (between the decoder's conv_out and the egress kernels) ----------------------
  * c fp32 NHWC [N,H,W,ld_c]: the restored image; src 16-bit NHWC [src_n,H,W,ld_s]: the image the encoder saw, image n is corrected
  * against source n % src_n (a task-major K*B batch against B sources); out fp32 NHWC [N,H,W,ld_c], not c.  Channels 0..2 are RGB;

@@ -118,6 +118,15 @@ SIGNATURES = {
     "ur_keyed_noise": (_I, [_P, C.c_uint32, _P, _I, _LL, _I, _P]),
     "ur_image_metrics": (_I, [_P, _P, _I, _I, _I, _I, _I, C.c_double, _P, _P, _P, _LL, _P]),
     "ur_image_metrics_ws_size": (_LL, [_I, _I, _I, _I, _I]),
+    "ur_lpips_prep": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "ur_conv2d_f32_wpack_dims": (_I, [_I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
+    "ur_conv2d_f32": (_I, [_P, _P, _P, _P] + [_I] * 10 + [_P]),
+    "ur_maxpool2d_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "ur_lpips_tap_hw": (_I, [_I, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
+    "ur_lpips_layer_parts": (_LL, [_LL]),
+    "ur_lpips_layer": (_I, [_P, _P, _I, _I, _I, _P, _LL, _P]),
+    "ur_lpips_ws_size": (_LL, [_I, _I, _I]),
+    "ur_lpips_finish": (_I, [_P, _LL, _I, _I, _I, _P, _P]),
     "ur_color_fix_wavelet": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "ur_color_fix_adain": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "ur_color_fix_adain_ws_bytes": (_SZ, [_I, _I, _I]),

@@ -160,14 +160,29 @@ def _start(r: dict, hf_root, random_init, model, **caller_args):
     return rank, world, dev, dist, lit
 
 
+def check_lpips_arg(lpips):
+    """--lpips ALEXNET.pth,LIN.pth (or a pair of paths) -> (alexnet_path, lin_path); ValueError unless both files exist."""
+    parts = [p for p in lpips.split(",")] if isinstance(lpips, str) else list(lpips)
+    if len(parts) != 2 or not all(parts):
+        raise ValueError("--lpips takes two files: ALEXNET.pth,LIN.pth (torchvision's AlexNet state dict, the LPIPS v0.1 linear layers)")
+    for p in parts:
+        if not os.path.isfile(p):
+            raise ValueError(f"--lpips: no such file: {p}")
+    return parts[0], parts[1]
+
+
 def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_16bit=False, metrics_device="cpu", tasks=None,
-             model=None) -> dict:
+             model=None, lpips=None) -> dict:
     """tasks: a list of task names - every batch is restored once and decoded for each of them (DiffUIE.forward_tasks).  PSNR / SSIM
     come from the "ir" output, so the list must hold "ir"; images_per_s counts input images.  model: a ready DiffUIE to use instead
     of building the config's.  With data.CorruptedImageFiles (and data.DistortedImageFiles: "snow/3") the result also holds by_corruption ("fog/3" -> psnr, ssim, images)
     and skipped (the subset members that are not built); with data.JpegImageFiles it holds by_corruption ("jpeg/10", the quality);
-    with either, resize = [lo, hi] when the data's resize-down / resize-back wrapper is on."""
+    with either, resize = [lo, hi] when the data's resize-down / resize-back wrapper is on.
+    lpips: "ALEXNET.pth,LIN.pth", a pair of paths or a loaded lpips.LpipsWeights - the result gains val_lq/lpips and every
+    by_corruption entry lpips (AlexNet LPIPS in fp32 on the GPU; the weights are the user's, none ship with the project)."""
     import torch
+    if lpips is not None and isinstance(lpips, (str, tuple, list)):
+        lpips = check_lpips_arg(lpips)                    # before the model is built
     r = resolve(cfg, allow_16bit=allow_16bit)
     if tasks is not None:
         tasks = list(tasks)
@@ -176,7 +191,9 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
                              "(it is not added silently)")
     from . import data as data_mod
     from .dist import all_gather_images, shard_range
-    rank, world, dev, dist, lit = _start(r, hf_root, random_init, model, metrics_device=metrics_device, **r["caller_args"])
+    rank, world, dev, dist, lit = _start(r, hf_root, random_init, model, metrics_device=metrics_device, lpips_weights=lpips,
+                                         **r["caller_args"])
+    sums = ("psnr", "ssim") + (("lpips",) if lpips is not None else ())          # the metric states, in all-reduce order
     data = getattr(data_mod, r["data_class"].rsplit(".", 1)[1])(**r["data_args"])
     if data.batch_size < world:
         raise ValueError(f"data batch_size {data.batch_size} < world size {world}: every rank needs at least one image per batch")
@@ -203,21 +220,21 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
         before = dict(lit.totals)
         lit.update_metrics(by_task["ir"], batch[1])           # this rank's shard; reduced over the ranks below (fp64 PSNR / SSIM: untimed)
         if by_corruption is not None:                     # the batch is homogeneous: its increment of the totals belongs to one key
-            acc = by_corruption.setdefault("%s/%d" % data.last, dict(psnr=0.0, ssim=0.0, images=0))
+            acc = by_corruption.setdefault("%s/%d" % data.last, dict({k: 0.0 for k in sums}, images=0))
             for k in acc:
                 acc[k] = acc[k] + (lit.totals[k] - before[k])
     if world > 1:                                         # the reference's metric states reduce with dist_reduce_fx="sum"
         # the totals are host floats (metrics_device "cpu") or 0-d fp64 device tensors ("gpu")
         tot = torch.stack([torch.as_tensor(v, dtype=torch.float64, device=dev)
-                           for v in (lit.totals["psnr"], lit.totals["ssim"], float(lit.totals["images"]))])
+                           for v in [lit.totals[k] for k in sums] + [float(lit.totals["images"])]])
         dist.all_reduce(tot)
-        lit.totals.update(psnr=float(tot[0]), ssim=float(tot[1]), images=int(tot[2]))
+        lit.totals.update({k: float(tot[i]) for i, k in enumerate(sums)}, images=int(tot[-1]))
     res = dict(config=r["data_args"], dtype=r["dtype"], n_gpus=world, denoise_steps=r["model_kwargs"]["cnet"]["num_inference_steps"],
                images_per_s=(n_img / secs) if secs > 0 else None, output_finite=finite, **lit.metrics())
     if tasks is not None:
         res["tasks"] = tasks
     if by_corruption is not None:
-        res["by_corruption"] = {k: dict(psnr=float(v["psnr"]) / v["images"], ssim=float(v["ssim"]) / v["images"], images=int(v["images"]))
+        res["by_corruption"] = {k: dict({m: float(v[m]) / v["images"] for m in sums}, images=int(v["images"]))
                                 for k, v in by_corruption.items()}
         if hasattr(data, "skipped"):
             res["skipped"] = list(data.skipped)
@@ -579,6 +596,8 @@ def main(argv=None):
     ap.add_argument("--allow-16bit", action="store_true", help="run a `precision: 32` config in fp16 (fp32 accumulation) instead of refusing it")
     ap.add_argument("--metrics-device", choices=["cpu", "gpu"], default="cpu",
                     help="where PSNR / SSIM run: cpu = host fp64 (default), gpu = the HIP metric kernels (fp64, no per-batch host sync)")
+    ap.add_argument("--lpips", default=None, metavar="ALEXNET.pth,LIN.pth",
+                    help="validate: also report LPIPS (AlexNet, fp32, on the GPU) from these two user-supplied weight files")
     ap.add_argument("--tasks", default=None, metavar="ir,cls,seg",
                     help="restore every batch once and decode it for each of these tasks (forward_tasks); validate: must hold 'ir', which "
                          "feeds PSNR / SSIM; restore: one sub-folder of --output per task")
@@ -623,6 +642,13 @@ def main(argv=None):
             check_noise_args(a.noise, a.samples)
         except ValueError as e:
             ap.error(str(e))
+    if a.lpips is not None:
+        if a.command != "validate":
+            ap.error("--lpips belongs to validate")
+        try:
+            a.lpips = check_lpips_arg(a.lpips)
+        except ValueError as e:
+            ap.error(str(e))
     cfg = apply_color_fix(load_config(a.config, a.set), a.color_fix)
     if a.command == "print_config":
         print(yaml.safe_dump(cfg, sort_keys=False))
@@ -635,7 +661,7 @@ def main(argv=None):
             print(json.dumps(res))
         return 0
     res = validate(cfg, hf_root=a.hf_root, max_batches=a.max_batches, allow_16bit=a.allow_16bit, metrics_device=a.metrics_device,
-                   tasks=[t for t in a.tasks.split(",") if t] if a.tasks is not None else None)
+                   tasks=[t for t in a.tasks.split(",") if t] if a.tasks is not None else None, lpips=a.lpips)
     if res is not None:
         print(json.dumps(res))
     return 0

@@ -1066,6 +1066,32 @@ def image_metrics(pred: torch.Tensor, target: torch.Tensor, data_range: float = 
     return psnr, ssim
 
 
+def lpips(pred: torch.Tensor, target: torch.Tensor, weights) -> torch.Tensor:
+    """LPIPS (AlexNet, normalize=True: inputs in [0,1]) of fp32 NCHW batches on the GPU -> fp64 [N] device tensor.  weights: what
+    lpips.load_weights / lpips.random_weights return.  Predictions and targets go through the network as one batch of 2N; exact
+    fp32 (fp32-input MFMA convolutions), fixed-order sums, so two calls give the same bits.  No host sync."""
+    from . import lpips as _lpips
+    dev = torch.device("cuda", torch.cuda.current_device())
+    for name, t in (("pred", pred), ("target", target)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.ndim != 4:
+            raise ValueError(f"lpips: {name} must be a 4-d fp32 NCHW tensor, got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        if t.device != dev:
+            raise ValueError(f"lpips: {name} is on {t.device}, not on the current device {dev}")
+        if not t.is_contiguous():
+            raise ValueError(f"lpips: {name} must be contiguous")
+    if pred.shape != target.shape:
+        raise ValueError(f"lpips: shapes differ: {tuple(pred.shape)} vs {tuple(target.shape)}")
+    n, c, h, w = pred.shape
+    if n < 1 or c != 3 or h < _lpips.MIN_HW or w < _lpips.MIN_HW:
+        raise ValueError(f"lpips: needs [N>=1, 3, H>={_lpips.MIN_HW}, W>={_lpips.MIN_HW}] images, got {tuple(pred.shape)}")
+    if not isinstance(weights, _lpips.LpipsWeights):
+        raise ValueError(f"lpips: weights must come from lpips.load_weights / lpips.random_weights, got {type(weights).__name__}")
+    if weights.device != dev:
+        raise ValueError(f"lpips: the weights are on {weights.device}, not on the current device {dev}")
+    return _lpips.forward(pred, target, weights)
+
+
 def profile_enable(on: bool):
     check(lib.ur_profile_enable(int(on)))
 

@@ -94,7 +94,8 @@ class LitUniFIE:
     runs the evaluator's crop / restore / quantise / metric steps on a batch tuple `(lq, hq, gt, fname, task)`."""
 
     def __init__(self, model_kwargs: dict, save_image: bool = False, eval_mode: str = "FR", need_crop: bool = True,
-                 dtype: str = "bf16", hf_root: str = None, model=None, metrics_device: str = "cpu", **_ignored):
+                 dtype: str = "bf16", hf_root: str = None, model=None, metrics_device: str = "cpu", lpips_weights=None,
+                 **_ignored):
         from . import checkpoint
         if metrics_device not in METRICS_DEVICES:
             raise ValueError(f"metrics_device={metrics_device!r}: choose from {METRICS_DEVICES}")
@@ -104,6 +105,13 @@ class LitUniFIE:
         self.task_dict = tedit.get("task", [])
         self.model = model if model is not None else checkpoint.build_from_config(model_kwargs, hf_root=hf_root, dtype=dtype)
         self.totals = dict(psnr=0.0, ssim=0.0, images=0)
+        # LPIPS (AlexNet, exact fp32 HIP kernels) is off unless weights are given: a (alexnet_path, lin_path) pair or a loaded
+        # lpips.LpipsWeights.  It runs on the GPU whatever metrics_device says - the product has no CPU implementation of it.
+        self.lpips_weights = None
+        if lpips_weights is not None:
+            from . import lpips
+            self.lpips_weights = lpips_weights if isinstance(lpips_weights, lpips.LpipsWeights) else lpips.load_weights(*lpips_weights)
+            self.totals["lpips"] = torch.zeros((), dtype=torch.float64, device=self.lpips_weights.device)
 
     def forward(self, inputs: Sequence[torch.Tensor], task: str, quantize: bool = False) -> List[torch.Tensor]:
         return forward(self.model, inputs, task, quantize=quantize)
@@ -133,6 +141,7 @@ class LitUniFIE:
             else:
                 self.totals["psnr"] += float(psnr_per_image(preds[-1], tgt).sum())          # sum over images (SKPSNR state)
                 self.totals["ssim"] += ssim(preds[-1], tgt) * n
+            self._add_lpips(preds[-1], tgt)
             self.totals["images"] += n
         return preds
 
@@ -142,6 +151,14 @@ class LitUniFIE:
         ps, ss = ops.image_metrics(preds.contiguous(), tgt.contiguous())
         self.totals["psnr"] = self.totals["psnr"] + ps.sum()
         self.totals["ssim"] = self.totals["ssim"] + ss.sum()
+
+    def _add_lpips(self, preds: torch.Tensor, tgt: torch.Tensor):
+        """Sum of the batch's per-image LPIPS into the fp64 device total (nothing when LPIPS is off)."""
+        if self.lpips_weights is None:
+            return
+        from . import ops
+        dev = self.lpips_weights.device
+        self.totals["lpips"] = self.totals["lpips"] + ops.lpips(preds.to(dev).contiguous(), tgt.to(dev).contiguous(), self.lpips_weights).sum()
 
     # ---- the training step's FORWARD halves (engine_unifie.py:135-191), values only: the HIP path has no autograd ------------
     @torch.no_grad()
@@ -192,9 +209,13 @@ class LitUniFIE:
             else:
                 self.totals["psnr"] += float(psnr_per_image(preds, tgt).sum())
                 self.totals["ssim"] += ssim(preds, tgt) * n
+            self._add_lpips(preds, tgt)
             self.totals["images"] += n
 
     def metrics(self) -> dict:
         n = max(self.totals["images"], 1)
         psnr_sum, ssim_sum = float(self.totals["psnr"]), float(self.totals["ssim"])     # (the one device read of the "gpu" totals)
-        return {"val_lq/psnr": psnr_sum / n, "val_lq/ssim": ssim_sum / n, "images": self.totals["images"]}
+        res = {"val_lq/psnr": psnr_sum / n, "val_lq/ssim": ssim_sum / n, "images": self.totals["images"]}
+        if self.lpips_weights is not None:
+            res["val_lq/lpips"] = float(self.totals["lpips"]) / n
+        return res
