@@ -423,6 +423,30 @@ int ur_lpips_layer(const float* feat, const float* lin, int N, int P, int C, dou
 long long ur_lpips_ws_size(int N, int H, int W);
 int ur_lpips_finish(const void* ws, long long ws_bytes, int N, int H, int W, double* out, ur_stream_t stream);
 
+/* ---- classifier scoring of the cls output (ResNet top-1 accuracy; exact fp32, NHWC, no atomics, fixed-order sums) ---------
+ * The network's convolutions, its FC layer included (a 1x1 convolution on a 1x1 map), are ur_conv2d_f32_res.
+ *
+ * ur_conv2d_f32_res: ur_conv2d_f32 with y = act(conv(x, w) + bias + res); res fp32 [N,OH,OW,Cout], not y, or NULL - with NULL it
+ *   is ur_conv2d_f32, bit for bit (ur_conv2d_f32 calls it so).
+ * ur_classify_preprocess: x fp32 NCHW [N,3,H,W] in [0,1] -> y fp32 NHWC [N,224,224,3]: separable resize, the W axis first (into
+ *   tmp, fp32 [N,3,H,224]), then the H axis, then (v - mean_c) / std_c with the ImageNet mean (.485, .456, .406) and std (.229,
+ *   .224, .225).  Each axis has a table on the device: first[224] (first input index of an output index), count[224] (its taps,
+ *   <= taps) and wt[224][taps] (fp32 weights, taps of one output consecutive, summed in ascending order).  The host builds them
+ *   (torch's antialiased bilinear rule in fp64, rounded to fp32); indices read from a table are clamped to the axis.  taps <= 64.
+ * ur_maxpool2d_pad_f32: 3x3 window, stride 2, padding 1 (-inf, not 0): x [N,H,W,C] -> y [N,(H-1)/2+1,(W-1)/2+1,C].
+ * ur_avgpool_f32: x [N,P,C] -> y [N,C], the mean over the P pixels: ascending order in fp64, rounded to fp32 once.
+ * ur_top1_counts: logits fp32 [N,C], labels int64 [N] (the CALLER checks 0 <= label < C) -> pred int64 [N], the argmax with ties
+ *   to the lowest index and NaN as the maximum (torch.argmax), and counts int64 [3][C] of THIS batch: tp_c (pred = label = c),
+ *   targets_c (label = c), predicted_c (pred = c).  Written, not accumulated. */
+int ur_conv2d_f32_res(const float* x, const float* w, const float* bias, const float* res, float* y, int N, int H, int W, int Cin, int Cout,
+                      int KH, int KW, int stride, int pad, int relu, ur_stream_t stream);
+int ur_classify_preprocess(const float* x, float* tmp, float* y, int N, int C, int H, int W, const int* first_w, const int* count_w,
+                           const float* wt_w, int taps_w, const int* first_h, const int* count_h, const float* wt_h, int taps_h,
+                           ur_stream_t stream);
+int ur_maxpool2d_pad_f32(const float* x, float* y, int N, int H, int W, int C, ur_stream_t stream);
+int ur_avgpool_f32(const float* x, float* y, int N, int P, int C, ur_stream_t stream);
+int ur_top1_counts(const float* logits, const long long* labels, int N, int C, long long* pred, long long* counts, ur_stream_t stream);
+
 /* ---- colour correction of a restored image (between the decoder's conv_out and the egress kernels) ----------------------
  * c fp32 NHWC [N,H,W,ld_c]: the restored image; src 16-bit NHWC [src_n,H,W,ld_s]: the image the encoder saw, image n is corrected
  * against source n % src_n (a task-major K*B batch against B sources); out fp32 NHWC [N,H,W,ld_c], not c.  Channels 0..2 are RGB;

@@ -127,6 +127,11 @@ SIGNATURES = {
     "ur_lpips_layer": (_I, [_P, _P, _I, _I, _I, _P, _LL, _P]),
     "ur_lpips_ws_size": (_LL, [_I, _I, _I]),
     "ur_lpips_finish": (_I, [_P, _LL, _I, _I, _I, _P, _P]),
+    "ur_conv2d_f32_res": (_I, [_P, _P, _P, _P, _P] + [_I] * 10 + [_P]),
+    "ur_classify_preprocess": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
+    "ur_maxpool2d_pad_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "ur_avgpool_f32": (_I, [_P, _P, _I, _I, _I, _P]),
+    "ur_top1_counts": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "ur_color_fix_wavelet": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "ur_color_fix_adain": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "ur_color_fix_adain_ws_bytes": (_SZ, [_I, _I, _I]),

@@ -11,7 +11,8 @@ reference src/main.py:17-28, configs/val.yaml:47-67, src/core/engine_unifie.py:2
 (`checkpoint.build_from_config`), caller (`runner.LitUniFIE`), synthetic data (`data.SyntheticImages`), and runs the
 validation loop.  One process per GPU: under `torch.distributed.run` the global batch is sharded over the ranks, the
 weights are broadcast from rank 0 and the restored shards all-gathered over RCCL.  There is no CPU path: `accelerator: cpu`
-is an error, not a fallback.  Prints one JSON line on rank 0.
+is an error, not a fallback.  Prints one JSON line on rank 0.  `validate --lpips` adds LPIPS, `validate --tasks ir,cls --classify
+NAME=ARCH:WEIGHTS.pth` the top-1 accuracy of a user-supplied ResNet on the `cls` output (unirestore_amd.classify); both are opt-in.
 """
 import argparse
 import json
@@ -171,29 +172,90 @@ def check_lpips_arg(lpips):
     return parts[0], parts[1]
 
 
+LABELLED_DATA = ("ImageListFiles", "CorruptedImageFiles", "DistortedImageFiles", "JpegImageFiles")      # take `labels: true`
+
+
+def check_classify_arg(classify):
+    """--classify NAME=ARCH:WEIGHTS.pth[,NAME=ARCH:OTHER.pth] (or a dict NAME -> (ARCH, path) | a loaded classify.ClassifierWeights)
+    -> {name: (arch, path) | ClassifierWeights}.  ValueError for a malformed item, an unknown arch, a missing file or a name given
+    twice.  ARCH is one of classify.ARCHS (torchvision's resnet18 / resnet50 / resnet101); the weights are the user's."""
+    from .classify import ARCHS
+    form = "--classify takes NAME=ARCH:WEIGHTS.pth[,NAME=ARCH:WEIGHTS.pth]: a result name, one of %s, a torchvision state dict" % sorted(ARCHS)
+    if isinstance(classify, str):
+        items = []
+        for part in classify.split(","):
+            name, eq, spec = part.partition("=")
+            arch, colon, path = spec.partition(":")
+            if not (name and eq and arch and colon and path):
+                raise ValueError(f"{form}; got {part!r}")
+            items.append((name, (arch, path)))
+    elif isinstance(classify, dict):
+        items = list(classify.items())
+    else:
+        raise ValueError(f"{form}; got {type(classify).__name__}")
+    if not items:
+        raise ValueError(form)
+    out = {}
+    for name, spec in items:
+        if name in out:
+            raise ValueError(f"--classify: the name {name!r} is given twice")
+        if isinstance(spec, (tuple, list)):
+            if len(spec) != 2:
+                raise ValueError(f"{form}; got {name!r}: {spec!r}")
+            arch, path = spec
+            if arch not in ARCHS:
+                raise ValueError(f"--classify {name}: unknown arch {arch!r}, choose from {sorted(ARCHS)}")
+            if not os.path.isfile(path):
+                raise ValueError(f"--classify {name}: no such file: {path}")
+            spec = (arch, path)
+        out[name] = spec
+    return out
+
+
+def check_classify_run(classify, tasks, r: dict):
+    """What a classifier run needs besides its weights, checked before the model is built: `cls` among the tasks (it is not added
+    silently, and `ir` stays required for PSNR) and a dataset that yields labels.  r = resolve(cfg)."""
+    if tasks is None or "cls" not in tasks:
+        raise ValueError(f"--classify scores the 'cls' output: pass --tasks with 'cls' in it, e.g. ir,cls (got "
+                         f"{'none' if tasks is None else ','.join(tasks)}; it is not added silently)")
+    cls_name = r["data_class"].rsplit(".", 1)[1]
+    if cls_name not in LABELLED_DATA or not r["data_args"].get("labels"):
+        raise ValueError(f"--classify needs labels, and data.{cls_name} yields none as configured: use an `lq hq label` list with one of "
+                         f"{list(LABELLED_DATA)} and set `labels: true` in data.init_args")
+
+
 def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_16bit=False, metrics_device="cpu", tasks=None,
-             model=None, lpips=None) -> dict:
+             model=None, lpips=None, classify=None) -> dict:
     """tasks: a list of task names - every batch is restored once and decoded for each of them (DiffUIE.forward_tasks).  PSNR / SSIM
     come from the "ir" output, so the list must hold "ir"; images_per_s counts input images.  model: a ready DiffUIE to use instead
     of building the config's.  With data.CorruptedImageFiles (and data.DistortedImageFiles: "snow/3") the result also holds by_corruption ("fog/3" -> psnr, ssim, images)
     and skipped (the subset members that are not built); with data.JpegImageFiles it holds by_corruption ("jpeg/10", the quality);
     with either, resize = [lo, hi] when the data's resize-down / resize-back wrapper is on.
     lpips: "ALEXNET.pth,LIN.pth", a pair of paths or a loaded lpips.LpipsWeights - the result gains val_lq/lpips and every
-    by_corruption entry lpips (AlexNet LPIPS in fp32 on the GPU; the weights are the user's, none ship with the project)."""
+    by_corruption entry lpips (AlexNet LPIPS in fp32 on the GPU; the weights are the user's, none ship with the project).
+    classify: "NAME=ARCH:WEIGHTS.pth,..." or {NAME: (ARCH, path) | classify.ClassifierWeights} - ResNet top-1 accuracy of the "cls"
+    output against the data's labels (tasks must hold "cls", the data must be built with labels: true): the result and every
+    by_corruption entry gain, per NAME, the macro accuracy (the reference's MulticlassAccuracy) and NAME_top1 (micro) of the
+    restored images (val_lq/NAME; by_corruption: NAME) and of the unrestored inputs (val_input/NAME; by_corruption: input/NAME)."""
     import torch
     if lpips is not None and isinstance(lpips, (str, tuple, list)):
         lpips = check_lpips_arg(lpips)                    # before the model is built
+    if classify is not None:
+        classify = check_classify_arg(classify)           # before the model is built, like everything check_classify_run checks
     r = resolve(cfg, allow_16bit=allow_16bit)
     if tasks is not None:
         tasks = list(tasks)
         if "ir" not in tasks:
             raise ValueError(f"--tasks {','.join(tasks)}: PSNR / SSIM are computed on the 'ir' output; add 'ir' to the list "
                              "(it is not added silently)")
+    if classify is not None:
+        check_classify_run(classify, tasks, r)
     from . import data as data_mod
     from .dist import all_gather_images, shard_range
     rank, world, dev, dist, lit = _start(r, hf_root, random_init, model, metrics_device=metrics_device, lpips_weights=lpips,
-                                         **r["caller_args"])
+                                         classifiers=classify, **r["caller_args"])
     sums = ("psnr", "ssim") + (("lpips",) if lpips is not None else ())          # the metric states, in all-reduce order
+    counts = [k for name in (classify or {}) for k in lit.classifier_keys(name)]  # the classifiers' int64 [3, classes] count states
     data = getattr(data_mod, r["data_class"].rsplit(".", 1)[1])(**r["data_args"])
     if data.batch_size < world:
         raise ValueError(f"data batch_size {data.batch_size} < world size {world}: every rank needs at least one image per batch")
@@ -219,8 +281,10 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
         finite = finite and bool(torch.isfinite(out).all()) and all(bool(torch.isfinite(v).all()) for v in by_task.values())
         before = dict(lit.totals)
         lit.update_metrics(by_task["ir"], batch[1])           # this rank's shard; reduced over the ranks below (fp64 PSNR / SSIM: untimed)
+        if classify is not None:
+            lit.update_classification(by_task["cls"], batch[0], batch[2])
         if by_corruption is not None:                     # the batch is homogeneous: its increment of the totals belongs to one key
-            acc = by_corruption.setdefault("%s/%d" % data.last, dict({k: 0.0 for k in sums}, images=0))
+            acc = by_corruption.setdefault("%s/%d" % data.last, dict({k: 0.0 for k in sums}, **{k: 0 for k in counts}, images=0))
             for k in acc:
                 acc[k] = acc[k] + (lit.totals[k] - before[k])
     if world > 1:                                         # the reference's metric states reduce with dist_reduce_fx="sum"
@@ -229,6 +293,11 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
                            for v in [lit.totals[k] for k in sums] + [float(lit.totals["images"])]])
         dist.all_reduce(tot)
         lit.totals.update({k: float(tot[i]) for i, k in enumerate(sums)}, images=int(tot[-1]))
+        if counts:                                        # appended to the reduced states: one more all-reduce, of integers
+            flat = torch.cat([lit.totals[k].to(dev).reshape(-1) for k in counts])
+            dist.all_reduce(flat)
+            for k, part in zip(counts, flat.split([lit.totals[k].numel() for k in counts])):
+                lit.totals[k] = part.view_as(lit.totals[k])
     res = dict(config=r["data_args"], dtype=r["dtype"], n_gpus=world, denoise_steps=r["model_kwargs"]["cnet"]["num_inference_steps"],
                images_per_s=(n_img / secs) if secs > 0 else None, output_finite=finite, **lit.metrics())
     if tasks is not None:
@@ -236,6 +305,11 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
     if by_corruption is not None:
         res["by_corruption"] = {k: dict({m: float(v[m]) / v["images"] for m in sums}, images=int(v["images"]))
                                 for k, v in by_corruption.items()}
+        from .classify import accuracy
+        for k, v in by_corruption.items():
+            for name in (classify or {}):
+                for prefix, key in zip(("", "input/"), lit.classifier_keys(name)):
+                    res["by_corruption"][k][f"{prefix}{name}"], res["by_corruption"][k][f"{prefix}{name}_top1"] = accuracy(*v[key])
         if hasattr(data, "skipped"):
             res["skipped"] = list(data.skipped)
         if data.resize is not None:
@@ -598,6 +672,10 @@ def main(argv=None):
                     help="where PSNR / SSIM run: cpu = host fp64 (default), gpu = the HIP metric kernels (fp64, no per-batch host sync)")
     ap.add_argument("--lpips", default=None, metavar="ALEXNET.pth,LIN.pth",
                     help="validate: also report LPIPS (AlexNet, fp32, on the GPU) from these two user-supplied weight files")
+    ap.add_argument("--classify", default=None, metavar="NAME=ARCH:WEIGHTS.pth[,...]",
+                    help="validate: also report ResNet top-1 accuracy of the 'cls' output (fp32, on the GPU) against the data's labels; "
+                         "ARCH is resnet18, resnet50 or resnet101, WEIGHTS a user-supplied torchvision state dict; needs --tasks with "
+                         "cls and a dataset built with labels: true")
     ap.add_argument("--tasks", default=None, metavar="ir,cls,seg",
                     help="restore every batch once and decode it for each of these tasks (forward_tasks); validate: must hold 'ir', which "
                          "feeds PSNR / SSIM; restore: one sub-folder of --output per task")
@@ -624,6 +702,8 @@ def main(argv=None):
     ap.add_argument("--quality", default=None, metavar="10,25,s3", help="jpeg: qualities 1..100 and / or s1..s5 (the reference's severities)")
     ap.add_argument("--subsampling", default="4:2:0", help="jpeg: 4:2:0 (Pillow's and the reference's default) or 4:4:4")
     a = ap.parse_args(argv)
+    if a.classify is not None and a.command != "validate":
+        ap.error("--classify belongs to validate")
     if a.command in FILE_COMMANDS:
         check, run, errors = FILE_COMMANDS[a.command]
         kw = dict(inp=a.input, output=a.output, batch=a.batch, resize=a.resize)
@@ -649,7 +729,14 @@ def main(argv=None):
             a.lpips = check_lpips_arg(a.lpips)
         except ValueError as e:
             ap.error(str(e))
+    tasks = [t for t in a.tasks.split(",") if t] if a.tasks is not None else None
     cfg = apply_color_fix(load_config(a.config, a.set), a.color_fix)
+    if a.classify is not None:
+        try:
+            a.classify = check_classify_arg(a.classify)
+            check_classify_run(a.classify, tasks, resolve(cfg, allow_16bit=a.allow_16bit))
+        except ValueError as e:
+            ap.error(str(e))
     if a.command == "print_config":
         print(yaml.safe_dump(cfg, sort_keys=False))
         print(json.dumps(resolve(cfg, allow_16bit=a.allow_16bit)))
@@ -661,7 +748,7 @@ def main(argv=None):
             print(json.dumps(res))
         return 0
     res = validate(cfg, hf_root=a.hf_root, max_batches=a.max_batches, allow_16bit=a.allow_16bit, metrics_device=a.metrics_device,
-                   tasks=[t for t in a.tasks.split(",") if t] if a.tasks is not None else None, lpips=a.lpips)
+                   tasks=tasks, lpips=a.lpips, classify=a.classify)
     if res is not None:
         print(json.dumps(res))
     return 0

@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void lpips_prep_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------ convolution
-// y[m][n] = act(sum_k A[m][k] * Wp[k][n] + bias[n]):  m = (image, oh, ow), k = (kh, kw, cin), n = cout.
+// y[m][n] = act(sum_k A[m][k] * Wp[k][n] + bias[n] (+ res[m][n])):  m = (image, oh, ow), k = (kh, kw, cin), n = cout.
 // Block = 128 (M) x 64 (N) outputs, K in tiles of 16; four waves, wave g owns rows 32g..32g+31 and both 32-column halves (two
 // 32x32 accumulators, one A read per two MFMAs).  Both operands sit in LDS K-major ([k][m], [k][n]), which is exactly what the
 // 32x32x2 operand map wants: lane l reads A[k0 + (l >> 5)][m = l & 31] - 32 consecutive floats per half wave, no bank conflict.
@@ -67,6 +67,7 @@ struct ConvArgs {
   const float* x;
   const float* w;
   const float* bias;
+  const float* res;      // [M][Cout] added after the bias, or null (ur_conv2d_f32: always null)
   float* y;
   int H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, K, nk, ldw, relu, M;
 };
@@ -175,7 +176,8 @@ __global__ __launch_bounds__(256) void conv2d_f32_kernel(ConvArgs p) {
     for (int r = 0; r < 16; ++r) {
       const int m = m0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
       if (m < p.M) {
-        const float v = (sum[j][r] + acc[j][r]) + bv;
+        float v = (sum[j][r] + acc[j][r]) + bv;
+        if (p.res) v += p.res[(long long)m * p.Cout + n];
         p.y[(long long)m * p.Cout + n] = p.relu ? fmaxf(v, 0.f) : v;
       }
     }
@@ -316,8 +318,8 @@ int ur_conv2d_f32_wpack_dims(int Cin, int Cout, int KH, int KW, int* kpad, int* 
   return 0;
 }
 
-int ur_conv2d_f32(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int KH, int KW,
-                  int stride, int pad, int relu, ur_stream_t stream) {
+int ur_conv2d_f32_res(const float* x, const float* w, const float* bias, const float* res, float* y, int N, int H, int W, int Cin, int Cout,
+                      int KH, int KW, int stride, int pad, int relu, ur_stream_t stream) {
   UR_REQUIRE(x && w && bias && y, "null pointer");
   UR_REQUIRE(N >= 1 && H >= 1 && W >= 1, "N, H and W must be >= 1");
   UR_REQUIRE(Cin >= 1 && Cout >= 1 && KH >= 1 && KW >= 1, "Cin, Cout, KH and KW must be >= 1");
@@ -325,11 +327,12 @@ int ur_conv2d_f32(const float* x, const float* w, const float* bias, float* y, i
   UR_REQUIRE(stride >= 1 && pad >= 0, "stride must be >= 1 and pad >= 0");
   UR_REQUIRE(H + 2 * pad >= KH && W + 2 * pad >= KW, "the padded map is smaller than the filter");
   UR_REQUIRE(((uintptr_t)w & 15) == 0, "w must be 16-byte aligned");
+  UR_REQUIRE(res != y || !res, "res and y must not be the same buffer");
   const int OH = conv_out(H, KH, stride, pad), OW = conv_out(W, KW, stride, pad);
   const long long M = (long long)N * OH * OW;
   UR_REQUIRE(M <= INT_MAX - CV_BM && (long long)N * H * W <= INT_MAX, "too many pixels: N*OH*OW and N*H*W must be below 2^31");
   ConvArgs p;
-  p.x = x; p.w = w; p.bias = bias; p.y = y;
+  p.x = x; p.w = w; p.bias = bias; p.res = res; p.y = y;
   p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.OH = OH; p.OW = OW;
   p.K = Cin * KH * KW;
   p.nk = (p.K + CV_BK - 1) / CV_BK;
@@ -339,12 +342,17 @@ int ur_conv2d_f32(const float* x, const float* w, const float* bias, float* y, i
   const dim3 grid((unsigned)((M + CV_BM - 1) / CV_BM), (unsigned)(p.ldw / CV_BN));
   UR_REQUIRE(grid.y <= 65535u, "Cout too large");
   hipStream_t s = (hipStream_t)stream;
-  ur::ProfScope prof("conv2d_f32", 2.0 * (double)M * Cout * p.K, 4.0 * ((double)N * H * W * Cin + (double)M * Cout), s);
+  ur::ProfScope prof("conv2d_f32", 2.0 * (double)M * Cout * p.K, 4.0 * ((double)N * H * W * Cin + (double)M * Cout * (res ? 2 : 1)), s);
   if (Cin % 4 == 0 && ((uintptr_t)x & 15) == 0)
     hipLaunchKernelGGL(conv2d_f32_kernel<4>, grid, dim3(256), 0, s, p);
   else
     hipLaunchKernelGGL(conv2d_f32_kernel<1>, grid, dim3(256), 0, s, p);
   return ur::check_launch("ur_conv2d_f32");
+}
+
+int ur_conv2d_f32(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int KH, int KW,
+                  int stride, int pad, int relu, ur_stream_t stream) {
+  return ur_conv2d_f32_res(x, w, bias, nullptr, y, N, H, W, Cin, Cout, KH, KW, stride, pad, relu, stream);
 }
 
 int ur_maxpool2d_f32(const float* x, float* y, int N, int H, int W, int C, ur_stream_t stream) {

@@ -2,7 +2,8 @@
 list files, `CorruptedImageFiles`, clean images corrupted on the GPU (unirestore_amd.corrupt), and `JpegImageFiles`, clean images
 JPEG-compressed on the GPU at a list of qualities (unirestore_amd.jpeg), and `DistortedImageFiles`, CorruptedImageFiles for glass blur,
 snow and elastic transform (unirestore_amd.distort).  The last three share `_DegradedImageFiles`: the constructor checks and the load /
-degrade / yield loop are written once there.
+degrade / yield loop are written once there.  The four file datasets take `labels=True`: gt is then the int64 labels of the list's
+third column (what a classifier is scored against) instead of None.
 
 `SyntheticImages` yields the evaluator's batch tuple `(lq, hq, gt, fname, task)` (reference
 src/core/base/eval_image_restoration.py:56) from seeded random images: hq = torch.rand (what the reference's own smoke
@@ -55,15 +56,39 @@ class SyntheticImages:
             yield lq[lo:hi].to(device), hq[lo:hi].to(device), None, names, self.task
 
 
+def read_labels(list_file: str) -> List[int]:
+    """The integer labels of an `lq hq label` list, one per pair line in file order (blank and `#` lines skipped, as every reader of
+    these lists does).  ValueError naming file and line for a line without a third column or with one that is no integer, and
+    for a folder: labels exist in three-column lists only."""
+    import os
+    if os.path.isdir(list_file):
+        raise ValueError(f"{list_file!r}: labels: true needs an `lq hq label` list file; a folder carries no labels")
+    out = []
+    with open(list_file) as f:
+        for ln, line in enumerate(f, 1):
+            cols = line.split()
+            if not cols or cols[0].startswith("#"):
+                continue
+            if len(cols) < 3:
+                raise ValueError(f"{list_file}:{ln}: labels: true needs `lq hq label`, got {line.strip()!r} (no label column)")
+            try:
+                out.append(int(cols[2]))
+            except ValueError:
+                raise ValueError(f"{list_file}:{ln}: the label {cols[2]!r} is not an integer") from None
+    return out
+
+
 class ImageListFiles:
     """Real pairs for `validate` (`data.class_path: unirestore_amd.data.ImageListFiles`): a text file with one `lq hq [label]`
     line per pair, paths relative to the list file's folder.  Yields the evaluator's tuple `(lq, hq, gt, fname, task)` with lq / hq
     fp32 NCHW in [0, 1] (u8 / 255, the reference's ToDtype(scale=True)); pairs are grouped by shape, list order kept inside a
-    group, so every batch is one tensor (the evaluator's centre crop makes nearly everything 512 x 512)."""
+    group, so every batch is one tensor (the evaluator's centre crop makes nearly everything 512 x 512).  labels=True: gt is an
+    int64 [B] tensor of the lines' third column (a classifier's targets) instead of None."""
 
-    def __init__(self, list_file: str, batch_size: int = 8, task: str = "ir", num_batches: int = None):
+    def __init__(self, list_file: str, batch_size: int = 8, task: str = "ir", num_batches: int = None, labels: bool = False):
         import os
         self.list_file, self.batch_size, self.task, self.num_batches = list_file, int(batch_size), task, num_batches
+        self.labels = read_labels(list_file) if labels else None
         base = os.path.dirname(os.path.abspath(list_file))
         self.pairs = []
         with open(list_file) as f:
@@ -103,7 +128,8 @@ class ImageListFiles:
             lq, hq = nchw([self.pairs[i][0] for i in idx]), nchw([self.pairs[i][1] for i in idx])
             if lq.shape != hq.shape:
                 raise ValueError(f"{self.list_file}: lq and hq of {self.pairs[idx[0]][0]!r}... differ in size: {tuple(lq.shape)} vs {tuple(hq.shape)}")
-            yield lq, hq, None, [os.path.splitext(os.path.basename(self.pairs[i][0]))[0] for i in idx], self.task
+            gt = None if self.labels is None else torch.tensor([self.labels[i] for i in idx], dtype=torch.int64)
+            yield lq, hq, gt, [os.path.splitext(os.path.basename(self.pairs[i][0]))[0] for i in idx], self.task
 
 
 class _DegradedImageFiles:
@@ -111,13 +137,14 @@ class _DegradedImageFiles:
     length and the loop over it.  A subclass gives `_plan()` -> the batches, each a tuple that ends in the batch's file indices,
     and `_degrade(hq, stems, *what)` -> (lq, label): `what` is the rest of that tuple, `label` what `last` holds after the batch."""
 
-    def __init__(self, source, batch_size, task, seed, num_batches, resize, min_side):
+    def __init__(self, source, batch_size, task, seed, num_batches, resize, min_side, labels=False):
         from . import resize as rz
         self.resize = None if resize is None else rz.check_range(resize, min_side)
         self.source, self.batch_size, self.task, self.seed, self.num_batches = source, int(batch_size), task, int(seed), num_batches
         if self.batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
         self.paths = corrupt.check_inputs(source)
+        self.labels = read_labels(source) if labels else None          # one per line of the list, the order of `paths`
         self.last = None
 
     def __len__(self):
@@ -138,7 +165,8 @@ class _DegradedImageFiles:
             stems = [corrupt.stem_of(self.paths[i]) for i in idx]
             hq = torch.stack([load_u8(self.paths[i]) for i in idx]).to(device)
             lq, self.last = self._degrade(hq, stems, *what)
-            yield nchw(lq), nchw(hq), None, stems, self.task
+            gt = None if self.labels is None else torch.tensor([self.labels[i] for i in idx], dtype=torch.int64)
+            yield nchw(lq), nchw(hq), gt, stems, self.task
 
 
 class CorruptedImageFiles(_DegradedImageFiles):
@@ -147,7 +175,8 @@ class CorruptedImageFiles(_DegradedImageFiles):
     name (unirestore_amd.corrupt.SUBSETS), a name, or a comma-separated string / list of names ("clean" only when it is named);
     `severity` an integer 1..5 or "mixed", the reference's per-image draw.  Every image's corruption, severity and randomness come
     from sha256 of (seed, file stem) alone.  Images are grouped by (shape, corruption, severity), so a batch is homogeneous; hq is
-    uploaded as u8 and corrupted there.  Yields `(lq, hq, None, names, task)` with fp32 NCHW tensors in [0, 1]; `last` holds the
+    uploaded as u8 and corrupted there.  Yields `(lq, hq, gt, names, task)` with fp32 NCHW tensors in [0, 1], gt None or, with
+    labels=True (an `lq hq label` list only), the int64 [B] labels of the list's third column; `last` holds the
     (corruption, severity) of the batch just yielded and `skipped` the subset members that are not built.  `resize` = [lo, hi]
     (lo >= 32) turns on the reference's resize-down / resize-back wrapper (corrupt.degrade): every image's short edge is drawn
     from [lo, hi) by (seed, stem) as well, lq keeps hq's shape; the reference's own range is [resolution // 4, resolution)."""
@@ -155,8 +184,8 @@ class CorruptedImageFiles(_DegradedImageFiles):
     _planner = corrupt                             # the module whose expand / degrade this class uses (DistortedImageFiles: distort)
 
     def __init__(self, source: str, corruptions="common", severity=3, batch_size: int = 8, task: str = "ir", seed: int = 42,
-                 num_batches: int = None, resize=None):
-        super().__init__(source, batch_size, task, seed, num_batches, resize, 32)
+                 num_batches: int = None, labels: bool = False, resize=None):
+        super().__init__(source, batch_size, task, seed, num_batches, resize, 32, labels)
         self.names = self._planner.expand(corruptions)
         self.skipped = corrupt.skipped(corruptions)
         self.severity = severity if severity == "mixed" else corrupt.check_severity(severity)
@@ -178,8 +207,8 @@ class DistortedImageFiles(CorruptedImageFiles):
     _planner = distort
 
     def __init__(self, source: str, corruptions="all", severity=3, batch_size: int = 8, task: str = "ir", seed: int = 42,
-                 num_batches: int = None, resize=None):
-        super().__init__(source, corruptions, severity, batch_size, task, seed, num_batches, resize)
+                 num_batches: int = None, labels: bool = False, resize=None):
+        super().__init__(source, corruptions, severity, batch_size, task, seed, num_batches, labels, resize)
         self.skipped = []
 
 
@@ -193,9 +222,9 @@ class JpegImageFiles(_DegradedImageFiles):
     (lo >= 16) turns on the reference's resize-down / resize-back wrapper (jpeg.degrade): every image's short edge is drawn from
     [lo, hi) by (`seed`, stem), the only use of `seed`; lq keeps hq's shape."""
 
-    def __init__(self, source: str, quality=(10, 25, 50), batch_size: int = 8, task: str = "ir", num_batches: int = None, resize=None,
-                 seed: int = 42):
-        super().__init__(source, batch_size, task, seed, num_batches, resize, jpeg.MIN_SIDE)
+    def __init__(self, source: str, quality=(10, 25, 50), batch_size: int = 8, task: str = "ir", num_batches: int = None,
+                 labels: bool = False, resize=None, seed: int = 42):
+        super().__init__(source, batch_size, task, seed, num_batches, resize, jpeg.MIN_SIDE, labels)
         specs = [s for s in quality.split(",") if s] if isinstance(quality, str) else \
             list(quality) if isinstance(quality, (list, tuple)) else [quality]
         self.qualities = []

@@ -1092,6 +1092,57 @@ def lpips(pred: torch.Tensor, target: torch.Tensor, weights) -> torch.Tensor:
     return _lpips.forward(pred, target, weights)
 
 
+def classify(images: torch.Tensor, weights) -> torch.Tensor:
+    """Logits [N, classes] (fp32, on the device) of fp32 NCHW images in [0,1], any H, W >= 1: the classification evaluator's
+    preprocess (antialiased bilinear resize to 224 x 224, ImageNet normalisation) and a ResNet, in exact fp32 on the GPU.  weights:
+    what classify.load_weights / classify.random_weights return.  An image's logits do not depend on its place in the batch, and
+    two calls give the same bits.  No host sync."""
+    from . import classify as _classify
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if not isinstance(images, torch.Tensor) or images.dtype != torch.float32 or images.ndim != 4:
+        raise ValueError(f"classify: images must be a 4-d fp32 NCHW tensor, got "
+                         f"{getattr(images, 'dtype', type(images))} {tuple(getattr(images, 'shape', ()))}")
+    if images.device != dev:
+        raise ValueError(f"classify: images is on {images.device}, not on the current device {dev}")
+    if not images.is_contiguous():
+        raise ValueError("classify: images must be contiguous")
+    n, c, h, w = images.shape
+    if n < 1 or c != 3 or h < 1 or w < 1:
+        raise ValueError(f"classify: needs [N>=1, 3, H>=1, W>=1] images, got {tuple(images.shape)}")
+    if not isinstance(weights, _classify.ClassifierWeights):
+        raise ValueError(f"classify: weights must come from classify.load_weights / classify.random_weights, got {type(weights).__name__}")
+    if weights.device != dev:
+        raise ValueError(f"classify: the weights are on {weights.device}, not on the current device {dev}")
+    return _classify.forward(images, weights)
+
+
+def top1(logits: torch.Tensor, labels: torch.Tensor):
+    """(pred, tp, targets, predicted) of one batch: pred int64 [N] = the argmax of logits fp32 [N,C] (ties to the lowest index, as
+    torch.argmax), and the three int64 [C] per-class counts of classify.accuracy - tp_c (pred = label = c), targets_c, predicted_c.
+    labels: an integer [N] tensor, on the host or the device; a label outside [0, C) is a ValueError raised before any launch
+    (checking device labels reads them back: one host sync)."""
+    from . import classify as _classify
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.ndim != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError(f"top1: logits must be a non-empty fp32 [N, C] tensor, got "
+                         f"{getattr(logits, 'dtype', type(logits))} {tuple(getattr(logits, 'shape', ()))}")
+    if logits.device != dev:
+        raise ValueError(f"top1: logits is on {logits.device}, not on the current device {dev}")
+    if not logits.is_contiguous():
+        raise ValueError("top1: logits must be contiguous")
+    if not isinstance(labels, torch.Tensor) or labels.dtype not in (torch.int64, torch.int32) or labels.shape != (logits.shape[0],):
+        raise ValueError(f"top1: labels must be an int64 / int32 [{logits.shape[0]}] tensor, got "
+                         f"{getattr(labels, 'dtype', type(labels))} {tuple(getattr(labels, 'shape', ()))}")
+    if labels.is_cuda and labels.device != dev:
+        raise ValueError(f"top1: labels is on {labels.device}, not on the host or the current device {dev}")
+    host = labels.cpu()
+    if int(host.min()) < 0 or int(host.max()) >= logits.shape[1]:
+        bad = [int(v) for v in host.tolist() if not 0 <= v < logits.shape[1]]
+        raise ValueError(f"top1: label {bad[0]} is outside [0, {logits.shape[1]}), the logits' classes")
+    pred, counts = _classify.top1_counts(logits, labels.to(device=dev, dtype=torch.int64).contiguous())
+    return pred, counts[0], counts[1], counts[2]
+
+
 def profile_enable(on: bool):
     check(lib.ur_profile_enable(int(on)))
 

@@ -95,7 +95,7 @@ class LitUniFIE:
 
     def __init__(self, model_kwargs: dict, save_image: bool = False, eval_mode: str = "FR", need_crop: bool = True,
                  dtype: str = "bf16", hf_root: str = None, model=None, metrics_device: str = "cpu", lpips_weights=None,
-                 **_ignored):
+                 classifiers=None, **_ignored):
         from . import checkpoint
         if metrics_device not in METRICS_DEVICES:
             raise ValueError(f"metrics_device={metrics_device!r}: choose from {METRICS_DEVICES}")
@@ -112,6 +112,23 @@ class LitUniFIE:
             from . import lpips
             self.lpips_weights = lpips_weights if isinstance(lpips_weights, lpips.LpipsWeights) else lpips.load_weights(*lpips_weights)
             self.totals["lpips"] = torch.zeros((), dtype=torch.float64, device=self.lpips_weights.device)
+        # Classifier scoring of the "cls" output (ResNet top-1 accuracy, exact fp32 HIP kernels) is off unless classifiers are given:
+        # {name: (arch, state-dict path) | classify.ClassifierWeights}.  Per name the totals hold the accuracy's counts as an int64
+        # [3, classes] device tensor (tp_c, targets_c, predicted_c) for the restored images ("cls/<name>") and for the unrestored
+        # inputs ("cls_input/<name>").  A total is REPLACED by a new tensor, never changed in place: callers keep the old one to
+        # take differences.
+        self.classifiers = {}
+        for name, spec in (classifiers or {}).items():
+            from . import classify
+            w = spec if isinstance(spec, classify.ClassifierWeights) else classify.load_weights(*spec)
+            self.classifiers[name] = w
+            for key in self.classifier_keys(name):
+                self.totals[key] = torch.zeros(3, w.num_classes, dtype=torch.int64, device=w.device)
+
+    @staticmethod
+    def classifier_keys(name: str):
+        """The two `totals` keys of classifier `name`: the restored images' counts, the unrestored inputs' counts."""
+        return f"cls/{name}", f"cls_input/{name}"
 
     def forward(self, inputs: Sequence[torch.Tensor], task: str, quantize: bool = False) -> List[torch.Tensor]:
         return forward(self.model, inputs, task, quantize=quantize)
@@ -122,13 +139,18 @@ class LitUniFIE:
     def validation_step(self, batch, eval_types: Sequence[str] = ("lq",), metrics: bool = True, tasks: Sequence[str] = None):
         """tasks (a list that holds "ir"): every input is restored once and decoded for each task (`forward_tasks`); the return
         value is then a list of {task: images}, and PSNR / SSIM still come from the "ir" output."""
-        lq, hq, _gt, _fname, _task = batch
+        lq, hq, gt, _fname, _task = batch
+        if self.classifiers and metrics and (tasks is None or "cls" not in tasks):
+            raise ValueError(f"tasks={None if tasks is None else list(tasks)}: the classifiers score the 'cls' output - pass tasks "
+                             "with 'cls' in it")
         if tasks is not None:
             if "ir" not in tasks:
                 raise ValueError(f"tasks={list(tasks)}: PSNR / SSIM are computed on the 'ir' output - add 'ir' to the list")
             outs, _ = validation_step(self.model, lq, hq, need_crop=self.need_crop, eval_types=eval_types, tasks=tasks)
             if metrics and hq is not None:
                 self.update_metrics(outs[-1]["ir"], hq)
+            if metrics and self.classifiers:
+                self.update_classification(outs[-1]["cls"], lq, gt)
             return outs
         # the IR evaluator always restores with the "ir" prompt (eval_image_restoration.py:70: self.forward(inputs, 'ir')), whatever
         # task tag the batch carries; task-driven decoding belongs to the downstream (MTL) evaluators, which are out of scope
@@ -212,10 +234,33 @@ class LitUniFIE:
             self._add_lpips(preds, tgt)
             self.totals["images"] += n
 
+    def update_classification(self, cls_preds: torch.Tensor, inputs: torch.Tensor, labels: torch.Tensor):
+        """The accuracy counts of one batch, for every classifier: of `cls_preds`, the quantised "cls" output (the tensor the
+        reference's evaluator hands to its classifiers), and of `inputs`, the unrestored lq images it was restored from (centre-
+        cropped as the restoration's input is when need_crop is on), so the two accuracies cover the same pixels.  labels: the
+        batch's int64 [N] targets.  Nothing when no classifier is configured."""
+        if not self.classifiers:
+            return
+        if labels is None:
+            raise ValueError("the classifiers need the batch's labels (gt is None): build the dataset with labels: true on an "
+                             "`lq hq label` list")
+        from . import ops
+        if self.need_crop:
+            inputs = crop_tensor(inputs)
+        for name, w in self.classifiers.items():
+            for key, images in zip(self.classifier_keys(name), (cls_preds, inputs)):
+                logits = ops.classify(images.to(device=w.device, dtype=torch.float32).contiguous(), w)
+                _pred, tp, targets, predicted = ops.top1(logits, labels)
+                self.totals[key] = self.totals[key] + torch.stack([tp, targets, predicted])
+
     def metrics(self) -> dict:
         n = max(self.totals["images"], 1)
         psnr_sum, ssim_sum = float(self.totals["psnr"]), float(self.totals["ssim"])     # (the one device read of the "gpu" totals)
         res = {"val_lq/psnr": psnr_sum / n, "val_lq/ssim": ssim_sum / n, "images": self.totals["images"]}
         if self.lpips_weights is not None:
             res["val_lq/lpips"] = float(self.totals["lpips"]) / n
+        for name in self.classifiers:                     # macro = the reference's MulticlassAccuracy(top_k=1); _top1 = micro
+            from .classify import accuracy
+            for prefix, key in zip(("val_lq", "val_input"), self.classifier_keys(name)):
+                res[f"{prefix}/{name}"], res[f"{prefix}/{name}_top1"] = accuracy(*self.totals[key])
         return res
