@@ -60,6 +60,20 @@ const char* ur_last_error(void);
  *   "virtual concat": x2), F.interpolate(nearest, 2x) in Upsample2D (upsample2x).
  * Epilogue order: acc (+bias[co]) -> act -> (*out_scale) -> (+residual) -> store.
  * Batched / grouped form: blockIdx.y = b in [0,nbatch): every base pointer advances by its bs_* stride.
+ * Size limits (checked in 64-bit arithmetic before any HIP call; a shape outside returns UR_E_INVALID naming ur_conv2d_nhwc):
+ *   - x, x2: N*H*W*max(ldx, ldx2) must be below 2^31 elements (32-bit element offsets).  The LDS-DMA kernels read the sources
+ *     through raw buffer descriptors whose byte offsets from 0xffffff00 up mean "read zero" (padding, ragged rows); the shapes
+ *     they take end below that byte (whole 8 x 32 patches or 8 x 8 / 16 x 16 images: a multiple of 512 elements), the pure-GEMM
+ *     LDS-DMA launchers (g1_*, gemm_256x*) are chosen only while M*ldx + K < 2^31 - 256, and every other shape runs on kernels
+ *     that read through 64-bit pointers.
+ *   - w: Cout*ldw must be below 2^31 - 256 elements (the same descriptors: the last weight rows must start below that byte).
+ *   - output rows M = N*OH*OW must be below 2^31 - 512 (int row indices; a tile may start up to 256 rows short of M).  Defensive:
+ *     with OH, OW derived from H, W the bound on x already implies it.
+ *   - the tile grid of the planned launcher (ur_conv2d_plan_launch; row tiles of 64 to 256 rows x column tiles of 32 to 320
+ *     columns) must be below 2^23 workgroups: a grid of 2^32 threads or more wraps silently, and workgroups have up to 512 threads.
+ *   - y, yt, residual, bias rows (bias_img_stride), gn_part, gn_ab, row_stats, ln_stats and the split-K planes of the workspace are
+ *     addressed with 64-bit offsets: no element limit of their own (M*ldy may exceed 2^31; tests/large_cases.py runs it).
+ *   ur_gemm_bias_act: 0 < M < 2^31, then the same limits; ur_groupconv3x3_nhwc: the same limits with ldx = Cg*groups.
  */
 typedef struct ur_conv_desc {
   const void* x;        /* bf16 [N,H,W,ldx]; first C1 input channels */
@@ -161,6 +175,11 @@ int ur_groupconv3x3_nhwc(const void* x, const void* w, const float* bias, void* 
  * Arguments are checked on the host before any arithmetic on them and before any launch: a null required pointer, a non-positive
  * N / HW / rows / C / C1 / G (C2 when x2 / part2 is given), C % 8 != 0, C % G != 0 or an unknown dtype returns UR_E_INVALID
  * (the size queries return UR_E_INVALID / the bytes of one partial).
+ * Size limits: images run along the grid's y dimension, so N <= 65535 for ur_groupnorm_stats / ur_instnorm_stats /
+ *   ur_groupnorm_finalize / ur_groupnorm_apply_act / ur_groupnorm_nhwc / ur_avgpool_hw (UR_E_INVALID beyond); N*HW*C itself has no
+ *   limit (64-bit offsets; run past 2^31 elements in tests/large_cases.py).  ur_layernorm_rows and ur_softmax_rows_f32: rows is
+ *   a long long without a limit of its own (more rows than one grid holds - 2^28 and 2^24 - run as several launches), and
+ *   neither have rows*C / rows*ldp.
  * Replaces: nn.GroupNorm(32,C)+SiLU in every ResnetBlock2D / conv_norm_out, Transformer2D / Attention
  *   pre-norms, AdaNAFV2.group_norm (cfrm.py:19), nn.InstanceNorm2d (taskeditor.py:31,40,49), nn.AdaptiveAvgPool2d(1).
  */
@@ -267,7 +286,10 @@ int ur_csce_fused(const void* x, const void* cond, const void* stream_w, size_t 
 
 /* ---- HBM-bound stencils / reductions / elementwise ---------------------------------------------*/
 /* Every entry point of this block returns UR_E_INVALID for a null required pointer, an empty tensor (non-positive N, H, W, HW,
- * rows, M, B, T, D, C or G), C % 8 != 0 (16-bit tensors) or an unknown dtype - checked on the host before anything is launched. */
+ * rows, M, B, T, D, C or G), C % 8 != 0 (16-bit tensors) or an unknown dtype - checked on the host before anything is launched.
+ * Size limits: ur_dwconv3x3_nhwc, ur_scale_channels, ur_scale_channels_fanout, ur_axpy_channels and ur_spade_modulate index with
+ * 64-bit grid-stride loops over at most 8192 workgroups: each dimension must fit its int / long long argument, their products
+ * (N*H*W*C, K*B*HW*C, rows*C, rows*ldgb) have no limit (run past 2^31 elements in tests/large_cases.py). */
 /* depthwise 3x3 (pad 1) + bias, optional SimpleGate (out channels C/2): nafnet_arch.py:41-49,22-25 */
 int ur_dwconv3x3_nhwc(const void* x, const float* w9c, const float* bias, void* y, int N, int H, int W, int C,
                       int gate, int dtype, ur_stream_t stream);
@@ -306,6 +328,10 @@ int ur_vec_mul_group(const float* a, const float* b, float* out, int N, int C, i
  * padding not smaller than the resized image, a crop window outside the input, a tile larger than the latent, slot_bytes smaller
  * than a canvas-sized image or an unknown dtype - checked on the host before any arithmetic on the arguments and before anything is
  * launched. */
+/* Size limits: every kernel of this block runs a 64-bit grid-stride loop over pixels (at most 8192 workgroups) and forms every
+ * offset in 64 bits.  Each dimension must fit its int / long long argument; the products N*H*W, N*C*H*W, N*XH*XW*ld, N*C*OH*OW, M*ld,
+ * M*Cpad and N*slot_bytes have no limit (tests/large_cases.py runs ur_nhwc_to_nchw_f32, ur_nchw_f32_to_nhwc, ur_f32_to_bf16_scaled,
+ * ur_image_unpad_resize_nchw and ur_image_u8_egress with an fp32 side past 2^32 bytes). */
 /* images NCHW fp32 in [0,1] -> NHWC 16-bit (x*2-1), channels padded with zeros to Cpad (autoencoder.py:149) */
 int ur_image_to_nhwc(const float* img, void* y, int N, int C, int H, int W, int Cpad, int dtype, ur_stream_t stream);
 /* NHWC fp32/16-bit [N,H,W,ld] first C channels -> NCHW fp32, out = x*mul+add (autoencoder.py:175) */

@@ -143,6 +143,30 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, ur_conv_plan* pl
   UR_REQUIRE(!d->y || (d->out_f32 ? d->ldy % 4 == 0 : d->ldy % 4 == 0), "ldy%4");
   UR_REQUIRE(!d->residual || d->ldr % 4 == 0, "ldr%4");
   UR_REQUIRE(!d->yt || (d->t_rows > 0 && d->n_split % 4 == 0 && !pair), "bad transposed-output spec");
+  // Size limits (include/unirestore_hip.h, "size limits"), checked before any int product of the dimensions, one factor at a time
+  // (every partial product is below 2^31 before the next int is multiplied in, so no 64-bit product can wrap either):
+  //  * output rows M = N * OH * OW: row indices are int and a tile may start up to one tile (<= 256 rows) short of M and run past it.
+  //    (OH and OW are the caller's: nothing ties them to H and W, so this is not implied by the bound on x.  Defensive: no caller
+  //    of this repository comes near it.);
+  //  * x, x2 and w are read through 32-bit element offsets.  (The LDS-DMA kernels read them through raw buffer descriptors whose range
+  //    check treats byte offsets >= 0xffffff00 as "read zero" (IG_OOB, csrc/igemm_impl.h), so a source of theirs must end below that
+  //    byte.  It always does: the halo / whole-image kernels take images of OH % 8 == 0, OW % 32 == 0 or 8 x 8 / 16 x 16 pixels with
+  //    ldx % 8 == 0, whose element count is a multiple of 512, and the pure-GEMM ones keep M * ldx + K < 2^31 - 256 in dispatch_conv;
+  //    the kernels that take any other shape use 64-bit pointers.  tests/test_large_tensors_cpu.py pins this.)
+  //    The WEIGHTS of the pure-GEMM LDS-DMA kernels had no such guard: with Cout * ldw = 2^31 - 32 in rows of 24 elements the last
+  //    four rows started past that byte and read as zeros (those output columns came out as their bias).  Hence the same margin
+  //    for w as dispatch_conv keeps for x: a row's last lane offset is its start + 112 bytes, below 0xffffff00 for every ldw.
+  //    y, yt, residual, bias rows, the statistics planes and the split-K planes are addressed with 64-bit offsets: no bound of their own;
+  //  * a grid of 2^32 threads or more is not refused by the runtime - it wraps, and the workgroups past the wrap never run - so the
+  //    tile grid of the launcher that is planned must stay below 2^23 workgroups (checked below, once the plan has counted its tiles).
+  UR_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0, "N, H, W must be positive");
+  UR_REQUIRE((long long)d->N * d->OH < (1ll << 31) && (long long)d->N * d->OH * d->OW < (1ll << 31) - 512,
+             "ur_conv2d_nhwc: too many output rows: N * OH * OW must be below 2^31 - 512");
+  UR_REQUIRE(d->ldx > 0 && d->ldx2 >= 0 && d->ldw > 0 && (long long)d->N * d->H < (1ll << 31) && (long long)d->N * d->H * d->W < (1ll << 31) &&
+                 (long long)d->N * d->H * d->W * (long long)std::max(d->ldx, d->ldx2) < (1ll << 31),
+             "ur_conv2d_nhwc: tensor too large for 32-bit element offsets: N * H * W * max(ldx, ldx2) must be below 2^31");
+  UR_REQUIRE((long long)d->Cout * d->ldw < (1ll << 31) - 256,
+             "ur_conv2d_nhwc: weights too large for 32-bit element offsets: Cout * ldw must be below 2^31 - 256");
 
   ConvK k;
   k.x = (const uint16_t*)d->x; k.x2 = (const uint16_t*)d->x2; k.w = (const uint16_t*)d->w; k.bias = d->bias;
@@ -157,8 +181,6 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, ur_conv_plan* pl
   k.M = d->N * d->OH * d->OW; k.Ktot = d->KH * d->KW * k.Cin; k.nk = (k.Ktot + 63) / 64; k.nbatch = d->nbatch;
   k.bs_x = d->bs_x; k.bs_x2 = d->bs_x2; k.bs_w = d->bs_w; k.bs_bias = d->bs_bias; k.bs_y = d->bs_y; k.bs_r = d->bs_r; k.bias_img = d->bias_img_stride;
   UR_REQUIRE(k.M > 0, "empty problem");
-  UR_REQUIRE((long long)d->N * d->H * d->W * (long long)std::max(d->ldx, d->ldx2) < (1ll << 31) &&
-                 (long long)d->Cout * d->ldw < (1ll << 31), "tensor too large for 32-bit element offsets");
 
   k.kcm = d->k_chunk_major; k.wf = (const uint16_t*)d->w_frag; k.wmajor = 0; k.xgm = 0; k.xbn = 0; k.patch_tw = 0;
   UR_REQUIRE(!k.kcm || (k.Cin % 64 == 0 && d->C1 % 64 == 0), "k_chunk_major needs C1 and C1+C2 to be multiples of 64");
@@ -185,6 +207,9 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, ur_conv_plan* pl
     fam = interned.emplace(buf, 0).first->first.c_str();
   }
   const ConvLaunch launch = dispatch_conv(k, pair, d->workspace_bytes);
+  // (the grid's x dimension is tiles_m * tiles_n; groups and K splits sit in y and z.  Workgroups have at most 512 threads.)
+  UR_REQUIRE((long long)k.tiles_m * k.tiles_n < (1ll << 23),
+             "ur_conv2d_nhwc: tile grid too large: the planned launcher's row tiles x column tiles must be below 2^23");
   // Grouped 3x3 convolutions whose groups are halo-kernel sized (chunk-major weights, >= 64 channels in, a multiple of 128 out):
   // one halo launch per group on the channel slice instead of the batched generic kernel, which gathers 64-byte runs per pixel and
   // tap (CFRM's AdaNAFV2.group_conv, densified to 128-channel blocks by the caller: 2.19 ms -> 4 x ~0.2 ms at 256 x 256 x 512)

@@ -291,6 +291,11 @@ int gn_stats_launch(const void* x, float* part, int N, int HW, int C, int dtype,
 }
 }  // namespace ur
 
+// Workgroups of 256 threads per launch of the row kernels: a grid of 2^32 threads or more is not refused by the runtime, it wraps
+// (gridDim.x * blockDim.x is kept in 32 bits) and the workgroups past the wrap never run.
+constexpr long long UR_MAX_BLOCKS = 1ll << 23;
+constexpr int UR_GN_MAX_N = 65535;      // images are gridDim.y of the statistics / finalize / apply launches
+
 extern "C" {
 
 int ur_groupnorm_stats_parts(int N, int HW, int C) { return (N > 0 && HW > 0 && C > 0 && C % 8 == 0) ? ur::gn_stats_parts(N, HW, C) : UR_E_INVALID; }
@@ -299,6 +304,7 @@ size_t ur_groupnorm_ab_bytes(int N, int C) { return (size_t)N * C * 2 * sizeof(f
 
 int ur_groupnorm_stats(const void* x, float* part, int N, int HW, int C, int dtype, ur_stream_t stream) {
   UR_REQUIRE(x && part && N > 0 && HW > 0 && C > 0 && C % 8 == 0, "bad args");
+  UR_REQUIRE(N <= UR_GN_MAX_N, "N must not exceed 65535 (images run along the grid's y dimension)");
   UR_REQUIRE_DT(dtype);
   hipStream_t s = (hipStream_t)stream;
   ur::ProfScope prof("groupnorm_stats", 0.0, 2.0 * N * HW * (double)C, s);
@@ -313,6 +319,7 @@ int ur_groupnorm_finalize(const float* part1, int parts1, int C1, const float* p
   const int C = C1 + (part2 ? C2 : 0);
   UR_REQUIRE(part1 && parts1 > 0 && C1 > 0 && (!part2 || (parts2 > 0 && C2 > 0)), "bad partial planes");
   UR_REQUIRE(G > 0 && C % G == 0 && N > 0 && HW > 0 && (ab || mean_out), "bad args");
+  UR_REQUIRE(N <= UR_GN_MAX_N, "N must not exceed 65535 (images run along the grid's y dimension)");
   hipStream_t s = (hipStream_t)stream;
   const int cpg = C / G;
   const long long entries = (long long)cpg * std::max(parts1, part2 ? parts2 : 0);
@@ -326,6 +333,7 @@ int ur_groupnorm_finalize(const float* part1, int parts1, int C1, const float* p
 int ur_groupnorm_apply_act(const void* x, const void* x2, void* y, const float* ab, int N, int HW, int C1, int C2, int silu,
                            int dtype, ur_stream_t stream) {
   UR_REQUIRE(x && y && ab && N > 0 && HW > 0, "null pointer / empty");
+  UR_REQUIRE(N <= UR_GN_MAX_N, "N must not exceed 65535 (images run along the grid's y dimension)");
   UR_REQUIRE_DT(dtype);
   UR_REQUIRE(C1 > 0 && C1 % 8 == 0 && (!x2 || (C2 > 0 && C2 % 8 == 0)), "C1 (and C2 with x2) must be positive multiples of 8");   // before gn_geom: 0 % 0
   const int C = C1 + (x2 ? C2 : 0);
@@ -368,6 +376,7 @@ int ur_groupnorm_nhwc(const void* x, const void* x2, void* y, const float* gamma
   // every shape check BEFORE gn_stats_parts (gn_geom divides by C / 8 and its divisors)
   UR_REQUIRE(N > 0 && HW > 0 && C1 > 0 && C1 % 8 == 0 && (!x2 || (C2 > 0 && C2 % 8 == 0)), "N, HW, C1 (and C2 with x2) must be positive, C % 8 == 0");
   UR_REQUIRE(G > 0 && (C1 + (x2 ? C2 : 0)) % G == 0, "G must be positive and divide C1 + C2");
+  UR_REQUIRE(N <= UR_GN_MAX_N, "N must not exceed 65535 (images run along the grid's y dimension)");
   UR_REQUIRE((!pre1 || parts1 > 0) && (!x2 || !pre2 || parts2 > 0), "producer-side partial planes need parts > 0");
   UR_REQUIRE((pre1 && (!x2 || pre2)) || ws, "a source without producer-side partials needs the ws scratch");
   // statistics pass only for sources whose producer left no partial plane (ws holds x's plane, then x2's)
@@ -392,6 +401,7 @@ int ur_groupnorm_nhwc(const void* x, const void* x2, void* y, const float* gamma
 /* mean over HW -> fp32 [N][C] (nn.AdaptiveAvgPool2d(1)): the statistics pass + a finalize with one group per channel */
 int ur_avgpool_hw(const void* x, float* out, int N, int HW, int C, float* ws, int dtype, ur_stream_t stream) {
   UR_REQUIRE(x && out && ws && N > 0 && HW > 0 && C > 0 && C % 8 == 0, "bad args");
+  UR_REQUIRE(N <= UR_GN_MAX_N, "N must not exceed 65535 (images run along the grid's y dimension)");
   UR_REQUIRE_DT(dtype);
   int rc = ur_groupnorm_stats(x, ws, N, HW, C, dtype, stream);
   if (rc != UR_OK) return rc;
@@ -407,14 +417,18 @@ int ur_layernorm_rows(const void* x, void* y, const float* gamma, const float* b
   ur::ProfScope prof("layernorm", 0.0, 4.0 * rows * (double)C, s);
   const int vpl = (C / 8 + 63) / 64;
   constexpr int R = 4;
-  dim3 grid((unsigned)((rows + 4 * R - 1) / (4 * R))), block(256);
-  const uint16_t* xi = (const uint16_t*)x;
-  uint16_t* yo = (uint16_t*)y;
-  switch (vpl) {
-    case 1: UR_DT_SWITCH(dtype, hipLaunchKernelGGL((ln_rows_kernel<1, R, F16>), grid, block, 0, s, xi, yo, gamma, beta, rows, C, eps)); break;
-    case 2: UR_DT_SWITCH(dtype, hipLaunchKernelGGL((ln_rows_kernel<2, R, F16>), grid, block, 0, s, xi, yo, gamma, beta, rows, C, eps)); break;
-    case 3: UR_DT_SWITCH(dtype, hipLaunchKernelGGL((ln_rows_kernel<3, R, F16>), grid, block, 0, s, xi, yo, gamma, beta, rows, C, eps)); break;
-    default: UR_DT_SWITCH(dtype, hipLaunchKernelGGL((ln_rows_kernel<4, R, F16>), grid, block, 0, s, xi, yo, gamma, beta, rows, C, eps)); break;
+  // one launch per UR_MAX_BLOCKS workgroups of 4 * R rows (a grid of >= 2^32 threads wraps: see UR_MAX_BLOCKS)
+  for (long long r0 = 0; r0 < rows; r0 += UR_MAX_BLOCKS * 4 * R) {
+    const long long nr = std::min<long long>(rows - r0, UR_MAX_BLOCKS * 4 * R);
+    dim3 grid((unsigned)((nr + 4 * R - 1) / (4 * R))), block(256);
+    const uint16_t* xi = (const uint16_t*)x + r0 * C;
+    uint16_t* yo = (uint16_t*)y + r0 * C;
+    switch (vpl) {
+      case 1: UR_DT_SWITCH(dtype, hipLaunchKernelGGL((ln_rows_kernel<1, R, F16>), grid, block, 0, s, xi, yo, gamma, beta, nr, C, eps)); break;
+      case 2: UR_DT_SWITCH(dtype, hipLaunchKernelGGL((ln_rows_kernel<2, R, F16>), grid, block, 0, s, xi, yo, gamma, beta, nr, C, eps)); break;
+      case 3: UR_DT_SWITCH(dtype, hipLaunchKernelGGL((ln_rows_kernel<3, R, F16>), grid, block, 0, s, xi, yo, gamma, beta, nr, C, eps)); break;
+      default: UR_DT_SWITCH(dtype, hipLaunchKernelGGL((ln_rows_kernel<4, R, F16>), grid, block, 0, s, xi, yo, gamma, beta, nr, C, eps)); break;
+    }
   }
   return ur::check_launch("ur_layernorm_rows");
 }
@@ -424,7 +438,12 @@ int ur_softmax_rows_f32(const float* sm, void* p, long long rows, int cols, int 
   UR_REQUIRE_DT(dtype);
   hipStream_t s = (hipStream_t)stream;
   ur::ProfScope prof("softmax_rows", 0.0, rows * (double)cols * 6.0, s);
-  UR_DT_SWITCH(dtype, hipLaunchKernelGGL(softmax_rows_kernel<F16>, dim3((unsigned)rows), dim3(256), 0, s, sm, (uint16_t*)p, cols, ldp));
+  // one workgroup per row, one launch per UR_MAX_BLOCKS rows: 2^24 or more workgroups of 256 threads in one grid wrap, and the rows
+  // past the wrap were never written (found at 29.8 M rows by tests/test_large_tensors_gpu.py)
+  for (long long r0 = 0; r0 < rows; r0 += UR_MAX_BLOCKS) {
+    const long long nr = std::min<long long>(rows - r0, UR_MAX_BLOCKS);
+    UR_DT_SWITCH(dtype, hipLaunchKernelGGL(softmax_rows_kernel<F16>, dim3((unsigned)nr), dim3(256), 0, s, sm + r0 * cols, (uint16_t*)p + r0 * ldp, cols, ldp));
+  }
   return ur::check_launch("ur_softmax_rows_f32");
 }
 
