@@ -473,6 +473,40 @@ int ur_maxpool2d_pad_f32(const float* x, float* y, int N, int H, int W, int C, u
 int ur_avgpool_f32(const float* x, float* y, int N, int P, int C, ur_stream_t stream);
 int ur_top1_counts(const float* logits, const long long* labels, int N, int C, long long* pred, long long* counts, ur_stream_t stream);
 
+/* ---- segmenter scoring of the seg output (RefineNet-LW mIoU; exact fp32, NHWC, no atomics, fixed-order sums) ----------------
+ * The network's convolutions are ur_conv2d_f32_res; its residual input carries the head's `x + up(y)` and `top + x` sums.
+ *
+ * An align_corners=True axis table (host-built in fp64): idx[n_out] = the first source index of an output index, wt[n_out][2] =
+ *   the fp32 weights of sources idx and idx + 1.  Indices read from a table are clamped to the axis.  A pixel is
+ *   h0 * (w0 * x00 + w1 * x01) + h1 * (w0 * x10 + w1 * x11), so weights (1, 0) copy a source whose neighbours (right, below) are
+ *   finite bit for bit - but for a -0.0, which a non-negative neighbour turns into +0.0; a NaN or infinite neighbour makes the
+ *   result NaN (0 x inf), as in torch's own resize.
+ * ur_seg_prep: x fp32 NCHW [N,3,H,W] in [0,1] -> y fp32 NHWC [N,OH,OW,3]: the bilinear resize, then v * 255 - mean_c with the
+ *   mean (123.68, 116.779, 103.939) of R, G, B, written in B, G, R order.
+ * ur_upsample_bilinear_ac_f32: x [N,h,w,C] -> y [N,H,W,C], any C.
+ * ur_maxpool5_f32: 5x5 window, stride 1, padding 2 (-inf): x [N,H,W,C] -> y of the same shape.
+ * ur_add_f32: y[i] = a[i] + b[i] over n fp32 values; y is neither a nor b.
+ * ur_seg_tta_argmax: nmaps (1..3) logit maps m_k fp32 [N,h_k,w_k,C], 1 <= C <= 255 (unused maps NULL, sizes ignored) -> pred
+ *   uint8 [N,H,W]: per pixel and class every map is sampled bilinearly, the samples averaged as ((a + b) + c) / nmaps, and the
+ *   best class kept - ties to the lowest index, NaN as the maximum (torch.argmax).  The tables hold the maps' axes one after the
+ *   other: idx_h [nmaps][H], wt_h [nmaps][H][2], idx_w [nmaps][W], wt_w [nmaps][W][2].  avg: NULL, or fp32 [N,H,W,C] that
+ *   receives the averaged logits (for tests; without it no full-resolution logit tensor exists anywhere).
+ * ur_seg_confusion: pred uint8 [P], target uint8 [P] (target_i64 = 0) or int64 [P] (1) -> conf int64 [C][C], conf[t][p] = the
+ *   pixels with target t and prediction p, over the pixels with 0 <= t < C, t != ignore_index and p < C.  Written, not
+ *   accumulated.  ws: ur_seg_confusion_ws_bytes(P, C) bytes (0 for invalid arguments) of per-block counts. */
+int ur_seg_prep(const float* x, float* y, int N, int C, int H, int W, int OH, int OW, const int* idx_h, const float* wt_h, const int* idx_w,
+                const float* wt_w, ur_stream_t stream);
+int ur_upsample_bilinear_ac_f32(const float* x, float* y, int N, int h, int w, int C, int H, int W, const int* idx_h, const float* wt_h,
+                                const int* idx_w, const float* wt_w, ur_stream_t stream);
+int ur_maxpool5_f32(const float* x, float* y, int N, int H, int W, int C, ur_stream_t stream);
+int ur_add_f32(const float* a, const float* b, float* y, long long n, ur_stream_t stream);
+int ur_seg_tta_argmax(const float* m0, const float* m1, const float* m2, int nmaps, int N, int C, int h0, int w0, int h1, int w1, int h2, int w2,
+                      int H, int W, const int* idx_h, const float* wt_h, const int* idx_w, const float* wt_w, unsigned char* pred, float* avg,
+                      ur_stream_t stream);
+long long ur_seg_confusion_ws_bytes(long long P, int C);
+int ur_seg_confusion(const unsigned char* pred, const void* target, int target_i64, long long P, int C, int ignore_index, void* ws,
+                     long long ws_bytes, long long* conf, ur_stream_t stream);
+
 /* ---- colour correction of a restored image (between the decoder's conv_out and the egress kernels) ----------------------
  * c fp32 NHWC [N,H,W,ld_c]: the restored image; src 16-bit NHWC [src_n,H,W,ld_s]: the image the encoder saw, image n is corrected
  * against source n % src_n (a task-major K*B batch against B sources); out fp32 NHWC [N,H,W,ld_c], not c.  Channels 0..2 are RGB;

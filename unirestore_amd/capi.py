@@ -132,6 +132,13 @@ SIGNATURES = {
     "ur_maxpool2d_pad_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "ur_avgpool_f32": (_I, [_P, _P, _I, _I, _I, _P]),
     "ur_top1_counts": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "ur_seg_prep": (_I, [_P, _P] + [_I] * 6 + [_P, _P, _P, _P, _P]),
+    "ur_upsample_bilinear_ac_f32": (_I, [_P, _P] + [_I] * 6 + [_P, _P, _P, _P, _P]),
+    "ur_maxpool5_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "ur_add_f32": (_I, [_P, _P, _P, _LL, _P]),
+    "ur_seg_tta_argmax": (_I, [_P, _P, _P] + [_I] * 11 + [_P, _P, _P, _P, _P, _P, _P]),
+    "ur_seg_confusion_ws_bytes": (_LL, [_LL, _I]),
+    "ur_seg_confusion": (_I, [_P, _P, _I, _LL, _I, _I, _P, _LL, _P, _P]),
     "ur_color_fix_wavelet": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "ur_color_fix_adain": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "ur_color_fix_adain_ws_bytes": (_SZ, [_I, _I, _I]),

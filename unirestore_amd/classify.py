@@ -28,7 +28,15 @@ def conv_plan(arch: str):
     """[(conv key, bn key, Cout, Cin, kernel, stride, pad)] of every convolution of `arch`, in state-dict order."""
     if arch not in ARCHS:
         raise ValueError(f"unknown classifier arch {arch!r}: choose from {sorted(ARCHS)}")
-    kind, depths = ARCHS[arch]
+    return _plan(*ARCHS[arch])
+
+
+def bottleneck_plan(depths):
+    """conv_plan of a bottleneck ResNet with `depths` blocks per stage (segment.py's backbones; tests build (1, 1, 1, 1))."""
+    return _plan("bottleneck", tuple(depths))
+
+
+def _plan(kind, depths):
     exp = EXPANSION[kind]
     plan = [("conv1", "bn1", 64, 3, 7, 2, 3)]
     cin = 64

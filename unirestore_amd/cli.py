@@ -12,7 +12,8 @@ reference src/main.py:17-28, configs/val.yaml:47-67, src/core/engine_unifie.py:2
 validation loop.  One process per GPU: under `torch.distributed.run` the global batch is sharded over the ranks, the
 weights are broadcast from rank 0 and the restored shards all-gathered over RCCL.  There is no CPU path: `accelerator: cpu`
 is an error, not a fallback.  Prints one JSON line on rank 0.  `validate --lpips` adds LPIPS, `validate --tasks ir,cls --classify
-NAME=ARCH:WEIGHTS.pth` the top-1 accuracy of a user-supplied ResNet on the `cls` output (unirestore_amd.classify); both are opt-in.
+NAME=ARCH:WEIGHTS.pth` the top-1 accuracy of a user-supplied ResNet on the `cls` output (unirestore_amd.classify), `validate --tasks
+ir,seg --segment NAME=ARCH:WEIGHTS.pth` the mIoU of a user-supplied RefineNet-LW on the `seg` output (unirestore_amd.segment); all opt-in.
 """
 import argparse
 import json
@@ -219,13 +220,74 @@ def check_classify_run(classify, tasks, r: dict):
         raise ValueError(f"--classify scores the 'cls' output: pass --tasks with 'cls' in it, e.g. ir,cls (got "
                          f"{'none' if tasks is None else ','.join(tasks)}; it is not added silently)")
     cls_name = r["data_class"].rsplit(".", 1)[1]
-    if cls_name not in LABELLED_DATA or not r["data_args"].get("labels"):
+    if cls_name not in LABELLED_DATA or not r["data_args"].get("labels") or r["data_args"].get("labels") == "map":
         raise ValueError(f"--classify needs labels, and data.{cls_name} yields none as configured: use an `lq hq label` list with one of "
                          f"{list(LABELLED_DATA)} and set `labels: true` in data.init_args")
 
 
+def check_segment_arg(segment):
+    """--segment NAME=ARCH:WEIGHTS.pth[,NAME=ARCH:OTHER.pth] (or a dict NAME -> (ARCH, path) | a loaded segment.SegmenterWeights)
+    -> {name: (arch, path) | SegmenterWeights}.  ValueError for a malformed item, an unknown arch, a missing file or a name given
+    twice.  ARCH is one of segment.ARCHS (RefineNet-LW on ResNet-50 / 101 / 152); the weights are the user's."""
+    from .segment import ARCHS
+    form = "--segment takes NAME=ARCH:WEIGHTS.pth[,NAME=ARCH:WEIGHTS.pth]: a result name, one of %s, a RefineNet-LW state dict" % sorted(ARCHS)
+    if isinstance(segment, str):
+        items = []
+        for part in segment.split(","):
+            name, eq, spec = part.partition("=")
+            arch, colon, path = spec.partition(":")
+            if not (name and eq and arch and colon and path):
+                raise ValueError(f"{form}; got {part!r}")
+            items.append((name, (arch, path)))
+    elif isinstance(segment, dict):
+        items = list(segment.items())
+    else:
+        raise ValueError(f"{form}; got {type(segment).__name__}")
+    if not items:
+        raise ValueError(form)
+    out = {}
+    for name, spec in items:
+        if name in out:
+            raise ValueError(f"--segment: the name {name!r} is given twice")
+        if isinstance(spec, (tuple, list)):
+            if len(spec) != 2:
+                raise ValueError(f"{form}; got {name!r}: {spec!r}")
+            arch, path = spec
+            if not isinstance(arch, str) or arch not in ARCHS:
+                raise ValueError(f"--segment {name}: unknown arch {arch!r}, choose from {sorted(ARCHS)}")
+            if not os.path.isfile(path):
+                raise ValueError(f"--segment {name}: no such file: {path}")
+            spec = (arch, path)
+        out[name] = spec
+    return out
+
+
+def check_segment_run(segment, tasks, r: dict):
+    """What a segmenter run needs besides its weights, checked before the model is built: `seg` among the tasks (it is not added
+    silently, and `ir` stays required for PSNR) and a dataset that yields label maps.  r = resolve(cfg)."""
+    if tasks is None or "seg" not in tasks:
+        raise ValueError(f"--segment scores the 'seg' output: pass --tasks with 'seg' in it, e.g. ir,seg (got "
+                         f"{'none' if tasks is None else ','.join(tasks)}; it is not added silently)")
+    cls_name = r["data_class"].rsplit(".", 1)[1]
+    if cls_name not in LABELLED_DATA or r["data_args"].get("labels") != "map":
+        raise ValueError(f"--segment needs label maps, and data.{cls_name} yields none as configured: use an `lq hq label.png` list with "
+                         f"one of {list(LABELLED_DATA)} and set `labels: map` in data.init_args")
+
+
+def check_crop_arg(crop):
+    """--crop H,W (or a pair of integers) -> (H, W): the evaluator's centre crop, 512,512 unless given (the reference's seg and
+    multi-task evaluators use 960,1664)."""
+    if isinstance(crop, str):
+        try:
+            crop = tuple(int(v) for v in crop.split(","))
+        except ValueError:
+            raise ValueError(f"--crop takes H,W, two integers >= 1; got {crop!r}") from None
+    from .runner import check_crop
+    return check_crop(crop)
+
+
 def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_16bit=False, metrics_device="cpu", tasks=None,
-             model=None, lpips=None, classify=None) -> dict:
+             model=None, lpips=None, classify=None, segment=None, crop=None) -> dict:
     """tasks: a list of task names - every batch is restored once and decoded for each of them (DiffUIE.forward_tasks).  PSNR / SSIM
     come from the "ir" output, so the list must hold "ir"; images_per_s counts input images.  model: a ready DiffUIE to use instead
     of building the config's.  With data.CorruptedImageFiles (and data.DistortedImageFiles: "snow/3") the result also holds by_corruption ("fog/3" -> psnr, ssim, images)
@@ -236,12 +298,20 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
     classify: "NAME=ARCH:WEIGHTS.pth,..." or {NAME: (ARCH, path) | classify.ClassifierWeights} - ResNet top-1 accuracy of the "cls"
     output against the data's labels (tasks must hold "cls", the data must be built with labels: true): the result and every
     by_corruption entry gain, per NAME, the macro accuracy (the reference's MulticlassAccuracy) and NAME_top1 (micro) of the
-    restored images (val_lq/NAME; by_corruption: NAME) and of the unrestored inputs (val_input/NAME; by_corruption: input/NAME)."""
+    restored images (val_lq/NAME; by_corruption: NAME) and of the unrestored inputs (val_input/NAME; by_corruption: input/NAME).
+    segment: "NAME=ARCH:WEIGHTS.pth,..." or {NAME: (ARCH, path) | segment.SegmenterWeights} - RefineNet-LW mIoU of the "seg" output
+    against the data's label maps (tasks must hold "seg", the data must be built with labels: map): the result and every
+    by_corruption entry gain, per NAME, the mIoU (the reference's MulticlassJaccardIndex(19, ignore_index=255)) and NAME_acc (pixel
+    accuracy) of the restored images (val_lq/NAME; by_corruption: NAME) and of the unrestored inputs (val_input/NAME;
+    by_corruption: input/NAME).  crop: (H, W) or "H,W", the centre crop's size instead of 512 x 512."""
     import torch
     if lpips is not None and isinstance(lpips, (str, tuple, list)):
         lpips = check_lpips_arg(lpips)                    # before the model is built
     if classify is not None:
         classify = check_classify_arg(classify)           # before the model is built, like everything check_classify_run checks
+    if segment is not None:
+        segment = check_segment_arg(segment)
+    crop_args = {} if crop is None else dict(crop=check_crop_arg(crop))
     r = resolve(cfg, allow_16bit=allow_16bit)
     if tasks is not None:
         tasks = list(tasks)
@@ -250,12 +320,15 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
                              "(it is not added silently)")
     if classify is not None:
         check_classify_run(classify, tasks, r)
+    if segment is not None:
+        check_segment_run(segment, tasks, r)
     from . import data as data_mod
     from .dist import all_gather_images, shard_range
     rank, world, dev, dist, lit = _start(r, hf_root, random_init, model, metrics_device=metrics_device, lpips_weights=lpips,
-                                         classifiers=classify, **r["caller_args"])
+                                         classifiers=classify, segmenters=segment, **crop_args, **r["caller_args"])
     sums = ("psnr", "ssim") + (("lpips",) if lpips is not None else ())          # the metric states, in all-reduce order
     counts = [k for name in (classify or {}) for k in lit.classifier_keys(name)]  # the classifiers' int64 [3, classes] count states
+    counts += [k for name in (segment or {}) for k in lit.segmenter_keys(name)]   # the segmenters' int64 [classes, classes] matrices
     data = getattr(data_mod, r["data_class"].rsplit(".", 1)[1])(**r["data_args"])
     if data.batch_size < world:
         raise ValueError(f"data batch_size {data.batch_size} < world size {world}: every rank needs at least one image per batch")
@@ -283,6 +356,8 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
         lit.update_metrics(by_task["ir"], batch[1])           # this rank's shard; reduced over the ranks below (fp64 PSNR / SSIM: untimed)
         if classify is not None:
             lit.update_classification(by_task["cls"], batch[0], batch[2])
+        if segment is not None:
+            lit.update_segmentation(by_task["seg"], batch[0], batch[2])
         if by_corruption is not None:                     # the batch is homogeneous: its increment of the totals belongs to one key
             acc = by_corruption.setdefault("%s/%d" % data.last, dict({k: 0.0 for k in sums}, **{k: 0 for k in counts}, images=0))
             for k in acc:
@@ -310,6 +385,10 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
             for name in (classify or {}):
                 for prefix, key in zip(("", "input/"), lit.classifier_keys(name)):
                     res["by_corruption"][k][f"{prefix}{name}"], res["by_corruption"][k][f"{prefix}{name}_top1"] = accuracy(*v[key])
+            for name in (segment or {}):
+                from .segment import miou
+                for prefix, key in zip(("", "input/"), lit.segmenter_keys(name)):
+                    res["by_corruption"][k][f"{prefix}{name}"], res["by_corruption"][k][f"{prefix}{name}_acc"] = miou(v[key])[:2]
         if hasattr(data, "skipped"):
             res["skipped"] = list(data.skipped)
         if data.resize is not None:
@@ -676,6 +755,12 @@ def main(argv=None):
                     help="validate: also report ResNet top-1 accuracy of the 'cls' output (fp32, on the GPU) against the data's labels; "
                          "ARCH is resnet18, resnet50 or resnet101, WEIGHTS a user-supplied torchvision state dict; needs --tasks with "
                          "cls and a dataset built with labels: true")
+    ap.add_argument("--segment", default=None, metavar="NAME=ARCH:WEIGHTS.pth[,...]",
+                    help="validate: also report RefineNet-LW mIoU and pixel accuracy of the 'seg' output (fp32, on the GPU) against the "
+                         "data's label maps; ARCH is rflw50, rflw101 or rflw152, WEIGHTS a user-supplied state dict; needs --tasks with "
+                         "seg and a dataset built with labels: map")
+    ap.add_argument("--crop", default=None, metavar="H,W",
+                    help="validate: the evaluator's centre crop (default 512,512; the reference's seg evaluator uses 960,1664)")
     ap.add_argument("--tasks", default=None, metavar="ir,cls,seg",
                     help="restore every batch once and decode it for each of these tasks (forward_tasks); validate: must hold 'ir', which "
                          "feeds PSNR / SSIM; restore: one sub-folder of --output per task")
@@ -704,6 +789,10 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.classify is not None and a.command != "validate":
         ap.error("--classify belongs to validate")
+    if a.segment is not None and a.command != "validate":
+        ap.error("--segment belongs to validate")
+    if a.crop is not None and a.command != "validate":
+        ap.error("--crop belongs to validate")
     if a.command in FILE_COMMANDS:
         check, run, errors = FILE_COMMANDS[a.command]
         kw = dict(inp=a.input, output=a.output, batch=a.batch, resize=a.resize)
@@ -737,6 +826,14 @@ def main(argv=None):
             check_classify_run(a.classify, tasks, resolve(cfg, allow_16bit=a.allow_16bit))
         except ValueError as e:
             ap.error(str(e))
+    try:
+        if a.segment is not None:
+            a.segment = check_segment_arg(a.segment)
+            check_segment_run(a.segment, tasks, resolve(cfg, allow_16bit=a.allow_16bit))
+        if a.crop is not None:
+            a.crop = check_crop_arg(a.crop)
+    except ValueError as e:
+        ap.error(str(e))
     if a.command == "print_config":
         print(yaml.safe_dump(cfg, sort_keys=False))
         print(json.dumps(resolve(cfg, allow_16bit=a.allow_16bit)))
@@ -748,7 +845,7 @@ def main(argv=None):
             print(json.dumps(res))
         return 0
     res = validate(cfg, hf_root=a.hf_root, max_batches=a.max_batches, allow_16bit=a.allow_16bit, metrics_device=a.metrics_device,
-                   tasks=tasks, lpips=a.lpips, classify=a.classify)
+                   tasks=tasks, lpips=a.lpips, classify=a.classify, segment=a.segment, crop=a.crop)
     if res is not None:
         print(json.dumps(res))
     return 0

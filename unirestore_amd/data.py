@@ -3,7 +3,8 @@ list files, `CorruptedImageFiles`, clean images corrupted on the GPU (unirestore
 JPEG-compressed on the GPU at a list of qualities (unirestore_amd.jpeg), and `DistortedImageFiles`, CorruptedImageFiles for glass blur,
 snow and elastic transform (unirestore_amd.distort).  The last three share `_DegradedImageFiles`: the constructor checks and the load /
 degrade / yield loop are written once there.  The four file datasets take `labels=True`: gt is then the int64 labels of the list's
-third column (what a classifier is scored against) instead of None.
+third column (what a classifier is scored against) instead of None; `labels="map"`: the third column is the path of a label PNG
+and gt the int64 [B,H,W] label maps (what a segmenter is scored against), Cityscapes labelIds mapped to trainIds by default.
 
 `SyntheticImages` yields the evaluator's batch tuple `(lq, hq, gt, fname, task)` (reference
 src/core/base/eval_image_restoration.py:56) from seeded random images: hq = torch.rand (what the reference's own smoke
@@ -78,17 +79,94 @@ def read_labels(list_file: str) -> List[int]:
     return out
 
 
+LABEL_ENCODINGS = ("cityscapes", "train_id")
+# the public Cityscapes labelId -> trainId table (cityscapesScripts, labels.py): the 19 evaluated classes; every other id is 255
+CITYSCAPES_TRAIN_ID = {7: 0, 8: 1, 11: 2, 12: 3, 13: 4, 17: 5, 19: 6, 20: 7, 21: 8, 22: 9, 23: 10, 24: 11, 25: 12, 26: 13, 27: 14, 28: 15,
+                       31: 16, 32: 17, 33: 18}
+
+
+def check_labels_arg(labels, label_encoding):
+    if labels not in (False, True, "map"):
+        raise ValueError(f"labels must be false, true (an integer per line) or \"map\" (a label PNG per line), got {labels!r}")
+    if label_encoding not in LABEL_ENCODINGS:
+        raise ValueError(f"unknown label_encoding {label_encoding!r}: choose from {LABEL_ENCODINGS}")
+
+
+def read_label_paths(list_file: str) -> List[Tuple[str, int]]:
+    """(path, line number) of the label map of every pair line of an `lq hq label.png` list, in file order; a relative path is taken
+    from the list file's folder, exactly as the first two columns are.  ValueError naming file and line for a line without a third
+    column, and for a folder: label maps exist in three-column lists only."""
+    import os
+    if os.path.isdir(list_file):
+        raise ValueError(f"{list_file!r}: labels: map needs an `lq hq label.png` list file; a folder carries no labels")
+    base = os.path.dirname(os.path.abspath(list_file))
+    out = []
+    with open(list_file) as f:
+        for ln, line in enumerate(f, 1):
+            cols = line.split()
+            if not cols or cols[0].startswith("#"):
+                continue
+            if len(cols) < 3:
+                raise ValueError(f"{list_file}:{ln}: labels: map needs `lq hq label.png`, got {line.strip()!r} (no label column)")
+            out.append((cols[2] if os.path.isabs(cols[2]) else os.path.join(base, cols[2]), ln))
+    return out
+
+
+def load_label_map(path: str, encoding: str, hw, where: str) -> torch.Tensor:
+    """One label PNG (8-bit, one channel) as int64 [H,W].  encoding "cityscapes": labelIds 0..33 go through CITYSCAPES_TRAIN_ID,
+    everything else becomes 255; "train_id": the values as they are.  ValueError naming `where` (file:line of the list) when the
+    file is missing, is no single-channel 8-bit image or differs in size from its image (hw)."""
+    import os
+
+    import numpy as np
+    from PIL import Image
+    if not os.path.isfile(path):
+        raise ValueError(f"{where}: the label map {path!r} does not exist")
+    with Image.open(path) as im:
+        if im.mode not in ("L", "P"):
+            raise ValueError(f"{where}: the label map {path!r} has mode {im.mode}, expected a single-channel 8-bit image")
+        a = torch.from_numpy(np.array(im, dtype=np.uint8))
+    if tuple(a.shape) != tuple(hw):
+        raise ValueError(f"{where}: the label map {path!r} is {a.shape[0]} x {a.shape[1]}, its image {hw[0]} x {hw[1]}")
+    if encoding == "cityscapes":
+        lut = torch.full((256,), 255, dtype=torch.int64)
+        for k, v in CITYSCAPES_TRAIN_ID.items():
+            lut[k] = v
+        return lut[a.long()]
+    return a.long()
+
+
+class _Labels:
+    """The `labels` / `label_encoding` arguments of the file datasets: gt of a batch from the list's third column."""
+
+    def __init__(self, list_file, labels, label_encoding):
+        check_labels_arg(labels, label_encoding)
+        self.kind, self.encoding, self.list_file = labels, label_encoding, list_file
+        self.values = read_label_paths(list_file) if labels == "map" else read_labels(list_file) if labels else None
+
+    def gt(self, idx, hw):
+        if self.values is None:
+            return None
+        if self.kind == "map":
+            return torch.stack([load_label_map(self.values[i][0], self.encoding, hw, f"{self.list_file}:{self.values[i][1]}") for i in idx])
+        return torch.tensor([self.values[i] for i in idx], dtype=torch.int64)
+
+
 class ImageListFiles:
     """Real pairs for `validate` (`data.class_path: unirestore_amd.data.ImageListFiles`): a text file with one `lq hq [label]`
     line per pair, paths relative to the list file's folder.  Yields the evaluator's tuple `(lq, hq, gt, fname, task)` with lq / hq
     fp32 NCHW in [0, 1] (u8 / 255, the reference's ToDtype(scale=True)); pairs are grouped by shape, list order kept inside a
     group, so every batch is one tensor (the evaluator's centre crop makes nearly everything 512 x 512).  labels=True: gt is an
-    int64 [B] tensor of the lines' third column (a classifier's targets) instead of None."""
+    int64 [B] tensor of the lines' third column (a classifier's targets) instead of None.  labels="map": the third column is the
+    path of a label PNG of the lq image's size and gt the int64 [B,H,W] maps (a segmenter's targets); label_encoding "cityscapes"
+    (the default) maps labelIds to trainIds, 255 for the rest, "train_id" takes the values as they are."""
 
-    def __init__(self, list_file: str, batch_size: int = 8, task: str = "ir", num_batches: int = None, labels: bool = False):
+    def __init__(self, list_file: str, batch_size: int = 8, task: str = "ir", num_batches: int = None, labels=False,
+                 label_encoding: str = "cityscapes"):
         import os
         self.list_file, self.batch_size, self.task, self.num_batches = list_file, int(batch_size), task, num_batches
-        self.labels = read_labels(list_file) if labels else None
+        self._labels = _Labels(list_file, labels, label_encoding)
+        self.labels = self._labels.values
         base = os.path.dirname(os.path.abspath(list_file))
         self.pairs = []
         with open(list_file) as f:
@@ -128,7 +206,7 @@ class ImageListFiles:
             lq, hq = nchw([self.pairs[i][0] for i in idx]), nchw([self.pairs[i][1] for i in idx])
             if lq.shape != hq.shape:
                 raise ValueError(f"{self.list_file}: lq and hq of {self.pairs[idx[0]][0]!r}... differ in size: {tuple(lq.shape)} vs {tuple(hq.shape)}")
-            gt = None if self.labels is None else torch.tensor([self.labels[i] for i in idx], dtype=torch.int64)
+            gt = self._labels.gt(idx, lq.shape[2:])
             yield lq, hq, gt, [os.path.splitext(os.path.basename(self.pairs[i][0]))[0] for i in idx], self.task
 
 
@@ -137,14 +215,15 @@ class _DegradedImageFiles:
     length and the loop over it.  A subclass gives `_plan()` -> the batches, each a tuple that ends in the batch's file indices,
     and `_degrade(hq, stems, *what)` -> (lq, label): `what` is the rest of that tuple, `label` what `last` holds after the batch."""
 
-    def __init__(self, source, batch_size, task, seed, num_batches, resize, min_side, labels=False):
+    def __init__(self, source, batch_size, task, seed, num_batches, resize, min_side, labels=False, label_encoding="cityscapes"):
         from . import resize as rz
         self.resize = None if resize is None else rz.check_range(resize, min_side)
         self.source, self.batch_size, self.task, self.seed, self.num_batches = source, int(batch_size), task, int(seed), num_batches
         if self.batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
         self.paths = corrupt.check_inputs(source)
-        self.labels = read_labels(source) if labels else None          # one per line of the list, the order of `paths`
+        self._labels = _Labels(source, labels, label_encoding)         # one per line of the list, the order of `paths`
+        self.labels = self._labels.values
         self.last = None
 
     def __len__(self):
@@ -165,7 +244,7 @@ class _DegradedImageFiles:
             stems = [corrupt.stem_of(self.paths[i]) for i in idx]
             hq = torch.stack([load_u8(self.paths[i]) for i in idx]).to(device)
             lq, self.last = self._degrade(hq, stems, *what)
-            gt = None if self.labels is None else torch.tensor([self.labels[i] for i in idx], dtype=torch.int64)
+            gt = self._labels.gt(idx, hq.shape[1:3])                   # a label map passes through untouched: only the image is degraded
             yield nchw(lq), nchw(hq), gt, stems, self.task
 
 
@@ -176,7 +255,8 @@ class CorruptedImageFiles(_DegradedImageFiles):
     `severity` an integer 1..5 or "mixed", the reference's per-image draw.  Every image's corruption, severity and randomness come
     from sha256 of (seed, file stem) alone.  Images are grouped by (shape, corruption, severity), so a batch is homogeneous; hq is
     uploaded as u8 and corrupted there.  Yields `(lq, hq, gt, names, task)` with fp32 NCHW tensors in [0, 1], gt None or, with
-    labels=True (an `lq hq label` list only), the int64 [B] labels of the list's third column; `last` holds the
+    labels=True (an `lq hq label` list only), the int64 [B] labels of the list's third column, or with labels="map" the int64 [B,H,W]
+    label maps it names (see ImageListFiles; a map is never degraded); `last` holds the
     (corruption, severity) of the batch just yielded and `skipped` the subset members that are not built.  `resize` = [lo, hi]
     (lo >= 32) turns on the reference's resize-down / resize-back wrapper (corrupt.degrade): every image's short edge is drawn
     from [lo, hi) by (seed, stem) as well, lq keeps hq's shape; the reference's own range is [resolution // 4, resolution)."""
@@ -184,8 +264,8 @@ class CorruptedImageFiles(_DegradedImageFiles):
     _planner = corrupt                             # the module whose expand / degrade this class uses (DistortedImageFiles: distort)
 
     def __init__(self, source: str, corruptions="common", severity=3, batch_size: int = 8, task: str = "ir", seed: int = 42,
-                 num_batches: int = None, labels: bool = False, resize=None):
-        super().__init__(source, batch_size, task, seed, num_batches, resize, 32, labels)
+                 num_batches: int = None, labels=False, label_encoding: str = "cityscapes", resize=None):
+        super().__init__(source, batch_size, task, seed, num_batches, resize, 32, labels, label_encoding)
         self.names = self._planner.expand(corruptions)
         self.skipped = corrupt.skipped(corruptions)
         self.severity = severity if severity == "mixed" else corrupt.check_severity(severity)
@@ -207,8 +287,8 @@ class DistortedImageFiles(CorruptedImageFiles):
     _planner = distort
 
     def __init__(self, source: str, corruptions="all", severity=3, batch_size: int = 8, task: str = "ir", seed: int = 42,
-                 num_batches: int = None, labels: bool = False, resize=None):
-        super().__init__(source, corruptions, severity, batch_size, task, seed, num_batches, labels, resize)
+                 num_batches: int = None, labels=False, label_encoding: str = "cityscapes", resize=None):
+        super().__init__(source, corruptions, severity, batch_size, task, seed, num_batches, labels, label_encoding, resize)
         self.skipped = []
 
 
@@ -223,8 +303,8 @@ class JpegImageFiles(_DegradedImageFiles):
     [lo, hi) by (`seed`, stem), the only use of `seed`; lq keeps hq's shape."""
 
     def __init__(self, source: str, quality=(10, 25, 50), batch_size: int = 8, task: str = "ir", num_batches: int = None,
-                 labels: bool = False, resize=None, seed: int = 42):
-        super().__init__(source, batch_size, task, seed, num_batches, resize, jpeg.MIN_SIDE, labels)
+                 labels=False, label_encoding: str = "cityscapes", resize=None, seed: int = 42):
+        super().__init__(source, batch_size, task, seed, num_batches, resize, jpeg.MIN_SIDE, labels, label_encoding)
         specs = [s for s in quality.split(",") if s] if isinstance(quality, str) else \
             list(quality) if isinstance(quality, (list, tuple)) else [quality]
         self.qualities = []

@@ -1143,6 +1143,76 @@ def top1(logits: torch.Tensor, labels: torch.Tensor):
     return pred, counts[0], counts[1], counts[2]
 
 
+def segment(images: torch.Tensor, weights, size=None, scales=(1, 0.8, 0.6)) -> torch.Tensor:
+    """Predicted classes uint8 [N,H,W] (on the device) of fp32 NCHW images in [0,1]: the segmentation evaluator's test-time
+    augmentation in exact fp32 on the GPU - for each scale a bilinear align_corners=True resize to floor(size * scale), RefineNet-LW's
+    preprocess and network; then every scale's logits resized to `size` (default: the images' own H, W), averaged, argmax (ties to
+    the lowest class).  weights: what segment.load_weights / segment.random_weights return.  ValueError when the smallest scale's
+    input falls below 32 px on a side.  An image's result does not depend on its place in the batch, and two calls give the same
+    bytes.  No host sync - except on the FIRST call for a new image size, target size or set of scales, which builds that shape's
+    tap tables on the host and uploads them with a blocking copy: run a shape once eagerly before capturing it in a graph.  The
+    tables (a few KB per shape) stay on the device for the life of the process, so a captured graph never loses the ones it reads."""
+    from . import segment as _segment
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if not isinstance(images, torch.Tensor) or images.dtype != torch.float32 or images.ndim != 4:
+        raise ValueError(f"segment: images must be a 4-d fp32 NCHW tensor, got "
+                         f"{getattr(images, 'dtype', type(images))} {tuple(getattr(images, 'shape', ()))}")
+    if images.device != dev:
+        raise ValueError(f"segment: images is on {images.device}, not on the current device {dev}")
+    if not images.is_contiguous():
+        raise ValueError("segment: images must be contiguous")
+    n, c, h, w = images.shape
+    if n < 1 or c != 3 or h < 1 or w < 1:
+        raise ValueError(f"segment: needs [N>=1, 3, H>=1, W>=1] images, got {tuple(images.shape)}")
+    if not isinstance(weights, _segment.SegmenterWeights):
+        raise ValueError(f"segment: weights must come from segment.load_weights / segment.random_weights, got {type(weights).__name__}")
+    if weights.device != dev:
+        raise ValueError(f"segment: the weights are on {weights.device}, not on the current device {dev}")
+    if size is not None and not (isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(v, int) and v >= 1 for v in size)):
+        raise ValueError(f"segment: size must be (H, W) with H, W >= 1, got {size!r}")
+    if not (isinstance(scales, (tuple, list)) and 1 <= len(scales) <= 3 and all(isinstance(v, (int, float)) and 0 < v <= 8 for v in scales)):
+        raise ValueError(f"segment: scales must be 1 to 3 numbers in (0, 8], got {scales!r}")
+    return _segment.segment(images, weights, size, scales)
+
+
+def checked_targets(target: torch.Tensor, classes: int = 19, ignore_index: int = 255) -> torch.Tensor:
+    """A uint8 / int64 target tensor on the current device, after checking that every value lies in [0, classes) or is
+    ignore_index (ValueError otherwise; one flag is read back: one host sync).  What `confusion` does to its targets; a caller
+    that scores several predictions against the same targets checks them once with this and calls segment.confusion."""
+    target = target.to(torch.device("cuda", torch.cuda.current_device()))
+    wrong = (target != ignore_index) & ((target < 0) | (target >= classes)) if target.dtype == torch.int64 else \
+        (target != ignore_index) & (target >= classes)
+    if bool(wrong.any()):
+        raise ValueError(f"confusion: target {int(target[wrong][0])} is neither in [0, {classes}) nor ignore_index {ignore_index}")
+    return target
+
+
+def confusion(pred: torch.Tensor, target: torch.Tensor, classes: int = 19, ignore_index: int = 255) -> torch.Tensor:
+    """The confusion matrix int64 [classes, classes] (on the device) of one batch, conf[target][pred], over the pixels whose target
+    is not ignore_index: pred uint8 on the device, target uint8 / int64 of the same shape, on the host or the device.  A target
+    outside [0, classes) that is not ignore_index, or a prediction >= classes, is a ValueError raised before any launch (checking
+    device tensors reads one flag back: one host sync).  segment.miou turns the summed matrices into mIoU and pixel accuracy."""
+    from . import segment as _segment
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if not isinstance(classes, int) or not 1 <= classes <= 255 or not isinstance(ignore_index, int):
+        raise ValueError(f"confusion: classes must be an int in [1, 255] and ignore_index an int, got {classes!r}, {ignore_index!r}")
+    if not isinstance(pred, torch.Tensor) or pred.dtype != torch.uint8 or pred.numel() < 1:
+        raise ValueError(f"confusion: pred must be a non-empty uint8 tensor, got {getattr(pred, 'dtype', type(pred))} {tuple(getattr(pred, 'shape', ()))}")
+    if pred.device != dev:
+        raise ValueError(f"confusion: pred is on {pred.device}, not on the current device {dev}")
+    if not isinstance(target, torch.Tensor) or target.dtype not in (torch.uint8, torch.int64) or target.shape != pred.shape:
+        raise ValueError(f"confusion: target must be a uint8 / int64 {tuple(pred.shape)} tensor, got "
+                         f"{getattr(target, 'dtype', type(target))} {tuple(getattr(target, 'shape', ()))}")
+    if target.is_cuda and target.device != dev:
+        raise ValueError(f"confusion: target is on {target.device}, not on the host or the current device {dev}")
+    if not pred.is_contiguous() or not target.is_contiguous():
+        raise ValueError("confusion: pred and target must be contiguous")
+    target = checked_targets(target, classes, ignore_index)
+    if bool((pred >= classes).any()):
+        raise ValueError(f"confusion: prediction {int(pred.max())} is outside [0, {classes})")
+    return _segment.confusion(pred, target, classes, ignore_index)
+
+
 def profile_enable(on: bool):
     check(lib.ur_profile_enable(int(on)))
 

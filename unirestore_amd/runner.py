@@ -15,11 +15,21 @@ def crop_box(h: int, w: int, upper_h: int = 512, upper_w: int = 512):
     return h // 2 - ch // 2, h // 2 + ch // 2, w // 2 - cw // 2, w // 2 + cw // 2
 
 
-def crop_tensor(image: torch.Tensor) -> torch.Tensor:
+DEFAULT_CROP = (512, 512)                               # the IR evaluator's; the reference's seg / multi-task ones use (960, 1664)
+
+
+def crop_tensor(image: torch.Tensor, crop=DEFAULT_CROP) -> torch.Tensor:
     if image.ndim not in (3, 4):
         raise NotImplementedError                       # the reference raises here as well (:136)
-    t, b, l, r = crop_box(image.shape[-2], image.shape[-1])
+    t, b, l, r = crop_box(image.shape[-2], image.shape[-1], crop[0], crop[1])
     return image[..., t:b, l:r]
+
+
+def check_crop(crop):
+    """(h, w) of a `crop` argument: two integers >= 1."""
+    if not (isinstance(crop, (tuple, list)) and len(crop) == 2 and all(isinstance(v, int) and not isinstance(v, bool) and v >= 1 for v in crop)):
+        raise ValueError(f"crop must be two integers (H, W) >= 1, got {crop!r}")
+    return int(crop[0]), int(crop[1])
 
 
 @torch.inference_mode()
@@ -37,12 +47,12 @@ def forward_tasks(model, inputs: Sequence[torch.Tensor], tasks: Sequence[str], q
 
 @torch.inference_mode()
 def validation_step(model, lq: torch.Tensor, hq: torch.Tensor = None, task: str = "ir", need_crop: bool = True,
-                    eval_types: Sequence[str] = ("lq",), tasks: Sequence[str] = None):
+                    eval_types: Sequence[str] = ("lq",), tasks: Sequence[str] = None, crop=DEFAULT_CROP):
     """Steps 1-2 of ImageRestorationEvaluator.validation_step: crop, restore, quantise to 8 bit.  Returns (preds, hq).
     tasks: restore with `forward_tasks` instead - preds is then a list of {task: images}."""
     if need_crop:
-        lq = crop_tensor(lq) if "lq" in eval_types else lq
-        hq = crop_tensor(hq) if (hq is not None and "hq" in eval_types) else hq
+        lq = crop_tensor(lq, crop) if "lq" in eval_types else lq
+        hq = crop_tensor(hq, crop) if (hq is not None and "hq" in eval_types) else hq
     inputs = ([hq] if "hq" in eval_types and hq is not None else []) + ([lq] if "lq" in eval_types else [])
     if tasks is not None:
         return forward_tasks(model, inputs, tasks, quantize=True), hq
@@ -95,11 +105,12 @@ class LitUniFIE:
 
     def __init__(self, model_kwargs: dict, save_image: bool = False, eval_mode: str = "FR", need_crop: bool = True,
                  dtype: str = "bf16", hf_root: str = None, model=None, metrics_device: str = "cpu", lpips_weights=None,
-                 classifiers=None, **_ignored):
+                 classifiers=None, segmenters=None, crop=DEFAULT_CROP, **_ignored):
         from . import checkpoint
         if metrics_device not in METRICS_DEVICES:
             raise ValueError(f"metrics_device={metrics_device!r}: choose from {METRICS_DEVICES}")
         self.metrics_device = metrics_device
+        self.crop = check_crop(crop)                       # the centre crop's upper size (need_crop)
         self.model_kwargs, self.need_crop, self.eval_mode = model_kwargs, need_crop, eval_mode
         tedit = model_kwargs.get("tedit") or {}
         self.task_dict = tedit.get("task", [])
@@ -125,6 +136,26 @@ class LitUniFIE:
             for key in self.classifier_keys(name):
                 self.totals[key] = torch.zeros(3, w.num_classes, dtype=torch.int64, device=w.device)
 
+        # Segmenter scoring of the "seg" output (RefineNet-LW mIoU, exact fp32 HIP kernels) is off unless segmenters are given:
+        # {name: (arch, state-dict path) | segment.SegmenterWeights}.  Per name the totals hold the confusion matrix conf[target][pred]
+        # as an int64 [classes, classes] device tensor for the restored images ("seg/<name>") and for the unrestored inputs
+        # ("seg_input/<name>"); replaced, never changed in place, like the classifiers' counts.
+        self.segmenters = {}
+        for name, spec in (segmenters or {}).items():
+            from . import segment
+            w = spec if isinstance(spec, segment.SegmenterWeights) else segment.load_weights(*spec)
+            self.segmenters[name] = w
+            for key in self.segmenter_keys(name):
+                self.totals[key] = torch.zeros(w.num_classes, w.num_classes, dtype=torch.int64, device=w.device)
+
+    @staticmethod
+    def segmenter_keys(name: str):
+        """The two `totals` keys of segmenter `name`: the restored images' confusion matrix, the unrestored inputs'."""
+        return f"seg/{name}", f"seg_input/{name}"
+
+    def _crop(self, t):
+        return crop_tensor(t, self.crop)
+
     @staticmethod
     def classifier_keys(name: str):
         """The two `totals` keys of classifier `name`: the restored images' counts, the unrestored inputs' counts."""
@@ -143,20 +174,25 @@ class LitUniFIE:
         if self.classifiers and metrics and (tasks is None or "cls" not in tasks):
             raise ValueError(f"tasks={None if tasks is None else list(tasks)}: the classifiers score the 'cls' output - pass tasks "
                              "with 'cls' in it")
+        if self.segmenters and metrics and (tasks is None or "seg" not in tasks):
+            raise ValueError(f"tasks={None if tasks is None else list(tasks)}: the segmenters score the 'seg' output - pass tasks "
+                             "with 'seg' in it")
         if tasks is not None:
             if "ir" not in tasks:
                 raise ValueError(f"tasks={list(tasks)}: PSNR / SSIM are computed on the 'ir' output - add 'ir' to the list")
-            outs, _ = validation_step(self.model, lq, hq, need_crop=self.need_crop, eval_types=eval_types, tasks=tasks)
+            outs, _ = validation_step(self.model, lq, hq, need_crop=self.need_crop, eval_types=eval_types, tasks=tasks, crop=self.crop)
             if metrics and hq is not None:
                 self.update_metrics(outs[-1]["ir"], hq)
             if metrics and self.classifiers:
                 self.update_classification(outs[-1]["cls"], lq, gt)
+            if metrics and self.segmenters:
+                self.update_segmentation(outs[-1]["seg"], lq, gt)
             return outs
         # the IR evaluator always restores with the "ir" prompt (eval_image_restoration.py:70: self.forward(inputs, 'ir')), whatever
         # task tag the batch carries; task-driven decoding belongs to the downstream (MTL) evaluators, which are out of scope
-        preds, hq_c = validation_step(self.model, lq, hq, task="ir", need_crop=self.need_crop, eval_types=eval_types)
-        if metrics and hq_c is not None and self.eval_mode in ("FR", "ALL") and preds[-1].shape == (crop_tensor(hq) if self.need_crop else hq).shape:
-            tgt = crop_tensor(hq) if self.need_crop else hq
+        preds, hq_c = validation_step(self.model, lq, hq, task="ir", need_crop=self.need_crop, eval_types=eval_types, crop=self.crop)
+        if metrics and hq_c is not None and self.eval_mode in ("FR", "ALL") and preds[-1].shape == (self._crop(hq) if self.need_crop else hq).shape:
+            tgt = self._crop(hq) if self.need_crop else hq
             n = preds[-1].shape[0]
             if self.metrics_device == "gpu":
                 self._add_gpu_metrics(preds[-1], tgt)
@@ -223,7 +259,7 @@ class LitUniFIE:
 
     def update_metrics(self, preds: torch.Tensor, hq: torch.Tensor):
         """Metric states for one batch of restored images vs their clean targets (for callers that time the forward separately)."""
-        tgt = crop_tensor(hq) if self.need_crop else hq
+        tgt = self._crop(hq) if self.need_crop else hq
         if self.eval_mode in ("FR", "ALL") and preds.shape == tgt.shape:
             n = preds.shape[0]
             if self.metrics_device == "gpu":
@@ -246,12 +282,34 @@ class LitUniFIE:
                              "`lq hq label` list")
         from . import ops
         if self.need_crop:
-            inputs = crop_tensor(inputs)
+            inputs = self._crop(inputs)
         for name, w in self.classifiers.items():
             for key, images in zip(self.classifier_keys(name), (cls_preds, inputs)):
                 logits = ops.classify(images.to(device=w.device, dtype=torch.float32).contiguous(), w)
                 _pred, tp, targets, predicted = ops.top1(logits, labels)
                 self.totals[key] = self.totals[key] + torch.stack([tp, targets, predicted])
+
+    def update_segmentation(self, seg_preds: torch.Tensor, inputs: torch.Tensor, label_maps: torch.Tensor):
+        """The confusion matrices of one batch, for every segmenter: of `seg_preds`, the quantised "seg" output (the tensor the
+        reference's evaluator hands to its segmenters), and of `inputs`, the unrestored lq images it was restored from.  Inputs and
+        label maps are centre-cropped with the restoration's own box when need_crop is on, so both sides are scored on the same
+        pixels.  label_maps: the batch's [N,H,W] integer trainId maps (255 = ignore).  Nothing when no segmenter is configured."""
+        if not self.segmenters:
+            return
+        if label_maps is None or not torch.is_tensor(label_maps) or label_maps.ndim != 3:
+            raise ValueError("the segmenters need the batch's label maps (gt is None or no [N,H,W] tensor): build the dataset with "
+                             "labels: map on an `lq hq label.png` list")
+        from . import ops, segment
+        if self.need_crop:
+            inputs, label_maps = self._crop(inputs), self._crop(label_maps)
+        if tuple(label_maps.shape) != (seg_preds.shape[0], *seg_preds.shape[2:]):
+            raise ValueError(f"the label maps are {tuple(label_maps.shape)}, the seg output {tuple(seg_preds.shape)}")
+        for name, w in self.segmenters.items():
+            # the targets are checked once per batch; ops.segment's own predictions always lie in [0, classes)
+            target = ops.checked_targets(label_maps.to(device=w.device, dtype=torch.int64).contiguous(), w.num_classes)
+            for key, images in zip(self.segmenter_keys(name), (seg_preds, inputs)):
+                pred = ops.segment(images.to(device=w.device, dtype=torch.float32).contiguous(), w)
+                self.totals[key] = self.totals[key] + segment.confusion(pred, target, w.num_classes)
 
     def metrics(self) -> dict:
         n = max(self.totals["images"], 1)
@@ -263,4 +321,8 @@ class LitUniFIE:
             from .classify import accuracy
             for prefix, key in zip(("val_lq", "val_input"), self.classifier_keys(name)):
                 res[f"{prefix}/{name}"], res[f"{prefix}/{name}_top1"] = accuracy(*self.totals[key])
+        for name in self.segmenters:                      # mIoU = the reference's MulticlassJaccardIndex(19, ignore_index=255)
+            from .segment import miou
+            for prefix, key in zip(("val_lq", "val_input"), self.segmenter_keys(name)):
+                res[f"{prefix}/{name}"], res[f"{prefix}/{name}_acc"] = miou(self.totals[key])[:2]
         return res
