@@ -413,7 +413,10 @@ int ur_keyed_noise(const uint32_t* keys, uint32_t draw, void* out, int N, long l
  *   psnr[n] = 10 log10(data_range^2 / mean over C*H*W of (pred - target)^2)   (+inf for identical images)
  *   ssim[n] = mean over channels and the valid (H-win+1) x (W-win+1) interior of the SSIM map: uniform win x win window
  *             (win odd, >= 3; skimage's default is 7), K1 = 0.01, K2 = 0.03, sample covariance (win^2 / (win^2 - 1)).
- * Arguments are checked before any HIP call (UR_E_INVALID).  ur_image_metrics_ws_size returns UR_E_INVALID for a bad shape. */
+ * Arguments are checked before any HIP call (UR_E_INVALID).  ur_image_metrics_ws_size returns UR_E_INVALID for a bad shape.
+ * Size limits: N*C*tiles must be below 2^23 (tiles = ceil((W-win+1)/64) * ceil((H-win+1)/16): one 256-thread workgroup per tile and
+ *   plane).  The planes are addressed with 64-bit offsets: N*C*H*W has no limit of its own (run past 2^32 bytes in
+ *   tests/scoring_large_cases.py). */
 int ur_image_metrics(const float* pred, const float* target, int N, int C, int H, int W, int win, double data_range,
                      double* psnr, double* ssim, void* ws, long long ws_bytes, ur_stream_t stream);
 long long ur_image_metrics_ws_size(int N, int C, int H, int W, int win);
@@ -437,7 +440,14 @@ long long ur_image_metrics_ws_size(int N, int C, int H, int W, int win);
  *   part fp64 [N][ur_lpips_layer_parts(P)]: partial sums over pixels of sum_c lin_c (u_c^pred - u_c^tgt)^2.
  * ur_lpips_finish: ws holds the five taps' partials one after the other (tap t of an H x W input has ur_lpips_tap_hw pixels, its
  *   block starts where tap t-1's N * parts doubles end; ur_lpips_ws_size bytes in all) -> out fp64 [N] = sum over taps, in tap
- *   order, of (sum of the tap's partials in ascending order) / pixels. */
+ *   order, of (sum of the tap's partials in ascending order) / pixels.
+ * Size limits (64-bit arithmetic, before any HIP call; run from the accepted side in tests/scoring_large_cases.py):
+ *   ur_lpips_prep, ur_lpips_ws_size, ur_lpips_finish: N*H*W must be below 2^28.
+ *   ur_conv2d_f32 / ur_conv2d_f32_res: N*OH*OW must be below 2^31 - 128 (int row indices; the last 128-row tile stays inside an int)
+ *     and N*H*W below 2^31; Cin*KH*KW and Cout at most 2^24.  x, y and res are addressed with 64-bit offsets: N*H*W*Cin and
+ *     N*OH*OW*Cout have no limit of their own.
+ *   ur_maxpool2d_f32: N*H*W*C must be below 2^31 (the launch is over the at most N*H*W*C / 9 outputs).
+ *   ur_lpips_layer: N in [1, 65535], ceil(P / 64) at most 2^23 - 1; feat is addressed with 64-bit offsets (2N*P*C has no limit). */
 int ur_lpips_prep(const float* x, float* y, int N, int C, int H, int W, ur_stream_t stream);
 int ur_conv2d_f32_wpack_dims(int Cin, int Cout, int KH, int KW, int* kpad, int* cout_pad);
 int ur_conv2d_f32(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int KH, int KW,
@@ -463,7 +473,13 @@ int ur_lpips_finish(const void* ws, long long ws_bytes, int N, int H, int W, dou
  * ur_avgpool_f32: x [N,P,C] -> y [N,C], the mean over the P pixels: ascending order in fp64, rounded to fp32 once.
  * ur_top1_counts: logits fp32 [N,C], labels int64 [N] (the CALLER checks 0 <= label < C) -> pred int64 [N], the argmax with ties
  *   to the lowest index and NaN as the maximum (torch.argmax), and counts int64 [3][C] of THIS batch: tp_c (pred = label = c),
- *   targets_c (label = c), predicted_c (pred = c).  Written, not accumulated. */
+ *   targets_c (label = c), predicted_c (pred = c).  Written, not accumulated.
+ * Size limits (64-bit arithmetic, before any HIP call).  One thread per element or per output, int indices, 256-thread workgroups:
+ *   a launch's count must be below 2^31 - 256 so that the whole last workgroup stays inside an int (csrc/launch_size.h), and the
+ *   element counts that can become a launch count carry that bound:
+ *   ur_classify_preprocess: N*3*H*max(W, 224) and N*3*224*224 must be below 2^31 - 256.
+ *   ur_maxpool2d_pad_f32: N*H*W*C must be below 2^31 - 256 (a 1 x 1 map has as many outputs as inputs).
+ *   ur_avgpool_f32: N*P*C must be below 2^31 - 256.          ur_top1_counts: N*C must be below 2^31 - 256. */
 int ur_conv2d_f32_res(const float* x, const float* w, const float* bias, const float* res, float* y, int N, int H, int W, int Cin, int Cout,
                       int KH, int KW, int stride, int pad, int relu, ur_stream_t stream);
 int ur_classify_preprocess(const float* x, float* tmp, float* y, int N, int C, int H, int W, const int* first_w, const int* count_w,
@@ -493,7 +509,13 @@ int ur_top1_counts(const float* logits, const long long* labels, int N, int C, l
  *   receives the averaged logits (for tests; without it no full-resolution logit tensor exists anywhere).
  * ur_seg_confusion: pred uint8 [P], target uint8 [P] (target_i64 = 0) or int64 [P] (1) -> conf int64 [C][C], conf[t][p] = the
  *   pixels with target t and prediction p, over the pixels with 0 <= t < C, t != ignore_index and p < C.  Written, not
- *   accumulated.  ws: ur_seg_confusion_ws_bytes(P, C) bytes (0 for invalid arguments) of per-block counts. */
+ *   accumulated.  ws: ur_seg_confusion_ws_bytes(P, C) bytes (0 for invalid arguments) of per-block counts.
+ * Size limits (64-bit arithmetic, before any HIP call; the launch rule of the classifier section):
+ *   ur_seg_prep: N*3*H*W and N*3*OH*OW must be below 2^31 (the launch is over the N*OH*OW outputs).
+ *   ur_upsample_bilinear_ac_f32: N*h*w*C and N*H*W*C must be below 2^31 - 256.     ur_maxpool5_f32: N*H*W*C must be below 2^31 - 256.
+ *   ur_add_f32: n in [1, 2^31 - 256).
+ *   ur_seg_tta_argmax: N*H*W (N*H*W*C with avg) must be below 2^31 - 256, N*h*w*C of every map below 2^31.
+ *   ur_seg_confusion: P in [1, 2^31) (64-bit pixel indices, at most 1024 workgroups that stride over the 4096-pixel chunks). */
 int ur_seg_prep(const float* x, float* y, int N, int C, int H, int W, int OH, int OW, const int* idx_h, const float* wt_h, const int* idx_w,
                 const float* wt_w, ur_stream_t stream);
 int ur_upsample_bilinear_ac_f32(const float* x, float* y, int N, int h, int w, int C, int H, int W, const int* idx_h, const float* wt_h,

@@ -217,6 +217,13 @@ def test_ops_reject_bad_inputs():
         with pytest.raises(ValueError):
             ops.top1(bad_l, bad_y)
     assert ops.top1(logits, labels)[2].sum() == 2
+    # the launchers' size limits, at the first refused count (placeholder pointers: a refusal comes before any HIP call)
+    from unirestore_amd import capi
+    lib, P, L = capi.lib, 256, (1 << 31) - 256                                # L: the 1-D launch limit of csrc/launch_size.h
+    for call in (lambda: lib.ur_maxpool2d_pad_f32(P, P + 256, L // 4, 1, 1, 4, None), lambda: lib.ur_avgpool_f32(P, P + 256, L // 4, 1, 4, None),
+                 lambda: lib.ur_top1_counts(P, P, 1, L, P, P, None), lambda: lib.ur_top1_counts(P, P, L // 4, 4, P, P, None),
+                 lambda: lib.ur_classify_preprocess(P, P + 256, P + 512, 10632, 3, 257, 262, P, P, P, 4, P, P, P, 4, None)):
+        assert call() == capi.UR_E_INVALID and "below 2^31 - 256" in lib.ur_last_error().decode(), lib.ur_last_error().decode()
 
 
 # ---- the caller ---------------------------------------------------------------------------------------------------------------

@@ -357,13 +357,15 @@ def test_launchers_refuse_bad_arguments():
         ("C must be 3", lambda: lib.ur_seg_prep(P, P, 1, 4, 8, 8, 8, 8, P, P, P, P, None)),
         ("null pointer", lambda: lib.ur_seg_prep(P, None, 1, 3, 8, 8, 8, 8, P, P, P, P, None)),
         ("below 2^31", lambda: lib.ur_seg_prep(P, P, 1 << 12, 3, 512, 512, 8, 8, P, P, P, P, None)),
-        ("below 2^31", lambda: lib.ur_upsample_bilinear_ac_f32(P, P + 256, 2, 8, 8, 256, 2048, 2048, P, P, P, P, None)),
+        ("below 2^31 - 256", lambda: lib.ur_upsample_bilinear_ac_f32(P, P + 256, 2, 8, 8, 256, 2048, 2048, P, P, P, P, None)),
         ("same buffer", lambda: lib.ur_upsample_bilinear_ac_f32(P, P, 1, 2, 2, 4, 4, 4, P, P, P, P, None)),
         (">= 1", lambda: lib.ur_upsample_bilinear_ac_f32(P, P + 256, 1, 0, 2, 4, 4, 4, P, P, P, P, None)),
-        ("below 2^31", lambda: lib.ur_maxpool5_f32(P, P + 256, 4, 1024, 1024, 512, None)),
+        ("below 2^31 - 256", lambda: lib.ur_maxpool5_f32(P, P + 256, 4, 1024, 1024, 512, None)),
+        ("below 2^31 - 256", lambda: lib.ur_maxpool5_f32(P, P + 256, 8388607, 1, 1, 256, None)),            # N*H*W*C = 2^31 - 256
         ("same buffer", lambda: lib.ur_maxpool5_f32(P, P, 1, 4, 4, 4, None)),
-        ("[1, 2^31)", lambda: lib.ur_add_f32(P, P, P, 1 << 31, None)),
-        ("[1, 2^31)", lambda: lib.ur_add_f32(P, P, P, 0, None)),
+        ("[1, 2^31 - 256)", lambda: lib.ur_add_f32(P, P, P, 1 << 31, None)),
+        ("[1, 2^31 - 256)", lambda: lib.ur_add_f32(P, P, P, (1 << 31) - 256, None)),       # the launch limit itself (csrc/launch_size.h)
+        ("[1, 2^31 - 256)", lambda: lib.ur_add_f32(P, P, P, 0, None)),
         ("neither a nor b", lambda: lib.ur_add_f32(P, P + 256, P, 4, None)),
         ("neither a nor b", lambda: lib.ur_add_f32(P + 256, P, P, 4, None)),
         ("nmaps", lambda: lib.ur_seg_tta_argmax(P, P, P, 4, 1, 19, 4, 4, 4, 4, 4, 4, 8, 8, P, P, P, P, P, None, None)),
@@ -371,8 +373,8 @@ def test_launchers_refuse_bad_arguments():
         ("[1, 255]", lambda: lib.ur_seg_tta_argmax(P, None, None, 1, 1, 256, 4, 4, 0, 0, 0, 0, 8, 8, P, P, P, P, P, None, None)),
         ("[1, 255]", lambda: lib.ur_seg_tta_argmax(P, None, None, 1, 1, 0, 4, 4, 0, 0, 0, 0, 8, 8, P, P, P, P, P, None, None)),
         ("h and w", lambda: lib.ur_seg_tta_argmax(P, P, None, 2, 1, 19, 4, 4, 0, 4, 0, 0, 8, 8, P, P, P, P, P, None, None)),
-        ("below 2^31", lambda: lib.ur_seg_tta_argmax(P, None, None, 1, 64, 19, 4, 4, 0, 0, 0, 0, 8192, 8192, P, P, P, P, P, None, None)),
-        ("below 2^31", lambda: lib.ur_seg_tta_argmax(P, None, None, 1, 8, 19, 4, 4, 0, 0, 0, 0, 4096, 4096, P, P, P, P, P, P + 256, None)),
+        ("below 2^31 - 256", lambda: lib.ur_seg_tta_argmax(P, None, None, 1, 64, 19, 4, 4, 0, 0, 0, 0, 8192, 8192, P, P, P, P, P, None, None)),
+        ("below 2^31 - 256", lambda: lib.ur_seg_tta_argmax(P, None, None, 1, 8, 19, 4, 4, 0, 0, 0, 0, 4096, 4096, P, P, P, P, P, P + 256, None)),
         ("below 2^31", lambda: lib.ur_seg_tta_argmax(P, None, None, 1, 8, 19, 4096, 4096, 0, 0, 0, 0, 8, 8, P, P, P, P, P, None, None)),
         ("[1, 255]", lambda: lib.ur_seg_confusion(P, P, 0, 100, 256, 255, P, 1 << 30, P, None)),
         ("[1, 2^31)", lambda: lib.ur_seg_confusion(P, P, 0, 1 << 31, 19, 255, P, 1 << 40, P, None)),

@@ -252,6 +252,13 @@ def test_ops_reject_bad_inputs():
         with pytest.raises(ValueError):
             ops.confusion(pred, tgt, **kw)
     assert int(ops.confusion(pred, tgt)[0, 0]) == 32
+    # the launchers' size limits, at the first refused count (placeholder pointers: a refusal comes before any HIP call)
+    from unirestore_amd import capi
+    lib, P, L = capi.lib, 256, (1 << 31) - 256                                # L: the 1-D launch limit of csrc/launch_size.h
+    for call in (lambda: lib.ur_add_f32(P, P + 256, P + 512, L, None), lambda: lib.ur_maxpool5_f32(P, P + 256, L // 256, 1, 1, 256, None),
+                 lambda: lib.ur_upsample_bilinear_ac_f32(P, P + 256, L // 256, 1, 1, 256, 1, 1, P, P, P, P, None),
+                 lambda: lib.ur_seg_tta_argmax(P, None, None, 1, L // 256, 19, 1, 1, 0, 0, 0, 0, 16, 16, P, P, P, P, P + 256, None, None)):
+        assert call() == capi.UR_E_INVALID and "2^31 - 256" in lib.ur_last_error().decode(), lib.ur_last_error().decode()
 
 
 # ---- the caller ---------------------------------------------------------------------------------------------------------------

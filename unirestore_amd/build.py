@@ -52,7 +52,7 @@ def build(force=False, verbose=True):
         src, extra, oname = unit
         obj = os.path.join(objdir, oname)
         cmd = [cc, *FLAGS, *EXTRA, *extra, "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, src), "-o", obj]
-        deps = [os.path.join(CSRC, src), os.path.join(CSRC, "common.h"), os.path.join(HERE, "..", "include", "unirestore_hip.h")]
+        deps = [os.path.join(CSRC, src), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "launch_size.h"), os.path.join(HERE, "..", "include", "unirestore_hip.h")]
         if src.startswith("igemm") or src.startswith("conv_wstream"):
             deps += [os.path.join(CSRC, "igemm_impl.h"), os.path.join(CSRC, "igemm_asm.inc")]
         if src.startswith("attention"):

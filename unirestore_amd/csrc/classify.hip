@@ -131,9 +131,9 @@ __global__ __launch_bounds__(256) void top1_counts_kernel(const long long* __res
     tg += t;
     pr += p;
   }
-  counts[c] = tp;
-  counts[C + c] = tg;
-  counts[2 * C + c] = pr;
+  counts[c] = tp;                          // (64-bit row offsets: 2 * C does not fit an int from C = 2^30 on)
+  counts[(long long)C + c] = tg;
+  counts[2ll * C + c] = pr;
 }
 
 }  // namespace
@@ -147,41 +147,47 @@ int ur_classify_preprocess(const float* x, float* tmp, float* y, int N, int C, i
   UR_REQUIRE(N >= 1 && H >= 1 && W >= 1, "N, H and W must be >= 1");
   UR_REQUIRE(C == 3, "C must be 3 (RGB)");
   UR_REQUIRE(taps_w >= 1 && taps_w <= CL_MAX_TAPS && taps_h >= 1 && taps_h <= CL_MAX_TAPS, "taps_w and taps_h must be in [1, 64]");
-  UR_REQUIRE((long long)N * 3 * H * W <= INT_MAX && (long long)N * 3 * H * CL_OUT <= INT_MAX && (long long)N * 3 * CL_OUT * CL_OUT <= INT_MAX,
-             "too many pixels: N*3*H*max(W, 224) must be below 2^31");
+  UR_REQUIRE((long long)N * 3 * H * W < ur::GRID_1D_LIMIT && (long long)N * 3 * H * CL_OUT < ur::GRID_1D_LIMIT &&
+                 (long long)N * 3 * CL_OUT * CL_OUT < ur::GRID_1D_LIMIT,
+             "too many pixels: N*3*H*max(W, 224) and N*3*224*224 must be below 2^31 - 256");
   hipStream_t s = (hipStream_t)stream;
   const int rows = N * 3 * H, t1 = rows * CL_OUT, t2 = N * CL_OUT * CL_OUT;
-  hipLaunchKernelGGL(classify_resize_w_kernel, dim3((t1 + 255) / 256), dim3(256), 0, s, x, tmp, rows, W, first_w, count_w, wt_w, taps_w);
-  hipLaunchKernelGGL(classify_resize_h_kernel, dim3((t2 + 255) / 256), dim3(256), 0, s, tmp, y, N, H, first_h, count_h, wt_h, taps_h);
+  UR_GRID_1D(blocks_w, t1, 256);
+  UR_GRID_1D(blocks_h, t2, 256);
+  hipLaunchKernelGGL(classify_resize_w_kernel, dim3(blocks_w), dim3(256), 0, s, x, tmp, rows, W, first_w, count_w, wt_w, taps_w);
+  hipLaunchKernelGGL(classify_resize_h_kernel, dim3(blocks_h), dim3(256), 0, s, tmp, y, N, H, first_h, count_h, wt_h, taps_h);
   return ur::check_launch("ur_classify_preprocess");
 }
 
 int ur_maxpool2d_pad_f32(const float* x, float* y, int N, int H, int W, int C, ur_stream_t stream) {
   UR_REQUIRE(x && y, "null pointer");
   UR_REQUIRE(N >= 1 && C >= 1 && H >= 1 && W >= 1, "N, C, H and W must be >= 1");
-  UR_REQUIRE((long long)N * H * W * C <= INT_MAX, "too many elements: N*H*W*C must be below 2^31");
+  UR_REQUIRE((long long)N * H * W * C < ur::GRID_1D_LIMIT, "too many elements: N*H*W*C must be below 2^31 - 256");
   const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  const int total = N * OH * OW * C;
-  hipLaunchKernelGGL(maxpool2d_pad_f32_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, y, total, H, W, C, OH, OW);
+  const int total = N * OH * OW * C;                   // = N*H*W*C on a 1 x 1 map
+  UR_GRID_1D(blocks, total, 256);
+  hipLaunchKernelGGL(maxpool2d_pad_f32_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, y, total, H, W, C, OH, OW);
   return ur::check_launch("ur_maxpool2d_pad_f32");
 }
 
 int ur_avgpool_f32(const float* x, float* y, int N, int P, int C, ur_stream_t stream) {
   UR_REQUIRE(x && y, "null pointer");
   UR_REQUIRE(N >= 1 && P >= 1 && C >= 1, "N, P and C must be >= 1");
-  UR_REQUIRE((long long)N * P * C <= INT_MAX, "too many elements: N*P*C must be below 2^31");
-  const int total = N * C;
-  hipLaunchKernelGGL(avgpool_f32_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, y, total, P, C);
+  UR_REQUIRE((long long)N * P * C < ur::GRID_1D_LIMIT, "too many elements: N*P*C must be below 2^31 - 256");
+  const int total = N * C;                             // = N*P*C for P = 1
+  UR_GRID_1D(blocks, total, 256);
+  hipLaunchKernelGGL(avgpool_f32_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, y, total, P, C);
   return ur::check_launch("ur_avgpool_f32");
 }
 
 int ur_top1_counts(const float* logits, const long long* labels, int N, int C, long long* pred, long long* counts, ur_stream_t stream) {
   UR_REQUIRE(logits && labels && pred && counts, "null pointer");
   UR_REQUIRE(N >= 1 && C >= 1, "N and C must be >= 1");
-  UR_REQUIRE((long long)N * C <= INT_MAX, "too many logits: N*C must be below 2^31");
+  UR_REQUIRE((long long)N * C < ur::GRID_1D_LIMIT, "too many logits: N*C must be below 2^31 - 256");
   hipStream_t s = (hipStream_t)stream;
+  UR_GRID_1D(blocks, C, 256);                          // C alone reaches the limit for N = 1
   hipLaunchKernelGGL(top1_kernel, dim3(N), dim3(64), 0, s, logits, C, pred);
-  hipLaunchKernelGGL(top1_counts_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (const long long*)pred, labels, N, C, counts);
+  hipLaunchKernelGGL(top1_counts_kernel, dim3(blocks), dim3(256), 0, s, (const long long*)pred, labels, N, C, counts);
   return ur::check_launch("ur_top1_counts");
 }
 

@@ -222,6 +222,8 @@ struct ProfScope {
 };
 }  // namespace ur
 
+#include "launch_size.h"      // ur::grid_1d / UR_GRID_1D: the block count of every 1-D launch
+
 #define UR_REQUIRE(cond, msg) \
   do {                        \
     if (!(cond)) return ur::fail(UR_E_INVALID, std::string(__func__) + ": " + (msg)); \

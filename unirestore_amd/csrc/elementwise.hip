@@ -724,9 +724,10 @@ int ur_spade_modulate(const void* n, const void* gb, int ldgb, const void* resid
 int ur_linear_f32(const float* x, const float* w, const float* bias, float* y, int M, int N, int K, int groups, int act,
                   ur_stream_t stream) {
   UR_REQUIRE(x && w && y && M > 0 && N > 0 && K > 0 && groups > 0 && N % groups == 0 && K % groups == 0, "bad args");
+  UR_GRID_1D(blocks, N, 4);                            // four output columns (one per wave) per block
   hipStream_t s = (hipStream_t)stream;
   ur::ProfScope prof("linear_f32", 2.0 * M * (double)N * K / groups, 4.0 * N * (double)K / groups, s);
-  hipLaunchKernelGGL(linear_f32_kernel, dim3((N + 3) / 4), dim3(256), 0, s, x, w, bias, y, M, N, K, groups, act);
+  hipLaunchKernelGGL(linear_f32_kernel, dim3(blocks), dim3(256), 0, s, x, w, bias, y, M, N, K, groups, act);
   return ur::check_launch("ur_linear_f32");
 }
 
@@ -747,7 +748,8 @@ int ur_tfa_prompt_update_fanout(const float* pooled, const float* cond, float* u
 int ur_vec_mul_group(const float* a, const float* b, float* out, int N, int C, int G, ur_stream_t stream) {
   UR_REQUIRE(a && b && out && N > 0 && C > 0 && G > 0, "null pointer / N, C, G must be positive");      // G > 0 before C % G
   UR_REQUIRE(C % G == 0 && (long long)N * C < (1ll << 31) - 256, "G must divide C and N * C must fit an int");
-  hipLaunchKernelGGL(vec_mul_group_kernel, dim3((N * C + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, b, out, N, C, G);
+  UR_GRID_1D(blocks, (long long)N * C, 256);
+  hipLaunchKernelGGL(vec_mul_group_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, b, out, N, C, G);
   return ur::check_launch("ur_vec_mul_group");
 }
 

@@ -304,8 +304,9 @@ int ur_lpips_prep(const float* x, float* y, int N, int C, int H, int W, ur_strea
   UR_REQUIRE(x && y, "null pointer");
   const char* why = bad_image_shape(N, C, H, W);
   UR_REQUIRE(!*why, why);
-  const int total = N * H * W;
-  hipLaunchKernelGGL(lpips_prep_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, y, total, H * W);
+  const int total = N * H * W;                         // below 2^28 (bad_image_shape): far inside the launch margin
+  UR_GRID_1D(blocks, total, 256);
+  hipLaunchKernelGGL(lpips_prep_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, y, total, H * W);
   return ur::check_launch("ur_lpips_prep");
 }
 
@@ -330,7 +331,7 @@ int ur_conv2d_f32_res(const float* x, const float* w, const float* bias, const f
   UR_REQUIRE(res != y || !res, "res and y must not be the same buffer");
   const int OH = conv_out(H, KH, stride, pad), OW = conv_out(W, KW, stride, pad);
   const long long M = (long long)N * OH * OW;
-  UR_REQUIRE(M <= INT_MAX - CV_BM && (long long)N * H * W <= INT_MAX, "too many pixels: N*OH*OW and N*H*W must be below 2^31");
+  UR_REQUIRE(M <= INT_MAX - CV_BM && (long long)N * H * W <= INT_MAX, "too many pixels: N*OH*OW must be below 2^31 - 128 and N*H*W below 2^31");
   ConvArgs p;
   p.x = x; p.w = w; p.bias = bias; p.res = res; p.y = y;
   p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.OH = OH; p.OW = OW;
@@ -361,8 +362,9 @@ int ur_maxpool2d_f32(const float* x, float* y, int N, int H, int W, int C, ur_st
   UR_REQUIRE(H >= 3 && W >= 3, "H and W must be >= 3");
   const int OH = pool_out(H), OW = pool_out(W);
   UR_REQUIRE((long long)N * H * W * C <= INT_MAX, "too many elements: N*H*W*C must be below 2^31");
-  const int total = N * OH * OW * C;
-  hipLaunchKernelGGL(maxpool2d_f32_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, y, total, H, W, C, OH, OW);
+  const int total = N * OH * OW * C;                   // <= N*H*W*C / 9 (H, W >= 3): far inside the launch margin
+  UR_GRID_1D(blocks, total, 256);
+  hipLaunchKernelGGL(maxpool2d_f32_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, y, total, H, W, C, OH, OW);
   return ur::check_launch("ur_maxpool2d_f32");
 }
 
@@ -387,7 +389,8 @@ int ur_lpips_finish(const void* ws, long long ws_bytes, int N, int H, int W, dou
   const FinishArgs f = finish_layout(N, H, W, &doubles);
   const long long need = doubles * (long long)sizeof(double);
   UR_REQUIRE(ws_bytes >= need, "workspace too small: " + std::to_string(ws_bytes) + " < " + std::to_string(need) + " bytes");
-  hipLaunchKernelGGL(lpips_finish_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, (const double*)ws, f, N, out);
+  UR_GRID_1D(blocks, N, 64);
+  hipLaunchKernelGGL(lpips_finish_kernel, dim3(blocks), dim3(64), 0, (hipStream_t)stream, (const double*)ws, f, N, out);
   return ur::check_launch("ur_lpips_finish");
 }
 

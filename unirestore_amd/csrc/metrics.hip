@@ -135,10 +135,11 @@ __global__ __launch_bounds__(256) void image_metrics_final_kernel(const double* 
   }
 }
 
-inline int tiles_of(int H, int W, int win, int* tx, int* ty) {
-  *tx = (W - win + 1 + MT_TW - 1) / MT_TW;
-  *ty = (H - win + 1 + MT_TH - 1) / MT_TH;
-  return *tx * *ty;
+// (64-bit: W + 63 and tx * ty do not fit an int for every W and H an int holds; bad_shape bounds the product afterwards)
+inline long long tiles_of(int H, int W, int win, int* tx, int* ty) {
+  *tx = (int)(((long long)W - win + MT_TW) / MT_TW);
+  *ty = (int)(((long long)H - win + MT_TH) / MT_TH);
+  return (long long)*tx * *ty;
 }
 
 // shape rules shared by the two entry points; "" when the shape is legal
@@ -148,7 +149,8 @@ const char* bad_shape(int N, int C, int H, int W, int win) {
   if (H < win || W < win) return "H and W must be >= win";
   int tx, ty;
   // one 256-thread block per tile and plane; the launch's work-item count has to stay below 2^31
-  if ((long long)N * C * tiles_of(H, W, win, &tx, &ty) > INT_MAX / 256) return "too many tiles: N*C*tiles must be below 2^23";
+  const long long tiles = tiles_of(H, W, win, &tx, &ty);
+  if (tiles > INT_MAX / 256 || (long long)N * C > INT_MAX / 256 || (long long)N * C * tiles > INT_MAX / 256) return "too many tiles: N*C*tiles must be below 2^23";
   return "";
 }
 
@@ -172,7 +174,7 @@ int ur_image_metrics(const float* pred, const float* target, int N, int C, int H
   const long long need = ur_image_metrics_ws_size(N, C, H, W, win);
   UR_REQUIRE(ws_bytes >= need, "workspace too small: " + std::to_string(ws_bytes) + " < " + std::to_string(need) + " bytes");
   int tx, ty;
-  const int T = tiles_of(H, W, win, &tx, &ty);
+  const int T = (int)tiles_of(H, W, win, &tx, &ty);
   const int blocks = N * C * T;
   double* ssim_part = (double*)ws;
   double* sse_part = ssim_part + blocks;

@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void seg_prep_kernel(const float* __restrict__
   const int oy = r % OH, n = r / OH;
   const int y0 = min(max(iy[oy], 0), H - 1), y1 = min(y0 + 1, H - 1);
   const int x0 = min(max(ix[ox], 0), W - 1), x1 = min(x0 + 1, W - 1);
-  const float h0 = wy[2 * oy], h1 = wy[2 * oy + 1], w0 = wx[2 * ox], w1 = wx[2 * ox + 1];
+  const float h0 = wy[2ll * oy], h1 = wy[2ll * oy + 1], w0 = wx[2ll * ox], w1 = wx[2ll * ox + 1];      // (an axis may have 2^30 outputs or more)
   const float mean[3] = {123.68f, 116.779f, 103.939f};                 // R, G, B
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void upsample_bilinear_ac_kernel(const float* 
   const int oy = r % H, n = r / H;
   const int y0 = min(max(iy[oy], 0), h - 1), y1 = min(y0 + 1, h - 1);
   const int x0 = min(max(ix[ox], 0), w - 1), x1 = min(x0 + 1, w - 1);
-  const float h0 = wy[2 * oy], h1 = wy[2 * oy + 1], w0 = wx[2 * ox], w1 = wx[2 * ox + 1];
+  const float h0 = wy[2ll * oy], h1 = wy[2ll * oy + 1], w0 = wx[2ll * ox], w1 = wx[2ll * ox + 1];      // (an axis may have 2^30 outputs or more)
   const float* img = x + (long long)n * h * w * C + c;
   const float* p00 = img + ((long long)y0 * w + x0) * C;
   const float* p01 = img + ((long long)y0 * w + x1) * C;
@@ -166,14 +166,15 @@ __global__ __launch_bounds__(256) void seg_tta_argmax_kernel(const TtaArgs p) {
 #pragma unroll
   for (int k = 0; k < NM; ++k) {
     const int h = p.h[k], w = p.w[k];
-    const int y0 = min(max(p.iy[k * p.H + oy], 0), h - 1), y1 = min(y0 + 1, h - 1);
-    const int x0 = min(max(p.ix[k * p.W + ox], 0), w - 1), x1 = min(x0 + 1, w - 1);
+    const long long ty = (long long)k * p.H + oy, tx = (long long)k * p.W + ox;      // table rows: 64-bit, k * H may pass 2^31
+    const int y0 = min(max(p.iy[ty], 0), h - 1), y1 = min(y0 + 1, h - 1);
+    const int x0 = min(max(p.ix[tx], 0), w - 1), x1 = min(x0 + 1, w - 1);
     t00[k] = p.m[k] + (((long long)n * h + y0) * w + x0) * p.C;
     d01[k] = (x1 - x0) * p.C;
     d10[k] = (y1 - y0) * w * p.C;
     d11[k] = d10[k] + d01[k];
-    h0[k] = p.wy[2 * (k * p.H + oy)]; h1[k] = p.wy[2 * (k * p.H + oy) + 1];
-    w0[k] = p.wx[2 * (k * p.W + ox)]; w1[k] = p.wx[2 * (k * p.W + ox) + 1];
+    h0[k] = p.wy[2 * ty]; h1[k] = p.wy[2 * ty + 1];
+    w0[k] = p.wx[2 * tx]; w1[k] = p.wx[2 * tx + 1];
   }
   float bv = 0.f;
   int bi = 0;
@@ -266,8 +267,9 @@ int ur_seg_prep(const float* x, float* y, int N, int C, int H, int W, int OH, in
   UR_REQUIRE(N >= 1 && H >= 1 && W >= 1 && OH >= 1 && OW >= 1, "N, H, W, OH and OW must be >= 1");
   UR_REQUIRE(C == 3, "C must be 3 (RGB)");
   UR_REQUIRE((long long)N * 3 * H * W <= INT_MAX && (long long)N * 3 * OH * OW <= INT_MAX, "too many pixels: N*3*H*W and N*3*OH*OW must be below 2^31");
-  const int total = N * OH * OW;
-  hipLaunchKernelGGL(seg_prep_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, y, total, H, W, OH, OW, idx_h, wt_h, idx_w,
+  const int total = N * OH * OW;                       // <= INT_MAX / 3 by the check above: far inside the launch margin
+  UR_GRID_1D(blocks, total, 256);
+  hipLaunchKernelGGL(seg_prep_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, y, total, H, W, OH, OW, idx_h, wt_h, idx_w,
                      wt_w);
   return ur::check_launch("ur_seg_prep");
 }
@@ -277,14 +279,17 @@ int ur_upsample_bilinear_ac_f32(const float* x, float* y, int N, int h, int w, i
   UR_REQUIRE(x && y && idx_h && wt_h && idx_w && wt_w, "null pointer");
   UR_REQUIRE(x != y, "x and y must not be the same buffer");
   UR_REQUIRE(N >= 1 && C >= 1 && h >= 1 && w >= 1 && H >= 1 && W >= 1, "N, C, h, w, H and W must be >= 1");
-  UR_REQUIRE((long long)N * h * w * C <= INT_MAX && (long long)N * H * W * C <= INT_MAX, "too many elements: N*h*w*C and N*H*W*C must be below 2^31");
+  UR_REQUIRE((long long)N * h * w * C < ur::GRID_1D_LIMIT && (long long)N * H * W * C < ur::GRID_1D_LIMIT,
+             "too many elements: N*h*w*C and N*H*W*C must be below 2^31 - 256");
   hipStream_t s = (hipStream_t)stream;
   if (C % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0) {
     const int total = N * H * W * (C / 4);
-    hipLaunchKernelGGL(upsample_bilinear_ac_kernel<4>, dim3((total + 255) / 256), dim3(256), 0, s, x, y, total, h, w, C, H, W, idx_h, wt_h, idx_w, wt_w);
+    UR_GRID_1D(blocks, total, 256);
+    hipLaunchKernelGGL(upsample_bilinear_ac_kernel<4>, dim3(blocks), dim3(256), 0, s, x, y, total, h, w, C, H, W, idx_h, wt_h, idx_w, wt_w);
   } else {
     const int total = N * H * W * C;
-    hipLaunchKernelGGL(upsample_bilinear_ac_kernel<1>, dim3((total + 255) / 256), dim3(256), 0, s, x, y, total, h, w, C, H, W, idx_h, wt_h, idx_w, wt_w);
+    UR_GRID_1D(blocks, total, 256);
+    hipLaunchKernelGGL(upsample_bilinear_ac_kernel<1>, dim3(blocks), dim3(256), 0, s, x, y, total, h, w, C, H, W, idx_h, wt_h, idx_w, wt_w);
   }
   return ur::check_launch("ur_upsample_bilinear_ac_f32");
 }
@@ -293,29 +298,33 @@ int ur_maxpool5_f32(const float* x, float* y, int N, int H, int W, int C, ur_str
   UR_REQUIRE(x && y, "null pointer");
   UR_REQUIRE(x != y, "x and y must not be the same buffer");
   UR_REQUIRE(N >= 1 && C >= 1 && H >= 1 && W >= 1, "N, C, H and W must be >= 1");
-  UR_REQUIRE((long long)N * H * W * C <= INT_MAX, "too many elements: N*H*W*C must be below 2^31");
+  UR_REQUIRE((long long)N * H * W * C < ur::GRID_1D_LIMIT, "too many elements: N*H*W*C must be below 2^31 - 256");
   hipStream_t s = (hipStream_t)stream;
   if (C % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0) {
     const int total = N * H * W * (C / 4);
-    hipLaunchKernelGGL(maxpool5_f32_kernel<4>, dim3((total + 255) / 256), dim3(256), 0, s, x, y, total, H, W, C);
+    UR_GRID_1D(blocks, total, 256);
+    hipLaunchKernelGGL(maxpool5_f32_kernel<4>, dim3(blocks), dim3(256), 0, s, x, y, total, H, W, C);
   } else {
     const int total = N * H * W * C;
-    hipLaunchKernelGGL(maxpool5_f32_kernel<1>, dim3((total + 255) / 256), dim3(256), 0, s, x, y, total, H, W, C);
+    UR_GRID_1D(blocks, total, 256);
+    hipLaunchKernelGGL(maxpool5_f32_kernel<1>, dim3(blocks), dim3(256), 0, s, x, y, total, H, W, C);
   }
   return ur::check_launch("ur_maxpool5_f32");
 }
 
 int ur_add_f32(const float* a, const float* b, float* y, long long n, ur_stream_t stream) {
   UR_REQUIRE(a && b && y, "null pointer");
-  UR_REQUIRE(n >= 1 && n <= INT_MAX, "n must be in [1, 2^31)");
+  UR_REQUIRE(n >= 1 && n < ur::GRID_1D_LIMIT, "n must be in [1, 2^31 - 256): inside [1, 2^31) with a whole last workgroup inside an int");
   UR_REQUIRE(y != a && y != b, "y must be neither a nor b");
   hipStream_t s = (hipStream_t)stream;
   if (n % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)y) & 15) == 0) {
     const int total = (int)(n / 4);
-    hipLaunchKernelGGL(add_f32_kernel<4>, dim3((total + 255) / 256), dim3(256), 0, s, a, b, y, total);
+    UR_GRID_1D(blocks, total, 256);
+    hipLaunchKernelGGL(add_f32_kernel<4>, dim3(blocks), dim3(256), 0, s, a, b, y, total);
   } else {
     const int total = (int)n;
-    hipLaunchKernelGGL(add_f32_kernel<1>, dim3((total + 255) / 256), dim3(256), 0, s, a, b, y, total);
+    UR_GRID_1D(blocks, total, 256);
+    hipLaunchKernelGGL(add_f32_kernel<1>, dim3(blocks), dim3(256), 0, s, a, b, y, total);
   }
   return ur::check_launch("ur_add_f32");
 }
@@ -336,11 +345,12 @@ int ur_seg_tta_argmax(const float* m0, const float* m1, const float* m2, int nma
     UR_REQUIRE((const void*)maps[k] != (const void*)avg, "a map and avg must not be the same buffer");
     p.m[k] = maps[k]; p.h[k] = hs[k]; p.w[k] = ws[k];
   }
-  UR_REQUIRE((long long)N * H * W <= INT_MAX && (!avg || (long long)N * H * W * C <= INT_MAX),
-             "too many pixels: N*H*W (N*H*W*C with avg) must be below 2^31");
+  UR_REQUIRE((long long)N * H * W < ur::GRID_1D_LIMIT && (!avg || (long long)N * H * W * C < ur::GRID_1D_LIMIT),
+             "too many pixels: N*H*W (N*H*W*C with avg) must be below 2^31 - 256");
   p.iy = idx_h; p.wy = wt_h; p.ix = idx_w; p.wx = wt_w; p.pred = pred; p.avg = avg;
   p.total = N * H * W; p.H = H; p.W = W; p.C = C;
-  const dim3 grid((p.total + 255) / 256);
+  UR_GRID_1D(blocks, p.total, 256);
+  const dim3 grid(blocks);
   hipStream_t s = (hipStream_t)stream;
   ur::ProfScope prof("seg_tta_argmax", 9.0 * nmaps * (double)p.total * C, (double)p.total, s);
   if (nmaps == 1) hipLaunchKernelGGL(seg_tta_argmax_kernel<1>, grid, dim3(256), 0, s, p);
@@ -363,6 +373,7 @@ int ur_seg_confusion(const unsigned char* pred, const void* target, int target_i
   UR_REQUIRE(ws_bytes >= ur_seg_confusion_ws_bytes(P, C), "workspace too small: see ur_seg_confusion_ws_bytes");
   UR_REQUIRE(((uintptr_t)ws & 3) == 0, "ws must be 4-byte aligned");
   const int blocks = confusion_blocks(P), bins = C * C;
+  UR_GRID_1D(finish_blocks, bins, 256);                // bins <= 255 * 255
   hipStream_t s = (hipStream_t)stream;
   if (target_i64)
     hipLaunchKernelGGL(seg_confusion_part_kernel<long long>, dim3(blocks), dim3(256), 0, s, pred, (const long long*)target, P, C, ignore_index,
@@ -370,7 +381,7 @@ int ur_seg_confusion(const unsigned char* pred, const void* target, int target_i
   else
     hipLaunchKernelGGL(seg_confusion_part_kernel<unsigned char>, dim3(blocks), dim3(256), 0, s, pred, (const unsigned char*)target, P, C, ignore_index,
                        (int*)ws);
-  hipLaunchKernelGGL(seg_confusion_finish_kernel, dim3((bins + 255) / 256), dim3(256), 0, s, (const int*)ws, blocks, bins, conf);
+  hipLaunchKernelGGL(seg_confusion_finish_kernel, dim3(finish_blocks), dim3(256), 0, s, (const int*)ws, blocks, bins, conf);
   return ur::check_launch("ur_seg_confusion");
 }
 
