@@ -724,6 +724,41 @@ int ur_distort_field(const uint32_t* keys, const float* taps_y, int ry, const fl
 size_t ur_distort_field_ws_bytes(int N, int H, int W);
 int ur_distort_warp(const uint8_t* x, const float* field, void* out, int N, int H, int W, int out_kind, ur_stream_t stream);
 
+/* ---- NIQE block features (no-reference quality, evaluator side; csrc/niqe.hip) ----------------------------------------------------
+ * The natural-scene-statistics features of the NIQE score, as unirestore_amd/niqe.py chains them.  Everything is fp64; no kernel
+ * uses atomics and every sum has a fixed order, so the same inputs give the same bits, eagerly and in a graph.  No expression is
+ * contracted into a fused multiply-add.  Elements are addressed with 64-bit offsets.
+ * ur_niqe_luma: x fp32 NCHW [N,3,H,W] in [0,1] -> y fp64 [N,h,w], the top-left h x w crop (h <= H, w <= W) of
+ *     color_space 0 (yiq):   rint(((0.299 R + 0.587 G) + 0.114 B) * 255)
+ *     color_space 1 (ycbcr): rint(((16 + 65.481 R) + 128.553 G) + 24.966 B)            (rint: round half to even)
+ * ur_niqe_mscn: y fp64 [N,h,w] -> m = (y - mu) / (sqrt(|G*y^2 - mu^2|) + 1), mu = G*y, G the 7 x 7 Gaussian of sigma 7/6 normalised
+ *     to sum 1 and applied separably (g_k = exp(-(k-3)^2 / (2 sigma^2)) / sum, the row pass first, taps ascending), with a replicate
+ *     border at the edge of the h x w field.  m must not be y.
+ * ur_niqe_block_moments: field fp64 [N,h,w], bs 96 or 48, h and w multiples of bs -> moments fp64 [N][blocks][5][6], the blocks in
+ *     row-major order.  Fields: M, then M * roll(M, s) for s = (0,1), (1,0), (1,1), (1,-1), roll(M, s)[i][j] =
+ *     M[(i - s0) mod bs][(j - s1) mod bs] INSIDE the block.  Moments: the count and the sum of squares of the entries < 0, the
+ *     same of the entries > 0, sum |v|, sum v^2.  One workgroup per block, the block in LDS (72 KiB at bs = 96).
+ * ur_niqe_halve: y fp64 [N,h,w], h and w even and >= 4 -> out fp64 [N,h/2,w/2] = halve(y / 255) * 255, the antialiased bicubic
+ *     (a = -0.5) halving: output o reads inputs 2o-3 .. 2o+4 with the weights (-0.0234375, -0.0703125, 0.2265625, 0.8671875,
+ *     0.8671875, 0.2265625, -0.0703125, -0.0234375) / 2, an index outside the axis mirrored with the edge sample repeated
+ *     (-1 -> 0, -2 -> 1, n -> n-1); along the rows first (every column's eight row taps, ascending), then along the columns.
+ * ur_niqe_fit: moments fp64 [rows][5][6] of blocks of block_pixels pixels -> the 18 features of every row at
+ *     features[row * ld + col_off ..]: (alpha, (bl + br) / 2) of M, then (alpha, (br - bl) * mean_ratio[i], bl, br) of each product.
+ *     l = sqrt(sum- / n-), r = sqrt(sum+ / n+), gam = l / r, R = (sum|v| / P)^2 / (sum v^2 / P) * (gam^3 + 1)(gam + 1) / (gam^2 + 1)^2;
+ *     i = the first index that minimises (rho[i] - R)^2 over the 9801-entry tables, found by bisection of the strictly increasing
+ *     rho; alpha = 0.2 + 0.001 i, bl = l * scale[i], br = r * scale[i].  A NaN R (a count of 0) gives NaN features and index -1.
+ *     rho, scale, mean_ratio: DEVICE fp64 [9801] = Gamma(2/a)^2 / (Gamma(1/a) Gamma(3/a)), sqrt(Gamma(1/a) / Gamma(3/a)),
+ *     Gamma(2/a) / Gamma(1/a), built on the host.  alpha_index: NULL, or int32 [rows][5] that receives i.
+ * UR_E_INVALID before any HIP call for a null required pointer or a malformed shape.  Size limits (64-bit arithmetic, before any HIP
+ * call; UR_E_UNSUPPORTED beyond): N*h*w < 2^31 - 256 (luma, halve), N * ceil(h/32) * ceil(w/32) < 2^31 - 256 (mscn),
+ * N * blocks < 2^31 - 256 (block_moments), rows * 5 < 2^31 - 256 (fit). */
+int ur_niqe_luma(const float* x, double* y, int N, int H, int W, int h, int w, int color_space, ur_stream_t stream);
+int ur_niqe_mscn(const double* y, double* m, int N, int h, int w, ur_stream_t stream);
+int ur_niqe_block_moments(const double* field, double* moments, int N, int h, int w, int bs, ur_stream_t stream);
+int ur_niqe_halve(const double* y, double* out, int N, int h, int w, ur_stream_t stream);
+int ur_niqe_fit(const double* moments, const double* rho, const double* scale, const double* mean_ratio, double* features,
+                int* alpha_index, long long rows, int block_pixels, int ld, int col_off, ur_stream_t stream);
+
 /* ---- live per-kernel-family timing (HIP events on the launch stream) ------------------------------*/
 int ur_profile_enable(int on);
 /* writes a JSON object {family: {launches, ms, flops, bytes}} into buf (host); synchronises the events */

@@ -164,6 +164,11 @@ SIGNATURES = {
     "ur_distort_field": (_I, [_P, _P, _I, _P, _I, _P, _I, _I, _I, _F, _F, _P, _SZ, _P]),
     "ur_distort_field_ws_bytes": (_SZ, [_I, _I, _I]),
     "ur_distort_warp": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "ur_niqe_luma": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "ur_niqe_mscn": (_I, [_P, _P, _I, _I, _I, _P]),
+    "ur_niqe_block_moments": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "ur_niqe_halve": (_I, [_P, _P, _I, _I, _I, _P]),
+    "ur_niqe_fit": (_I, [_P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _P]),
     "ur_profile_enable": (_I, [_I]),
     "ur_profile_report": (_I, [C.c_char_p, _SZ]),
 }

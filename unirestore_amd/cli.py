@@ -13,7 +13,8 @@ validation loop.  One process per GPU: under `torch.distributed.run` the global 
 weights are broadcast from rank 0 and the restored shards all-gathered over RCCL.  There is no CPU path: `accelerator: cpu`
 is an error, not a fallback.  Prints one JSON line on rank 0.  `validate --lpips` adds LPIPS, `validate --tasks ir,cls --classify
 NAME=ARCH:WEIGHTS.pth` the top-1 accuracy of a user-supplied ResNet on the `cls` output (unirestore_amd.classify), `validate --tasks
-ir,seg --segment NAME=ARCH:WEIGHTS.pth` the mIoU of a user-supplied RefineNet-LW on the `seg` output (unirestore_amd.segment); all opt-in.
+ir,seg --segment NAME=ARCH:WEIGHTS.pth` the mIoU of a user-supplied RefineNet-LW on the `seg` output (unirestore_amd.segment), `validate --niqe PARAMS` the no-reference NIQE score of the restored images and of the
+inputs against a user-supplied pristine model (unirestore_amd.niqe); all opt-in.
 """
 import argparse
 import json
@@ -173,6 +174,35 @@ def check_lpips_arg(lpips):
     return parts[0], parts[1]
 
 
+def check_niqe_arg(niqe):
+    """--niqe PARAMS (or a loaded niqe.NiqeParams, returned as it is) -> the path; ValueError unless the file exists and its
+    extension is one niqe.load_params reads (.pt / .pth / .npz / .mat with the keys mu_prisparam and cov_prisparam)."""
+    from .niqe import EXTENSIONS, NiqeParams
+    if isinstance(niqe, NiqeParams):
+        return niqe
+    if not isinstance(niqe, (str, os.PathLike)) or not str(niqe):
+        raise ValueError(f"--niqe takes one file of NIQE model parameters ({', '.join(EXTENSIONS)}); got {type(niqe).__name__}")
+    path = str(niqe)
+    if not os.path.isfile(path):
+        raise ValueError(f"--niqe: no such file: {path}")
+    if os.path.splitext(path)[1].lower() not in EXTENSIONS:
+        raise ValueError(f"--niqe: {path}: unknown extension, expected one of {', '.join(EXTENSIONS)}")
+    return path
+
+
+def check_niqe_run(crop, r: dict):
+    """What a NIQE run needs besides its parameters, checked before the model is built: an evaluator crop (the given one or the
+    default, when the config's need_crop is on) that holds at least two 96 x 96 blocks.  r = resolve(cfg)."""
+    from .niqe import BLOCK, MIN_BLOCKS
+    from .runner import DEFAULT_CROP
+    if not r["caller_args"].get("need_crop", True):
+        return
+    ch, cw = DEFAULT_CROP if crop is None else crop
+    if (ch // BLOCK) * (cw // BLOCK) < MIN_BLOCKS:
+        raise ValueError(f"--niqe: the evaluator's crop {ch} x {cw} holds {(ch // BLOCK) * (cw // BLOCK)} block(s) of {BLOCK} x {BLOCK}; "
+                         f"the score needs at least {MIN_BLOCKS} (pass a larger --crop)")
+
+
 LABELLED_DATA = ("ImageListFiles", "CorruptedImageFiles", "DistortedImageFiles", "JpegImageFiles")      # take `labels: true`
 
 
@@ -287,7 +317,7 @@ def check_crop_arg(crop):
 
 
 def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_16bit=False, metrics_device="cpu", tasks=None,
-             model=None, lpips=None, classify=None, segment=None, crop=None) -> dict:
+             model=None, lpips=None, classify=None, segment=None, crop=None, niqe=None) -> dict:
     """tasks: a list of task names - every batch is restored once and decoded for each of them (DiffUIE.forward_tasks).  PSNR / SSIM
     come from the "ir" output, so the list must hold "ir"; images_per_s counts input images.  model: a ready DiffUIE to use instead
     of building the config's.  With data.CorruptedImageFiles (and data.DistortedImageFiles: "snow/3") the result also holds by_corruption ("fog/3" -> psnr, ssim, images)
@@ -303,8 +333,14 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
     against the data's label maps (tasks must hold "seg", the data must be built with labels: map): the result and every
     by_corruption entry gain, per NAME, the mIoU (the reference's MulticlassJaccardIndex(19, ignore_index=255)) and NAME_acc (pixel
     accuracy) of the restored images (val_lq/NAME; by_corruption: NAME) and of the unrestored inputs (val_input/NAME;
-    by_corruption: input/NAME).  crop: (H, W) or "H,W", the centre crop's size instead of 512 x 512."""
+    by_corruption: input/NAME).  crop: (H, W) or "H,W", the centre crop's size instead of 512 x 512.
+    niqe: a file of NIQE model parameters (.pt / .pth / .npz / .mat with mu_prisparam and cov_prisparam; the user's, none ship with
+    the project) or a loaded niqe.NiqeParams - the no-reference NIQE score (fp64 on the GPU) of the restored images (val_lq/niqe;
+    by_corruption: niqe) and of the unrestored inputs (val_input/niqe; by_corruption: input/niqe), each the mean over the images
+    with a finite score, and niqe_skipped = [restored, input], the images without one.  The crop must hold two 96 x 96 blocks."""
     import torch
+    if niqe is not None:
+        niqe = check_niqe_arg(niqe)                       # before the model is built
     if lpips is not None and isinstance(lpips, (str, tuple, list)):
         lpips = check_lpips_arg(lpips)                    # before the model is built
     if classify is not None:
@@ -322,10 +358,15 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
         check_classify_run(classify, tasks, r)
     if segment is not None:
         check_segment_run(segment, tasks, r)
+    niqe_args = {}
+    if niqe is not None:
+        check_niqe_run(crop_args.get("crop"), r)
+        niqe_args = dict(niqe_params=niqe)
     from . import data as data_mod
     from .dist import all_gather_images, shard_range
     rank, world, dev, dist, lit = _start(r, hf_root, random_init, model, metrics_device=metrics_device, lpips_weights=lpips,
-                                         classifiers=classify, segmenters=segment, **crop_args, **r["caller_args"])
+                                         classifiers=classify, segmenters=segment, **crop_args, **niqe_args, **r["caller_args"])
+    pairs = lit.NIQE_KEYS if niqe is not None else ()     # the NIQE states: fp64 [2] device tensors (sum of finite scores, count)
     sums = ("psnr", "ssim") + (("lpips",) if lpips is not None else ())          # the metric states, in all-reduce order
     counts = [k for name in (classify or {}) for k in lit.classifier_keys(name)]  # the classifiers' int64 [3, classes] count states
     counts += [k for name in (segment or {}) for k in lit.segmenter_keys(name)]   # the segmenters' int64 [classes, classes] matrices
@@ -358,8 +399,10 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
             lit.update_classification(by_task["cls"], batch[0], batch[2])
         if segment is not None:
             lit.update_segmentation(by_task["seg"], batch[0], batch[2])
+        lit.update_niqe(by_task["ir"], batch[0])              # (nothing without --niqe)
         if by_corruption is not None:                     # the batch is homogeneous: its increment of the totals belongs to one key
-            acc = by_corruption.setdefault("%s/%d" % data.last, dict({k: 0.0 for k in sums}, **{k: 0 for k in counts}, images=0))
+            acc = by_corruption.setdefault("%s/%d" % data.last, dict({k: 0.0 for k in sums}, **{k: 0 for k in counts},
+                                                                     **{k: 0.0 for k in pairs}, images=0))
             for k in acc:
                 acc[k] = acc[k] + (lit.totals[k] - before[k])
     if world > 1:                                         # the reference's metric states reduce with dist_reduce_fx="sum"
@@ -373,6 +416,12 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
             dist.all_reduce(flat)
             for k, part in zip(counts, flat.split([lit.totals[k].numel() for k in counts])):
                 lit.totals[k] = part.view_as(lit.totals[k])
+        if pairs:                                         # the NIQE sums and counts, and the images they were asked for
+            flat = torch.cat([lit.totals[k].to(dev) for k in pairs] + [torch.tensor([lit.niqe_seen], dtype=torch.float64, device=dev)])
+            dist.all_reduce(flat)
+            for j, k in enumerate(pairs):
+                lit.totals[k] = flat[2 * j:2 * j + 2].clone()
+            lit.niqe_seen = int(flat[-1])
     res = dict(config=r["data_args"], dtype=r["dtype"], n_gpus=world, denoise_steps=r["model_kwargs"]["cnet"]["num_inference_steps"],
                images_per_s=(n_img / secs) if secs > 0 else None, output_finite=finite, **lit.metrics())
     if tasks is not None:
@@ -389,6 +438,9 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
                 from .segment import miou
                 for prefix, key in zip(("", "input/"), lit.segmenter_keys(name)):
                     res["by_corruption"][k][f"{prefix}{name}"], res["by_corruption"][k][f"{prefix}{name}_acc"] = miou(v[key])[:2]
+            for prefix, key in zip(("", "input/"), pairs):    # the mean over this key's images with a finite score
+                total, count = v[key].tolist()
+                res["by_corruption"][k][f"{prefix}niqe"] = total / count if count else float("nan")
         if hasattr(data, "skipped"):
             res["skipped"] = list(data.skipped)
         if data.resize is not None:
@@ -761,6 +813,10 @@ def main(argv=None):
                          "seg and a dataset built with labels: map")
     ap.add_argument("--crop", default=None, metavar="H,W",
                     help="validate: the evaluator's centre crop (default 512,512; the reference's seg evaluator uses 960,1664)")
+    ap.add_argument("--niqe", default=None, metavar="PARAMS",
+                    help="validate: also report the no-reference NIQE score (fp64, on the GPU) of the restored images and of the inputs; "
+                         "PARAMS is a user-supplied file of model parameters (.pt / .pth / .npz / .mat with mu_prisparam and "
+                         "cov_prisparam); the crop must hold two 96 x 96 blocks")
     ap.add_argument("--tasks", default=None, metavar="ir,cls,seg",
                     help="restore every batch once and decode it for each of these tasks (forward_tasks); validate: must hold 'ir', which "
                          "feeds PSNR / SSIM; restore: one sub-folder of --output per task")
@@ -793,6 +849,8 @@ def main(argv=None):
         ap.error("--segment belongs to validate")
     if a.crop is not None and a.command != "validate":
         ap.error("--crop belongs to validate")
+    if a.niqe is not None and a.command != "validate":
+        ap.error("--niqe belongs to validate")
     if a.command in FILE_COMMANDS:
         check, run, errors = FILE_COMMANDS[a.command]
         kw = dict(inp=a.input, output=a.output, batch=a.batch, resize=a.resize)
@@ -832,6 +890,9 @@ def main(argv=None):
             check_segment_run(a.segment, tasks, resolve(cfg, allow_16bit=a.allow_16bit))
         if a.crop is not None:
             a.crop = check_crop_arg(a.crop)
+        if a.niqe is not None:
+            a.niqe = check_niqe_arg(a.niqe)
+            check_niqe_run(a.crop, resolve(cfg, allow_16bit=a.allow_16bit))
     except ValueError as e:
         ap.error(str(e))
     if a.command == "print_config":
@@ -845,7 +906,7 @@ def main(argv=None):
             print(json.dumps(res))
         return 0
     res = validate(cfg, hf_root=a.hf_root, max_batches=a.max_batches, allow_16bit=a.allow_16bit, metrics_device=a.metrics_device,
-                   tasks=tasks, lpips=a.lpips, classify=a.classify, segment=a.segment, crop=a.crop)
+                   tasks=tasks, lpips=a.lpips, classify=a.classify, segment=a.segment, crop=a.crop, niqe=a.niqe)
     if res is not None:
         print(json.dumps(res))
     return 0

@@ -1092,6 +1092,35 @@ def lpips(pred: torch.Tensor, target: torch.Tensor, weights) -> torch.Tensor:
     return _lpips.forward(pred, target, weights)
 
 
+def niqe(images: torch.Tensor, params, color_space: str = "yiq") -> torch.Tensor:
+    """NIQE (no reference; lower is better) of fp32 NCHW images in [0,1] -> fp64 [N] device tensor.  params: what niqe.load_params /
+    niqe.random_params / niqe.fit_params return.  The block features are fp64 HIP kernels with fixed-order sums (two calls give
+    the same bits); the 36-dimensional algebra of the score runs on the host (one device-to-host copy).  The top-left
+    (H // 96 * 96, W // 96 * 96) crop must hold at least two 96 x 96 blocks."""
+    from . import niqe as _niqe
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if not isinstance(images, torch.Tensor) or images.dtype != torch.float32 or images.ndim != 4:
+        raise ValueError(f"niqe: images must be a 4-d fp32 NCHW tensor, got "
+                         f"{getattr(images, 'dtype', type(images))} {tuple(getattr(images, 'shape', ()))}")
+    if images.device != dev:
+        raise ValueError(f"niqe: images is on {images.device}, not on the current device {dev}")
+    if not images.is_contiguous():
+        raise ValueError("niqe: images must be contiguous")
+    n, c, h, w = images.shape
+    if n < 1 or c != 3:
+        raise ValueError(f"niqe: needs [N>=1, 3, H, W] images, got {tuple(images.shape)}")
+    if h < _niqe.BLOCK or w < _niqe.BLOCK or (h // _niqe.BLOCK) * (w // _niqe.BLOCK) < _niqe.MIN_BLOCKS:
+        raise ValueError(f"niqe: images of shape {tuple(images.shape)} hold {(h // _niqe.BLOCK) * (w // _niqe.BLOCK)} block(s) of "
+                         f"{_niqe.BLOCK} x {_niqe.BLOCK}; the score needs at least {_niqe.MIN_BLOCKS}")
+    if not isinstance(params, _niqe.NiqeParams):
+        raise ValueError(f"niqe: params must come from niqe.load_params / niqe.random_params / niqe.fit_params, got {type(params).__name__}")
+    if params.device != dev:
+        raise ValueError(f"niqe: the params are on {params.device}, not on the current device {dev}")
+    if color_space not in _niqe.COLOR_SPACES:
+        raise ValueError(f"niqe: unknown color_space {color_space!r}, choose from {_niqe.COLOR_SPACES}")
+    return _niqe.forward(images, params, color_space)
+
+
 def classify(images: torch.Tensor, weights) -> torch.Tensor:
     """Logits [N, classes] (fp32, on the device) of fp32 NCHW images in [0,1], any H, W >= 1: the classification evaluator's
     preprocess (antialiased bilinear resize to 224 x 224, ImageNet normalisation) and a ResNet, in exact fp32 on the GPU.  weights:

@@ -105,7 +105,7 @@ class LitUniFIE:
 
     def __init__(self, model_kwargs: dict, save_image: bool = False, eval_mode: str = "FR", need_crop: bool = True,
                  dtype: str = "bf16", hf_root: str = None, model=None, metrics_device: str = "cpu", lpips_weights=None,
-                 classifiers=None, segmenters=None, crop=DEFAULT_CROP, **_ignored):
+                 classifiers=None, segmenters=None, crop=DEFAULT_CROP, niqe_params=None, **_ignored):
         from . import checkpoint
         if metrics_device not in METRICS_DEVICES:
             raise ValueError(f"metrics_device={metrics_device!r}: choose from {METRICS_DEVICES}")
@@ -148,6 +148,19 @@ class LitUniFIE:
             for key in self.segmenter_keys(name):
                 self.totals[key] = torch.zeros(w.num_classes, w.num_classes, dtype=torch.int64, device=w.device)
 
+        # NIQE (no reference, fp64 HIP kernels) is off unless a pristine model is given: a path niqe.load_params reads or a loaded
+        # niqe.NiqeParams.  It needs no hq and runs whatever eval_mode says.  totals["niqe"] (the restored images) and
+        # totals["niqe_input"] (the unrestored inputs) are fp64 [2] device tensors, the sum of the finite scores and their count -
+        # replaced, never changed in place; niqe_seen counts the images handed to update_niqe.
+        self.niqe_params, self.niqe_seen = None, 0
+        if niqe_params is not None:
+            from . import niqe
+            self.niqe_params = niqe_params if isinstance(niqe_params, niqe.NiqeParams) else niqe.load_params(niqe_params)
+            for key in self.NIQE_KEYS:
+                self.totals[key] = torch.zeros(2, dtype=torch.float64, device=self.niqe_params.device)
+
+    NIQE_KEYS = ("niqe", "niqe_input")                  # the `totals` keys of the restored images' and the unrestored inputs' NIQE
+
     @staticmethod
     def segmenter_keys(name: str):
         """The two `totals` keys of segmenter `name`: the restored images' confusion matrix, the unrestored inputs'."""
@@ -187,6 +200,8 @@ class LitUniFIE:
                 self.update_classification(outs[-1]["cls"], lq, gt)
             if metrics and self.segmenters:
                 self.update_segmentation(outs[-1]["seg"], lq, gt)
+            if metrics:
+                self.update_niqe(outs[-1]["ir"], lq)
             return outs
         # the IR evaluator always restores with the "ir" prompt (eval_image_restoration.py:70: self.forward(inputs, 'ir')), whatever
         # task tag the batch carries; task-driven decoding belongs to the downstream (MTL) evaluators, which are out of scope
@@ -201,6 +216,8 @@ class LitUniFIE:
                 self.totals["ssim"] += ssim(preds[-1], tgt) * n
             self._add_lpips(preds[-1], tgt)
             self.totals["images"] += n
+        if metrics:
+            self.update_niqe(preds[-1], lq)
         return preds
 
     def _add_gpu_metrics(self, preds: torch.Tensor, tgt: torch.Tensor):
@@ -311,6 +328,23 @@ class LitUniFIE:
                 pred = ops.segment(images.to(device=w.device, dtype=torch.float32).contiguous(), w)
                 self.totals[key] = self.totals[key] + segment.confusion(pred, target, w.num_classes)
 
+    def update_niqe(self, preds: torch.Tensor, lq: torch.Tensor):
+        """The NIQE states of one batch: of `preds`, the quantised "ir" output, and of `lq`, the unrestored inputs it was restored
+        from (centre-cropped as the restoration's input is when need_crop is on), so the two scores cover the same pixels.  An
+        image whose score is not finite (fewer than two NaN-free blocks: a black image) is left out of the sum and the count and
+        shows up in metrics()["niqe_skipped"].  Needs no hq.  Nothing when no pristine model is configured."""
+        if self.niqe_params is None:
+            return
+        from . import ops
+        if self.need_crop:
+            lq = self._crop(lq)
+        dev = self.niqe_params.device
+        for key, images in zip(self.NIQE_KEYS, (preds, lq)):
+            s = ops.niqe(images.to(device=dev, dtype=torch.float32).contiguous(), self.niqe_params)
+            ok = torch.isfinite(s)
+            self.totals[key] = self.totals[key] + torch.stack([torch.where(ok, s, torch.zeros_like(s)).sum(), ok.sum().double()])
+        self.niqe_seen += preds.shape[0]
+
     def metrics(self) -> dict:
         n = max(self.totals["images"], 1)
         psnr_sum, ssim_sum = float(self.totals["psnr"]), float(self.totals["ssim"])     # (the one device read of the "gpu" totals)
@@ -325,4 +359,10 @@ class LitUniFIE:
             from .segment import miou
             for prefix, key in zip(("val_lq", "val_input"), self.segmenter_keys(name)):
                 res[f"{prefix}/{name}"], res[f"{prefix}/{name}_acc"] = miou(self.totals[key])[:2]
+        if self.niqe_params is not None:                  # the mean over the images with a finite score; the others are counted
+            res["niqe_skipped"] = []
+            for prefix, key in zip(("val_lq", "val_input"), self.NIQE_KEYS):
+                total, count = self.totals[key].tolist()
+                res[f"{prefix}/niqe"] = total / count if count else float("nan")
+                res["niqe_skipped"].append(self.niqe_seen - int(count))
         return res
