@@ -53,7 +53,7 @@ E32_AVGPOOL = 2.03e-07                       # max over the cases of |mean32 - m
 # per NET_CASES entry, max |logits32 - logits64| / max |logits64| (the stand-in logits reach |max| 14 .. 540)
 E32_LOGITS = {"resnet50_4x64x64": 4.06e-07, "resnet50_3x33x47": 3.82e-07, "resnet18_200_2x64x64": 3.10e-07, "resnet101_2x32x32": 8.28e-07}
 E32_FORWARD = 2.71e-07                       # the same for FORWARD_CASE (preprocess + network; |max| 196)
-# Measured on an MI355X against fp64 (test_classify_gpu.py prints each figure): preprocess 6.5e-07 .. 7.2e-07 on the resizing cases,
+# Measured on an MI355X against fp64 (test_classify_gpu.py and test_f32net_gpu.py print each figure): preprocess 6.5e-07 .. 7.2e-07 on the resizing cases,
 # 3.43e-07 on the identity resize (torch's own figure), 1.2e-07 at 1 x 1; convolutions 4.2e-08 (FC) .. 2.3e-07; average pool up to
 # 5.9e-08; logits 3.9e-07, 5.1e-07, 4.0e-07, 7.0e-07 of max |logit| on the four NET_CASES; forward 2.8e-07.
 PREP_TOL = GPU_FACTOR * E32_PREP

@@ -26,7 +26,7 @@ E2E_CASES = {(2, 3, 31, 31): 1, (3, 3, 33, 47): 2, (1, 3, 96, 80): 3, (2, 3, 64,
 #   [2,3,64,64]     2.20e-10     2.00e-07 7.93e-08 4.65e-08 3.82e-08 4.19e-08             1.19e-08
 #   [1,3,512,512]   6.69e-11     3.46e-07 8.46e-08 5.46e-08 4.99e-08 4.51e-08             7.03e-09
 # (the metric itself is about 6e-4 with these random weights; the input scaling is off by 3.09e-07, one ulp at 2.6)
-# Measured on an MI355X against fp64 (test_lpips_gpu.py prints each figure): metric 4.4e-11 1.6e-10 3.8e-12 5.5e-11 1.2e-11;
+# Measured on an MI355X against fp64 (test_lpips_gpu.py and test_f32net_gpu.py print each figure): metric 4.4e-11 1.6e-10 3.8e-12 5.5e-11 1.2e-11;
 # convolutions 4.9e-08 .. 1.4e-07 of sum|a b|; tap distance 2.7e-09 .. 5.1e-08 of layer_abs; input scaling 3.09e-07.
 E32_METRIC = 2.20e-10                                            # max |ref_fp32 - ref_fp64|, absolute
 E32_CONV = (3.47e-7, 8.47e-8, 5.47e-8, 5.25e-8, 6.79e-8)         # per conv, relative to sum |a b| + |bias|

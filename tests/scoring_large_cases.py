@@ -1,8 +1,8 @@
 """Case table of the scoring kernels at their stated size limits (tests/test_scoring_large_gpu.py; host gate in
 tests/test_scoring_large_cpu.py).  Importable without torch: the unit builders below import it when they are called.
 
-The scoring side - LPIPS (csrc/lpips.hip), the classifier (csrc/classify.hip), the segmenter (csrc/segment.hip), PSNR / SSIM
-(csrc/metrics.hip) - is tested everywhere else at a few thousand elements.  Every entry point states a size limit (include/
+The scoring side - the fp32 layers (csrc/f32_layers.hip), LPIPS (csrc/lpips.hip), the classifier (csrc/classify.hip), the
+segmenter (csrc/segment.hip), PSNR / SSIM (csrc/metrics.hip) - is tested everywhere else at a few thousand elements.  Every entry point states a size limit (include/
 unirestore_hip.h, "size limits" of each section); the cases here launch just below each limit, on tensors whose bytes cross 2^31 or
 2^32, and on the paths no small case reaches (the second and third trip of the confusion kernel's chunk loop, its 255 bin passes).
 
@@ -30,7 +30,7 @@ def _c(cid, op, export, props=(), **kw):
 
 
 CASES = [
-    # ---- csrc/segment.hip ------------------------------------------------------------------------------------------------------------
+    # ---- csrc/f32_layers.hip ---------------------------------------------------------------------------------------------------------
     _c("add_vec_limit", "add", "ur_add_f32", ("vector", "limit"), n=GRID - 4, count=GRID - 4, limit=GRID, more=dict(n=GRID)),
     _c("add_scalar_limit", "add", "ur_add_f32", ("scalar", "limit"), n=GRID - 3, count=GRID - 3, limit=GRID, more=dict(n=GRID + 1)),
     # 64219 x 32 x 55 x 19 = 2^31 - 288: inside the last block below the limit (`total + 255` does not fit an int from 2^31 - 255 on)
@@ -42,6 +42,28 @@ CASES = [
        limit=GRID, more=dict(N=64220)),
     _c("maxpool5_c256_limit", "maxpool5", "ur_maxpool5_f32", ("vector", "limit"), N=2049, H=46, W=89, C=256, count=2049 * 46 * 89 * 256,
        limit=GRID, more=dict(N=2050)),
+    # a 1 x 1 map: the launch is over all N*C = 2^31 - 257 elements (= limit - 1), each output the one tap inside the map
+    _c("maxpool_pad_limit", "maxpool_pad", "ur_maxpool2d_pad_f32", ("limit",), N=715827797, H=1, W=1, C=3, count=GRID - 1, limit=GRID,
+       more=dict(N=715827798)),
+    # 941 x 99223 x 23 = 2^31 - 259: image n starts at byte 4 * n * P * C, past 2^31 from image 236 on
+    _c("avgpool_limit", "avgpool", "ur_avgpool_f32", ("limit", "plane offsets past 2^31 bytes"), N=941, P=99223, C=23, count=941 * 99223 * 23,
+       limit=GRID, more=dict(N=942)),
+    # 99962 x 31 x 33 x 21 = 2^31 - 2 (2^31 - 1 is prime)
+    _c("maxpool2d_limit", "maxpool2d", "ur_maxpool2d_f32", ("limit",), N=99962, H=31, W=33, C=21, count=99962 * 31 * 33 * 21, limit=INT31,
+       more=dict(N=99963)),
+    # (a) x of 2^24 + 129 rows x 64 channels = 2^32 + 33024 bytes; M % 128 = 1: the last block holds one row, whose taps are the far-end reads
+    _c("conv_a_x_past_4g", "conv", "ur_conv2d_f32_res", ("vector", "x past 2^32 bytes", "M tail of 1 row"), unit="row", N=1, H=1, W=(1 << 24) + 129,
+       Cin=64, Cout=8, k=1, stride=1, pad=0, res=False, relu=True, tol="1x1_s2_256_512"),
+    # (b) 86540 images of 33 x 47 x 4: 2^31 + 93 KiB bytes; K = 36 = two tiles of 16 and a tail of 4, gathered four channels at a time
+    _c("conv_b_3x3_s2_past_2g", "conv", "ur_conv2d_f32_res", ("vector", "x past 2^31 bytes", "K tail"), unit="image", N=86540, H=33, W=47, Cin=4,
+       Cout=8, k=3, stride=2, pad=1, res=False, relu=True, tol="3x3_s2_128_128"),
+    # (c) 10737500 rows x 200 columns = 2^31 + 16352 elements of y and of the residual; 200 = three 64-column tiles and a tail of 8
+    _c("conv_c_y_past_2g_elems", "conv", "ur_conv2d_f32_res", ("vector", "y past 2^31 elements", "residual", "Cout tail"), unit="row", N=1, H=1,
+       W=10737500, Cin=8, Cout=200, k=1, stride=1, pad=0, res=True, relu=False, tol="1x1_64_256_res_no_relu"),
+    # (d) the scalar gather (Cin = 3, as the stems): 115400 images of 33 x 47 x 3 = 2^31 + 333 KiB bytes
+    _c("conv_d_cin3_past_2g", "conv", "ur_conv2d_f32_res", ("scalar", "x past 2^31 bytes"), unit="image", N=115400, H=33, W=47, Cin=3, Cout=8,
+       k=3, stride=1, pad=1, res=False, relu=True, tol="7x7_s2_3_64"),
+    # ---- csrc/segment.hip ------------------------------------------------------------------------------------------------------------
     # N*3*H*W = 2^31 - 2 (2^31 - 1 is prime); the launch is over the N*8*8 outputs, the input is read through 64-bit plane offsets
     _c("seg_prep_limit", "seg_prep", "ur_seg_prep", ("limit",), N=993, H=434, W=1661, OH=8, OW=8, count=993 * 3 * 434 * 1661, limit=INT31,
        more=dict(N=994)),
@@ -58,33 +80,12 @@ CASES = [
     _c("confusion_c255", "confusion", "ur_seg_confusion", ("255 bin passes",), P=5000, C=255, i64=False),
     _c("confusion_c1", "confusion", "ur_seg_confusion", ("C = 1",), P=5000, C=1, i64=False),
     # ---- csrc/classify.hip -----------------------------------------------------------------------------------------------------------
-    # a 1 x 1 map: the launch is over all N*C = 2^31 - 257 elements (= limit - 1), each output the one tap inside the map
-    _c("maxpool_pad_limit", "maxpool_pad", "ur_maxpool2d_pad_f32", ("limit",), N=715827797, H=1, W=1, C=3, count=GRID - 1, limit=GRID,
-       more=dict(N=715827798)),
-    # 941 x 99223 x 23 = 2^31 - 259: image n starts at byte 4 * n * P * C, past 2^31 from image 236 on
-    _c("avgpool_limit", "avgpool", "ur_avgpool_f32", ("limit", "plane offsets past 2^31 bytes"), N=941, P=99223, C=23, count=941 * 99223 * 23,
-       limit=GRID, more=dict(N=942)),
     # 10631 x 3 x 257 x 262 = 2^31 - 386 (H and W >= 224, so the input is the largest of x, tmp and y and its count the binding one)
     _c("classify_prep_limit", "classify_prep", "ur_classify_preprocess", ("limit",), N=10631, H=257, W=262, count=10631 * 3 * 257 * 262,
        limit=GRID, more=dict(N=10632)),
     _c("top1_limit", "top1", "ur_top1_counts", ("limit",), N=21643, C=99223, count=21643 * 99223, limit=GRID, more=dict(N=21644)),
     # ---- csrc/lpips.hip --------------------------------------------------------------------------------------------------------------
     _c("lpips_prep_limit", "lpips_prep", "ur_lpips_prep", ("limit",), N=55245, H=43, W=113, count=55245 * 43 * 113, limit=P28, more=dict(N=55246)),
-    # 99962 x 31 x 33 x 21 = 2^31 - 2 (2^31 - 1 is prime)
-    _c("maxpool2d_limit", "maxpool2d", "ur_maxpool2d_f32", ("limit",), N=99962, H=31, W=33, C=21, count=99962 * 31 * 33 * 21, limit=INT31,
-       more=dict(N=99963)),
-    # (a) x of 2^24 + 129 rows x 64 channels = 2^32 + 33024 bytes; M % 128 = 1: the last block holds one row, whose taps are the far-end reads
-    _c("conv_a_x_past_4g", "conv", "ur_conv2d_f32_res", ("vector", "x past 2^32 bytes", "M tail of 1 row"), unit="row", N=1, H=1, W=(1 << 24) + 129,
-       Cin=64, Cout=8, k=1, stride=1, pad=0, res=False, relu=True, tol="1x1_s2_256_512"),
-    # (b) 86540 images of 33 x 47 x 4: 2^31 + 93 KiB bytes; K = 36 = two tiles of 16 and a tail of 4, gathered four channels at a time
-    _c("conv_b_3x3_s2_past_2g", "conv", "ur_conv2d_f32_res", ("vector", "x past 2^31 bytes", "K tail"), unit="image", N=86540, H=33, W=47, Cin=4,
-       Cout=8, k=3, stride=2, pad=1, res=False, relu=True, tol="3x3_s2_128_128"),
-    # (c) 10737500 rows x 200 columns = 2^31 + 16352 elements of y and of the residual; 200 = three 64-column tiles and a tail of 8
-    _c("conv_c_y_past_2g_elems", "conv", "ur_conv2d_f32_res", ("vector", "y past 2^31 elements", "residual", "Cout tail"), unit="row", N=1, H=1,
-       W=10737500, Cin=8, Cout=200, k=1, stride=1, pad=0, res=True, relu=False, tol="1x1_64_256_res_no_relu"),
-    # (d) the scalar gather (Cin = 3, as the stems): 115400 images of 33 x 47 x 3 = 2^31 + 333 KiB bytes
-    _c("conv_d_cin3_past_2g", "conv", "ur_conv2d_f32_res", ("scalar", "x past 2^31 bytes"), unit="image", N=115400, H=33, W=47, Cin=3, Cout=8,
-       k=3, stride=1, pad=1, res=False, relu=True, tol="7x7_s2_3_64"),
     _c("lpips_layer_c64", "lpips_layer", "ur_lpips_layer", ("feat past 2^31 elements",), N=1025, P=16401, C=64),
     _c("lpips_layer_c384", "lpips_layer", "ur_lpips_layer", ("feat past 2^31 elements",), N=1025, P=2737, C=384),
     # the largest batch of 31 x 31 images: N*H*W = 2^28 - 287 (the next image is refused); five taps of one chunk each

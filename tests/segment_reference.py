@@ -10,7 +10,7 @@ import functools
 import torch
 import torch.nn.functional as F
 
-from classify_reference import GPU_FACTOR, images, nchw, nhwc, varied_images  # noqa: F401  (shared helpers, re-exported)
+from classify_reference import GPU_FACTOR, _conv_bn, images, nchw, nhwc, varied_images  # noqa: F401  (shared helpers, re-exported)
 
 MEAN = (123.68, 116.779, 103.939)            # R, G, B of the 0..255 image
 SCALES = (1, 0.8, 0.6)
@@ -48,7 +48,7 @@ E32_TTA = 5.86e-08                           # max |avg32 - avg64| / max |logit|
 E32_LOGITS = {"tiny_2x64x96": 9.88e-07, "rflw101_1x64x96": 9.55e-07}
 # the same for the three-scale averaged logits at the image's size (what the argmax sees)
 E32_TTA_LOGITS = {"tiny_2x64x96": 6.14e-07, "rflw101_1x64x96": 6.73e-07}
-# Measured on an MI355X against fp64 (test_segment_gpu.py prints each figure): prep 3.45e-05 .. 3.53e-05; up-sample 0 (1 x 1 source)
+# Measured on an MI355X against fp64 (test_segment_gpu.py and test_f32net_gpu.py print each figure): prep 3.45e-05 .. 3.53e-05; up-sample 0 (1 x 1 source)
 # .. 5.23e-08; averaged logits 3.08e-08 .. 5.86e-08 of max |logit|; scale-1 logits 1.42e-06 (depth (1, 1, 1, 1)) and 1.09e-06
 # (rflw101) of max |logit|; no pixel left out and no argmax flip on either network.
 PREP_TOL = GPU_FACTOR * E32_PREP
@@ -162,15 +162,6 @@ def decidable(avg64, bound):
 
 
 # ---- the network (ResNetLW: the torchvision-layout bottleneck ResNet + the light-weight RefineNet head) ------------------------
-
-def _bn(x, sd, key):
-    return F.batch_norm(x, sd[f"{key}.running_mean"].to(x.dtype), sd[f"{key}.running_var"].to(x.dtype), sd[f"{key}.weight"].to(x.dtype),
-                        sd[f"{key}.bias"].to(x.dtype), training=False, eps=1e-5)
-
-
-def _conv_bn(x, sd, ckey, bkey, stride=1, pad=0):
-    return _bn(F.conv2d(x, sd[f"{ckey}.weight"].to(x.dtype), None, stride=stride, padding=pad), sd, bkey)
-
 
 def _conv(x, sd, key, pad=0):
     b = sd.get(f"{key}.bias")

@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bn_fold_matches_the_unfused_block():
     """One Bottleneck (layer2.0: stride 2, a downsample path) with the folded fp32 weights the kernels get, evaluated in fp64,
     against the unfused fp64 restatement: the only difference is the fp32 rounding of the folded weights and biases."""
-    from unirestore_amd import classify
+    from unirestore_amd import f32net
     sd = R.state_dict("resnet50", 3, 1000)
     x = F.relu(torch.randn(2, 256, 9, 7, generator=torch.Generator().manual_seed(1))).double()
     p = "layer2.0"
@@ -27,7 +27,7 @@ def test_bn_fold_matches_the_unfused_block():
     want = F.relu(R._conv_bn(out, sd, f"{p}.conv3", f"{p}.bn3") + R._conv_bn(x, sd, f"{p}.downsample.0", f"{p}.downsample.1", 2, 0))
 
     def folded(t, ckey, bkey, stride=1, pad=0):
-        w, b = classify.fold_bn(sd[f"{ckey}.weight"], *(sd[f"{bkey}.{n}"] for n in ("weight", "bias", "running_mean", "running_var")))
+        w, b = f32net.fold_bn(sd[f"{ckey}.weight"], *(sd[f"{bkey}.{n}"] for n in ("weight", "bias", "running_mean", "running_var")))
         assert w.dtype == torch.float64 and b.dtype == torch.float64
         return F.conv2d(t, w.float().double(), b.float().double(), stride=stride, padding=pad)
     got = F.relu(folded(x, f"{p}.conv1", f"{p}.bn1"))

@@ -1,5 +1,5 @@
-"""Classifier scoring on the GPU (ops.classify / ops.top1, unirestore_amd/classify.py, csrc/classify.hip, ur_conv2d_f32_res): every
-launcher against the fp64 restatement element by element, whole networks on tiny maps, `forward` end to end, batch-place
+"""Classifier scoring on the GPU (ops.classify / ops.top1, unirestore_amd/classify.py, csrc/classify.hip): every launcher
+of its own against the fp64 restatement element by element (the shared fp32 layers: test_f32net_gpu.py), whole networks on tiny maps, `forward` end to end, batch-place
 independence, bit-reproducibility (eager and hipGraph replay), argument checks, and the caller path (LitUniFIE, cli.validate).
 Every bound is 8 x fp32's own measured error (classify_reference.py: E32_* / *_TOL, kept honest by
 test_classify_cpu.py::test_tolerances_follow_the_measured_fp32_error); the weights are seeded stand-ins - no trained weights exist
@@ -40,62 +40,6 @@ def test_preprocess_matches_fp64_and_writes_nhwc(shape):
     print(f"preprocess {shape}: max |err| {err:.2e} (bound {R.PREP_TOL:.2e}; torch's fp32 interpolate {R.TORCH32_PREP[shape]:.2e})")
     assert err <= R.PREP_TOL
     assert err <= R.TORCH32_PREP[shape]                       # no further from fp64 than torch's own fp32 path
-
-
-@pytest.mark.parametrize("name", sorted(R.CONV_CASES))
-def test_conv2d_f32_res_matches_fp64_elementwise(name):
-    from unirestore_amd import classify, lpips
-    _n, _h, _w, _cin, cout, _k, stride, pad, has_res, relu = R.CONV_CASES[name]
-    x, wt, b, res = R.conv_case(name)
-    pc = lpips.PackedConvF32(wt, b, stride, pad, "cuda")
-    y = classify.conv2d_f32_res(R.nhwc(x).cuda(), pc, None if res is None else R.nhwc(res).cuda(), relu=relu)
-    want = R.conv(x, wt, b, stride, pad, res, relu)
-    assert tuple(y.shape) == (want.shape[0], want.shape[2], want.shape[3], cout) and (res is not None) == has_res
-    ratio = float(((R.nchw(y.cpu()).double() - want).abs() / R.conv_abs(x, wt, b, stride, pad, res)).max())
-    print(f"{name}: max |err| / (sum|ab| + |bias| + |res|) {ratio:.2e} (bound {R.CONV_TOL[name]:.2e})")
-    assert ratio <= R.CONV_TOL[name]
-    assert (float(y.min()) >= 0.0) if relu else (float(y.min()) < 0.0)
-
-
-def test_null_residual_is_conv2d_f32_bit_for_bit():
-    from unirestore_amd import classify, lpips
-    for name in ("1x1_64_256_res_relu", "7x7_s2_3_64", "fc_2048_1000"):
-        _n, _h, _w, _cin, _cout, _k, stride, pad, _r, relu = R.CONV_CASES[name]
-        x, wt, b, _res = R.conv_case(name)
-        pc = lpips.PackedConvF32(wt, b, stride, pad, "cuda")
-        xg = R.nhwc(x).cuda()
-        assert torch.equal(lpips.conv2d_f32(xg, pc, relu=relu), classify.conv2d_f32_res(xg, pc, None, relu=relu))
-    with pytest.raises(ValueError):
-        classify.conv2d_f32_res(xg, pc, torch.zeros(1, 1, 1, 3, device="cuda"))      # a residual of the wrong shape
-
-
-POOL_CASES = {"17x24_to_9x12": (2, 64, 17, 24), "8x8_to_4x4": (1, 128, 8, 8), "1x1": (2, 5, 1, 1), "16x16_all_negative": (1, 64, 16, 16)}
-
-
-@pytest.mark.parametrize("name", sorted(POOL_CASES))
-def test_maxpool2d_pad_f32_is_exact(name):
-    from unirestore_amd import classify
-    n, c, h, w_ = POOL_CASES[name]
-    x = torch.randn(n, c, h, w_, generator=torch.Generator().manual_seed(len(name)))
-    if "negative" in name:
-        x = -x.abs() - 0.5                                   # padding with 0 instead of -inf would win at every border
-    y = classify.maxpool2d_pad_f32(R.nhwc(x).cuda()).cpu()
-    want = R.maxpool(x)
-    assert tuple(y.shape) == (n, want.shape[2], want.shape[3], c)
-    assert torch.equal(R.nchw(y), want)
-    if "negative" in name:
-        assert float(y.max()) < 0
-
-
-@pytest.mark.parametrize("shape", R.AVGPOOL_CASES, ids=["x".join(map(str, s)) for s in R.AVGPOOL_CASES])
-def test_avgpool_f32_matches_fp64(shape):
-    from unirestore_amd import classify
-    x = R.avgpool_case(shape)
-    y = classify.avgpool_f32(R.nhwc(x).cuda()).cpu()
-    assert tuple(y.shape) == shape[:2]
-    ratio = float(((y.double() - R.avgpool(x)).abs() / x.double().abs().mean(dim=(2, 3))).max())
-    print(f"avgpool {shape}: max |err| / mean|x| {ratio:.2e} (bound {R.AVGPOOL_TOL:.2e})")
-    assert ratio <= R.AVGPOOL_TOL
 
 
 @pytest.mark.parametrize("classes", [1000, 200])

@@ -27,7 +27,7 @@ def _dicts(seed=3):
 # ---- the loader ---------------------------------------------------------------------------------------------------------------
 
 def test_loader_reads_the_two_real_key_layouts_and_ignores_the_classifier(tmp_path):
-    from unirestore_amd import lpips
+    from unirestore_amd import f32net, lpips
     asd, lsd = _dicts()
     asd["classifier.1.weight"], asd["classifier.1.bias"] = torch.zeros(8, 16), torch.zeros(8)      # torchvision's file has them
     w = lpips.load_weights(*_save(tmp_path, asd, lsd), dev="cpu")
@@ -35,7 +35,7 @@ def test_loader_reads_the_two_real_key_layouts_and_ignores_the_classifier(tmp_pa
     for i, (idx, cout, cin, k, stride, pad) in enumerate(lpips.CONVS):
         pc = w.convs[i]
         assert (pc.cout, pc.cin, pc.kh, pc.kw, pc.stride, pc.pad) == (cout, cin, k, k, stride, pad)
-        kpad, cpad = lpips.wpack_dims(cin, cout, k, k)
+        kpad, cpad = f32net.wpack_dims(cin, cout, k, k)
         assert tuple(pc.w.shape) == (kpad, cpad) and kpad % 16 == 0 and cpad % 64 == 0 and kpad >= cin * k * k and cpad >= cout
         src = asd[f"features.{idx}.weight"]
         for (o, c, y, x) in ((0, 0, 0, 0), (cout - 1, cin - 1, k - 1, k - 1), (cout // 2, cin // 2, 1, 2)):

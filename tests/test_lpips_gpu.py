@@ -1,5 +1,5 @@
-"""LPIPS on the GPU (ops.lpips, unirestore_amd/lpips.py, csrc/lpips.hip): every launcher against the fp64 restatement element by
-element, the whole metric on the end-to-end cases, bit-reproducibility (eager and hipGraph replay), argument checks, and the
+"""LPIPS on the GPU (ops.lpips, unirestore_amd/lpips.py, csrc/lpips.hip): every launcher of its own against the fp64 restatement element by
+element (the shared fp32 layers: test_f32net_gpu.py), the whole metric on the end-to-end cases, bit-reproducibility (eager and hipGraph replay), argument checks, and the
 caller path (LitUniFIE, cli.validate).  Every bound is 8 x fp32's own measured error (lpips_reference.py: E32_* / *_TOL, kept
 honest by test_lpips_cpu.py::test_tolerances_follow_the_measured_fp32_error); the weights are seeded stand-ins - no real LPIPS
 weights exist where this runs, so nothing here says anything about published LPIPS values."""
@@ -36,59 +36,6 @@ def test_prep_matches_fp64_and_writes_nhwc():
     err = float((R.nchw(y).double() - R.scale_input(x)).abs().max())
     print(f"prep: max |err| {err:.2e} (bound {R.PREP_TOL:.2e})")
     assert err <= R.PREP_TOL
-
-
-# name -> (conv index whose measured bound applies, N, H, W, Cin, Cout, k, stride, pad, relu, zero bias)
-CONV_CASES = {
-    "conv1_2x31x31": (0, 2, 31, 31, 3, 64, 11, 4, 2, True, False),              # output 7 x 7, K = 363: a K tail and the scalar gather
-    "conv1_1x33x47": (0, 1, 33, 47, 3, 64, 11, 4, 2, True, False),
-    "conv1_2x64x64_four_blocks": (0, 2, 64, 64, 3, 64, 11, 4, 2, True, False),  # M = 450: more than one block, the last partial
-    "conv2_filter_larger_than_map": (1, 2, 3, 3, 64, 192, 5, 1, 2, True, False),
-    "conv2_no_relu": (1, 1, 6, 5, 64, 192, 5, 1, 2, False, False),
-    "conv3_1x1_map": (2, 2, 1, 1, 192, 384, 3, 1, 1, True, False),              # eight of nine taps are padding
-    "conv3_zero_bias": (2, 1, 5, 4, 192, 384, 3, 1, 1, True, True),
-    "conv4_m105": (3, 3, 7, 5, 384, 256, 3, 1, 1, True, False),                 # M = 105 is no tile multiple; K = 3456
-    "conv5_two_blocks": (4, 2, 9, 8, 256, 256, 3, 1, 1, True, False),           # M = 144
-}
-
-
-@pytest.mark.parametrize("name", sorted(CONV_CASES))
-def test_conv2d_f32_matches_fp64_elementwise(name):
-    from unirestore_amd import lpips
-    idx, n, h, w_, cin, cout, k, stride, pad, relu, zero_bias = CONV_CASES[name]
-    g = torch.Generator().manual_seed(len(name) + 17 * idx)
-    x = torch.randn(n, cin, h, w_, generator=g)
-    if cin != 3:
-        x = F.relu(x)                                        # what the later convs see
-    wt = torch.randn(cout, cin, k, k, generator=g) * math.sqrt(2.0 / (cin * k * k))
-    b = torch.zeros(cout) if zero_bias else 0.1 * torch.randn(cout, generator=g)
-    pc = lpips.PackedConvF32(wt, b, stride, pad, "cuda")
-    y = lpips.conv2d_f32(R.nhwc(x).cuda(), pc, relu=relu)
-    want = R.conv(x, wt, b, stride, pad, relu)
-    assert tuple(y.shape) == (n, want.shape[2], want.shape[3], cout)
-    ratio = float(((R.nchw(y.cpu()).double() - want).abs() / R.conv_abs(x, wt, b, stride, pad)).max())
-    print(f"{name}: max |err| / sum|ab| {ratio:.2e} (bound {R.CONV_TOL[idx]:.2e})")
-    assert ratio <= R.CONV_TOL[idx]
-    if relu:
-        assert float(y.min()) >= 0.0
-    else:
-        assert float(y.min()) < 0.0
-
-
-POOL_CASES = {"7x7_to_3x3": (2, 64, 7, 7), "8x9_to_3x4_floor_drops_a_row": (1, 192, 8, 9), "3x3_to_1x1_negative": (2, 5, 3, 3)}
-
-
-@pytest.mark.parametrize("name", sorted(POOL_CASES))
-def test_maxpool2d_f32_is_exact(name):
-    from unirestore_amd import lpips
-    n, c, h, w_ = POOL_CASES[name]
-    x = torch.randn(n, c, h, w_, generator=torch.Generator().manual_seed(len(name)))
-    if "negative" in name:
-        x = -x.abs() - 0.5                                   # the maximum is not 0: a kernel that starts from 0 fails
-    y = lpips.maxpool2d_f32(R.nhwc(x).cuda()).cpu()
-    want = R.pool(x)
-    assert tuple(y.shape) == (n, want.shape[2], want.shape[3], c)
-    assert torch.equal(R.nchw(y), want)
 
 
 LAYER_CASES = {"c64_1px": (2, 64, 1, 1), "c64_15x11": (2, 64, 15, 11), "c384_1px": (1, 384, 1, 1), "c384_15x11": (3, 384, 15, 11)}

@@ -1,7 +1,7 @@
 """Host gate of the scoring limit cases (tests/scoring_large_cases.py, run on the GPU by tests/test_scoring_large_gpu.py), and the
 stand-alone host program that checks the 1-D launch helper (csrc/launch_size.h) under UBSan / ASan.  Nothing here needs a GPU:
-  * the case table reaches every launching export of lpips.hip, classify.hip, segment.hip and metrics.hip, both kernels of the ops
-    that have a float4 and a scalar one, and every named property (confusion trips, bin passes, tensors past 2^31 / 2^32);
+  * the case table reaches every launching export of f32_layers.hip, lpips.hip, classify.hip, segment.hip and metrics.hip, both
+    kernels of the ops that have a float4 and a scalar one, and every named property (confusion trips, bin passes, tensors past 2^31 / 2^32);
   * every "limit" case sits at the stated limit from below, and one more unit is refused before any HIP call;
   * the fp64 reference of one period of each case, against the reference's own fp32 restatement, stays inside the bound the GPU test
     uses, and the decidability cap of the argmax cases holds - so the GPU test hides nothing under a cap.
@@ -36,10 +36,10 @@ def test_the_scoring_files_launch_through_the_helper():
     converted with them)."""
     import re
     pat = re.compile(r"dim3\(\s*\(+[^;]*\+\s*(255|63)\)\s*/")
-    for name in ("lpips.hip", "classify.hip", "segment.hip", "metrics.hip", "elementwise.hip"):
+    for name in ("f32_layers.hip", "lpips.hip", "classify.hip", "segment.hip", "metrics.hip", "elementwise.hip"):
         src = open(os.path.join(ROOT, "unirestore_amd", "csrc", name)).read()
         assert not pat.search(src), name
-    for name in ("lpips.hip", "classify.hip", "segment.hip"):
+    for name in ("f32_layers.hip", "lpips.hip", "classify.hip", "segment.hip"):
         assert "UR_GRID_1D(" in open(os.path.join(ROOT, "unirestore_amd", "csrc", name)).read(), name
 
 

@@ -159,9 +159,9 @@ def _image_op(c, lib, u, out_elems_per_image, launch, key="x", extra=0):
 
 
 def _run_upsample(c, lib, u):
-    from unirestore_amd import segment
-    iy, wy = segment._device_tables((c["h"],), c["H"], 0)
-    ix, wx = segment._device_tables((c["w"],), c["W"], 0)
+    from unirestore_amd import f32net
+    iy, wy = f32net._device_tables((c["h"],), c["H"], 0)
+    ix, wx = f32net._device_tables((c["w"],), c["W"], 0)
     worst, t = _image_op(c, lib, u, c["H"] * c["W"] * c["C"], lambda x, y: lib.ur_upsample_bilinear_ac_f32(
         x.ptr, y.ptr, c["N"], c["h"], c["w"], c["C"], c["H"], c["W"], iy.data_ptr(), wy.data_ptr(), ix.data_ptr(), wx.data_ptr(), _stream()))
     return worst, "UPSAMPLE_TOL x max |x|", t
@@ -192,9 +192,9 @@ def _run_avgpool(c, lib, u):
 
 
 def _run_seg_prep(c, lib, u):
-    from unirestore_amd import segment
-    iy, wy = segment._device_tables((c["H"],), c["OH"], 0)
-    ix, wx = segment._device_tables((c["W"],), c["OW"], 0)
+    from unirestore_amd import f32net
+    iy, wy = f32net._device_tables((c["H"],), c["OH"], 0)
+    ix, wx = f32net._device_tables((c["W"],), c["OW"], 0)
     worst, t = _image_op(c, lib, u, c["OH"] * c["OW"] * 3, lambda x, y: lib.ur_seg_prep(
         x.ptr, y.ptr, c["N"], 3, c["H"], c["W"], c["OH"], c["OW"], iy.data_ptr(), wy.data_ptr(), ix.data_ptr(), wx.data_ptr(), _stream()))
     return worst, "PREP_TOL (segment)", t
@@ -221,14 +221,14 @@ def _run_classify_prep(c, lib, u):
 
 
 def _run_tta(c, lib, u):
-    from unirestore_amd import segment
+    from unirestore_amd import f32net
     N, C, Ho, Wo = c["N"], c["C"], c["H"], c["W"]
     px = Ho * Wo
     map_elems = sum(h * w for h, w in c["maps"]) * C * N
     _need(4 * map_elems + 2 * N * px * (1 + (4 * C if c["avg"] else 0)), c["id"])
     maps = [_tile(u["ins"][f"m{k}"], N) for k in range(3)]
-    iy, wy = segment._device_tables(tuple(h for h, _ in c["maps"]), Ho, 0)
-    ix, wx = segment._device_tables(tuple(w for _, w in c["maps"]), Wo, 0)
+    iy, wy = f32net._device_tables(tuple(h for h, _ in c["maps"]), Ho, 0)
+    ix, wx = f32net._device_tables(tuple(w for _, w in c["maps"]), Wo, 0)
     hw = [v for m in c["maps"] for v in m]
 
     def make():
@@ -299,14 +299,14 @@ def _run_top1(c, lib, u):
 
 
 def _run_conv(c, lib, u):
-    from unirestore_amd import lpips
+    from unirestore_amd import f32net
     oh, ow = T.conv_out(c)
     rows = c["unit"] == "row"
     U = c["W"] if rows else c["N"]
     M, cout = c["N"] * oh * ow, c["Cout"]
     x_unit = u["ins"]["x"][0].numel()
     _need(4 * (U * x_unit + M * cout * (3 if c["res"] else 2)), c["id"])
-    pc = lpips.PackedConvF32(u["weight"], u["bias"], c["stride"], c["pad"], torch.device("cuda", 0))
+    pc = f32net.PackedConvF32(u["weight"], u["bias"], c["stride"], c["pad"], torch.device("cuda", 0))
     x = _tile(u["ins"]["x"], U)
     res = _tile(u["ins"]["res"], U) if c["res"] else None
     (y,) = _twice(lib, c["id"], lambda: (Buf(M * cout, F32, True),), lambda y: lib.ur_conv2d_f32_res(

@@ -82,8 +82,8 @@ def test_scaled_size_is_torchs_for_every_size():
 
 @pytest.mark.parametrize("n_in,n_out", [(1, 1), (1, 5), (5, 1), (2, 2), (16, 64), (12, 64), (9, 64), (54, 32), (97, 58), (131, 78), (7, 7), (416, 1664)])
 def test_tap_tables_match_torch_fp64(n_in, n_out):
-    from unirestore_amd import segment
-    idx, wt = segment.ac_table(n_in, n_out)
+    from unirestore_amd import f32net
+    idx, wt = f32net.ac_table(n_in, n_out)
     assert idx.dtype == torch.int32 and wt.dtype == torch.float64 and tuple(wt.shape) == (n_out, 2) and tuple(idx.shape) == (n_out,)
     assert int(idx.min()) >= 0 and int(idx.max()) <= n_in - 1 and float(wt.min()) >= 0 and float((wt.sum(dim=1) - 1).abs().max()) <= 1e-15
     a = torch.zeros(n_out, n_in, dtype=torch.float64)
@@ -94,7 +94,7 @@ def test_tap_tables_match_torch_fp64(n_in, n_out):
     if n_in == n_out:
         assert torch.equal(a, torch.eye(n_in, dtype=torch.float64))      # the same size: weights (1, 0), the identity bit for bit
     with pytest.raises(ValueError):
-        segment.ac_table(0, n_out)
+        f32net.ac_table(0, n_out)
 
 
 # ---- mIoU -----------------------------------------------------------------------------------------------------------------------

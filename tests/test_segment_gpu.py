@@ -1,8 +1,8 @@
-"""Segmenter scoring on the GPU (ops.segment / ops.confusion, unirestore_amd/segment.py, csrc/segment.hip): every launcher against
-the fp64 restatement element by element, whole networks on tiny maps, `ops.segment` end to end, batch-place independence,
+"""Segmenter scoring on the GPU (ops.segment / ops.confusion, unirestore_amd/segment.py, csrc/segment.hip): every launcher of
+its own against the fp64 restatement element by element (the shared fp32 layers: test_f32net_gpu.py), whole networks on tiny maps, `ops.segment` end to end, batch-place independence,
 bit-reproducibility (eager and hipGraph replay), argument checks, and the caller path (LitUniFIE, cli.validate).  Every bound
 is 8 x fp32's own measured error (segment_reference.py: E32_* / *_TOL, kept honest by
-test_segment_cpu.py::test_tolerances_follow_the_measured_fp32_error); max-pool, confusion and argmax on exact inputs are
+test_segment_cpu.py::test_tolerances_follow_the_measured_fp32_error); confusion and argmax on exact inputs are
 compared for equality.  The weights are seeded stand-ins - no trained weights exist where this runs, so nothing here says
 anything about any published mIoU."""
 import numpy as np
@@ -46,48 +46,6 @@ def test_prep_at_scale_1_is_bit_exact():
     x = R.images((2, 3, 37, 53), 5)
     y = segment.prep(x.cuda()).cpu()
     assert torch.equal(R.nchw(y), R.preprocess(x, torch.float32))
-
-
-@pytest.mark.parametrize("case", R.UPSAMPLE_CASES, ids=["x".join(map(str, c)) for c in R.UPSAMPLE_CASES])
-def test_upsample_matches_fp64(case):
-    from unirestore_amd import segment
-    x = R.upsample_case(case)
-    y = segment.upsample_bilinear_ac_f32(R.nhwc(x).cuda(), case[4:]).cpu()
-    assert tuple(y.shape) == (case[0], case[4], case[5], case[1])
-    err = float((R.nchw(y).double() - R.resize_ac(x, case[4:])).abs().max() / x.abs().max())
-    print(f"upsample {case}: max |err| / max |x| {err:.2e} (bound {R.UPSAMPLE_TOL:.2e})")
-    assert err <= R.UPSAMPLE_TOL
-
-
-@pytest.mark.parametrize("c", [19, 256])
-def test_upsample_to_the_same_size_is_the_identity(c):
-    from unirestore_amd import segment
-    x = torch.randn(2, 5, 7, c, generator=torch.Generator().manual_seed(c)).cuda()
-    assert torch.equal(segment.upsample_bilinear_ac_f32(x, (5, 7)), x)
-
-
-POOL_CASES = {"1x1": (2, 5, 1, 1), "2x3_window_larger_than_the_map": (1, 8, 2, 3), "7x9": (2, 19, 7, 9), "7x9_c256": (1, 256, 7, 9),
-              "6x6_all_negative": (1, 64, 6, 6)}
-
-
-@pytest.mark.parametrize("name", sorted(POOL_CASES))
-def test_maxpool5_is_exact(name):
-    from unirestore_amd import segment
-    n, c, h, w_ = POOL_CASES[name]
-    x = torch.randn(n, c, h, w_, generator=torch.Generator().manual_seed(len(name)))
-    if "negative" in name:
-        x = -x.abs() - 0.5                                   # padding with 0 instead of -inf would win at every border
-    y = segment.maxpool5_f32(R.nhwc(x).cuda()).cpu()
-    assert torch.equal(R.nchw(y), R.maxpool5(x))
-    if "negative" in name:
-        assert float(y.max()) < 0
-
-
-def test_add_f32_is_exact():
-    from unirestore_amd import segment
-    for shape in ((1, 3, 5, 19), (2, 4, 4, 256)):
-        a, b = (torch.randn(shape, generator=torch.Generator().manual_seed(i)) for i in (1, 2))
-        assert torch.equal(segment.add_f32(a.cuda(), b.cuda()).cpu(), a + b)
 
 
 @pytest.mark.parametrize("name", sorted(R.TTA_CASES))

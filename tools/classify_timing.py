@@ -1,4 +1,4 @@
-"""Time the classifier scoring (`ops.classify`: preprocess + ResNet in exact fp32, csrc/classify.hip + ur_conv2d_f32_res) for one
+"""Time the classifier scoring (`ops.classify`: preprocess + ResNet in exact fp32, csrc/classify.hip + csrc/f32_layers.hip) for one
 batch on cuda:0, per architecture.  Seeded random weights (classify.random_weights: no trained weights are needed to time the
 kernels) and seeded 8-bit-quantised images.
 
@@ -42,7 +42,7 @@ def main():
     ap.add_argument("--archs", default="resnet18,resnet50,resnet101")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    from unirestore_amd import classify, ops
+    from unirestore_amd import classify, f32net, ops
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(3)
     x = torch.round(torch.rand(a.batch, 3, a.res, a.res, generator=g, device=dev) * 255) / 255
@@ -55,7 +55,7 @@ def main():
         prep_ms = _host_times(lambda: classify.preprocess(x), a.reps)
         # every convolution launch under its own event pair (separate passes: the events serialise nothing, but keep them out of
         # the end-to-end figure above)
-        launches, real = [], classify.conv2d_f32_res
+        launches, real = [], f32net.conv2d_f32
 
         def timed(xi, pc, res=None, relu=True):
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -65,7 +65,7 @@ def main():
             launches.append((s, e, 2.0 * y.shape[0] * y.shape[1] * y.shape[2] * pc.cout * pc.cin * pc.kh * pc.kw))
             return y
         per_launch, flops = None, 0.0
-        classify.conv2d_f32_res = timed
+        f32net.conv2d_f32 = timed
         try:
             for _ in range(a.reps):
                 launches.clear()
@@ -75,7 +75,7 @@ def main():
                 per_launch = [[m] for m in ms] if per_launch is None else [p + [m] for p, m in zip(per_launch, ms)]
                 flops = sum(f for _, _, f in launches)
         finally:
-            classify.conv2d_f32_res = real
+            f32net.conv2d_f32 = real
         conv_ms = sum(statistics.median(p) for p in per_launch)
         lines.append(json.dumps(dict(
             arch=arch, batch=a.batch, res=a.res, classes=w.num_classes, classify_ms_median=round(statistics.median(total_ms), 3),

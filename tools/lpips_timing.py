@@ -1,4 +1,4 @@
-"""Time ops.lpips (AlexNet LPIPS, exact fp32, csrc/lpips.hip) for one evaluator batch, and each of its five convolutions alone.
+"""Time ops.lpips (AlexNet LPIPS, exact fp32, csrc/lpips.hip + csrc/f32_layers.hip) for one evaluator batch, and each of its five convolutions alone.
 
   python tools/lpips_timing.py [--batch 8 --res 512 --reps 20] [--out result.txt]
 
@@ -53,7 +53,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    from unirestore_amd import lpips, ops
+    from unirestore_amd import f32net, lpips, ops
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(3)
     tgt = torch.rand(a.batch, 3, a.res, a.res, generator=g, device=dev)
@@ -69,11 +69,11 @@ def main():
     flops_all, conv_ms_all = 0.0, 0.0
     for i, (pc, pool) in enumerate(zip(w.convs, lpips.POOL_BEFORE)):
         if pool:
-            f = lpips.maxpool2d_f32(f)
+            f = f32net.maxpool2d_f32(f)
         x = f
         for _ in range(3):
-            f = lpips.conv2d_f32(x, pc)
-        t = statistics.median(_events(lambda: lpips.conv2d_f32(x, pc), a.reps))
+            f = f32net.conv2d_f32(x, pc)
+        t = statistics.median(_events(lambda: f32net.conv2d_f32(x, pc), a.reps))
         m, k = f.shape[0] * f.shape[1] * f.shape[2], pc.cin * pc.kh * pc.kw
         flops = 2.0 * m * k * pc.cout
         flops_all += flops

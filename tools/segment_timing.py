@@ -1,5 +1,5 @@
 """Time the segmenter scoring (`ops.segment`: three scales of preprocess + RefineNet-LW in exact fp32 + the multi-scale argmax;
-csrc/segment.hip + ur_conv2d_f32_res) on cuda:0, per shape.  Seeded random weights (segment.random_weights: no trained weights
+csrc/segment.hip + csrc/f32_layers.hip) on cuda:0, per shape.  Seeded random weights (segment.random_weights: no trained weights
 are needed to time the kernels) and seeded 8-bit-quantised images.
 
   python tools/segment_timing.py [--arch rflw101 --shapes 8x512x512,2x960x1664 --reps 10] [--out profiles/segment_timing.txt]
@@ -55,7 +55,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    from unirestore_amd import ops, segment
+    from unirestore_amd import f32net, ops, segment
     dev = torch.device("cuda", 0)
     w = segment.random_weights(a.arch, 0)
     lines = []
@@ -66,7 +66,7 @@ def main():
         for _ in range(2):
             ops.segment(x, w)
         total_ms = _host_times(lambda: ops.segment(x, w), a.reps)
-        launches, real = [], segment.conv2d_f32_res
+        launches, real = [], f32net.conv2d_f32
 
         def timed(xi, pc, res=None, relu=True):
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -76,7 +76,7 @@ def main():
             launches.append((s, e, 2.0 * y.shape[0] * y.shape[1] * y.shape[2] * pc.cout * pc.cin * pc.kh * pc.kw))
             return y
         per_launch, flops = None, 0.0
-        segment.conv2d_f32_res = timed
+        f32net.conv2d_f32 = timed
         try:
             for _ in range(max(a.reps // 2, 3)):
                 launches.clear()
@@ -86,7 +86,7 @@ def main():
                 per_launch = [[m] for m in ms] if per_launch is None else [p + [m] for p, m in zip(per_launch, ms)]
                 flops = sum(f for _, _, f in launches)
         finally:
-            segment.conv2d_f32_res = real
+            f32net.conv2d_f32 = real
         conv_ms = sum(statistics.median(p) for p in per_launch)
         # the last kernel alone, on this shape's three logit maps, against what it replaces
         maps = [segment.logits(segment.prep(x, (segment.scaled_size(h, s), segment.scaled_size(wd, s))), w) for s in segment.SCALES]

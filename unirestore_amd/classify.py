@@ -1,6 +1,6 @@
-"""Classifier scoring of the `cls` output on the GPU in exact fp32: torchvision-layout ResNets (18 / 50 / 101) on the fp32
-convolution of csrc/lpips.hip and the kernels of csrc/classify.hip - weight loading and BatchNorm folding, the evaluator's
-preprocess, the launch wrappers, and the accuracy formulas.  What the reference's `ClassificationMetric` builds
+"""Classifier scoring of the `cls` output on the GPU in exact fp32: torchvision-layout ResNets (18 / 50 / 101) on the fp32 layers
+and the ResNet backbone of f32net.py and the kernels of csrc/classify.hip - weight loading, the evaluator's preprocess, the
+launch wrappers, and the accuracy formulas.  What the reference's `ClassificationMetric` builds
 (eval_classification.py:193-309): quantised image -> Resize((224, 224)) -> ImageNet Normalize -> ResNet -> MulticlassAccuracy(top_k=1).
 
 The project ships NO weights.  `load_weights` reads the torchvision state dict (or Lightning checkpoint) a user of the metric
@@ -11,14 +11,12 @@ import math
 
 import torch
 
+from . import f32net
 from .capi import check, lib
-from .lpips import PackedConvF32, _stream
+from .f32net import EXPANSION, PLANES, PackedConvF32, stream, take
 
 # arch -> (block kind, blocks per stage); torchvision's layout, the stride on the 3x3 convolution (ResNet v1.5)
 ARCHS = {"resnet18": ("basic", (2, 2, 2, 2)), "resnet50": ("bottleneck", (3, 4, 6, 3)), "resnet101": ("bottleneck", (3, 4, 23, 3))}
-PLANES = (64, 128, 256, 512)
-EXPANSION = {"basic": 1, "bottleneck": 4}
-BN_EPS = 1e-5
 OUT_HW = 224                                             # T.Resize((224, 224))
 MIN_HW = 32                                              # the smallest network input whose last stage still has one pixel
 MAX_TAPS = 64                                            # ur_classify_preprocess's limit per output index
@@ -28,37 +26,7 @@ def conv_plan(arch: str):
     """[(conv key, bn key, Cout, Cin, kernel, stride, pad)] of every convolution of `arch`, in state-dict order."""
     if arch not in ARCHS:
         raise ValueError(f"unknown classifier arch {arch!r}: choose from {sorted(ARCHS)}")
-    return _plan(*ARCHS[arch])
-
-
-def bottleneck_plan(depths):
-    """conv_plan of a bottleneck ResNet with `depths` blocks per stage (segment.py's backbones; tests build (1, 1, 1, 1))."""
-    return _plan("bottleneck", tuple(depths))
-
-
-def _plan(kind, depths):
-    exp = EXPANSION[kind]
-    plan = [("conv1", "bn1", 64, 3, 7, 2, 3)]
-    cin = 64
-    for li, (planes, depth) in enumerate(zip(PLANES, depths), 1):
-        for bi in range(depth):
-            stride = 2 if (li > 1 and bi == 0) else 1
-            p = f"layer{li}.{bi}"
-            if kind == "basic":
-                plan += [(f"{p}.conv1", f"{p}.bn1", planes, cin, 3, stride, 1), (f"{p}.conv2", f"{p}.bn2", planes, planes, 3, 1, 1)]
-            else:
-                plan += [(f"{p}.conv1", f"{p}.bn1", planes, cin, 1, 1, 0), (f"{p}.conv2", f"{p}.bn2", planes, planes, 3, stride, 1),
-                         (f"{p}.conv3", f"{p}.bn3", planes * exp, planes, 1, 1, 0)]
-            if stride != 1 or cin != planes * exp:
-                plan.append((f"{p}.downsample.0", f"{p}.downsample.1", planes * exp, cin, 1, stride, 0))
-            cin = planes * exp
-    return plan
-
-
-def fold_bn(w, gamma, beta, mean, var, eps: float = BN_EPS):
-    """conv (no bias) followed by eval-mode BatchNorm as one convolution, folded in fp64: (weight fp64, bias fp64)."""
-    scale = gamma.double() / torch.sqrt(var.double() + eps)
-    return w.double() * scale.view(-1, 1, 1, 1), beta.double() - mean.double() * scale
+    return f32net.resnet_plan(*ARCHS[arch])
 
 
 class ClassifierWeights:
@@ -70,56 +38,20 @@ class ClassifierWeights:
         dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else torch.device(dev)
         plan = conv_plan(arch)
         self.arch, self.device, self.kind = arch, dev, ARCHS[arch][0]
-        self.cpu, self.convs, folded = {}, {}, []
-        for ckey, bkey, cout, cin, k, stride, pad in plan:                    # every check first: nothing is uploaded for a bad file
-            w = self._take(sd, source, f"{ckey}.weight", (cout, cin, k, k))
-            bn = [self._take(sd, source, f"{bkey}.{n}", (cout,)) for n in ("weight", "bias", "running_mean", "running_var")]
-            if not bool((bn[3].double() + BN_EPS > 0).all()):
-                raise ValueError(f"{source}: {bkey + '.running_var'!r} + eps is not positive: not a trained BatchNorm")
-            fw, fb = fold_bn(w, *bn)
-            if not (bool(torch.isfinite(fw).all()) and bool(torch.isfinite(fb).all())):
-                raise ValueError(f"{source}: folding {bkey!r} into {ckey!r} gives a non-finite value")
-            folded.append((ckey, fw.float(), fb.float(), stride, pad))
+        self.cpu, self.convs = {}, {}
+        folded = f32net.fold_convs(plan, sd, source, self.cpu)                # every check first: nothing is uploaded for a bad file
         if "fc.weight" not in sd or not torch.is_tensor(sd["fc.weight"]) or sd["fc.weight"].ndim != 2:
             raise ValueError(f"{source}: key 'fc.weight' is missing or is no [classes, features] matrix")
         feat = PLANES[-1] * EXPANSION[self.kind]
         self.num_classes = int(sd["fc.weight"].shape[0])
-        fcw = self._take(sd, source, "fc.weight", (self.num_classes, feat))
-        fcb = self._take(sd, source, "fc.bias", (self.num_classes,))
+        fcw = take(sd, source, "fc.weight", (self.num_classes, feat), keep=self.cpu)
+        fcb = take(sd, source, "fc.bias", (self.num_classes,), keep=self.cpu)
         for ckey, fw, fb, stride, pad in folded:
             self.convs[ckey] = PackedConvF32(fw, fb, stride, pad, dev)
         self.fc = PackedConvF32(fcw.view(self.num_classes, feat, 1, 1), fcb, 1, 0, dev)
-        # the blocks in execution order: (conv keys of the main path, downsample key or None)
-        self.blocks = []
-        per_block = 2 if self.kind == "basic" else 3
-        for li, depth in enumerate(ARCHS[arch][1], 1):
-            for bi in range(depth):
-                p = f"layer{li}.{bi}"
-                down = f"{p}.downsample.0" if f"{p}.downsample.0" in self.convs else None
-                self.blocks.append(([f"{p}.conv{j}" for j in range(1, per_block + 1)], down))
-
-    def _take(self, sd, source, key, shape):
-        if key not in sd:
-            raise ValueError(f"{source}: key {key!r} is missing")
-        t = sd[key]
-        if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{source}: {key!r} has shape {tuple(getattr(t, 'shape', ()))}, expected {tuple(shape)}")
-        t = t.detach().float().cpu()
-        if not bool(torch.isfinite(t).all()):
-            raise ValueError(f"{source}: {key!r} holds a non-finite value")
-        self.cpu[key] = t
-        return t
-
-
-def read_state_dict(path) -> dict:
-    """A torchvision state dict, or a Lightning checkpoint: its ["state_dict"] with a leading `model.` stripped from every key,
-    as the reference's `_load_ckpt` does."""
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    if isinstance(sd, dict) and "state_dict" in sd and isinstance(sd["state_dict"], dict):
-        sd = {(k[len("model."):] if k.startswith("model.") else k): v for k, v in sd["state_dict"].items()}
-    if not isinstance(sd, dict):
-        raise ValueError(f"{path}: not a state dict")
-    return sd
+        # the blocks in execution order: (conv keys of the main path, downsample key or None), by stage and flat
+        self.stages = f32net.resnet_stages(self.kind, ARCHS[arch][1], self.convs)
+        self.blocks = [b for blocks in self.stages for b in blocks]
 
 
 def load_weights(arch: str, path, dev=None) -> ClassifierWeights:
@@ -128,7 +60,7 @@ def load_weights(arch: str, path, dev=None) -> ClassifierWeights:
     classes is fc.weight's.  ValueError (file and key named) for a missing key, a wrong shape, a non-finite value or a
     non-positive running_var + eps."""
     conv_plan(arch)                                                  # an unknown arch, before the file is read
-    return ClassifierWeights(arch, read_state_dict(path), dev, source=str(path))
+    return ClassifierWeights(arch, f32net.read_state_dict(path), dev, source=str(path))
 
 
 def random_state_dict(arch: str, seed: int, num_classes: int = 1000) -> dict:
@@ -137,15 +69,7 @@ def random_state_dict(arch: str, seed: int, num_classes: int = 1000) -> dict:
     grow), running_var in [0.5, 1.5], small beta and running_mean, a uniform(+-1/sqrt(fan_in)) FC layer: fp32 logits stay
     finite.  NOT trained weights - its predictions say nothing about any published accuracy."""
     g = torch.Generator().manual_seed(seed)
-    sd = {}
-    for ckey, bkey, cout, cin, k, _s, _p in conv_plan(arch):
-        sd[f"{ckey}.weight"] = torch.randn(cout, cin, k, k, generator=g) * math.sqrt(2.0 / (cin * k * k))
-        last = ckey.endswith("conv3") or (ARCHS[arch][0] == "basic" and ckey.endswith("conv2"))
-        sd[f"{bkey}.weight"] = (0.5 + torch.rand(cout, generator=g)) * (0.5 if last else 1.0)
-        sd[f"{bkey}.bias"] = 0.1 * torch.randn(cout, generator=g)
-        sd[f"{bkey}.running_mean"] = 0.1 * torch.randn(cout, generator=g)
-        sd[f"{bkey}.running_var"] = 0.5 + torch.rand(cout, generator=g)
-        sd[f"{bkey}.num_batches_tracked"] = torch.tensor(0)
+    sd = f32net.random_backbone(conv_plan(arch), ARCHS[arch][0], g)
     feat = PLANES[-1] * EXPANSION[ARCHS[arch][0]]
     sd["fc.weight"] = (2 * torch.rand(num_classes, feat, generator=g) - 1) / math.sqrt(feat)
     sd["fc.bias"] = (2 * torch.rand(num_classes, generator=g) - 1) / math.sqrt(feat)
@@ -192,7 +116,7 @@ def _device_table(n_in: int, dev_index: int):
     return first.to(dev), count.to(dev), wt.float().contiguous().to(dev), int(wt.shape[1])
 
 
-# ---- launch wrappers (each one kernel family; fp32 device tensors, NHWC behind the preprocess) ---------------------------------
+# ---- launch wrappers of csrc/classify.hip (fp32 device tensors, NHWC behind the preprocess) -------------------------------------
 
 def preprocess(x: torch.Tensor) -> torch.Tensor:
     """fp32 NCHW [N,3,H,W] in [0,1] -> NHWC [N,224,224,3]: antialiased bilinear resize, then (v - mean_c) / std_c.  The first call
@@ -203,38 +127,7 @@ def preprocess(x: torch.Tensor) -> torch.Tensor:
     tmp = torch.empty(n, 3, h, OUT_HW, dtype=torch.float32, device=x.device)
     y = torch.empty(n, OUT_HW, OUT_HW, 3, dtype=torch.float32, device=x.device)
     check(lib.ur_classify_preprocess(x.data_ptr(), tmp.data_ptr(), y.data_ptr(), n, c, h, w, fw.data_ptr(), cw.data_ptr(), ww.data_ptr(), tw,
-                                     fh.data_ptr(), ch.data_ptr(), wh.data_ptr(), th, _stream()))
-    return y
-
-
-def conv2d_f32_res(x: torch.Tensor, pc: PackedConvF32, res: torch.Tensor = None, relu: bool = True) -> torch.Tensor:
-    """act(conv(x) + bias + res) on NHWC fp32; res None: exactly lpips.conv2d_f32."""
-    n, h, w, cin = x.shape
-    if cin != pc.cin:
-        raise ValueError(f"conv2d_f32_res: input has {cin} channels, the filter {pc.cin}")
-    oh, ow = (h + 2 * pc.pad - pc.kh) // pc.stride + 1, (w + 2 * pc.pad - pc.kw) // pc.stride + 1
-    y = torch.empty(n, max(oh, 0), max(ow, 0), pc.cout, dtype=torch.float32, device=x.device)
-    if res is not None and (res.shape != y.shape or res.dtype != torch.float32 or not res.is_contiguous() or res.device != x.device):
-        raise ValueError(f"conv2d_f32_res: the residual must be a contiguous fp32 {tuple(y.shape)} tensor on {x.device}, got "
-                         f"{res.dtype} {tuple(res.shape)} on {res.device}")
-    check(lib.ur_conv2d_f32_res(x.data_ptr(), pc.w.data_ptr(), pc.bias.data_ptr(), None if res is None else res.data_ptr(), y.data_ptr(),
-                                n, h, w, cin, pc.cout, pc.kh, pc.kw, pc.stride, pc.pad, int(relu), _stream()))
-    return y
-
-
-def maxpool2d_pad_f32(x: torch.Tensor) -> torch.Tensor:
-    """3x3 / stride 2 / padding 1 (-inf) on NHWC fp32."""
-    n, h, w, c = x.shape
-    y = torch.empty(n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c, dtype=torch.float32, device=x.device)
-    check(lib.ur_maxpool2d_pad_f32(x.data_ptr(), y.data_ptr(), n, h, w, c, _stream()))
-    return y
-
-
-def avgpool_f32(x: torch.Tensor) -> torch.Tensor:
-    """[N,H,W,C] -> [N,C], the mean over the map."""
-    n, h, w, c = x.shape
-    y = torch.empty(n, c, dtype=torch.float32, device=x.device)
-    check(lib.ur_avgpool_f32(x.data_ptr(), y.data_ptr(), n, h * w, c, _stream()))
+                                     fh.data_ptr(), ch.data_ptr(), wh.data_ptr(), th, stream()))
     return y
 
 
@@ -243,7 +136,7 @@ def top1_counts(logits: torch.Tensor, labels: torch.Tensor):
     n, c = logits.shape
     pred = torch.empty(n, dtype=torch.int64, device=logits.device)
     counts = torch.empty(3, c, dtype=torch.int64, device=logits.device)
-    check(lib.ur_top1_counts(logits.data_ptr(), labels.data_ptr(), n, c, pred.data_ptr(), counts.data_ptr(), _stream()))
+    check(lib.ur_top1_counts(logits.data_ptr(), labels.data_ptr(), n, c, pred.data_ptr(), counts.data_ptr(), stream()))
     return pred, counts
 
 
@@ -252,15 +145,8 @@ def logits(x: torch.Tensor, wts: ClassifierWeights) -> torch.Tensor:
     n, h, w, c = x.shape
     if c != 3 or h < MIN_HW or w < MIN_HW:
         raise ValueError(f"classify.logits: needs an NHWC [N, H>={MIN_HW}, W>={MIN_HW}, 3] input, got {tuple(x.shape)}")
-    f = maxpool2d_pad_f32(conv2d_f32_res(x, wts.convs["conv1"]))
-    for main, down in wts.blocks:
-        identity = f if down is None else conv2d_f32_res(f, wts.convs[down], relu=False)
-        y = f
-        for key in main[:-1]:
-            y = conv2d_f32_res(y, wts.convs[key])
-        f = conv2d_f32_res(y, wts.convs[main[-1]], res=identity)
-    pooled = avgpool_f32(f)
-    return conv2d_f32_res(pooled.view(n, 1, 1, -1), wts.fc, relu=False).view(n, wts.num_classes)
+    pooled = f32net.avgpool_f32(f32net.resnet_trunk(x, wts.convs, wts.stages)[-1])
+    return f32net.conv2d_f32(pooled.view(n, 1, 1, -1), wts.fc, relu=False).view(n, wts.num_classes)
 
 
 def forward(images: torch.Tensor, wts: ClassifierWeights) -> torch.Tensor:

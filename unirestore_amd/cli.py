@@ -206,41 +206,48 @@ def check_niqe_run(crop, r: dict):
 LABELLED_DATA = ("ImageListFiles", "CorruptedImageFiles", "DistortedImageFiles", "JpegImageFiles")      # take `labels: true`
 
 
-def check_classify_arg(classify):
-    """--classify NAME=ARCH:WEIGHTS.pth[,NAME=ARCH:OTHER.pth] (or a dict NAME -> (ARCH, path) | a loaded classify.ClassifierWeights)
-    -> {name: (arch, path) | ClassifierWeights}.  ValueError for a malformed item, an unknown arch, a missing file or a name given
-    twice.  ARCH is one of classify.ARCHS (torchvision's resnet18 / resnet50 / resnet101); the weights are the user's."""
-    from .classify import ARCHS
-    form = "--classify takes NAME=ARCH:WEIGHTS.pth[,NAME=ARCH:WEIGHTS.pth]: a result name, one of %s, a torchvision state dict" % sorted(ARCHS)
-    if isinstance(classify, str):
+def _check_scorer_arg(flag, value, archs, what):
+    """`flag` NAME=ARCH:WEIGHTS.pth[,NAME=ARCH:OTHER.pth] (or a dict NAME -> (ARCH, path) | loaded weights) -> {name: (arch, path) |
+    weights}.  ValueError for a malformed item, an arch outside `archs`, a missing file or a name given twice.  what: the kind of
+    file, for the usage text."""
+    form = f"{flag} takes NAME=ARCH:WEIGHTS.pth[,NAME=ARCH:WEIGHTS.pth]: a result name, one of {sorted(archs)}, {what}"
+    if isinstance(value, str):
         items = []
-        for part in classify.split(","):
+        for part in value.split(","):
             name, eq, spec = part.partition("=")
             arch, colon, path = spec.partition(":")
             if not (name and eq and arch and colon and path):
                 raise ValueError(f"{form}; got {part!r}")
             items.append((name, (arch, path)))
-    elif isinstance(classify, dict):
-        items = list(classify.items())
+    elif isinstance(value, dict):
+        items = list(value.items())
     else:
-        raise ValueError(f"{form}; got {type(classify).__name__}")
+        raise ValueError(f"{form}; got {type(value).__name__}")
     if not items:
         raise ValueError(form)
     out = {}
     for name, spec in items:
         if name in out:
-            raise ValueError(f"--classify: the name {name!r} is given twice")
+            raise ValueError(f"{flag}: the name {name!r} is given twice")
         if isinstance(spec, (tuple, list)):
             if len(spec) != 2:
                 raise ValueError(f"{form}; got {name!r}: {spec!r}")
             arch, path = spec
-            if arch not in ARCHS:
-                raise ValueError(f"--classify {name}: unknown arch {arch!r}, choose from {sorted(ARCHS)}")
+            if not isinstance(arch, str) or arch not in archs:
+                raise ValueError(f"{flag} {name}: unknown arch {arch!r}, choose from {sorted(archs)}")
             if not os.path.isfile(path):
-                raise ValueError(f"--classify {name}: no such file: {path}")
+                raise ValueError(f"{flag} {name}: no such file: {path}")
             spec = (arch, path)
         out[name] = spec
     return out
+
+
+def check_classify_arg(classify):
+    """--classify NAME=ARCH:WEIGHTS.pth[,NAME=ARCH:OTHER.pth] (or a dict NAME -> (ARCH, path) | a loaded classify.ClassifierWeights)
+    -> {name: (arch, path) | ClassifierWeights}.  ValueError for a malformed item, an unknown arch, a missing file or a name given
+    twice.  ARCH is one of classify.ARCHS (torchvision's resnet18 / resnet50 / resnet101); the weights are the user's."""
+    from .classify import ARCHS
+    return _check_scorer_arg("--classify", classify, ARCHS, "a torchvision state dict")
 
 
 def check_classify_run(classify, tasks, r: dict):
@@ -260,36 +267,7 @@ def check_segment_arg(segment):
     -> {name: (arch, path) | SegmenterWeights}.  ValueError for a malformed item, an unknown arch, a missing file or a name given
     twice.  ARCH is one of segment.ARCHS (RefineNet-LW on ResNet-50 / 101 / 152); the weights are the user's."""
     from .segment import ARCHS
-    form = "--segment takes NAME=ARCH:WEIGHTS.pth[,NAME=ARCH:WEIGHTS.pth]: a result name, one of %s, a RefineNet-LW state dict" % sorted(ARCHS)
-    if isinstance(segment, str):
-        items = []
-        for part in segment.split(","):
-            name, eq, spec = part.partition("=")
-            arch, colon, path = spec.partition(":")
-            if not (name and eq and arch and colon and path):
-                raise ValueError(f"{form}; got {part!r}")
-            items.append((name, (arch, path)))
-    elif isinstance(segment, dict):
-        items = list(segment.items())
-    else:
-        raise ValueError(f"{form}; got {type(segment).__name__}")
-    if not items:
-        raise ValueError(form)
-    out = {}
-    for name, spec in items:
-        if name in out:
-            raise ValueError(f"--segment: the name {name!r} is given twice")
-        if isinstance(spec, (tuple, list)):
-            if len(spec) != 2:
-                raise ValueError(f"{form}; got {name!r}: {spec!r}")
-            arch, path = spec
-            if not isinstance(arch, str) or arch not in ARCHS:
-                raise ValueError(f"--segment {name}: unknown arch {arch!r}, choose from {sorted(ARCHS)}")
-            if not os.path.isfile(path):
-                raise ValueError(f"--segment {name}: no such file: {path}")
-            spec = (arch, path)
-        out[name] = spec
-    return out
+    return _check_scorer_arg("--segment", segment, ARCHS, "a RefineNet-LW state dict")
 
 
 def check_segment_run(segment, tasks, r: dict):

@@ -1,8 +1,9 @@
 // The classifier's own kernels for gfx950, exact fp32: the evaluator's preprocess (antialiased bilinear resize to 224 x 224 from
-// host-built tap tables + ImageNet normalisation, NCHW in, NHWC out), the padded 3x3 / stride-2 max-pool, the global average
-// pool, and top-1 with the per-class counts of the accuracy.  The convolutions (and the FC layer, a 1x1 convolution on a 1x1 map)
-// are ur_conv2d_f32_res of lpips.hip.  No atomics; every sum runs in a fixed order, so the same inputs give the same bits on
-// every run, eagerly and under graph replay, and an image's results do not depend on its place in the batch.
+// host-built tap tables + ImageNet normalisation, NCHW in, NHWC out) and top-1 with the per-class counts of the accuracy.  The
+// convolutions (and the FC layer, a 1x1 convolution on a 1x1 map), the padded 3x3 / stride-2 max-pool and the global average
+// pool are ur_conv2d_f32_res, ur_maxpool2d_pad_f32 and ur_avgpool_f32 of f32_layers.hip.  No atomics; every sum runs in a fixed
+// order, so the same inputs give the same bits on every run, eagerly and under graph replay, and an image's results do not
+// depend on its place in the batch.
 #include "common.h"
 
 #include <climits>
@@ -51,39 +52,6 @@ __global__ __launch_bounds__(256) void classify_resize_h_kernel(const float* __r
     for (int j = 0; j < cnt; ++j) s = fmaf(wv[j], src[(long long)j * CL_OUT], s);
     y[(long long)i * 3 + c] = (s - mean[c]) / sd[c];
   }
-}
-
-// ------------------------------------------------------------------------------------------ max-pool 3x3 / 2, padding 1 (= -inf)
-__global__ __launch_bounds__(256) void maxpool2d_pad_f32_kernel(const float* __restrict__ x, float* __restrict__ y, int total, int H,
-                                                                int W, int C, int OH, int OW) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int c = i % C;
-  int r = i / C;
-  const int ow = r % OW;
-  r /= OW;
-  const int oh = r % OH, n = r / OH;
-  float v = -INFINITY;                     // the centre tap is always inside the map, so every output is a real input value
-#pragma unroll
-  for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-    for (int dx = 0; dx < 3; ++dx) {
-      const int ih = 2 * oh - 1 + dy, iw = 2 * ow - 1 + dx;
-      if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W) v = fmaxf(v, x[(((long long)n * H + ih) * W + iw) * C + c]);
-    }
-  y[i] = v;
-}
-
-// ------------------------------------------------------------------------------------------ global average pool
-// x [N][P][C] -> y [N][C]: one thread per (image, channel), the P pixels in ascending order in an fp64 sum, rounded to fp32 once.
-__global__ __launch_bounds__(256) void avgpool_f32_kernel(const float* __restrict__ x, float* __restrict__ y, int total, int P, int C) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int n = i / C, c = i - n * C;
-  const float* src = x + (long long)n * P * C + c;
-  double s = 0.0;
-  for (int p = 0; p < P; ++p) s += (double)src[(long long)p * C];
-  y[i] = (float)(s / (double)P);
 }
 
 // ------------------------------------------------------------------------------------------ top-1 and the accuracy's counts
@@ -157,27 +125,6 @@ int ur_classify_preprocess(const float* x, float* tmp, float* y, int N, int C, i
   hipLaunchKernelGGL(classify_resize_w_kernel, dim3(blocks_w), dim3(256), 0, s, x, tmp, rows, W, first_w, count_w, wt_w, taps_w);
   hipLaunchKernelGGL(classify_resize_h_kernel, dim3(blocks_h), dim3(256), 0, s, tmp, y, N, H, first_h, count_h, wt_h, taps_h);
   return ur::check_launch("ur_classify_preprocess");
-}
-
-int ur_maxpool2d_pad_f32(const float* x, float* y, int N, int H, int W, int C, ur_stream_t stream) {
-  UR_REQUIRE(x && y, "null pointer");
-  UR_REQUIRE(N >= 1 && C >= 1 && H >= 1 && W >= 1, "N, C, H and W must be >= 1");
-  UR_REQUIRE((long long)N * H * W * C < ur::GRID_1D_LIMIT, "too many elements: N*H*W*C must be below 2^31 - 256");
-  const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  const int total = N * OH * OW * C;                   // = N*H*W*C on a 1 x 1 map
-  UR_GRID_1D(blocks, total, 256);
-  hipLaunchKernelGGL(maxpool2d_pad_f32_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, y, total, H, W, C, OH, OW);
-  return ur::check_launch("ur_maxpool2d_pad_f32");
-}
-
-int ur_avgpool_f32(const float* x, float* y, int N, int P, int C, ur_stream_t stream) {
-  UR_REQUIRE(x && y, "null pointer");
-  UR_REQUIRE(N >= 1 && P >= 1 && C >= 1, "N, P and C must be >= 1");
-  UR_REQUIRE((long long)N * P * C < ur::GRID_1D_LIMIT, "too many elements: N*P*C must be below 2^31 - 256");
-  const int total = N * C;                             // = N*P*C for P = 1
-  UR_GRID_1D(blocks, total, 256);
-  hipLaunchKernelGGL(avgpool_f32_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, y, total, P, C);
-  return ur::check_launch("ur_avgpool_f32");
 }
 
 int ur_top1_counts(const float* logits, const long long* labels, int N, int C, long long* pred, long long* counts, ur_stream_t stream) {

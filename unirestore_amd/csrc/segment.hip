@@ -1,26 +1,16 @@
 // The segmenter's own kernels for gfx950, exact fp32: one scale of the evaluator's test-time augmentation fused with
-// RefineNet-LW's preprocess (bilinear align_corners=True resize, v * 255 - mean, RGB -> BGR, NCHW in, NHWC out), the head's bilinear
-// up-sample and 5x5 max-pool, the multi-scale average + argmax that ends the metric, and the confusion matrix of the mIoU.  The
-// convolutions are ur_conv2d_f32_res of lpips.hip.  No atomics; every sum runs in a fixed order, so the same inputs give the same
-// bits on every run, eagerly and under graph replay, and an image's results do not depend on its place in the batch.
-//
-// An align_corners=True axis table: idx[o] = the first source index of output o, wt[2 * o], wt[2 * o + 1] = the fp32 weights of
-// source idx[o] and idx[o] + 1 (built on the host in fp64).  The kernels clamp both indices to the axis, so a wrong table gives
-// wrong numbers, never an access outside the map.  A pixel is combined as torch's upsample_bilinear2d does:
-// h0 * (w0 * x00 + w1 * x01) + h1 * (w0 * x10 + w1 * x11); with weights (1, 0) that is x00 bit for bit
-// while the neighbours are finite (0 x NaN and 0 x inf are NaN, as in torch) - but for x00 = -0.0, which comes out as +0.0 unless
-// the neighbours' products are -0.0 too.
+// RefineNet-LW's preprocess (bilinear align_corners=True resize, v * 255 - mean, RGB -> BGR, NCHW in, NHWC out), the multi-scale
+// average + argmax that ends the metric, and the confusion matrix of the mIoU.  The convolutions, the head's bilinear up-sample,
+// 5x5 max-pool and a + b are in f32_layers.hip; the bilinear sample and its axis tables are f32_layers.h's.  No atomics; every
+// sum runs in a fixed order, so the same inputs give the same bits on every run, eagerly and under graph replay, and an image's
+// results do not depend on its place in the batch.
 #include "common.h"
+#include "f32_layers.h"
 
 #include <climits>
 #include <cmath>
 
 namespace {
-
-__device__ __forceinline__ float bilerp(float x00, float x01, float x10, float x11, float w0, float w1, float h0, float h1) {
-  const float top = fmaf(w1, x01, w0 * x00), bot = fmaf(w1, x11, w0 * x10);
-  return fmaf(h1, bot, h0 * top);
-}
 
 // v * 255 - mean with two roundings, as torch computes x * 255 - mean: never contracted into one fma.
 __device__ __forceinline__ float scale255_minus(float v, float mean) {
@@ -48,92 +38,6 @@ __global__ __launch_bounds__(256) void seg_prep_kernel(const float* __restrict__
     const float* src = x + ((long long)n * 3 + c) * H * W;
     const float v = bilerp(src[y0 * W + x0], src[y0 * W + x1], src[y1 * W + x0], src[y1 * W + x1], w0, w1, h0, h1);
     y[(long long)i * 3 + (2 - c)] = scale255_minus(v, mean[c]);
-  }
-}
-
-// ------------------------------------------------------------------------------------------ bilinear up-sample, align_corners
-// x [N][h][w][C] -> y [N][H][W][C]; V channels per thread (float4 when C % 4 == 0).
-template <int V>
-__global__ __launch_bounds__(256) void upsample_bilinear_ac_kernel(const float* __restrict__ x, float* __restrict__ y, int total, int h, int w,
-                                                                   int C, int H, int W, const int* __restrict__ iy,
-                                                                   const float* __restrict__ wy, const int* __restrict__ ix,
-                                                                   const float* __restrict__ wx) {
-  const int i = blockIdx.x * 256 + threadIdx.x;       // over N*H*W*(C/V)
-  if (i >= total) return;
-  const int cv = C / V;
-  const int c = (i % cv) * V;
-  int r = i / cv;
-  const int ox = r % W;
-  r /= W;
-  const int oy = r % H, n = r / H;
-  const int y0 = min(max(iy[oy], 0), h - 1), y1 = min(y0 + 1, h - 1);
-  const int x0 = min(max(ix[ox], 0), w - 1), x1 = min(x0 + 1, w - 1);
-  const float h0 = wy[2ll * oy], h1 = wy[2ll * oy + 1], w0 = wx[2ll * ox], w1 = wx[2ll * ox + 1];      // (an axis may have 2^30 outputs or more)
-  const float* img = x + (long long)n * h * w * C + c;
-  const float* p00 = img + ((long long)y0 * w + x0) * C;
-  const float* p01 = img + ((long long)y0 * w + x1) * C;
-  const float* p10 = img + ((long long)y1 * w + x0) * C;
-  const float* p11 = img + ((long long)y1 * w + x1) * C;
-  float* dst = y + (long long)i * V;
-  if constexpr (V == 4) {
-    const float4 a = *(const float4*)p00, b = *(const float4*)p01, cc = *(const float4*)p10, d = *(const float4*)p11;
-    float4 o;
-    o.x = bilerp(a.x, b.x, cc.x, d.x, w0, w1, h0, h1);
-    o.y = bilerp(a.y, b.y, cc.y, d.y, w0, w1, h0, h1);
-    o.z = bilerp(a.z, b.z, cc.z, d.z, w0, w1, h0, h1);
-    o.w = bilerp(a.w, b.w, cc.w, d.w, w0, w1, h0, h1);
-    *(float4*)dst = o;
-  } else {
-    *dst = bilerp(*p00, *p01, *p10, *p11, w0, w1, h0, h1);
-  }
-}
-
-// ------------------------------------------------------------------------------------------ max-pool 5x5 / 1, padding 2 (= -inf)
-template <int V>
-__global__ __launch_bounds__(256) void maxpool5_f32_kernel(const float* __restrict__ x, float* __restrict__ y, int total, int H, int W, int C) {
-  const int i = blockIdx.x * 256 + threadIdx.x;       // over N*H*W*(C/V)
-  if (i >= total) return;
-  const int cv = C / V;
-  const int c = (i % cv) * V;
-  int r = i / cv;
-  const int ow = r % W;
-  r /= W;
-  const int oh = r % H, n = r / H;
-  float v[V];                              // the centre tap is always inside the map, so every output is a real input value
-#pragma unroll
-  for (int k = 0; k < V; ++k) v[k] = -INFINITY;
-#pragma unroll
-  for (int dy = -2; dy <= 2; ++dy)
-#pragma unroll
-    for (int dx = -2; dx <= 2; ++dx) {
-      const int ih = oh + dy, iw = ow + dx;
-      if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W) {
-        const float* src = x + (((long long)n * H + ih) * W + iw) * C + c;
-        if constexpr (V == 4) {
-          const float4 t = *(const float4*)src;
-          v[0] = fmaxf(v[0], t.x); v[1] = fmaxf(v[1], t.y); v[2] = fmaxf(v[2], t.z); v[3] = fmaxf(v[3], t.w);
-        } else {
-          v[0] = fmaxf(v[0], *src);
-        }
-      }
-    }
-  float* dst = y + (long long)i * V;
-  if constexpr (V == 4) *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
-  else *dst = v[0];
-}
-
-// ------------------------------------------------------------------------------------------ a + b
-// The chained residual pooling's `x = top + x` where `top` itself feeds the next pool (its last stage rides the convolution's
-// residual input instead).  V floats per thread.
-template <int V>
-__global__ __launch_bounds__(256) void add_f32_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ y, int total) {
-  const int i = blockIdx.x * 256 + threadIdx.x;       // over n / V
-  if (i >= total) return;
-  if constexpr (V == 4) {
-    const float4 p = ((const float4*)a)[i], q = ((const float4*)b)[i];
-    ((float4*)y)[i] = make_float4(p.x + q.x, p.y + q.y, p.z + q.z, p.w + q.w);
-  } else {
-    y[i] = a[i] + b[i];
   }
 }
 
@@ -272,61 +176,6 @@ int ur_seg_prep(const float* x, float* y, int N, int C, int H, int W, int OH, in
   hipLaunchKernelGGL(seg_prep_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, y, total, H, W, OH, OW, idx_h, wt_h, idx_w,
                      wt_w);
   return ur::check_launch("ur_seg_prep");
-}
-
-int ur_upsample_bilinear_ac_f32(const float* x, float* y, int N, int h, int w, int C, int H, int W, const int* idx_h, const float* wt_h,
-                                const int* idx_w, const float* wt_w, ur_stream_t stream) {
-  UR_REQUIRE(x && y && idx_h && wt_h && idx_w && wt_w, "null pointer");
-  UR_REQUIRE(x != y, "x and y must not be the same buffer");
-  UR_REQUIRE(N >= 1 && C >= 1 && h >= 1 && w >= 1 && H >= 1 && W >= 1, "N, C, h, w, H and W must be >= 1");
-  UR_REQUIRE((long long)N * h * w * C < ur::GRID_1D_LIMIT && (long long)N * H * W * C < ur::GRID_1D_LIMIT,
-             "too many elements: N*h*w*C and N*H*W*C must be below 2^31 - 256");
-  hipStream_t s = (hipStream_t)stream;
-  if (C % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0) {
-    const int total = N * H * W * (C / 4);
-    UR_GRID_1D(blocks, total, 256);
-    hipLaunchKernelGGL(upsample_bilinear_ac_kernel<4>, dim3(blocks), dim3(256), 0, s, x, y, total, h, w, C, H, W, idx_h, wt_h, idx_w, wt_w);
-  } else {
-    const int total = N * H * W * C;
-    UR_GRID_1D(blocks, total, 256);
-    hipLaunchKernelGGL(upsample_bilinear_ac_kernel<1>, dim3(blocks), dim3(256), 0, s, x, y, total, h, w, C, H, W, idx_h, wt_h, idx_w, wt_w);
-  }
-  return ur::check_launch("ur_upsample_bilinear_ac_f32");
-}
-
-int ur_maxpool5_f32(const float* x, float* y, int N, int H, int W, int C, ur_stream_t stream) {
-  UR_REQUIRE(x && y, "null pointer");
-  UR_REQUIRE(x != y, "x and y must not be the same buffer");
-  UR_REQUIRE(N >= 1 && C >= 1 && H >= 1 && W >= 1, "N, C, H and W must be >= 1");
-  UR_REQUIRE((long long)N * H * W * C < ur::GRID_1D_LIMIT, "too many elements: N*H*W*C must be below 2^31 - 256");
-  hipStream_t s = (hipStream_t)stream;
-  if (C % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0) {
-    const int total = N * H * W * (C / 4);
-    UR_GRID_1D(blocks, total, 256);
-    hipLaunchKernelGGL(maxpool5_f32_kernel<4>, dim3(blocks), dim3(256), 0, s, x, y, total, H, W, C);
-  } else {
-    const int total = N * H * W * C;
-    UR_GRID_1D(blocks, total, 256);
-    hipLaunchKernelGGL(maxpool5_f32_kernel<1>, dim3(blocks), dim3(256), 0, s, x, y, total, H, W, C);
-  }
-  return ur::check_launch("ur_maxpool5_f32");
-}
-
-int ur_add_f32(const float* a, const float* b, float* y, long long n, ur_stream_t stream) {
-  UR_REQUIRE(a && b && y, "null pointer");
-  UR_REQUIRE(n >= 1 && n < ur::GRID_1D_LIMIT, "n must be in [1, 2^31 - 256): inside [1, 2^31) with a whole last workgroup inside an int");
-  UR_REQUIRE(y != a && y != b, "y must be neither a nor b");
-  hipStream_t s = (hipStream_t)stream;
-  if (n % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)y) & 15) == 0) {
-    const int total = (int)(n / 4);
-    UR_GRID_1D(blocks, total, 256);
-    hipLaunchKernelGGL(add_f32_kernel<4>, dim3(blocks), dim3(256), 0, s, a, b, y, total);
-  } else {
-    const int total = (int)n;
-    UR_GRID_1D(blocks, total, 256);
-    hipLaunchKernelGGL(add_f32_kernel<1>, dim3(blocks), dim3(256), 0, s, a, b, y, total);
-  }
-  return ur::check_launch("ur_add_f32");
 }
 
 int ur_seg_tta_argmax(const float* m0, const float* m1, const float* m2, int nmaps, int N, int C, int h0, int w0, int h1, int w1, int h2, int w2,

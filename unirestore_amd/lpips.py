@@ -1,5 +1,5 @@
-"""LPIPS (AlexNet, v0.1 linear layers) on the GPU in exact fp32: weight loading / repacking, the layer plan and the launch
-wrappers of csrc/lpips.hip.  What the reference's evaluator builds as `LPIPS(net_type="alex", normalize=True)`
+"""LPIPS (AlexNet, v0.1 linear layers) on the GPU in exact fp32: weight loading, the layer plan and the launch wrappers of
+csrc/lpips.hip, on the fp32 layers of f32net.py.  What the reference's evaluator builds as `LPIPS(net_type="alex", normalize=True)`
 (eval_image_restoration.py:181-185), run with autocast off.
 
 The project ships NO weights.  `load_weights` reads the two files a user of the metric already has (torchvision's AlexNet state
@@ -10,43 +10,14 @@ import math
 
 import torch
 
-from . import capi
+from . import f32net
 from .capi import check, lib
+from .f32net import PackedConvF32, stream, take
 
 # (state-dict index, Cout, Cin, kernel, stride, pad) of AlexNet's five convolutions; every ReLU output is a tap
 CONVS = ((0, 64, 3, 11, 4, 2), (3, 192, 64, 5, 1, 2), (6, 384, 192, 3, 1, 1), (8, 256, 384, 3, 1, 1), (10, 256, 256, 3, 1, 1))
 POOL_BEFORE = (False, True, True, False, False)          # a 3x3 / stride-2 max-pool in front of conv2 and conv3
 MIN_HW = 31                                              # the smallest input at which the fifth tap still has one pixel
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def wpack_dims(cin, cout, kh, kw):
-    """(Kpad, Cout_pad) of the kernel's weight layout."""
-    kpad, cpad = C.c_int(), C.c_int()
-    check(lib.ur_conv2d_f32_wpack_dims(cin, cout, kh, kw, kpad, cpad))
-    return kpad.value, cpad.value
-
-
-def pack_conv_weight(w: torch.Tensor) -> torch.Tensor:
-    """OIHW fp32 filter -> the kernel's [Kpad][Cout_pad] layout (CPU tensor): row k = (kh * KW + kw) * Cin + cin, zero-filled."""
-    cout, cin, kh, kw = w.shape
-    kpad, cpad = wpack_dims(cin, cout, kh, kw)
-    out = torch.zeros(kpad, cpad, dtype=torch.float32)
-    out[:cin * kh * kw, :cout] = w.float().permute(2, 3, 1, 0).reshape(kh * kw * cin, cout)
-    return out
-
-
-class PackedConvF32:
-    """One fp32 convolution ready for ur_conv2d_f32: the repacked filter and the bias on the device, and its geometry."""
-
-    def __init__(self, weight: torch.Tensor, bias: torch.Tensor, stride: int, pad: int, dev):
-        self.cout, self.cin, self.kh, self.kw = weight.shape
-        self.stride, self.pad = stride, pad
-        self.w = pack_conv_weight(weight).to(dev)
-        self.bias = bias.float().contiguous().to(dev)
 
 
 class LpipsWeights:
@@ -68,15 +39,6 @@ def _load(path):
     return torch.load(path, map_location="cpu", weights_only=True)
 
 
-def _take(sd, path, key, shape):
-    if key not in sd:
-        raise ValueError(f"{path}: key {key!r} is missing")
-    t = sd[key]
-    if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{path}: {key!r} has shape {tuple(getattr(t, 'shape', ()))}, expected {tuple(shape)}")
-    return t.detach().float()
-
-
 def load_weights(alexnet_path, lin_path, dev=None) -> LpipsWeights:
     """alexnet_path: torchvision's AlexNet state dict (`features.{0,3,6,8,10}.{weight,bias}`; `classifier.*` is ignored);
     lin_path: the LPIPS v0.1 linear layers (`lin{0..4}.model.1.weight`, [1,C,1,1]).  Both are user-supplied: none ship here.
@@ -85,10 +47,10 @@ def load_weights(alexnet_path, lin_path, dev=None) -> LpipsWeights:
     asd, lsd = _load(alexnet_path), _load(lin_path)
     convs, lins = [], []
     for i, (idx, cout, cin, k, _s, _p) in enumerate(CONVS):
-        convs.append((_take(asd, alexnet_path, f"features.{idx}.weight", (cout, cin, k, k)),
-                      _take(asd, alexnet_path, f"features.{idx}.bias", (cout,))))
+        convs.append((take(asd, alexnet_path, f"features.{idx}.weight", (cout, cin, k, k), finite=False),
+                      take(asd, alexnet_path, f"features.{idx}.bias", (cout,), finite=False)))
         key = f"lin{i}.model.1.weight"
-        lin = _take(lsd, lin_path, key, (1, cout, 1, 1))
+        lin = take(lsd, lin_path, key, (1, cout, 1, 1), finite=False)
         if bool((lin < 0).any()) or not bool(torch.isfinite(lin).all()):
             raise ValueError(f"{lin_path}: {key!r} holds a negative or non-finite weight: not an LPIPS linear layer")
         lins.append(lin)
@@ -115,7 +77,7 @@ def random_weights(seed: int = 0, dev=None) -> LpipsWeights:
                         [lsd[f"lin{i}.model.1.weight"] for i in range(len(CONVS))], dev)
 
 
-# ---- launch wrappers (each one kernel family; fp32 NHWC device tensors) -------------------------------------------------------
+# ---- launch wrappers of csrc/lpips.hip (fp32 NHWC device tensors) --------------------------------------------------------------
 
 def tap_hw(h: int, w: int, tap: int):
     oh, ow = C.c_int(), C.c_int()
@@ -127,25 +89,7 @@ def prep(x: torch.Tensor) -> torch.Tensor:
     """fp32 NCHW [N,3,H,W] in [0,1] -> NHWC [N,H,W,3], scaled as LPIPS's ScalingLayer does after normalize=True."""
     n, c, h, w = x.shape
     y = torch.empty(n, h, w, 3, dtype=torch.float32, device=x.device)
-    check(lib.ur_lpips_prep(x.data_ptr(), y.data_ptr(), n, c, h, w, _stream()))
-    return y
-
-
-def conv2d_f32(x: torch.Tensor, pc: PackedConvF32, relu: bool = True) -> torch.Tensor:
-    n, h, w, cin = x.shape
-    if cin != pc.cin:
-        raise ValueError(f"conv2d_f32: input has {cin} channels, the filter {pc.cin}")
-    oh, ow = (h + 2 * pc.pad - pc.kh) // pc.stride + 1, (w + 2 * pc.pad - pc.kw) // pc.stride + 1
-    y = torch.empty(n, max(oh, 0), max(ow, 0), pc.cout, dtype=torch.float32, device=x.device)
-    check(lib.ur_conv2d_f32(x.data_ptr(), pc.w.data_ptr(), pc.bias.data_ptr(), y.data_ptr(), n, h, w, cin, pc.cout, pc.kh, pc.kw,
-                            pc.stride, pc.pad, int(relu), _stream()))
-    return y
-
-
-def maxpool2d_f32(x: torch.Tensor) -> torch.Tensor:
-    n, h, w, c = x.shape
-    y = torch.empty(n, max((h - 3) // 2 + 1, 0), max((w - 3) // 2 + 1, 0), c, dtype=torch.float32, device=x.device)
-    check(lib.ur_maxpool2d_f32(x.data_ptr(), y.data_ptr(), n, h, w, c, _stream()))
+    check(lib.ur_lpips_prep(x.data_ptr(), y.data_ptr(), n, c, h, w, stream()))
     return y
 
 
@@ -164,7 +108,7 @@ def layer(feat: torch.Tensor, lin: torch.Tensor, part: torch.Tensor = None) -> t
         raise ValueError(f"lpips layer: feat {tuple(feat.shape)} needs an even batch and {c} linear weights, got {lin.numel()}")
     if part is None:
         part = torch.empty(n, layer_parts(p), dtype=torch.float64, device=feat.device)
-    check(lib.ur_lpips_layer(feat.data_ptr(), lin.data_ptr(), n, p, c, part.data_ptr(), part.numel() * 8, _stream()))
+    check(lib.ur_lpips_layer(feat.data_ptr(), lin.data_ptr(), n, p, c, part.data_ptr(), part.numel() * 8, stream()))
     return part
 
 
@@ -173,8 +117,8 @@ def features(x2: torch.Tensor, wts: LpipsWeights):
     taps, f = [], prep(x2)
     for pc, pool in zip(wts.convs, POOL_BEFORE):
         if pool:
-            f = maxpool2d_f32(f)
-        f = conv2d_f32(f, pc, relu=True)
+            f = f32net.maxpool2d_f32(f)
+        f = f32net.conv2d_f32(f, pc, relu=True)
         taps.append(f)
     return taps
 
@@ -193,5 +137,5 @@ def forward(pred: torch.Tensor, target: torch.Tensor, wts: LpipsWeights) -> torc
         cnt = n * layer_parts(feat.shape[1] * feat.shape[2])
         layer(feat, lin, ws[off:off + cnt])
         off += cnt
-    check(lib.ur_lpips_finish(ws.data_ptr(), ws_bytes, n, h, w, out.data_ptr(), _stream()))
+    check(lib.ur_lpips_finish(ws.data_ptr(), ws_bytes, n, h, w, out.data_ptr(), stream()))
     return out

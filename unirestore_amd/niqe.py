@@ -26,7 +26,7 @@ import os
 import torch
 
 from .capi import check, lib
-from .lpips import _stream
+from .f32net import stream
 
 BLOCK = 96                                               # block edge at the first scale; BLOCK // 2 at the second
 MIN_BLOCKS = 2                                           # a covariance needs two rows
@@ -151,7 +151,7 @@ def luma(x: torch.Tensor, color_space: str = "yiq") -> torch.Tensor:
     n, _c, h, w = x.shape
     ch, cw = crop_hw(h, w)
     y = torch.empty(n, ch, cw, dtype=torch.float64, device=x.device)
-    check(lib.ur_niqe_luma(x.data_ptr(), y.data_ptr(), n, h, w, ch, cw, COLOR_SPACES.index(color_space), _stream()))
+    check(lib.ur_niqe_luma(x.data_ptr(), y.data_ptr(), n, h, w, ch, cw, COLOR_SPACES.index(color_space), stream()))
     return y
 
 
@@ -159,7 +159,7 @@ def mscn(y: torch.Tensor) -> torch.Tensor:
     """fp64 [N,h,w] -> its MSCN field (y - mu) / (sigma + 1), replicate border at the field's edge."""
     n, h, w = _f64(y, "mscn", 3).shape
     m = torch.empty_like(y)
-    check(lib.ur_niqe_mscn(y.data_ptr(), m.data_ptr(), n, h, w, _stream()))
+    check(lib.ur_niqe_mscn(y.data_ptr(), m.data_ptr(), n, h, w, stream()))
     return m
 
 
@@ -169,7 +169,7 @@ def block_moments(field: torch.Tensor, bs: int = BLOCK) -> torch.Tensor:
     of the positive ones, sum |v| and sum v^2."""
     n, h, w = _f64(field, "block_moments", 3).shape
     out = torch.empty(n, max(h // bs, 0) * max(w // bs, 0) if bs in (96, 48) else 0, 5, 6, dtype=torch.float64, device=field.device)
-    check(lib.ur_niqe_block_moments(field.data_ptr(), out.data_ptr(), n, h, w, bs, _stream()))
+    check(lib.ur_niqe_block_moments(field.data_ptr(), out.data_ptr(), n, h, w, bs, stream()))
     return out
 
 
@@ -177,7 +177,7 @@ def halve(y: torch.Tensor) -> torch.Tensor:
     """fp64 [N,h,w] (h, w even, >= 4) -> halve(y / 255) * 255, fp64 [N,h/2,w/2]: MATLAB's antialiased bicubic imresize(., 0.5)."""
     n, h, w = _f64(y, "halve", 3).shape
     out = torch.empty(n, h // 2, w // 2, dtype=torch.float64, device=y.device)
-    check(lib.ur_niqe_halve(y.data_ptr(), out.data_ptr(), n, h, w, _stream()))
+    check(lib.ur_niqe_halve(y.data_ptr(), out.data_ptr(), n, h, w, stream()))
     return out
 
 
@@ -195,7 +195,7 @@ def fit(moments: torch.Tensor, block_pixels: int = None, out=None, col_off: int 
     idx = torch.empty(n, b, 5, dtype=torch.int32, device=moments.device) if want_index else None
     check(lib.ur_niqe_fit(moments.data_ptr(), rho.data_ptr(), scale.data_ptr(), ratio.data_ptr(), feat.data_ptr(),
                           None if idx is None else idx.data_ptr(), n * b, BLOCK * BLOCK if block_pixels is None else int(block_pixels),
-                          feat.shape[2], col_off, _stream()))
+                          feat.shape[2], col_off, stream()))
     return (feat, idx) if want_index else feat
 
 

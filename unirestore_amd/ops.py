@@ -1037,19 +1037,34 @@ def f32_to_bf16(x, c, mul=1.0, cpad=8):
     return out
 
 
+def _check_images(who, name, t):
+    """t must be a contiguous 4-d fp32 NCHW tensor on the current device."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.ndim != 4:
+        raise ValueError(f"{who}: {name} must be a 4-d fp32 NCHW tensor, got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    if t.device != dev:
+        raise ValueError(f"{who}: {name} is on {t.device}, not on the current device {dev}")
+    if not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be contiguous")
+
+
+def _check_scorer(who, what, obj, cls, makers):
+    """obj (a scorer's `what`: its weights or params) must be a `cls`, which `makers` return, on the current device."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if not isinstance(obj, cls):
+        raise ValueError(f"{who}: {what} must come from {makers}, got {type(obj).__name__}")
+    if obj.device != dev:
+        raise ValueError(f"{who}: the {what} are on {obj.device}, not on the current device {dev}")
+
+
 def image_metrics(pred: torch.Tensor, target: torch.Tensor, data_range: float = 1.0, win: int = 7):
     """Per-image PSNR and SSIM of fp32 NCHW batches on the GPU -> (psnr, ssim), fp64 [N] device tensors.  Same semantics as
     runner.psnr_per_image / runner.ssim per image (skimage defaults: uniform win x win window, K1 0.01, K2 0.03, sample
     covariance, valid interior); fp64 moments and fixed-order sums, so two calls give the same bits.  No host sync."""
     dev = torch.device("cuda", torch.cuda.current_device())
     for name, t in (("pred", pred), ("target", target)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.ndim != 4:
-            raise ValueError(f"image_metrics: {name} must be a 4-d fp32 NCHW tensor, got "
-                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-        if t.device != dev:
-            raise ValueError(f"image_metrics: {name} is on {t.device}, not on the current device {dev}")
-        if not t.is_contiguous():
-            raise ValueError(f"image_metrics: {name} must be contiguous")
+        _check_images("image_metrics", name, t)
     if pred.shape != target.shape:
         raise ValueError(f"image_metrics: shapes differ: {tuple(pred.shape)} vs {tuple(target.shape)}")
     n, c, h, w = pred.shape
@@ -1071,24 +1086,14 @@ def lpips(pred: torch.Tensor, target: torch.Tensor, weights) -> torch.Tensor:
     lpips.load_weights / lpips.random_weights return.  Predictions and targets go through the network as one batch of 2N; exact
     fp32 (fp32-input MFMA convolutions), fixed-order sums, so two calls give the same bits.  No host sync."""
     from . import lpips as _lpips
-    dev = torch.device("cuda", torch.cuda.current_device())
     for name, t in (("pred", pred), ("target", target)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.ndim != 4:
-            raise ValueError(f"lpips: {name} must be a 4-d fp32 NCHW tensor, got "
-                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-        if t.device != dev:
-            raise ValueError(f"lpips: {name} is on {t.device}, not on the current device {dev}")
-        if not t.is_contiguous():
-            raise ValueError(f"lpips: {name} must be contiguous")
+        _check_images("lpips", name, t)
     if pred.shape != target.shape:
         raise ValueError(f"lpips: shapes differ: {tuple(pred.shape)} vs {tuple(target.shape)}")
     n, c, h, w = pred.shape
     if n < 1 or c != 3 or h < _lpips.MIN_HW or w < _lpips.MIN_HW:
         raise ValueError(f"lpips: needs [N>=1, 3, H>={_lpips.MIN_HW}, W>={_lpips.MIN_HW}] images, got {tuple(pred.shape)}")
-    if not isinstance(weights, _lpips.LpipsWeights):
-        raise ValueError(f"lpips: weights must come from lpips.load_weights / lpips.random_weights, got {type(weights).__name__}")
-    if weights.device != dev:
-        raise ValueError(f"lpips: the weights are on {weights.device}, not on the current device {dev}")
+    _check_scorer("lpips", "weights", weights, _lpips.LpipsWeights, "lpips.load_weights / lpips.random_weights")
     return _lpips.forward(pred, target, weights)
 
 
@@ -1098,24 +1103,14 @@ def niqe(images: torch.Tensor, params, color_space: str = "yiq") -> torch.Tensor
     the same bits); the 36-dimensional algebra of the score runs on the host (one device-to-host copy).  The top-left
     (H // 96 * 96, W // 96 * 96) crop must hold at least two 96 x 96 blocks."""
     from . import niqe as _niqe
-    dev = torch.device("cuda", torch.cuda.current_device())
-    if not isinstance(images, torch.Tensor) or images.dtype != torch.float32 or images.ndim != 4:
-        raise ValueError(f"niqe: images must be a 4-d fp32 NCHW tensor, got "
-                         f"{getattr(images, 'dtype', type(images))} {tuple(getattr(images, 'shape', ()))}")
-    if images.device != dev:
-        raise ValueError(f"niqe: images is on {images.device}, not on the current device {dev}")
-    if not images.is_contiguous():
-        raise ValueError("niqe: images must be contiguous")
+    _check_images("niqe", "images", images)
     n, c, h, w = images.shape
     if n < 1 or c != 3:
         raise ValueError(f"niqe: needs [N>=1, 3, H, W] images, got {tuple(images.shape)}")
     if h < _niqe.BLOCK or w < _niqe.BLOCK or (h // _niqe.BLOCK) * (w // _niqe.BLOCK) < _niqe.MIN_BLOCKS:
         raise ValueError(f"niqe: images of shape {tuple(images.shape)} hold {(h // _niqe.BLOCK) * (w // _niqe.BLOCK)} block(s) of "
                          f"{_niqe.BLOCK} x {_niqe.BLOCK}; the score needs at least {_niqe.MIN_BLOCKS}")
-    if not isinstance(params, _niqe.NiqeParams):
-        raise ValueError(f"niqe: params must come from niqe.load_params / niqe.random_params / niqe.fit_params, got {type(params).__name__}")
-    if params.device != dev:
-        raise ValueError(f"niqe: the params are on {params.device}, not on the current device {dev}")
+    _check_scorer("niqe", "params", params, _niqe.NiqeParams, "niqe.load_params / niqe.random_params / niqe.fit_params")
     if color_space not in _niqe.COLOR_SPACES:
         raise ValueError(f"niqe: unknown color_space {color_space!r}, choose from {_niqe.COLOR_SPACES}")
     return _niqe.forward(images, params, color_space)
@@ -1127,21 +1122,11 @@ def classify(images: torch.Tensor, weights) -> torch.Tensor:
     what classify.load_weights / classify.random_weights return.  An image's logits do not depend on its place in the batch, and
     two calls give the same bits.  No host sync."""
     from . import classify as _classify
-    dev = torch.device("cuda", torch.cuda.current_device())
-    if not isinstance(images, torch.Tensor) or images.dtype != torch.float32 or images.ndim != 4:
-        raise ValueError(f"classify: images must be a 4-d fp32 NCHW tensor, got "
-                         f"{getattr(images, 'dtype', type(images))} {tuple(getattr(images, 'shape', ()))}")
-    if images.device != dev:
-        raise ValueError(f"classify: images is on {images.device}, not on the current device {dev}")
-    if not images.is_contiguous():
-        raise ValueError("classify: images must be contiguous")
+    _check_images("classify", "images", images)
     n, c, h, w = images.shape
     if n < 1 or c != 3 or h < 1 or w < 1:
         raise ValueError(f"classify: needs [N>=1, 3, H>=1, W>=1] images, got {tuple(images.shape)}")
-    if not isinstance(weights, _classify.ClassifierWeights):
-        raise ValueError(f"classify: weights must come from classify.load_weights / classify.random_weights, got {type(weights).__name__}")
-    if weights.device != dev:
-        raise ValueError(f"classify: the weights are on {weights.device}, not on the current device {dev}")
+    _check_scorer("classify", "weights", weights, _classify.ClassifierWeights, "classify.load_weights / classify.random_weights")
     return _classify.forward(images, weights)
 
 
@@ -1182,21 +1167,11 @@ def segment(images: torch.Tensor, weights, size=None, scales=(1, 0.8, 0.6)) -> t
     tap tables on the host and uploads them with a blocking copy: run a shape once eagerly before capturing it in a graph.  The
     tables (a few KB per shape) stay on the device for the life of the process, so a captured graph never loses the ones it reads."""
     from . import segment as _segment
-    dev = torch.device("cuda", torch.cuda.current_device())
-    if not isinstance(images, torch.Tensor) or images.dtype != torch.float32 or images.ndim != 4:
-        raise ValueError(f"segment: images must be a 4-d fp32 NCHW tensor, got "
-                         f"{getattr(images, 'dtype', type(images))} {tuple(getattr(images, 'shape', ()))}")
-    if images.device != dev:
-        raise ValueError(f"segment: images is on {images.device}, not on the current device {dev}")
-    if not images.is_contiguous():
-        raise ValueError("segment: images must be contiguous")
+    _check_images("segment", "images", images)
     n, c, h, w = images.shape
     if n < 1 or c != 3 or h < 1 or w < 1:
         raise ValueError(f"segment: needs [N>=1, 3, H>=1, W>=1] images, got {tuple(images.shape)}")
-    if not isinstance(weights, _segment.SegmenterWeights):
-        raise ValueError(f"segment: weights must come from segment.load_weights / segment.random_weights, got {type(weights).__name__}")
-    if weights.device != dev:
-        raise ValueError(f"segment: the weights are on {weights.device}, not on the current device {dev}")
+    _check_scorer("segment", "weights", weights, _segment.SegmenterWeights, "segment.load_weights / segment.random_weights")
     if size is not None and not (isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(v, int) and v >= 1 for v in size)):
         raise ValueError(f"segment: size must be (H, W) with H, W >= 1, got {size!r}")
     if not (isinstance(scales, (tuple, list)) and 1 <= len(scales) <= 3 and all(isinstance(v, (int, float)) and 0 < v <= 8 for v in scales)):

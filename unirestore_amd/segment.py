@@ -1,5 +1,5 @@
 """Segmenter scoring of the `seg` output on the GPU in exact fp32: RefineNet-LightWeight (ResNet-50 / 101 / 152 backbone) on the
-fp32 convolution of csrc/lpips.hip and the kernels of csrc/segment.hip - weight loading and BatchNorm folding, the evaluator's
+fp32 layers and the ResNet backbone of f32net.py and the kernels of csrc/segment.hip - weight loading, the evaluator's
 three-scale test-time augmentation, the launch wrappers, and the mIoU formula.  What the reference's `SemanticSegmentationMetric`
 builds (eval_semantic_segmentation.py:170-251): quantised image -> scales (1, 0.8, 0.6), bilinear align_corners=True -> the
 segmenter (x * 255 - mean, BGR, ResNetLW) -> every scale's logits resized to the label map -> mean -> argmax ->
@@ -8,15 +8,13 @@ MulticlassJaccardIndex(19, ignore_index=255).
 The project ships NO weights.  `load_weights` reads the state dict (or Lightning checkpoint) a user of the metric already has;
 `random_weights` makes seeded stand-ins for tests and timing, which say nothing about any published mIoU.
 """
-import functools
 import math
 
 import torch
 
-from . import classify
+from . import f32net
 from .capi import check, lib
-from .classify import BN_EPS, conv2d_f32_res, fold_bn, maxpool2d_pad_f32, read_state_dict
-from .lpips import PackedConvF32, _stream
+from .f32net import PackedConvF32, stream, take
 
 # arch -> bottleneck blocks per stage (the torchvision layout, the stride on the 3x3 convolution)
 ARCHS = {"rflw50": (3, 4, 6, 3), "rflw101": (3, 4, 23, 3), "rflw152": (3, 8, 36, 3)}
@@ -36,7 +34,7 @@ def depths_of(arch):
 
 def conv_plan(arch):
     """[(conv key, bn key, Cout, Cin, kernel, stride, pad)] of every backbone convolution, in state-dict order."""
-    return classify.bottleneck_plan(depths_of(arch))
+    return f32net.resnet_plan("bottleneck", depths_of(arch))
 
 
 def head_plan(num_classes: int = 19):
@@ -61,16 +59,8 @@ class SegmenterWeights:
     def __init__(self, arch, sd: dict, dev=None, source: str = "state dict"):
         dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else torch.device(dev)
         self.arch, self.device, self.depths = arch, dev, depths_of(arch)
-        self.cpu, self.convs, ready = {}, {}, []
-        for ckey, bkey, cout, cin, k, stride, pad in conv_plan(arch):        # every check first: nothing is uploaded for a bad file
-            w = self._take(sd, source, f"{ckey}.weight", (cout, cin, k, k))
-            bn = [self._take(sd, source, f"{bkey}.{n}", (cout,)) for n in ("weight", "bias", "running_mean", "running_var")]
-            if not bool((bn[3].double() + BN_EPS > 0).all()):
-                raise ValueError(f"{source}: {bkey + '.running_var'!r} + eps is not positive: not a trained BatchNorm")
-            fw, fb = fold_bn(w, *bn)
-            if not (bool(torch.isfinite(fw).all()) and bool(torch.isfinite(fb).all())):
-                raise ValueError(f"{source}: folding {bkey!r} into {ckey!r} gives a non-finite value")
-            ready.append((ckey, fw.float(), fb.float(), stride, pad))
+        self.cpu, self.convs = {}, {}
+        ready = f32net.fold_convs(conv_plan(arch), sd, source, self.cpu)      # every check first: nothing is uploaded for a bad file
         clf = sd.get("clf_conv.weight")
         if not torch.is_tensor(clf) or clf.ndim != 4:
             raise ValueError(f"{source}: key 'clf_conv.weight' is missing or is no [classes, 256, 3, 3] filter")
@@ -78,31 +68,13 @@ class SegmenterWeights:
         if not 1 <= self.num_classes <= 255:
             raise ValueError(f"{source}: 'clf_conv.weight' has {self.num_classes} classes, the one-byte prediction holds 1..255")
         for ckey, cout, cin, k in head_plan(self.num_classes):
-            w = self._take(sd, source, f"{ckey}.weight", (cout, cin, k, k))
-            b = self._take(sd, source, "clf_conv.bias", (cout,)) if ckey == "clf_conv" else torch.zeros(cout)
+            w = take(sd, source, f"{ckey}.weight", (cout, cin, k, k), keep=self.cpu)
+            b = take(sd, source, "clf_conv.bias", (cout,), keep=self.cpu) if ckey == "clf_conv" else torch.zeros(cout)
             ready.append((ckey, w, b, 1, k // 2))
         for ckey, w, b, stride, pad in ready:
             self.convs[ckey] = PackedConvF32(w, b, stride, pad, dev)
         # the backbone's blocks in execution order, by stage: (conv keys of the main path, downsample key or None)
-        self.stages = []
-        for li, depth in enumerate(self.depths, 1):
-            blocks = []
-            for bi in range(depth):
-                p = f"layer{li}.{bi}"
-                blocks.append(([f"{p}.conv{j}" for j in (1, 2, 3)], f"{p}.downsample.0" if f"{p}.downsample.0" in self.convs else None))
-            self.stages.append(blocks)
-
-    def _take(self, sd, source, key, shape):
-        if key not in sd:
-            raise ValueError(f"{source}: key {key!r} is missing")
-        t = sd[key]
-        if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{source}: {key!r} has shape {tuple(getattr(t, 'shape', ()))}, expected {tuple(shape)}")
-        t = t.detach().float().cpu()
-        if not bool(torch.isfinite(t).all()):
-            raise ValueError(f"{source}: {key!r} holds a non-finite value")
-        self.cpu[key] = t
-        return t
+        self.stages = f32net.resnet_stages("bottleneck", self.depths, self.convs)
 
 
 def load_weights(arch, path, dev=None) -> SegmenterWeights:
@@ -112,7 +84,7 @@ def load_weights(arch, path, dev=None) -> SegmenterWeights:
     checkpoint of one.  The number of classes is clf_conv.weight's.  ValueError (file and key named) for a missing key, a wrong
     shape, a non-finite value or a non-positive running_var + eps."""
     depths_of(arch)                                                  # an unknown arch, before the file is read
-    return SegmenterWeights(arch, read_state_dict(path), dev, source=str(path))
+    return SegmenterWeights(arch, f32net.read_state_dict(path), dev, source=str(path))
 
 
 def random_state_dict(arch, seed: int, num_classes: int = 19) -> dict:
@@ -125,15 +97,7 @@ def random_state_dict(arch, seed: int, num_classes: int = 19) -> dict:
     the stand-in residual sums grow: fp32 logits stay O(10) at every depth.  NOT trained weights -
     its predictions say nothing about any published mIoU."""
     g = torch.Generator().manual_seed(seed)
-    sd = {}
-    for ckey, bkey, cout, cin, k, _s, _p in conv_plan(arch):
-        gain = 1.0 / 255.0 if ckey == "conv1" else 1.0
-        sd[f"{ckey}.weight"] = torch.randn(cout, cin, k, k, generator=g) * (gain * math.sqrt(2.0 / (cin * k * k)))
-        sd[f"{bkey}.weight"] = (0.5 + torch.rand(cout, generator=g)) * (0.5 if ckey.endswith("conv3") else 1.0)
-        sd[f"{bkey}.bias"] = 0.1 * torch.randn(cout, generator=g)
-        sd[f"{bkey}.running_mean"] = 0.1 * torch.randn(cout, generator=g)
-        sd[f"{bkey}.running_var"] = 0.5 + torch.rand(cout, generator=g)
-        sd[f"{bkey}.num_batches_tracked"] = torch.tensor(0)
+    sd = f32net.random_backbone(conv_plan(arch), "bottleneck", g, conv1_gain=1.0 / 255.0)
     depths = depths_of(arch)
     for ckey, cout, cin, k in head_plan(num_classes):
         gain = 0.5 if "_pool." in ckey else 4.0 if ckey == "clf_conv" else 1.0
@@ -151,37 +115,14 @@ def random_weights(arch, seed: int = 0, num_classes: int = 19, dev=None) -> Segm
     return SegmenterWeights(arch, random_state_dict(arch, seed, num_classes), dev, source=f"random_state_dict({arch!r}, {seed})")
 
 
-# ---- sizes and tap tables on the host ------------------------------------------------------------------------------------------
+# ---- sizes on the host ---------------------------------------------------------------------------------------------------------
 
 def scaled_size(n: int, s) -> int:
     """The output size of `F.interpolate(scale_factor=s)` for an axis of n: floor(n * s) in host double."""
     return math.floor(n * s)
 
 
-def ac_table(n_in: int, n_out: int):
-    """One axis of `interpolate(mode="bilinear", align_corners=True)`: (idx [n_out] int32, wt [n_out, 2] fp64).  Output o reads
-    sources idx[o] and idx[o] + 1 with weights wt[o]; its source coordinate o * (n_in - 1) / (n_out - 1) (0 when n_out == 1) is
-    split into index and fraction in integers, so the fraction is the correctly rounded fp64 value."""
-    if n_in < 1 or n_out < 1:
-        raise ValueError(f"ac_table: sizes must be >= 1, got {n_in} -> {n_out}")
-    idx, wt = [], []
-    for o in range(n_out):
-        q, rem = divmod(o * (n_in - 1), n_out - 1) if n_out > 1 else (0, 0)
-        frac = rem / (n_out - 1) if rem else 0.0                     # (rem == 0 also where the last output sits on the last source)
-        idx.append(q)
-        wt.append((1.0 - frac, frac))
-    return torch.tensor(idx, dtype=torch.int32), torch.tensor(wt, dtype=torch.float64)
-
-
-@functools.lru_cache(maxsize=None)                       # never evicted: a captured graph keeps reading the tables it was captured with
-def _device_tables(n_ins: tuple, n_out: int, dev_index: int):
-    """The tables of several source axes to one output axis, one after the other: (idx [len(n_ins) * n_out], wt [.., 2] fp32)."""
-    tabs = [ac_table(n_in, n_out) for n_in in n_ins]
-    dev = torch.device("cuda", dev_index)
-    return torch.cat([t[0] for t in tabs]).to(dev), torch.cat([t[1] for t in tabs]).float().contiguous().to(dev)
-
-
-# ---- launch wrappers (each one kernel family; fp32 device tensors, NHWC behind the preprocess) ---------------------------------
+# ---- launch wrappers of csrc/segment.hip (fp32 device tensors, NHWC behind the preprocess) --------------------------------------
 
 def prep(x: torch.Tensor, size=None) -> torch.Tensor:
     """fp32 NCHW [N,3,H,W] in [0,1] -> NHWC [N,h,w,3] (size = (h, w), default the input's): bilinear align_corners=True resize, then
@@ -189,31 +130,10 @@ def prep(x: torch.Tensor, size=None) -> torch.Tensor:
     for a new pair of sizes uploads its tables: run a shape once eagerly before capturing it in a graph."""
     n, c, h, w = x.shape
     oh, ow = (h, w) if size is None else size
-    iy, wy = _device_tables((h,), oh, x.device.index)
-    ix, wx = _device_tables((w,), ow, x.device.index)
+    iy, wy = f32net._device_tables((h,), oh, x.device.index)
+    ix, wx = f32net._device_tables((w,), ow, x.device.index)
     y = torch.empty(n, oh, ow, 3, dtype=torch.float32, device=x.device)
-    check(lib.ur_seg_prep(x.data_ptr(), y.data_ptr(), n, c, h, w, oh, ow, iy.data_ptr(), wy.data_ptr(), ix.data_ptr(), wx.data_ptr(), _stream()))
-    return y
-
-
-def upsample_bilinear_ac_f32(x: torch.Tensor, size) -> torch.Tensor:
-    """NHWC fp32 [N,h,w,C] -> [N,H,W,C], bilinear with align_corners=True; the same size is the identity, bit for bit, while the
-    values are finite (0 x inf from a neighbour is NaN, as in torch; a -0.0 may come out as +0.0)."""
-    n, h, w, c = x.shape
-    oh, ow = size
-    iy, wy = _device_tables((h,), oh, x.device.index)
-    ix, wx = _device_tables((w,), ow, x.device.index)
-    y = torch.empty(n, oh, ow, c, dtype=torch.float32, device=x.device)
-    check(lib.ur_upsample_bilinear_ac_f32(x.data_ptr(), y.data_ptr(), n, h, w, c, oh, ow, iy.data_ptr(), wy.data_ptr(), ix.data_ptr(),
-                                          wx.data_ptr(), _stream()))
-    return y
-
-
-def maxpool5_f32(x: torch.Tensor) -> torch.Tensor:
-    """5x5 / stride 1 / padding 2 (-inf) on NHWC fp32."""
-    n, h, w, c = x.shape
-    y = torch.empty_like(x)
-    check(lib.ur_maxpool5_f32(x.data_ptr(), y.data_ptr(), n, h, w, c, _stream()))
+    check(lib.ur_seg_prep(x.data_ptr(), y.data_ptr(), n, c, h, w, oh, ow, iy.data_ptr(), wy.data_ptr(), ix.data_ptr(), wx.data_ptr(), stream()))
     return y
 
 
@@ -232,14 +152,14 @@ def tta_argmax(maps, size, want_avg: bool = False):
                              f"{m.dtype} {tuple(m.shape)} on {m.device}")
     oh, ow = size
     dev = maps[0].device
-    iy, wy = _device_tables(tuple(m.shape[1] for m in maps), oh, dev.index)
-    ix, wx = _device_tables(tuple(m.shape[2] for m in maps), ow, dev.index)
+    iy, wy = f32net._device_tables(tuple(m.shape[1] for m in maps), oh, dev.index)
+    ix, wx = f32net._device_tables(tuple(m.shape[2] for m in maps), ow, dev.index)
     pred = torch.empty(n, oh, ow, dtype=torch.uint8, device=dev)
     avg = torch.empty(n, oh, ow, c, dtype=torch.float32, device=dev) if want_avg else None
     ptr = [m.data_ptr() for m in maps] + [None] * (3 - len(maps))
     hw = [v for m in maps for v in m.shape[1:3]] + [0] * (2 * (3 - len(maps)))
     check(lib.ur_seg_tta_argmax(*ptr, len(maps), n, c, *hw, oh, ow, iy.data_ptr(), wy.data_ptr(), ix.data_ptr(), wx.data_ptr(), pred.data_ptr(),
-                                None if avg is None else avg.data_ptr(), _stream()))
+                                None if avg is None else avg.data_ptr(), stream()))
     return (pred, avg) if want_avg else pred
 
 
@@ -250,18 +170,11 @@ def confusion(pred: torch.Tensor, target: torch.Tensor, classes: int = 19, ignor
     ws = torch.empty(int(lib.ur_seg_confusion_ws_bytes(p, classes)) // 4, dtype=torch.int32, device=pred.device)
     conf = torch.empty(classes, classes, dtype=torch.int64, device=pred.device)
     check(lib.ur_seg_confusion(pred.data_ptr(), target.data_ptr(), int(target.dtype == torch.int64), p, classes, ignore_index, ws.data_ptr(),
-                               ws.numel() * 4, conf.data_ptr(), _stream()))
+                               ws.numel() * 4, conf.data_ptr(), stream()))
     return conf
 
 
 # ---- the network ---------------------------------------------------------------------------------------------------------------
-
-def add_f32(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """a + b on contiguous fp32 tensors of one shape."""
-    y = torch.empty_like(a)
-    check(lib.ur_add_f32(a.data_ptr(), b.data_ptr(), y.data_ptr(), a.numel(), _stream()))
-    return y
-
 
 def _crp(x, wts, g):
     """Chained residual pooling: four times top = conv(maxpool5(top)), x = top + x.  `top` feeds the next pool, so the sum is a
@@ -270,9 +183,9 @@ def _crp(x, wts, g):
     for i in range(1, CRP_STAGES + 1):
         pc = wts.convs[f"mflow_conv_g{g}_pool.0.{i}_outvar_dimred"]
         if i == CRP_STAGES:
-            return conv2d_f32_res(maxpool5_f32(top), pc, res=x, relu=False)
-        top = conv2d_f32_res(maxpool5_f32(top), pc, relu=False)
-        x = add_f32(top, x)
+            return f32net.conv2d_f32(f32net.maxpool5_f32(top), pc, res=x, relu=False)
+        top = f32net.conv2d_f32(f32net.maxpool5_f32(top), pc, relu=False)
+        x = f32net.add_f32(top, x)
 
 
 def logits(x: torch.Tensor, wts: SegmenterWeights) -> torch.Tensor:
@@ -282,22 +195,14 @@ def logits(x: torch.Tensor, wts: SegmenterWeights) -> torch.Tensor:
     if c != 3 or h < MIN_HW or w < MIN_HW:
         raise ValueError(f"segment.logits: needs an NHWC [N, H>={MIN_HW}, W>={MIN_HW}, 3] input, got {tuple(x.shape)}")
     cv = wts.convs
-    f = maxpool2d_pad_f32(conv2d_f32_res(x, cv["conv1"]))
-    feats = []
-    for blocks in wts.stages:
-        for main, down in blocks:
-            identity = f if down is None else conv2d_f32_res(f, cv[down], relu=False)
-            y = conv2d_f32_res(conv2d_f32_res(f, cv[main[0]]), cv[main[1]])
-            f = conv2d_f32_res(y, cv[main[2]], res=identity)
-        feats.append(f)
-    l1, l2, l3, l4 = feats
-    x = _crp(conv2d_f32_res(l4, cv["p_ims1d2_outl1_dimred"]), wts, 1)
+    l1, l2, l3, l4 = f32net.resnet_trunk(x, cv, wts.stages)
+    x = _crp(f32net.conv2d_f32(l4, cv["p_ims1d2_outl1_dimred"]), wts, 1)
     for g, skip in ((2, l3), (3, l2), (4, l1)):
-        x = conv2d_f32_res(x, cv[f"mflow_conv_g{g - 1}_b3_joint_varout_dimred"], relu=False)
-        x = upsample_bilinear_ac_f32(x, skip.shape[1:3])
-        s = conv2d_f32_res(skip, cv[f"p_ims1d2_outl{g}_dimred"], relu=False)
-        x = _crp(conv2d_f32_res(s, cv[f"adapt_stage{g}_b2_joint_varout_dimred"], res=x), wts, g)
-    return conv2d_f32_res(x, cv["clf_conv"], relu=False)
+        x = f32net.conv2d_f32(x, cv[f"mflow_conv_g{g - 1}_b3_joint_varout_dimred"], relu=False)
+        x = f32net.upsample_bilinear_ac_f32(x, skip.shape[1:3])
+        s = f32net.conv2d_f32(skip, cv[f"p_ims1d2_outl{g}_dimred"], relu=False)
+        x = _crp(f32net.conv2d_f32(s, cv[f"adapt_stage{g}_b2_joint_varout_dimred"], res=x), wts, g)
+    return f32net.conv2d_f32(x, cv["clf_conv"], relu=False)
 
 
 def segment(images: torch.Tensor, wts: SegmenterWeights, size=None, scales=SCALES) -> torch.Tensor:
