@@ -529,6 +529,51 @@ long long ur_seg_confusion_ws_bytes(long long P, int C);
 int ur_seg_confusion(const unsigned char* pred, const void* target, int target_i64, long long P, int C, int ignore_index, void* ws,
                      long long ws_bytes, long long* conf, ur_stream_t stream);
 
+/* ---- DeepLabV3+ scoring of the seg output (ResNet-50 / 101, output stride 16; exact fp32, NHWC, no atomics) ------------------
+ * The backbone's undilated convolutions are ur_conv2d_f32_res, the pooled branch's mean ur_avgpool_f32, the head's half-pixel
+ * resize ur_upsample_bilinear_ac_f32 with a half-pixel table, the confusion matrix ur_seg_confusion.
+ *
+ * A half-pixel (align_corners=False) axis table has the layout of the align_corners=True one: idx[n_out], wt[n_out][2], with the
+ *   source coordinate max(0, (o + 0.5) * n_in / n_out - 0.5); idx + 1 is clamped to the axis by the kernels.
+ * ur_dlv3_conv2d_f32: ur_conv2d_f32_res (the same kernel: with dil = 1 and ldy = Cout the same bits) with a dilation dil >= 1 -
+ *   tap (kh, kw) of output (oh, ow) reads input (oh stride - pad + kh dil, ow stride - pad + kw dil),
+ *   OH = (H + 2 pad - dil (KH - 1) - 1) / stride + 1 - and an output row stride ldy >= Cout: pixel m's Cout values go to
+ *   y + m * ldy, so with y offset by a channel count a launch fills a channel slice of a wider NHWC buffer (ASPP's five branches
+ *   in one 1280-channel tensor) and touches nothing else of it.  res keeps its own dense [N*OH*OW][Cout] layout.
+ * ur_dlv3_prep: x fp32 NCHW [N,3,H,W] in [0,1] -> y fp32 NHWC [N,OH,OW,3]: the align_corners=True bilinear resize (tables as for
+ *   ur_seg_prep; the identity at the input's own size), then (v - mean_c) / std_c with the ImageNet mean (.485, .456, .406) and
+ *   std (.229, .224, .225), channels in R, G, B order.
+ * ur_dlv3_broadcast_f32: v fp32 [N][C] -> y[(n * P + p) * ldy + c] = v[n][c] for every pixel p < P: the resize of a 1 x 1 map.
+ * ur_dlv3_upsample_f32: ur_upsample_bilinear_ac_f32 (the same table-driven sample; the head passes half-pixel tables) with an
+ *   output row stride ldy >= C: x [N,h,w,C] -> y[((n H + oy) W + ox) * ldy + c], a channel slice of a wider NHWC buffer.
+ * ur_dlv3_tta_argmax: nmaps (1..3) classifier maps q_k fp32 [N,hq_k,wq_k,C], 1 <= C <= 255 (unused maps NULL, sizes ignored) ->
+ *   pred uint8 [N,H,W].  Per output pixel and class, map k is sampled in two stages, neither of which is stored: the
+ *   align_corners=True sample of L_k at (H, W) <- (hs_k, ws_k), whose four values are each the half-pixel sample of q_k at
+ *   (hs_k, ws_k) <- (hq_k, wq_k); both in fp32 as h0 * (w0 * x00 + w1 * x01) + h1 * (w0 * x10 + w1 * x11).  The samples are
+ *   averaged as ((a + b) + c) / nmaps and the best class kept - ties to the lowest index, NaN as the maximum (torch.argmax).
+ *   ac_* hold the align_corners=True tables of the maps one after the other: idx [nmaps][H] / [nmaps][W], wt [..][2]; hp_* the
+ *   half-pixel ones: idx [hs_0 + hs_1 + ..] / [ws_0 + ws_1 + ..], wt [..][2].  avg: NULL, or fp32 [N,H,W,C] that receives the
+ *   averaged logits (for tests).
+ * Size limits (64-bit arithmetic, before any HIP call; the launch rule of the classifier section):
+ *   ur_dlv3_conv2d_f32: those of ur_conv2d_f32_res - N*OH*OW below 2^31 - 128, N*H*W below 2^31, Cin*KH*KW and Cout at most 2^24,
+ *     64-bit offsets into x, y and res - and ldy >= Cout, dil >= 1, and H + 2 pad, W + 2 pad, dil (KH - 1) + 1 and
+ *     dil (KW - 1) + 1 each inside an int, the padded map no smaller than the dilated filter.
+ *   ur_dlv3_prep: N*3*H*W and N*3*OH*OW must be below 2^31.     ur_dlv3_broadcast_f32: N*P*C must be below 2^31 - 256, ldy >= C.
+ *   ur_dlv3_upsample_f32: N*h*w*C and N*H*W*C must be below 2^31 - 256, ldy >= C.
+ *   ur_dlv3_tta_argmax: N*H*W (N*H*W*C with avg) must be below 2^31 - 256, N*hq*wq*C of every map below 2^31; hs, ws >= 1.
+ *   Runs at these limits on 2-4 GiB tensors are not part of tests/scoring_large_cases.py yet. */
+int ur_dlv3_conv2d_f32(const float* x, const float* w, const float* bias, const float* res, float* y, int N, int H, int W, int Cin, int Cout,
+                       int KH, int KW, int stride, int pad, int dil, int ldy, int relu, ur_stream_t stream);
+int ur_dlv3_prep(const float* x, float* y, int N, int C, int H, int W, int OH, int OW, const int* idx_h, const float* wt_h, const int* idx_w,
+                 const float* wt_w, ur_stream_t stream);
+int ur_dlv3_broadcast_f32(const float* v, float* y, int N, int P, int C, int ldy, ur_stream_t stream);
+int ur_dlv3_upsample_f32(const float* x, float* y, int N, int h, int w, int C, int H, int W, int ldy, const int* idx_h, const float* wt_h,
+                         const int* idx_w, const float* wt_w, ur_stream_t stream);
+int ur_dlv3_tta_argmax(const float* q0, const float* q1, const float* q2, int nmaps, int N, int C, int hq0, int wq0, int hs0, int ws0, int hq1,
+                       int wq1, int hs1, int ws1, int hq2, int wq2, int hs2, int ws2, int H, int W, const int* ac_idx_h,
+                       const float* ac_wt_h, const int* ac_idx_w, const float* ac_wt_w, const int* hp_idx_h, const float* hp_wt_h,
+                       const int* hp_idx_w, const float* hp_wt_w, unsigned char* pred, float* avg, ur_stream_t stream);
+
 /* ---- colour correction of a restored image (between the decoder's conv_out and the egress kernels) ----------------------
  * c fp32 NHWC [N,H,W,ld_c]: the restored image; src 16-bit NHWC [src_n,H,W,ld_s]: the image the encoder saw, image n is corrected
  * against source n % src_n (a task-major K*B batch against B sources); out fp32 NHWC [N,H,W,ld_c], not c.  Channels 0..2 are RGB;

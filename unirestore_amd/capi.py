@@ -139,6 +139,11 @@ SIGNATURES = {
     "ur_seg_tta_argmax": (_I, [_P, _P, _P] + [_I] * 11 + [_P, _P, _P, _P, _P, _P, _P]),
     "ur_seg_confusion_ws_bytes": (_LL, [_LL, _I]),
     "ur_seg_confusion": (_I, [_P, _P, _I, _LL, _I, _I, _P, _LL, _P, _P]),
+    "ur_dlv3_conv2d_f32": (_I, [_P, _P, _P, _P, _P] + [_I] * 12 + [_P]),
+    "ur_dlv3_prep": (_I, [_P, _P] + [_I] * 6 + [_P, _P, _P, _P, _P]),
+    "ur_dlv3_broadcast_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "ur_dlv3_upsample_f32": (_I, [_P, _P] + [_I] * 7 + [_P, _P, _P, _P, _P]),
+    "ur_dlv3_tta_argmax": (_I, [_P, _P, _P] + [_I] * 17 + [_P] * 8 + [_P, _P, _P]),
     "ur_color_fix_wavelet": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "ur_color_fix_adain": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "ur_color_fix_adain_ws_bytes": (_SZ, [_I, _I, _I]),

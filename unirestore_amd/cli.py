@@ -13,7 +13,8 @@ validation loop.  One process per GPU: under `torch.distributed.run` the global 
 weights are broadcast from rank 0 and the restored shards all-gathered over RCCL.  There is no CPU path: `accelerator: cpu`
 is an error, not a fallback.  Prints one JSON line on rank 0.  `validate --lpips` adds LPIPS, `validate --tasks ir,cls --classify
 NAME=ARCH:WEIGHTS.pth` the top-1 accuracy of a user-supplied ResNet on the `cls` output (unirestore_amd.classify), `validate --tasks
-ir,seg --segment NAME=ARCH:WEIGHTS.pth` the mIoU of a user-supplied RefineNet-LW on the `seg` output (unirestore_amd.segment), `validate --niqe PARAMS` the no-reference NIQE score of the restored images and of the
+ir,seg --segment NAME=ARCH:WEIGHTS.pth` the mIoU of a user-supplied RefineNet-LW on the `seg` output (unirestore_amd.segment) and
+`--deeplab NAME=ARCH:WEIGHTS.pth` that of a user-supplied DeepLabV3+ (unirestore_amd.deeplab), `validate --niqe PARAMS` the no-reference NIQE score of the restored images and of the
 inputs against a user-supplied pristine model (unirestore_amd.niqe); all opt-in.
 """
 import argparse
@@ -270,16 +271,30 @@ def check_segment_arg(segment):
     return _check_scorer_arg("--segment", segment, ARCHS, "a RefineNet-LW state dict")
 
 
-def check_segment_run(segment, tasks, r: dict):
+def check_segment_run(segment, tasks, r: dict, flag="--segment"):
     """What a segmenter run needs besides its weights, checked before the model is built: `seg` among the tasks (it is not added
-    silently, and `ir` stays required for PSNR) and a dataset that yields label maps.  r = resolve(cfg)."""
+    silently, and `ir` stays required for PSNR) and a dataset that yields label maps.  r = resolve(cfg).  flag: the option the
+    errors name (--deeplab has the same needs)."""
     if tasks is None or "seg" not in tasks:
-        raise ValueError(f"--segment scores the 'seg' output: pass --tasks with 'seg' in it, e.g. ir,seg (got "
+        raise ValueError(f"{flag} scores the 'seg' output: pass --tasks with 'seg' in it, e.g. ir,seg (got "
                          f"{'none' if tasks is None else ','.join(tasks)}; it is not added silently)")
     cls_name = r["data_class"].rsplit(".", 1)[1]
     if cls_name not in LABELLED_DATA or r["data_args"].get("labels") != "map":
-        raise ValueError(f"--segment needs label maps, and data.{cls_name} yields none as configured: use an `lq hq label.png` list with "
+        raise ValueError(f"{flag} needs label maps, and data.{cls_name} yields none as configured: use an `lq hq label.png` list with "
                          f"one of {list(LABELLED_DATA)} and set `labels: map` in data.init_args")
+
+
+def check_deeplab_arg(deeplab, segment=None):
+    """--deeplab NAME=ARCH:WEIGHTS.pth[,NAME=ARCH:OTHER.pth] (or a dict NAME -> (ARCH, path) | a loaded deeplab.DeepLabWeights)
+    -> {name: (arch, path) | DeepLabWeights}.  ValueError for a malformed item, an unknown arch, a missing file, a name given
+    twice or a name that `segment` (the checked --segment argument) already uses: both write val_lq/NAME.  ARCH is one of
+    deeplab.ARCHS (DeepLabV3+ on ResNet-50 / 101, output stride 16); the weights are the user's."""
+    from .deeplab import ARCHS
+    out = _check_scorer_arg("--deeplab", deeplab, ARCHS, "a DeepLabV3+ checkpoint")
+    both = sorted(set(out) & set(segment or {}))
+    if both:
+        raise ValueError(f"--deeplab: the name {both[0]!r} is used by --segment too; every segmenter needs a name of its own")
+    return out
 
 
 def check_crop_arg(crop):
@@ -295,7 +310,7 @@ def check_crop_arg(crop):
 
 
 def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_16bit=False, metrics_device="cpu", tasks=None,
-             model=None, lpips=None, classify=None, segment=None, crop=None, niqe=None) -> dict:
+             model=None, lpips=None, classify=None, segment=None, crop=None, niqe=None, deeplab=None) -> dict:
     """tasks: a list of task names - every batch is restored once and decoded for each of them (DiffUIE.forward_tasks).  PSNR / SSIM
     come from the "ir" output, so the list must hold "ir"; images_per_s counts input images.  model: a ready DiffUIE to use instead
     of building the config's.  With data.CorruptedImageFiles (and data.DistortedImageFiles: "snow/3") the result also holds by_corruption ("fog/3" -> psnr, ssim, images)
@@ -311,7 +326,9 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
     against the data's label maps (tasks must hold "seg", the data must be built with labels: map): the result and every
     by_corruption entry gain, per NAME, the mIoU (the reference's MulticlassJaccardIndex(19, ignore_index=255)) and NAME_acc (pixel
     accuracy) of the restored images (val_lq/NAME; by_corruption: NAME) and of the unrestored inputs (val_input/NAME;
-    by_corruption: input/NAME).  crop: (H, W) or "H,W", the centre crop's size instead of 512 x 512.
+    by_corruption: input/NAME).  deeplab: the same form with deeplab.ARCHS and deeplab.DeepLabWeights - the reference's other
+    segmenter, DeepLabV3+, scored under the same keys (a name may be used by only one of the two).
+    crop: (H, W) or "H,W", the centre crop's size instead of 512 x 512.
     niqe: a file of NIQE model parameters (.pt / .pth / .npz / .mat with mu_prisparam and cov_prisparam; the user's, none ship with
     the project) or a loaded niqe.NiqeParams - the no-reference NIQE score (fp64 on the GPU) of the restored images (val_lq/niqe;
     by_corruption: niqe) and of the unrestored inputs (val_input/niqe; by_corruption: input/niqe), each the mean over the images
@@ -325,6 +342,8 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
         classify = check_classify_arg(classify)           # before the model is built, like everything check_classify_run checks
     if segment is not None:
         segment = check_segment_arg(segment)
+    if deeplab is not None:
+        deeplab = check_deeplab_arg(deeplab, segment)
     crop_args = {} if crop is None else dict(crop=check_crop_arg(crop))
     r = resolve(cfg, allow_16bit=allow_16bit)
     if tasks is not None:
@@ -336,6 +355,9 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
         check_classify_run(classify, tasks, r)
     if segment is not None:
         check_segment_run(segment, tasks, r)
+    if deeplab is not None:
+        check_segment_run(deeplab, tasks, r, flag="--deeplab")
+        segment = {**(segment or {}), **deeplab}          # from here on one dict of segmenters: the evaluator tells them apart
     niqe_args = {}
     if niqe is not None:
         check_niqe_run(crop_args.get("crop"), r)
@@ -789,6 +811,10 @@ def main(argv=None):
                     help="validate: also report RefineNet-LW mIoU and pixel accuracy of the 'seg' output (fp32, on the GPU) against the "
                          "data's label maps; ARCH is rflw50, rflw101 or rflw152, WEIGHTS a user-supplied state dict; needs --tasks with "
                          "seg and a dataset built with labels: map")
+    ap.add_argument("--deeplab", default=None, metavar="NAME=ARCH:WEIGHTS.pth[,...]",
+                    help="validate: also report DeepLabV3+ (output stride 16) mIoU and pixel accuracy of the 'seg' output (fp32, on the "
+                         "GPU) against the data's label maps; ARCH is dlv3pr50 or dlv3pr101, WEIGHTS a user-supplied checkpoint; needs "
+                         "--tasks with seg and a dataset built with labels: map; a NAME may not be one of --segment's")
     ap.add_argument("--crop", default=None, metavar="H,W",
                     help="validate: the evaluator's centre crop (default 512,512; the reference's seg evaluator uses 960,1664)")
     ap.add_argument("--niqe", default=None, metavar="PARAMS",
@@ -825,6 +851,8 @@ def main(argv=None):
         ap.error("--classify belongs to validate")
     if a.segment is not None and a.command != "validate":
         ap.error("--segment belongs to validate")
+    if a.deeplab is not None and a.command != "validate":
+        ap.error("--deeplab belongs to validate")
     if a.crop is not None and a.command != "validate":
         ap.error("--crop belongs to validate")
     if a.niqe is not None and a.command != "validate":
@@ -865,7 +893,12 @@ def main(argv=None):
     try:
         if a.segment is not None:
             a.segment = check_segment_arg(a.segment)
+        if a.deeplab is not None:
+            a.deeplab = check_deeplab_arg(a.deeplab, a.segment)
+        if a.segment is not None:
             check_segment_run(a.segment, tasks, resolve(cfg, allow_16bit=a.allow_16bit))
+        if a.deeplab is not None:
+            check_segment_run(a.deeplab, tasks, resolve(cfg, allow_16bit=a.allow_16bit), flag="--deeplab")
         if a.crop is not None:
             a.crop = check_crop_arg(a.crop)
         if a.niqe is not None:
@@ -884,7 +917,7 @@ def main(argv=None):
             print(json.dumps(res))
         return 0
     res = validate(cfg, hf_root=a.hf_root, max_batches=a.max_batches, allow_16bit=a.allow_16bit, metrics_device=a.metrics_device,
-                   tasks=tasks, lpips=a.lpips, classify=a.classify, segment=a.segment, crop=a.crop, niqe=a.niqe)
+                   tasks=tasks, lpips=a.lpips, classify=a.classify, segment=a.segment, crop=a.crop, niqe=a.niqe, deeplab=a.deeplab)
     if res is not None:
         print(json.dumps(res))
     return 0

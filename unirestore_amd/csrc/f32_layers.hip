@@ -1,9 +1,9 @@
-// The fp32 NHWC layers of the scoring networks (LPIPS's AlexNet, the classifier's ResNet, the segmenter's RefineNet-LW) for gfx950,
-// exact fp32: an implicit-GEMM convolution on the fp32-input MFMA (v_mfma_f32_32x32x2_f32: k-ordered fp32 fma chains, bit for
-// bit) with bias, residual and ReLU in its epilogue, the three max-pools, the global average pool, the bilinear
+// The fp32 NHWC layers of the scoring networks (LPIPS's AlexNet, the classifier's ResNet, the segmenters' RefineNet-LW and
+// DeepLabV3+) for gfx950, exact fp32: an implicit-GEMM convolution on the fp32-input MFMA (v_mfma_f32_32x32x2_f32: k-ordered fp32
+// fma chains, bit for bit) with a dilation, bias, residual and ReLU in its epilogue and an output row stride, the three max-pools, the global average pool, the bilinear
 // align_corners=True up-sample and a + b.  No atomics, no split-K; every sum runs in a fixed order, so the same inputs give the
 // same bits on every run, eagerly and under graph replay, and an image's results do not depend on its place in the batch.
-// What belongs to one metric alone (its preprocess, its distance or counts) is in lpips.hip, classify.hip and segment.hip.
+// What belongs to one metric alone (its preprocess, its distance or counts) is in lpips.hip, classify.hip, segment.hip and deeplab.hip.
 #include "common.h"
 #include "f32_layers.h"
 
@@ -33,13 +33,15 @@ struct ConvArgs {
   const float* w;
   const float* bias;
   const float* res;      // [M][Cout] added after the bias, or null (ur_conv2d_f32: always null)
-  float* y;
-  int H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, K, nk, ldw, relu, M;
+  float* y;              // row m starts at y + m * ldy: ldy > Cout writes a channel slice of a wider NHWC buffer
+  int H, W, Cin, Cout, KH, KW, stride, pad, dil, OH, OW, K, nk, ldw, ldy, relu, M;
 };
 
 // VEC = 4: Cin % 4 == 0 and x 16-byte aligned - one 16-byte load covers four consecutive k (channels of one filter tap);
 // VEC = 1: any Cin (conv1's 3): one k per thread and tile, eight rows.
-template <int VEC>
+// DIL: the taps are p.dil apart; false (dil = 1) keeps the two multiplies per tile out of the undilated networks' gather, which
+// measured 1.4 % on the classifier and the RefineNet-LW segmenter with the multiply in it.
+template <int VEC, bool DIL>
 __global__ __launch_bounds__(256) void conv2d_f32_kernel(ConvArgs p) {
   __shared__ float As[2][CV_BK][CV_LDA];
   __shared__ __attribute__((aligned(16))) float Bs[2][CV_BK][CV_LDB];
@@ -77,7 +79,7 @@ __global__ __launch_bounds__(256) void conv2d_f32_kernel(ConvArgs p) {
     const bool k_ok = k < p.K;
 #pragma unroll
     for (int i = 0; i < NR; ++i) {
-      const int ih = ih0[i] + kh, iw = iw0[i] + kw;
+      const int ih = ih0[i] + (DIL ? kh * p.dil : kh), iw = iw0[i] + (DIL ? kw * p.dil : kw);
       const bool ok = k_ok && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
       const float* src = p.x + base[i] + ((long long)ih * p.W + iw) * p.Cin + c;
       if constexpr (VEC == 4) {
@@ -143,7 +145,7 @@ __global__ __launch_bounds__(256) void conv2d_f32_kernel(ConvArgs p) {
       if (m < p.M) {
         float v = (sum[j][r] + acc[j][r]) + bv;
         if (p.res) v += p.res[(long long)m * p.Cout + n];
-        p.y[(long long)m * p.Cout + n] = p.relu ? fmaxf(v, 0.f) : v;
+        p.y[(long long)m * p.ldy + n] = p.relu ? fmaxf(v, 0.f) : v;
       }
     }
   }
@@ -287,6 +289,54 @@ __global__ __launch_bounds__(256) void add_f32_kernel(const float* __restrict__ 
   }
 }
 
+// ------------------------------------------------------------------------------------------ the convolution's one launcher
+// `who` names the export in a refusal, `launch_name` in a launch error.  dil = 1 and ldy = Cout is the dense convolution.
+#define CV_REQUIRE(cond, msg)                                                      \
+  do {                                                                             \
+    if (!(cond)) return ur::fail(UR_E_INVALID, std::string(who) + ": " + (msg));  \
+  } while (0)
+
+int conv2d_f32_launch(const char* who, const char* launch_name, const float* x, const float* w, const float* bias, const float* res, float* y,
+                      int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int dil, int ldy, int relu,
+                      ur_stream_t stream) {
+  CV_REQUIRE(x && w && bias && y, "null pointer");
+  CV_REQUIRE(N >= 1 && H >= 1 && W >= 1, "N, H and W must be >= 1");
+  CV_REQUIRE(Cin >= 1 && Cout >= 1 && KH >= 1 && KW >= 1, "Cin, Cout, KH and KW must be >= 1");
+  CV_REQUIRE((long long)Cin * KH * KW <= (1 << 24) && Cout <= (1 << 24), "filter too large");
+  CV_REQUIRE(stride >= 1 && pad >= 0, "stride must be >= 1 and pad >= 0");
+  CV_REQUIRE(dil >= 1 && ldy >= Cout, "dil must be >= 1 and ldy >= Cout");
+  const long long PH = (long long)H + 2ll * pad, PW = (long long)W + 2ll * pad;            // the padded map
+  const long long EH = (long long)dil * (KH - 1) + 1, EW = (long long)dil * (KW - 1) + 1;  // the dilated filter's extent
+  CV_REQUIRE(PH <= INT_MAX && PW <= INT_MAX && EH <= INT_MAX && EW <= INT_MAX,
+             "H + 2 pad, W + 2 pad, dil * (KH - 1) + 1 and dil * (KW - 1) + 1 must fit an int");
+  CV_REQUIRE(PH >= EH && PW >= EW, "the padded map is smaller than the filter");
+  CV_REQUIRE(((uintptr_t)w & 15) == 0, "w must be 16-byte aligned");
+  CV_REQUIRE(res != y || !res, "res and y must not be the same buffer");
+  const int OH = conv_out(H, (int)EH, stride, pad), OW = conv_out(W, (int)EW, stride, pad);
+  const long long M = (long long)N * OH * OW;
+  CV_REQUIRE(M <= INT_MAX - CV_BM && (long long)N * H * W <= INT_MAX, "too many pixels: N*OH*OW must be below 2^31 - 128 and N*H*W below 2^31");
+  ConvArgs p;
+  p.x = x; p.w = w; p.bias = bias; p.res = res; p.y = y;
+  p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.dil = dil; p.OH = OH; p.OW = OW;
+  p.K = Cin * KH * KW;
+  p.nk = (p.K + CV_BK - 1) / CV_BK;
+  p.ldw = (Cout + CV_BN - 1) / CV_BN * CV_BN;
+  p.ldy = ldy;
+  p.relu = relu != 0;
+  p.M = (int)M;
+  const dim3 grid((unsigned)((M + CV_BM - 1) / CV_BM), (unsigned)(p.ldw / CV_BN));
+  CV_REQUIRE(grid.y <= 65535u, "Cout too large");
+  hipStream_t s = (hipStream_t)stream;
+  ur::ProfScope prof("conv2d_f32", 2.0 * (double)M * Cout * p.K, 4.0 * ((double)N * H * W * Cin + (double)M * Cout * (res ? 2 : 1)), s);
+  const bool vec = Cin % 4 == 0 && ((uintptr_t)x & 15) == 0;
+  if (vec && dil == 1) hipLaunchKernelGGL((conv2d_f32_kernel<4, false>), grid, dim3(256), 0, s, p);
+  else if (vec) hipLaunchKernelGGL((conv2d_f32_kernel<4, true>), grid, dim3(256), 0, s, p);
+  else if (dil == 1) hipLaunchKernelGGL((conv2d_f32_kernel<1, false>), grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((conv2d_f32_kernel<1, true>), grid, dim3(256), 0, s, p);
+  return ur::check_launch(launch_name);
+}
+#undef CV_REQUIRE
+
 }  // namespace
 
 extern "C" {
@@ -302,34 +352,13 @@ int ur_conv2d_f32_wpack_dims(int Cin, int Cout, int KH, int KW, int* kpad, int* 
 
 int ur_conv2d_f32_res(const float* x, const float* w, const float* bias, const float* res, float* y, int N, int H, int W, int Cin, int Cout,
                       int KH, int KW, int stride, int pad, int relu, ur_stream_t stream) {
-  UR_REQUIRE(x && w && bias && y, "null pointer");
-  UR_REQUIRE(N >= 1 && H >= 1 && W >= 1, "N, H and W must be >= 1");
-  UR_REQUIRE(Cin >= 1 && Cout >= 1 && KH >= 1 && KW >= 1, "Cin, Cout, KH and KW must be >= 1");
-  UR_REQUIRE((long long)Cin * KH * KW <= (1 << 24) && Cout <= (1 << 24), "filter too large");
-  UR_REQUIRE(stride >= 1 && pad >= 0, "stride must be >= 1 and pad >= 0");
-  UR_REQUIRE(H + 2 * pad >= KH && W + 2 * pad >= KW, "the padded map is smaller than the filter");
-  UR_REQUIRE(((uintptr_t)w & 15) == 0, "w must be 16-byte aligned");
-  UR_REQUIRE(res != y || !res, "res and y must not be the same buffer");
-  const int OH = conv_out(H, KH, stride, pad), OW = conv_out(W, KW, stride, pad);
-  const long long M = (long long)N * OH * OW;
-  UR_REQUIRE(M <= INT_MAX - CV_BM && (long long)N * H * W <= INT_MAX, "too many pixels: N*OH*OW must be below 2^31 - 128 and N*H*W below 2^31");
-  ConvArgs p;
-  p.x = x; p.w = w; p.bias = bias; p.res = res; p.y = y;
-  p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.OH = OH; p.OW = OW;
-  p.K = Cin * KH * KW;
-  p.nk = (p.K + CV_BK - 1) / CV_BK;
-  p.ldw = (Cout + CV_BN - 1) / CV_BN * CV_BN;
-  p.relu = relu != 0;
-  p.M = (int)M;
-  const dim3 grid((unsigned)((M + CV_BM - 1) / CV_BM), (unsigned)(p.ldw / CV_BN));
-  UR_REQUIRE(grid.y <= 65535u, "Cout too large");
-  hipStream_t s = (hipStream_t)stream;
-  ur::ProfScope prof("conv2d_f32", 2.0 * (double)M * Cout * p.K, 4.0 * ((double)N * H * W * Cin + (double)M * Cout * (res ? 2 : 1)), s);
-  if (Cin % 4 == 0 && ((uintptr_t)x & 15) == 0)
-    hipLaunchKernelGGL(conv2d_f32_kernel<4>, grid, dim3(256), 0, s, p);
-  else
-    hipLaunchKernelGGL(conv2d_f32_kernel<1>, grid, dim3(256), 0, s, p);
-  return ur::check_launch("ur_conv2d_f32");
+  return conv2d_f32_launch("ur_conv2d_f32_res", "ur_conv2d_f32", x, w, bias, res, y, N, H, W, Cin, Cout, KH, KW, stride, pad, 1, Cout, relu, stream);
+}
+
+int ur_dlv3_conv2d_f32(const float* x, const float* w, const float* bias, const float* res, float* y, int N, int H, int W, int Cin, int Cout,
+                       int KH, int KW, int stride, int pad, int dil, int ldy, int relu, ur_stream_t stream) {
+  return conv2d_f32_launch("ur_dlv3_conv2d_f32", "ur_dlv3_conv2d_f32", x, w, bias, res, y, N, H, W, Cin, Cout, KH, KW, stride, pad, dil, ldy, relu,
+                           stream);
 }
 
 int ur_conv2d_f32(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int KH, int KW,

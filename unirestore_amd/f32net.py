@@ -40,30 +40,46 @@ def pack_conv_weight(w: torch.Tensor) -> torch.Tensor:
 
 
 class PackedConvF32:
-    """One fp32 convolution ready for ur_conv2d_f32_res: the repacked filter and the bias on the device, and its geometry."""
+    """One fp32 convolution ready for ur_conv2d_f32_res (ur_dlv3_conv2d_f32 when dilated): the repacked filter and the bias on the
+    device, and its geometry."""
 
-    def __init__(self, weight: torch.Tensor, bias: torch.Tensor, stride: int, pad: int, dev):
+    def __init__(self, weight: torch.Tensor, bias: torch.Tensor, stride: int, pad: int, dev, dilation: int = 1):
         self.cout, self.cin, self.kh, self.kw = weight.shape
-        self.stride, self.pad = stride, pad
+        self.stride, self.pad, self.dilation = stride, pad, dilation
         self.w = pack_conv_weight(weight).to(dev)
         self.bias = bias.float().contiguous().to(dev)
 
 
 # ---- launch wrappers (each one kernel family; fp32 NHWC device tensors) -------------------------------------------------------
 
-def conv2d_f32(x: torch.Tensor, pc: PackedConvF32, res: torch.Tensor = None, relu: bool = True) -> torch.Tensor:
-    """act(conv(x) + bias + res) on NHWC fp32; res None: no residual."""
+def conv2d_f32(x: torch.Tensor, pc: PackedConvF32, res: torch.Tensor = None, relu: bool = True, out=None) -> torch.Tensor:
+    """act(conv(x) + bias + res) on NHWC fp32; res None: no residual.  out = (buffer, channel_offset): the result goes to channels
+    channel_offset .. channel_offset + Cout - 1 of `buffer`, a contiguous fp32 [N,OH,OW,C >= offset + Cout] tensor whose other
+    channels stay as they are, and `buffer` is returned.  An undilated convolution without `out` is ur_conv2d_f32_res; a dilated
+    one, or one with `out`, is ur_dlv3_conv2d_f32 - the same kernel."""
     n, h, w, cin = x.shape
     if cin != pc.cin:
         raise ValueError(f"conv2d_f32: input has {cin} channels, the filter {pc.cin}")
-    oh, ow = (h + 2 * pc.pad - pc.kh) // pc.stride + 1, (w + 2 * pc.pad - pc.kw) // pc.stride + 1
-    y = torch.empty(n, max(oh, 0), max(ow, 0), pc.cout, dtype=torch.float32, device=x.device)
-    if res is not None and (res.shape != y.shape or res.dtype != torch.float32 or not res.is_contiguous() or res.device != x.device):
-        raise ValueError(f"conv2d_f32: the residual must be a contiguous fp32 {tuple(y.shape)} tensor on {x.device}, got "
+    dil = pc.dilation
+    oh, ow = (h + 2 * pc.pad - dil * (pc.kh - 1) - 1) // pc.stride + 1, (w + 2 * pc.pad - dil * (pc.kw - 1) - 1) // pc.stride + 1
+    shape = (n, max(oh, 0), max(ow, 0), pc.cout)
+    if res is not None and (tuple(res.shape) != shape or res.dtype != torch.float32 or not res.is_contiguous() or res.device != x.device):
+        raise ValueError(f"conv2d_f32: the residual must be a contiguous fp32 {shape} tensor on {x.device}, got "
                          f"{res.dtype} {tuple(res.shape)} on {res.device}")
-    check(lib.ur_conv2d_f32_res(x.data_ptr(), pc.w.data_ptr(), pc.bias.data_ptr(), None if res is None else res.data_ptr(), y.data_ptr(),
-                                n, h, w, cin, pc.cout, pc.kh, pc.kw, pc.stride, pc.pad, int(relu), stream()))
-    return y
+    if out is None and dil == 1:
+        y = torch.empty(shape, dtype=torch.float32, device=x.device)
+        check(lib.ur_conv2d_f32_res(x.data_ptr(), pc.w.data_ptr(), pc.bias.data_ptr(), None if res is None else res.data_ptr(), y.data_ptr(),
+                                    n, h, w, cin, pc.cout, pc.kh, pc.kw, pc.stride, pc.pad, int(relu), stream()))
+        return y
+    buf, off = (torch.empty(shape, dtype=torch.float32, device=x.device), 0) if out is None else out
+    if (buf.ndim != 4 or tuple(buf.shape[:3]) != shape[:3] or buf.dtype != torch.float32 or not buf.is_contiguous() or buf.device != x.device
+            or not 0 <= off <= buf.shape[3] - pc.cout):
+        raise ValueError(f"conv2d_f32: out must be a contiguous fp32 [{n}, {shape[1]}, {shape[2]}, C] tensor on {x.device} with "
+                         f"offset + {pc.cout} <= C, got {buf.dtype} {tuple(buf.shape)} on {buf.device}, offset {off}")
+    check(lib.ur_dlv3_conv2d_f32(x.data_ptr(), pc.w.data_ptr(), pc.bias.data_ptr(), None if res is None else res.data_ptr(),
+                                 buf.data_ptr() + 4 * off, n, h, w, cin, pc.cout, pc.kh, pc.kw, pc.stride, pc.pad, dil, buf.shape[3], int(relu),
+                                 stream()))
+    return buf
 
 
 def maxpool2d_f32(x: torch.Tensor) -> torch.Tensor:
@@ -117,6 +133,30 @@ def ac_table(n_in: int, n_out: int):
         idx.append(q)
         wt.append((1.0 - frac, frac))
     return torch.tensor(idx, dtype=torch.int32), torch.tensor(wt, dtype=torch.float64)
+
+
+def hp_table(n_in: int, n_out: int):
+    """One axis of `interpolate(mode="bilinear", align_corners=False)` (half-pixel centres), in ac_table's layout: output o has the
+    source coordinate max(0, (o + 0.5) * n_in / n_out - 0.5) = max(0, (2 o + 1) n_in - n_out) / (2 n_out), split into index and
+    fraction in integers, so the fraction is the correctly rounded fp64 value.  idx[o] + 1 may be n_in: the kernels clamp it to the
+    axis, as torch does (both taps then read the last source)."""
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"hp_table: sizes must be >= 1, got {n_in} -> {n_out}")
+    idx, wt = [], []
+    for o in range(n_out):
+        q, rem = divmod(max((2 * o + 1) * n_in - n_out, 0), 2 * n_out)      # q <= n_in - 1: the coordinate is below n_in - 1/2
+        frac = rem / (2 * n_out) if rem else 0.0
+        idx.append(q)
+        wt.append((1.0 - frac, frac))
+    return torch.tensor(idx, dtype=torch.int32), torch.tensor(wt, dtype=torch.float64)
+
+
+@functools.lru_cache(maxsize=None)                       # never evicted: a captured graph keeps reading the tables it was captured with
+def _device_tables_hp(pairs: tuple, dev_index: int):
+    """The half-pixel tables of several (n_in, n_out) axes, one after the other: (idx [sum n_out], wt [sum n_out, 2] fp32)."""
+    tabs = [hp_table(n_in, n_out) for n_in, n_out in pairs]
+    dev = torch.device("cuda", dev_index)
+    return torch.cat([t[0] for t in tabs]).to(dev), torch.cat([t[1] for t in tabs]).float().contiguous().to(dev)
 
 
 @functools.lru_cache(maxsize=None)                       # never evicted: a captured graph keeps reading the tables it was captured with

@@ -1179,6 +1179,27 @@ def segment(images: torch.Tensor, weights, size=None, scales=(1, 0.8, 0.6)) -> t
     return _segment.segment(images, weights, size, scales)
 
 
+def deeplab(images: torch.Tensor, weights, size=None, scales=(1, 0.8, 0.6)) -> torch.Tensor:
+    """`segment` with the reference's other segmenter, DeepLabV3+ on ResNet-50 / 101 at output stride 16: predicted classes uint8
+    [N,H,W] (on the device) of fp32 NCHW images in [0,1].  For each scale a bilinear align_corners=True resize to floor(size *
+    scale), the ImageNet Normalize and the network; then one kernel takes every scale's classifier map through the model's own
+    half-pixel resize to that scale's input and the evaluator's align_corners=True resize to `size` (default: the images' own H,
+    W), averages and takes the argmax (ties to the lowest class).  weights: what deeplab.load_weights / deeplab.random_weights
+    return.  ValueError when the smallest scale's input falls below 16 px on a side.  The same guarantees and the same first-call
+    table upload as `segment`: run a shape once eagerly before capturing it in a graph."""
+    from . import deeplab as _deeplab
+    _check_images("deeplab", "images", images)
+    n, c, h, w = images.shape
+    if n < 1 or c != 3 or h < 1 or w < 1:
+        raise ValueError(f"deeplab: needs [N>=1, 3, H>=1, W>=1] images, got {tuple(images.shape)}")
+    _check_scorer("deeplab", "weights", weights, _deeplab.DeepLabWeights, "deeplab.load_weights / deeplab.random_weights")
+    if size is not None and not (isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(v, int) and v >= 1 for v in size)):
+        raise ValueError(f"deeplab: size must be (H, W) with H, W >= 1, got {size!r}")
+    if not (isinstance(scales, (tuple, list)) and 1 <= len(scales) <= 3 and all(isinstance(v, (int, float)) and 0 < v <= 8 for v in scales)):
+        raise ValueError(f"deeplab: scales must be 1 to 3 numbers in (0, 8], got {scales!r}")
+    return _deeplab.segment(images, weights, size, scales)
+
+
 def checked_targets(target: torch.Tensor, classes: int = 19, ignore_index: int = 255) -> torch.Tensor:
     """A uint8 / int64 target tensor on the current device, after checking that every value lies in [0, classes) or is
     ignore_index (ValueError otherwise; one flag is read back: one host sync).  What `confusion` does to its targets; a caller

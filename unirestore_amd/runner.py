@@ -139,11 +139,15 @@ class LitUniFIE:
         # Segmenter scoring of the "seg" output (RefineNet-LW mIoU, exact fp32 HIP kernels) is off unless segmenters are given:
         # {name: (arch, state-dict path) | segment.SegmenterWeights}.  Per name the totals hold the confusion matrix conf[target][pred]
         # as an int64 [classes, classes] device tensor for the restored images ("seg/<name>") and for the unrestored inputs
-        # ("seg_input/<name>"); replaced, never changed in place, like the classifiers' counts.
+        # ("seg_input/<name>"); replaced, never changed in place, like the classifiers' counts.  A deeplab.DeepLabWeights, or an
+        # (arch, path) whose arch is one of deeplab.ARCHS, is the reference's other segmenter (DeepLabV3+) under the same keys.
         self.segmenters = {}
         for name, spec in (segmenters or {}).items():
-            from . import segment
-            w = spec if isinstance(spec, segment.SegmenterWeights) else segment.load_weights(*spec)
+            from . import deeplab, segment
+            if isinstance(spec, (segment.SegmenterWeights, deeplab.DeepLabWeights)):
+                w = spec
+            else:
+                w = deeplab.load_weights(*spec) if isinstance(spec[0], str) and spec[0] in deeplab.ARCHS else segment.load_weights(*spec)
             self.segmenters[name] = w
             for key in self.segmenter_keys(name):
                 self.totals[key] = torch.zeros(w.num_classes, w.num_classes, dtype=torch.int64, device=w.device)
@@ -316,16 +320,17 @@ class LitUniFIE:
         if label_maps is None or not torch.is_tensor(label_maps) or label_maps.ndim != 3:
             raise ValueError("the segmenters need the batch's label maps (gt is None or no [N,H,W] tensor): build the dataset with "
                              "labels: map on an `lq hq label.png` list")
-        from . import ops, segment
+        from . import deeplab, ops, segment
         if self.need_crop:
             inputs, label_maps = self._crop(inputs), self._crop(label_maps)
         if tuple(label_maps.shape) != (seg_preds.shape[0], *seg_preds.shape[2:]):
             raise ValueError(f"the label maps are {tuple(label_maps.shape)}, the seg output {tuple(seg_preds.shape)}")
         for name, w in self.segmenters.items():
-            # the targets are checked once per batch; ops.segment's own predictions always lie in [0, classes)
+            # the targets are checked once per batch; ops.segment's / ops.deeplab's own predictions always lie in [0, classes)
             target = ops.checked_targets(label_maps.to(device=w.device, dtype=torch.int64).contiguous(), w.num_classes)
+            predict = ops.deeplab if isinstance(w, deeplab.DeepLabWeights) else ops.segment
             for key, images in zip(self.segmenter_keys(name), (seg_preds, inputs)):
-                pred = ops.segment(images.to(device=w.device, dtype=torch.float32).contiguous(), w)
+                pred = predict(images.to(device=w.device, dtype=torch.float32).contiguous(), w)
                 self.totals[key] = self.totals[key] + segment.confusion(pred, target, w.num_classes)
 
     def update_niqe(self, preds: torch.Tensor, lq: torch.Tensor):
