@@ -1,4 +1,4 @@
-"""DeepLabV3+ scoring on the GPU (ops.deeplab, unirestore_amd/deeplab.py, csrc/deeplab.hip and the dilated, strided-output
+"""DeepLabV3+ scoring on the GPU (ops.deeplab, unirestore_amd/deeplab.py, csrc/segment.hip and the dilated, strided-output
 convolution of csrc/f32_layers.hip): every new launcher against the fp64 restatement element by element, whole networks on tiny
 maps, `ops.deeplab` end to end, batch-place independence, bit-reproducibility (eager and hipGraph replay), argument checks, and
 the caller path (LitUniFIE, cli.validate).  Every bound is 8 x fp32's own measured error (deeplab_reference.py: E32_* / *_TOL,

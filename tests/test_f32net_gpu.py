@@ -1,5 +1,5 @@
 """The fp32 NHWC layers on the GPU (unirestore_amd/f32net.py, csrc/f32_layers.hip): every launcher that LPIPS, the classifier and
-the segmenter share, against the fp64 restatement element by element.  The cases, restatements and bounds are those of the three
+the segmenters share, against the fp64 restatement element by element.  The cases, restatements and bounds are those of the three
 networks (lpips_reference.py, classify_reference.py, segment_reference.py: 8 x fp32's own measured error, kept honest by the
 test_*_cpu.py::test_tolerances_follow_the_measured_fp32_error tests); the max-pools and the sum are compared for equality."""
 import math
@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 import classify_reference as CR
+import deeplab_reference as DR
 import lpips_reference as LR
 import segment_reference as SR
 
@@ -171,6 +172,72 @@ def test_upsample_to_the_same_size_is_the_identity(c):
     from unirestore_amd import f32net
     x = torch.randn(2, 5, 7, c, generator=torch.Generator().manual_seed(c)).cuda()
     assert torch.equal(f32net.upsample_bilinear_ac_f32(x, (5, 7)), x)
+
+
+# One table-driven resize kernel behind two entry points: (N, C, h, w, H, W) of the two networks' UPSAMPLE_CASES, the channel
+# count of the buffer the slice is written into and the slice's first channel.
+SLICE_CASES = {
+    "float4": ((2, 48, 4, 5, 16, 20), 100, 48),
+    "scalar_c19": ((1, 19, 3, 4, 12, 16), 71, 48),
+    "scalar_c48_in_51_channels": ((1, 48, 3, 4, 12, 16), 51, 3),     # C % 4 == 0 but ldy % 4 != 0: float4 stores would be misaligned
+}
+SENTINEL = -12345.0
+
+
+@pytest.mark.parametrize("table", ["align_corners", "half_pixel"])
+@pytest.mark.parametrize("name", sorted(SLICE_CASES))
+def test_upsample_into_a_slice_is_the_dense_result_bit_for_bit(name, table):
+    """Dense (ldy = C: ur_upsample_bilinear_ac_f32 for the align_corners table, ur_dlv3_upsample_f32 for the half-pixel one) and
+    into a channel slice of a wider buffer (ur_dlv3_upsample_f32, either table): the same bits, and no other channel is touched."""
+    from unirestore_amd import capi, f32net
+    case, channels, off = SLICE_CASES[name]
+    assert case in DR.UPSAMPLE_CASES
+    n, c, h, w_, H, W = case
+    x = DR.nhwc(DR.upsample_case(case)).cuda()
+    if table == "align_corners":
+        dense = f32net.upsample_bilinear_ac_f32(x, (H, W))
+        tabs = f32net._device_tables((h,), H, x.device.index), f32net._device_tables((w_,), W, x.device.index)
+        want, tol = SR.resize_ac(DR.nchw(x.cpu()), (H, W)), SR.UPSAMPLE_TOL
+    else:
+        dense = f32net.upsample_bilinear_hp_f32(x, (H, W))
+        tabs = f32net._device_tables_hp(((h, H),), x.device.index), f32net._device_tables_hp(((w_, W),), x.device.index)
+        want, tol = DR.resize_hp(DR.nchw(x.cpu()), (H, W)), DR.UPSAMPLE_TOL
+    assert tuple(dense.shape) == (n, H, W, c)
+    err = float((DR.nchw(dense.cpu()).double() - want).abs().max() / x.abs().max())
+    print(f"{name} {table}: dense max |err| / max |x| {err:.2e} (bound {tol:.2e})")
+    assert err <= tol                                                # (not vacuous: the dense result is the resize)
+    buf = torch.full((n, H, W, channels), SENTINEL, device="cuda")
+    assert f32net._upsample_bilinear("test", x, (H, W), *tabs, (buf, off), capi.lib.ur_dlv3_upsample_f32) is buf
+    assert torch.equal(buf[..., off:off + c], dense)
+    rest = torch.cat([buf[..., :off], buf[..., off + c:]], dim=3)
+    assert rest.numel() == n * H * W * (channels - c) and bool((rest == SENTINEL).all())
+
+
+def test_both_preps_reach_one_resize():
+    """segment.prep and deeplab.prep are one kernel with two per-channel functors.  The stage in front of the functors is the
+    align_corners=True resize of the image, which `upsample_bilinear_ac_f32` computes from the same tables with the same `bilerp`:
+    each prep result is that resized image put through its network's arithmetic in fp32, bit for bit; and inverting each
+    functor in fp64 on the host recovers it within the side's own PREP_TOL carried to the image (/ 255, x std).  (The inverse
+    cannot be exact: both functors round twice.)  The per-network prep tests stay the authority on the values."""
+    from unirestore_amd import deeplab, f32net, segment
+    shape, s = (2, 3, 64, 96), 0.8
+    assert (shape, s) in SR.PREP_CASES and (shape, s) in DR.PREP_CASES
+    x = SR.images(shape, sum(shape))
+    size = (segment.scaled_size(shape[2], s), segment.scaled_size(shape[3], s))
+    resized = f32net.upsample_bilinear_ac_f32(SR.nhwc(x).cuda(), size).cpu()                  # NHWC, R, G, B
+    seg, dl = segment.prep(x.cuda(), size).cpu(), deeplab.prep(x.cuda(), size).cpu()
+    assert tuple(resized.shape) == tuple(seg.shape) == tuple(dl.shape) == (shape[0], *size, 3)
+    mean255, mean, std = (torch.tensor(v, dtype=torch.float32) for v in (SR.MEAN, DR.MEAN, DR.STD))
+    assert torch.equal(seg, (resized * 255.0 - mean255).flip(3))
+    assert torch.equal(dl, (resized - mean) / std)
+    from_seg = (seg.double().flip(3) + mean255.double()) / 255.0
+    from_dl = dl.double() * std.double() + mean.double()
+    for what, d in (("segment", (from_seg - resized.double()).abs()), ("deeplab", (from_dl - resized.double()).abs()),
+                    ("segment vs deeplab", (from_seg - from_dl).abs())):
+        e_seg, e_dl = float(d.max()) * 255.0, float((d / std.double()).max())
+        print(f"{what}: recovered image off by {float(d.max()):.2e}; as segment's output {e_seg:.2e} (bound {SR.PREP_TOL:.2e}), "
+              f"as deeplab's {e_dl:.2e} (bound {DR.PREP_TOL:.2e})")
+        assert e_seg <= SR.PREP_TOL and e_dl <= DR.PREP_TOL
 
 
 def test_add_f32_is_exact():

@@ -308,6 +308,35 @@ def test_crop_box_default_is_unchanged():
             runner.check_crop(bad)
 
 
+# ---- one segmenter path ---------------------------------------------------------------------------------------------------------
+
+def test_both_networks_share_one_path(monkeypatch):
+    import inspect
+    from unirestore_amd import build, deeplab, ops, runner, segment
+    assert not os.path.exists(os.path.join(ROOT, "unirestore_amd", "csrc", "deeplab.hip"))
+    sources = [unit[0] for unit in build.SOURCES]
+    assert "deeplab.hip" not in sources and "segment.hip" in sources and "f32_layers.hip" in sources
+    # one test-time augmentation under both module names, and both public ops end in it
+    assert deeplab.segment is segment.segment and deeplab.scaled_size is segment.scaled_size and deeplab.SCALES is segment.SCALES
+    calls = []
+    monkeypatch.setattr(ops, "_check_images", lambda *a: None)
+    monkeypatch.setattr(ops, "_check_scorer", lambda who, what, obj, cls, makers: calls.append((who, cls, makers)))
+    monkeypatch.setattr(segment, "segment", lambda images, weights, size, scales: calls.append((weights, size, tuple(scales))) or "pred")
+    x = torch.zeros(1, 3, 64, 64)
+    assert ops.segment(x, "w1") == "pred" and ops.deeplab(x, "w2", size=(5, 7), scales=(1,)) == "pred"
+    assert calls == [("segment", segment.SegmenterWeights, "segment.load_weights / segment.random_weights"), ("w1", None, (1, 0.8, 0.6)),
+                     ("deeplab", deeplab.DeepLabWeights, "deeplab.load_weights / deeplab.random_weights"), ("w2", (5, 7), (1,))]
+    for op, word in ((ops.segment, "segment: size"), (ops.deeplab, "deeplab: size")):
+        with pytest.raises(ValueError, match=word):
+            op(x, "w", size=(0, 4))
+    # the driver reads what differs from the weights object
+    for cls, name, min_hw in ((segment.SegmenterWeights, "segment", 32), (deeplab.DeepLabWeights, "deeplab", 16)):
+        assert (cls.name, cls.min_hw) == (name, min_hw) and all(callable(getattr(cls, m)) for m in ("prep", "logits", "tta_argmax"))
+    # the evaluator tells the networks apart only where it loads them
+    assert "isinstance(" not in inspect.getsource(runner.LitUniFIE.update_segmentation)
+    assert inspect.getsource(runner).count("DeepLabWeights)") == inspect.getsource(runner.LitUniFIE.__init__).count("DeepLabWeights)") == 1
+
+
 # ---- the yardstick's own constants ----------------------------------------------------------------------------------------------
 
 def test_tolerances_follow_the_measured_fp32_error():

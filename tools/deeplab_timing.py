@@ -1,5 +1,5 @@
 """Time the DeepLabV3+ scoring (`ops.deeplab`: three scales of Normalize + DeepLabV3+ in exact fp32 + the two-stage multi-scale
-argmax; csrc/deeplab.hip + csrc/f32_layers.hip) on cuda:0, per shape.  Seeded random weights (deeplab.random_weights: no trained
+argmax; csrc/segment.hip + csrc/f32_layers.hip) on cuda:0, per shape.  Seeded random weights (deeplab.random_weights: no trained
 weights are needed to time the kernels) and seeded 8-bit-quantised images.
 
   python tools/deeplab_timing.py [--arch dlv3pr50 --shapes 8x512x512,2x960x1664 --reps 10] [--out profiles/deeplab_timing.txt]

@@ -297,6 +297,17 @@ def check_deeplab_arg(deeplab, segment=None):
     return out
 
 
+def check_segmenters_arg(segment, deeplab):
+    """The checked --segment and --deeplab arguments (either may be None) as the one dict of segmenters the evaluator takes - it
+    tells the two networks apart - and the option that errors about the run name: (None, None) when neither is given."""
+    if segment is None and deeplab is None:
+        return None, None
+    flag = "--deeplab" if segment is None else "--segment"
+    segment = {} if segment is None else check_segment_arg(segment)
+    deeplab = {} if deeplab is None else check_deeplab_arg(deeplab, segment)
+    return {**segment, **deeplab}, flag
+
+
 def check_crop_arg(crop):
     """--crop H,W (or a pair of integers) -> (H, W): the evaluator's centre crop, 512,512 unless given (the reference's seg and
     multi-task evaluators use 960,1664)."""
@@ -340,10 +351,7 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
         lpips = check_lpips_arg(lpips)                    # before the model is built
     if classify is not None:
         classify = check_classify_arg(classify)           # before the model is built, like everything check_classify_run checks
-    if segment is not None:
-        segment = check_segment_arg(segment)
-    if deeplab is not None:
-        deeplab = check_deeplab_arg(deeplab, segment)
+    segment, seg_flag = check_segmenters_arg(segment, deeplab)      # from here on one dict of segmenters
     crop_args = {} if crop is None else dict(crop=check_crop_arg(crop))
     r = resolve(cfg, allow_16bit=allow_16bit)
     if tasks is not None:
@@ -354,10 +362,7 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
     if classify is not None:
         check_classify_run(classify, tasks, r)
     if segment is not None:
-        check_segment_run(segment, tasks, r)
-    if deeplab is not None:
-        check_segment_run(deeplab, tasks, r, flag="--deeplab")
-        segment = {**(segment or {}), **deeplab}          # from here on one dict of segmenters: the evaluator tells them apart
+        check_segment_run(segment, tasks, r, flag=seg_flag)
     niqe_args = {}
     if niqe is not None:
         check_niqe_run(crop_args.get("crop"), r)
@@ -847,16 +852,9 @@ def main(argv=None):
     ap.add_argument("--quality", default=None, metavar="10,25,s3", help="jpeg: qualities 1..100 and / or s1..s5 (the reference's severities)")
     ap.add_argument("--subsampling", default="4:2:0", help="jpeg: 4:2:0 (Pillow's and the reference's default) or 4:4:4")
     a = ap.parse_args(argv)
-    if a.classify is not None and a.command != "validate":
-        ap.error("--classify belongs to validate")
-    if a.segment is not None and a.command != "validate":
-        ap.error("--segment belongs to validate")
-    if a.deeplab is not None and a.command != "validate":
-        ap.error("--deeplab belongs to validate")
-    if a.crop is not None and a.command != "validate":
-        ap.error("--crop belongs to validate")
-    if a.niqe is not None and a.command != "validate":
-        ap.error("--niqe belongs to validate")
+    for flag in ("classify", "segment", "deeplab", "crop", "niqe"):
+        if getattr(a, flag) is not None and a.command != "validate":
+            ap.error(f"--{flag} belongs to validate")
     if a.command in FILE_COMMANDS:
         check, run, errors = FILE_COMMANDS[a.command]
         kw = dict(inp=a.input, output=a.output, batch=a.batch, resize=a.resize)
@@ -891,14 +889,9 @@ def main(argv=None):
         except ValueError as e:
             ap.error(str(e))
     try:
-        if a.segment is not None:
-            a.segment = check_segment_arg(a.segment)
-        if a.deeplab is not None:
-            a.deeplab = check_deeplab_arg(a.deeplab, a.segment)
-        if a.segment is not None:
-            check_segment_run(a.segment, tasks, resolve(cfg, allow_16bit=a.allow_16bit))
-        if a.deeplab is not None:
-            check_segment_run(a.deeplab, tasks, resolve(cfg, allow_16bit=a.allow_16bit), flag="--deeplab")
+        segmenters, seg_flag = check_segmenters_arg(a.segment, a.deeplab)
+        if segmenters is not None:
+            check_segment_run(segmenters, tasks, resolve(cfg, allow_16bit=a.allow_16bit), flag=seg_flag)
         if a.crop is not None:
             a.crop = check_crop_arg(a.crop)
         if a.niqe is not None:

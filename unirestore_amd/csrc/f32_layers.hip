@@ -1,9 +1,10 @@
 // The fp32 NHWC layers of the scoring networks (LPIPS's AlexNet, the classifier's ResNet, the segmenters' RefineNet-LW and
 // DeepLabV3+) for gfx950, exact fp32: an implicit-GEMM convolution on the fp32-input MFMA (v_mfma_f32_32x32x2_f32: k-ordered fp32
-// fma chains, bit for bit) with a dilation, bias, residual and ReLU in its epilogue and an output row stride, the three max-pools, the global average pool, the bilinear
-// align_corners=True up-sample and a + b.  No atomics, no split-K; every sum runs in a fixed order, so the same inputs give the
+// fma chains, bit for bit) with a dilation, bias, residual and ReLU in its epilogue and an output row stride, the three max-pools, the global average pool, the
+// table-driven bilinear resize (align_corners=True or half-pixel, dense or into a channel slice), the broadcast of a pooled vector
+// and a + b.  No atomics, no split-K; every sum runs in a fixed order, so the same inputs give the
 // same bits on every run, eagerly and under graph replay, and an image's results do not depend on its place in the batch.
-// What belongs to one metric alone (its preprocess, its distance or counts) is in lpips.hip, classify.hip, segment.hip and deeplab.hip.
+// What belongs to one metric alone (its preprocess, its distance or counts) is in lpips.hip, classify.hip and segment.hip.
 #include "common.h"
 #include "f32_layers.h"
 
@@ -237,18 +238,34 @@ __global__ __launch_bounds__(256) void avgpool_f32_kernel(const float* __restric
   y[i] = (float)(s / (double)P);
 }
 
-// ------------------------------------------------------------------------------------------ bilinear up-sample, align_corners
-// x [N][h][w][C] -> y [N][H][W][C]; V channels per thread (float4 when C % 4 == 0).
+// ------------------------------------------------------------------------------------------ broadcast of a pooled vector
+// v [N][C] -> y[(n * P + p) * ldy + c] for every pixel p: the bilinear resize of a 1 x 1 map, which is the value itself.
+__global__ __launch_bounds__(256) void dlv3_broadcast_kernel(const float* __restrict__ v, float* __restrict__ y, int total, int P, int C,
+                                                             int ldy) {
+  const int i = blockIdx.x * 256 + threadIdx.x;       // over N*P*C
+  if (i >= total) return;
+  const int c = i % C;
+  const int r = i / C;                                // = n * P + p
+  const int n = r / P;
+  y[(long long)r * ldy + c] = v[n * C + c];
+}
+
+// ------------------------------------------------------------------------------------------ bilinear resize by axis tables
+// x [N][h][w][C] -> y[((n * H + oy) * W + ox) * ldy + c], with whatever tables it is given (align_corners=True or half-pixel).
+// ldy == C is the dense [N][H][W][C]; ldy > C writes a channel slice of a wider NHWC buffer, so DeepLabV3+'s ASPP features land in
+// channels 48..303 of the classifier's input with no concat copy.  V channels per thread (float4 when C, ldy % 4 == 0 and both
+// pointers are 16-byte aligned).
 template <int V>
-__global__ __launch_bounds__(256) void upsample_bilinear_ac_kernel(const float* __restrict__ x, float* __restrict__ y, int total, int h, int w,
-                                                                   int C, int H, int W, const int* __restrict__ iy,
-                                                                   const float* __restrict__ wy, const int* __restrict__ ix,
-                                                                   const float* __restrict__ wx) {
+__global__ __launch_bounds__(256) void upsample_bilinear_kernel(const float* __restrict__ x, float* __restrict__ y, int total, int h, int w,
+                                                                int C, int H, int W, int ldy, const int* __restrict__ iy,
+                                                                const float* __restrict__ wy, const int* __restrict__ ix,
+                                                                const float* __restrict__ wx) {
   const int i = blockIdx.x * 256 + threadIdx.x;       // over N*H*W*(C/V)
   if (i >= total) return;
   const int cv = C / V;
   const int c = (i % cv) * V;
-  int r = i / cv;
+  int r = i / cv;                                     // = (n * H + oy) * W + ox
+  const int pix = r;
   const int ox = r % W;
   r /= W;
   const int oy = r % H, n = r / H;
@@ -260,7 +277,7 @@ __global__ __launch_bounds__(256) void upsample_bilinear_ac_kernel(const float* 
   const float* p01 = img + ((long long)y0 * w + x1) * C;
   const float* p10 = img + ((long long)y1 * w + x0) * C;
   const float* p11 = img + ((long long)y1 * w + x1) * C;
-  float* dst = y + (long long)i * V;
+  float* dst = y + (long long)pix * ldy + c;
   if constexpr (V == 4) {
     const float4 a = *(const float4*)p00, b = *(const float4*)p01, cc = *(const float4*)p10, d = *(const float4*)p11;
     float4 o;
@@ -334,6 +351,25 @@ int conv2d_f32_launch(const char* who, const char* launch_name, const float* x, 
   else if (dil == 1) hipLaunchKernelGGL((conv2d_f32_kernel<1, false>), grid, dim3(256), 0, s, p);
   else hipLaunchKernelGGL((conv2d_f32_kernel<1, true>), grid, dim3(256), 0, s, p);
   return ur::check_launch(launch_name);
+}
+
+// ------------------------------------------------------------------------------------------ the table-driven resize's one launcher
+// ldy = C is the dense resize.
+int upsample_bilinear_launch(const char* who, const float* x, float* y, int N, int h, int w, int C, int H, int W, int ldy, const int* idx_h,
+                             const float* wt_h, const int* idx_w, const float* wt_w, ur_stream_t stream) {
+  CV_REQUIRE(x && y && idx_h && wt_h && idx_w && wt_w, "null pointer");
+  CV_REQUIRE(x != y, "x and y must not be the same buffer");
+  CV_REQUIRE(N >= 1 && C >= 1 && h >= 1 && w >= 1 && H >= 1 && W >= 1, "N, C, h, w, H and W must be >= 1");
+  CV_REQUIRE(ldy >= C, "ldy must be >= C");
+  CV_REQUIRE((long long)N * h * w * C < ur::GRID_1D_LIMIT && (long long)N * H * W * C < ur::GRID_1D_LIMIT,
+             "too many elements: N*h*w*C and N*H*W*C must be below 2^31 - 256");
+  const bool vec = C % 4 == 0 && ldy % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
+  const int total = N * H * W * (vec ? C / 4 : C);
+  unsigned blocks = 0;
+  if (int rc = ur::grid_1d(who, total, 256, &blocks)) return rc;
+  const auto kernel = vec ? upsample_bilinear_kernel<4> : upsample_bilinear_kernel<1>;
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, y, total, h, w, C, H, W, ldy, idx_h, wt_h, idx_w, wt_w);
+  return ur::check_launch(who);
 }
 #undef CV_REQUIRE
 
@@ -419,22 +455,24 @@ int ur_avgpool_f32(const float* x, float* y, int N, int P, int C, ur_stream_t st
 
 int ur_upsample_bilinear_ac_f32(const float* x, float* y, int N, int h, int w, int C, int H, int W, const int* idx_h, const float* wt_h,
                                 const int* idx_w, const float* wt_w, ur_stream_t stream) {
-  UR_REQUIRE(x && y && idx_h && wt_h && idx_w && wt_w, "null pointer");
-  UR_REQUIRE(x != y, "x and y must not be the same buffer");
-  UR_REQUIRE(N >= 1 && C >= 1 && h >= 1 && w >= 1 && H >= 1 && W >= 1, "N, C, h, w, H and W must be >= 1");
-  UR_REQUIRE((long long)N * h * w * C < ur::GRID_1D_LIMIT && (long long)N * H * W * C < ur::GRID_1D_LIMIT,
-             "too many elements: N*h*w*C and N*H*W*C must be below 2^31 - 256");
-  hipStream_t s = (hipStream_t)stream;
-  if (C % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0) {
-    const int total = N * H * W * (C / 4);
-    UR_GRID_1D(blocks, total, 256);
-    hipLaunchKernelGGL(upsample_bilinear_ac_kernel<4>, dim3(blocks), dim3(256), 0, s, x, y, total, h, w, C, H, W, idx_h, wt_h, idx_w, wt_w);
-  } else {
-    const int total = N * H * W * C;
-    UR_GRID_1D(blocks, total, 256);
-    hipLaunchKernelGGL(upsample_bilinear_ac_kernel<1>, dim3(blocks), dim3(256), 0, s, x, y, total, h, w, C, H, W, idx_h, wt_h, idx_w, wt_w);
-  }
-  return ur::check_launch("ur_upsample_bilinear_ac_f32");
+  return upsample_bilinear_launch("ur_upsample_bilinear_ac_f32", x, y, N, h, w, C, H, W, C, idx_h, wt_h, idx_w, wt_w, stream);
+}
+
+int ur_dlv3_upsample_f32(const float* x, float* y, int N, int h, int w, int C, int H, int W, int ldy, const int* idx_h, const float* wt_h,
+                         const int* idx_w, const float* wt_w, ur_stream_t stream) {
+  return upsample_bilinear_launch("ur_dlv3_upsample_f32", x, y, N, h, w, C, H, W, ldy, idx_h, wt_h, idx_w, wt_w, stream);
+}
+
+int ur_dlv3_broadcast_f32(const float* v, float* y, int N, int P, int C, int ldy, ur_stream_t stream) {
+  UR_REQUIRE(v && y, "null pointer");
+  UR_REQUIRE(v != y, "v and y must not be the same buffer");
+  UR_REQUIRE(N >= 1 && P >= 1 && C >= 1, "N, P and C must be >= 1");
+  UR_REQUIRE(ldy >= C, "ldy must be >= C");
+  UR_REQUIRE((long long)N * P * C < ur::GRID_1D_LIMIT, "too many elements: N*P*C must be below 2^31 - 256");
+  const int total = N * P * C;
+  UR_GRID_1D(blocks, total, 256);
+  hipLaunchKernelGGL(dlv3_broadcast_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, v, y, total, P, C, ldy);
+  return ur::check_launch("ur_dlv3_broadcast_f32");
 }
 
 int ur_add_f32(const float* a, const float* b, float* y, long long n, ur_stream_t stream) {

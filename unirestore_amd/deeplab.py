@@ -1,7 +1,9 @@
 """DeepLabV3+ scoring of the `seg` output on the GPU in exact fp32: the reference's second segmenter, `dlv3pr50` =
 `deeplabv3plus_resnet50(num_classes=19, output_stride=16)` behind an ImageNet Normalize, on the fp32 layers and the ResNet
-backbone of f32net.py and the kernels of csrc/deeplab.hip - weight loading, the evaluator's three-scale test-time augmentation
-and the launch wrappers.  What the reference's `SemanticSegmentationMetric` builds for this network: quantised image -> scales
+backbone of f32net.py and the kernels of csrc/segment.hip - what is this network's alone: its plans, its weight loading, the
+network and the wrapper of its two-stage argmax.  The three-scale test-time augmentation, the checks and the preprocess launch
+are segment.py's, shared with RefineNet-LW; the half-pixel resize and the broadcast are f32net.py's.  What the reference's
+`SemanticSegmentationMetric` builds for this network: quantised image -> scales
 (1, 0.8, 0.6), bilinear align_corners=True -> Normalize -> ResNet (layer4 dilated by 2, stride 16) -> ASPP (dilations 6, 12, 18
 and a pooled branch) -> decoder on layer1's features -> the model's own align_corners=False resize to its input -> the
 evaluator's align_corners=True resize to the label map -> mean -> argmax.  The confusion matrix and the mIoU are segment.py's
@@ -16,27 +18,23 @@ import math
 import torch
 
 from . import f32net
+from . import segment as _segment
 from .capi import check, lib
-from .f32net import PackedConvF32, stream, take
-from .segment import scaled_size
+from .f32net import PackedConvF32, broadcast_f32, stream, take, upsample_bilinear_hp_f32
+from .segment import SCALES, scaled_size, segment        # `segment`: the one test-time augmentation, under this module's name too
 
 # arch -> bottleneck blocks per stage (the torchvision layout, replace_stride_with_dilation = [False, False, True])
 ARCHS = {"dlv3pr50": (3, 4, 6, 3), "dlv3pr101": (3, 4, 23, 3)}
 # The smallest network input: one whole cell of the stride-16 map.  (The layers themselves run on anything - ASPP's padding equals
 # its dilation - but below 16 px the 1/16 map is a single pixel that is mostly padding, which no use of the metric means.)
 MIN_HW = 16
-SCALES = (1, 0.8, 0.6)                                   # the reference's test-time augmentation
 ASPP_DILATIONS = (6, 12, 18)
 LOW_CH, ASPP_CH = 48, 256                                # the decoder's input: low-level channels 0..47, then ASPP's 48..303
 
 
 def depths_of(arch):
-    """ARCHS[arch], or `arch` itself when it is a tuple of four block counts (tests build a (1, 1, 1, 1) network)."""
-    if isinstance(arch, (tuple, list)) and len(arch) == 4 and all(isinstance(d, int) and d >= 1 for d in arch):
-        return tuple(arch)
-    if not isinstance(arch, str) or arch not in ARCHS:
-        raise ValueError(f"unknown DeepLabV3+ arch {arch!r}: choose from {sorted(ARCHS)}")
-    return ARCHS[arch]
+    """segment.depths_of with this network's ARCHS."""
+    return _segment.depths_of(arch, ARCHS, "DeepLabV3+")
 
 
 def conv_plan(arch):
@@ -74,18 +72,15 @@ CLF_KEY = "classifier.classifier.3"
 class DeepLabWeights:
     """One DeepLabV3+ ready for the fp32 kernels: every convolution with its BatchNorm folded in (fp64 fold, rounded to fp32,
     repacked, on the device), the last one with its own bias.  `cpu` keeps the UNFUSED state dict (fp32 tensors under the reference
-    module's keys): what a host restatement of the network needs."""
+    module's keys): what a host restatement of the network needs.  `name`, `min_hw`, `prep`, `logits` and `tta_argmax` are what the
+    test-time augmentation (segment.segment) reads."""
+    name, min_hw = "deeplab", MIN_HW
 
     def __init__(self, arch, sd: dict, dev=None, source: str = "state dict"):
         dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else torch.device(dev)
         self.arch, self.device, self.depths = arch, dev, depths_of(arch)
         self.cpu, self.convs = {}, {}
-        clf = sd.get(f"{CLF_KEY}.weight") if isinstance(sd, dict) else None
-        if not torch.is_tensor(clf) or clf.ndim != 4:
-            raise ValueError(f"{source}: key '{CLF_KEY}.weight' is missing or is no [classes, 256, 1, 1] filter")
-        self.num_classes = int(clf.shape[0])
-        if not 1 <= self.num_classes <= 255:
-            raise ValueError(f"{source}: '{CLF_KEY}.weight' has {self.num_classes} classes, the one-byte prediction holds 1..255")
+        self.num_classes = _segment.class_count(sd, source, CLF_KEY, "256, 1, 1")
         plan = conv_plan(arch) + head_plan(self.num_classes)
         geometry = {e[0]: e[5:] for e in plan}
         ready = f32net.fold_convs([e[:7] for e in plan if e[1] is not None], sd, source, self.cpu)      # every check first
@@ -97,6 +92,15 @@ class DeepLabWeights:
         # the backbone under f32net's own keys, and its blocks in execution order
         self.backbone = {k[len("backbone."):]: v for k, v in self.convs.items() if k.startswith("backbone.")}
         self.stages = f32net.resnet_stages("bottleneck", self.depths, self.backbone)
+
+    def prep(self, images, size):
+        return prep(images, size)
+
+    def logits(self, x):
+        return logits(x, self)
+
+    def tta_argmax(self, maps, in_sizes, size, want_avg=False):
+        return tta_argmax(maps, in_sizes, size, want_avg)
 
 
 def read_state_dict(path) -> dict:
@@ -148,49 +152,12 @@ def random_weights(arch, seed: int = 0, num_classes: int = 19, dev=None) -> Deep
     return DeepLabWeights(arch, random_state_dict(arch, seed, num_classes), dev, source=f"random_state_dict({arch!r}, {seed})")
 
 
-# ---- launch wrappers of csrc/deeplab.hip (fp32 device tensors, NHWC behind the preprocess) --------------------------------------
+# ---- launch wrappers of csrc/segment.hip (fp32 device tensors, NHWC behind the preprocess) --------------------------------------
 
 def prep(x: torch.Tensor, size=None) -> torch.Tensor:
-    """fp32 NCHW [N,3,H,W] in [0,1] -> NHWC [N,h,w,3] (size = (h, w), default the input's): bilinear align_corners=True resize, then
-    (v - mean_c) / std_c with the ImageNet constants, channels in R, G, B order.  At the input's own size the resize is the
-    identity, bit for bit (finite images).  The first call for a new pair of sizes uploads its tables: run a shape once eagerly
-    before capturing it in a graph."""
-    n, c, h, w = x.shape
-    oh, ow = (h, w) if size is None else size
-    iy, wy = f32net._device_tables((h,), oh, x.device.index)
-    ix, wx = f32net._device_tables((w,), ow, x.device.index)
-    y = torch.empty(n, oh, ow, 3, dtype=torch.float32, device=x.device)
-    check(lib.ur_dlv3_prep(x.data_ptr(), y.data_ptr(), n, c, h, w, oh, ow, iy.data_ptr(), wy.data_ptr(), ix.data_ptr(), wx.data_ptr(), stream()))
-    return y
-
-
-def broadcast_f32(v: torch.Tensor, out, channel_offset: int) -> torch.Tensor:
-    """v fp32 [N,C] -> channels channel_offset .. channel_offset + C - 1 of every pixel of `out` (contiguous fp32 [N,H,W,C_all]);
-    returns `out`.  The bilinear resize of a 1 x 1 map, which is the value itself whatever align_corners says."""
-    n, c = v.shape
-    if (out.ndim != 4 or out.shape[0] != n or out.dtype != torch.float32 or not out.is_contiguous() or out.device != v.device
-            or not v.is_contiguous() or v.dtype != torch.float32 or not 0 <= channel_offset <= out.shape[3] - c):
-        raise ValueError(f"broadcast_f32: needs a contiguous fp32 [{n}, C] vector and a contiguous fp32 [{n}, H, W, >= offset + C] buffer on one "
-                         f"device, got {v.dtype} {tuple(v.shape)} and {out.dtype} {tuple(out.shape)}, offset {channel_offset}")
-    check(lib.ur_dlv3_broadcast_f32(v.data_ptr(), out.data_ptr() + 4 * channel_offset, n, out.shape[1] * out.shape[2], c, out.shape[3], stream()))
-    return out
-
-
-def upsample_bilinear_hp_f32(x: torch.Tensor, size, out=None) -> torch.Tensor:
-    """NHWC fp32 [N,h,w,C] -> [N,H,W,C], bilinear with align_corners=False (half-pixel centres, f32net.hp_table).  out = (buffer,
-    channel_offset): the result goes to that channel slice of a contiguous fp32 [N,H,W,C_all] buffer, which is returned."""
-    n, h, w, c = x.shape
-    oh, ow = size
-    iy, wy = f32net._device_tables_hp(((h, oh),), x.device.index)
-    ix, wx = f32net._device_tables_hp(((w, ow),), x.device.index)
-    buf, off = (torch.empty(n, oh, ow, c, dtype=torch.float32, device=x.device), 0) if out is None else out
-    if (buf.ndim != 4 or tuple(buf.shape[:3]) != (n, oh, ow) or buf.dtype != torch.float32 or not buf.is_contiguous() or buf.device != x.device
-            or not 0 <= off <= buf.shape[3] - c):
-        raise ValueError(f"upsample_bilinear_hp_f32: out must be a contiguous fp32 [{n}, {oh}, {ow}, >= offset + {c}] tensor on {x.device}, got "
-                         f"{buf.dtype} {tuple(buf.shape)} on {buf.device}, offset {off}")
-    check(lib.ur_dlv3_upsample_f32(x.data_ptr(), buf.data_ptr() + 4 * off, n, h, w, c, oh, ow, buf.shape[3], iy.data_ptr(), wy.data_ptr(),
-                                   ix.data_ptr(), wx.data_ptr(), stream()))
-    return buf
+    """segment.prep with this network's arithmetic: fp32 NCHW [N,3,H,W] in [0,1] -> NHWC [N,h,w,3], bilinear align_corners=True
+    resize, then (v - mean_c) / std_c with the ImageNet constants, channels in R, G, B order."""
+    return _segment.prep(x, size, lib.ur_dlv3_prep)
 
 
 def tta_argmax(maps, in_sizes, size, want_avg: bool = False):
@@ -199,23 +166,13 @@ def tta_argmax(maps, in_sizes, size, want_avg: bool = False):
     (the model's own resize) and from there to (H, W) with align_corners=True (the evaluator's), in one kernel that stores neither;
     the maps are averaged as ((a + b) + c) / len(maps); ties go to the lowest class and a NaN is the maximum, as torch.argmax has
     it.  want_avg: also return the averaged logits fp32 [N,H,W,C] - for tests."""
-    maps, in_sizes = list(maps), [tuple(s) for s in in_sizes]
-    if not 1 <= len(maps) <= 3 or len(in_sizes) != len(maps):
-        raise ValueError(f"tta_argmax: needs 1 to 3 maps and as many input sizes, got {len(maps)} and {len(in_sizes)}")
-    n, _h, _w, c = maps[0].shape
-    for m in maps:
-        if m.ndim != 4 or m.dtype != torch.float32 or not m.is_contiguous() or m.shape[0] != n or m.shape[3] != c or m.device != maps[0].device:
-            raise ValueError(f"tta_argmax: every map must be a contiguous fp32 [{n}, h, w, {c}] tensor on {maps[0].device}, got "
-                             f"{m.dtype} {tuple(m.shape)} on {m.device}")
-    oh, ow = size
-    dev = maps[0].device
+    in_sizes = [tuple(s) for s in in_sizes]
+    maps, pred, avg, ptr = _segment.tta_setup(maps, size, want_avg, in_sizes)
+    (n, oh, ow), c, dev = pred.shape, maps[0].shape[3], pred.device
     aiy, awy = f32net._device_tables(tuple(s[0] for s in in_sizes), oh, dev.index)
     aix, awx = f32net._device_tables(tuple(s[1] for s in in_sizes), ow, dev.index)
     hiy, hwy = f32net._device_tables_hp(tuple((m.shape[1], s[0]) for m, s in zip(maps, in_sizes)), dev.index)
     hix, hwx = f32net._device_tables_hp(tuple((m.shape[2], s[1]) for m, s in zip(maps, in_sizes)), dev.index)
-    pred = torch.empty(n, oh, ow, dtype=torch.uint8, device=dev)
-    avg = torch.empty(n, oh, ow, c, dtype=torch.float32, device=dev) if want_avg else None
-    ptr = [m.data_ptr() for m in maps] + [None] * (3 - len(maps))
     dims = [v for m, s in zip(maps, in_sizes) for v in (m.shape[1], m.shape[2], s[0], s[1])] + [0] * (4 * (3 - len(maps)))
     check(lib.ur_dlv3_tta_argmax(*ptr, len(maps), n, c, *dims, oh, ow, aiy.data_ptr(), awy.data_ptr(), aix.data_ptr(), awx.data_ptr(),
                                  hiy.data_ptr(), hwy.data_ptr(), hix.data_ptr(), hwx.data_ptr(), pred.data_ptr(),
@@ -246,20 +203,3 @@ def logits(x: torch.Tensor, wts: DeepLabWeights) -> torch.Tensor:
     aspp = f32net.conv2d_f32(branches, cv["classifier.aspp.project.0"])
     upsample_bilinear_hp_f32(aspp, cat.shape[1:3], out=(cat, LOW_CH))
     return f32net.conv2d_f32(f32net.conv2d_f32(cat, cv["classifier.classifier.0"]), cv[CLF_KEY], relu=False)
-
-
-def segment(images: torch.Tensor, wts: DeepLabWeights, size=None, scales=SCALES) -> torch.Tensor:
-    """ops.deeplab after its argument checks: pred uint8 [N,H,W] at `size` (default: the images' own).  For each scale s the image
-    is resized to (floor(H s), floor(W s)), normalised and run through the network; one kernel resizes every scale's map to that
-    scale's input size (half-pixel) and on to `size` (align_corners=True), averages them and takes the argmax.  ValueError when
-    the smallest scale's input falls below 16 px on a side."""
-    n, _c, h, w = images.shape
-    scales = tuple(scales)
-    if not 1 <= len(scales) <= 3:
-        raise ValueError(f"deeplab: needs 1 to 3 scales, got {scales}")
-    sizes = [(scaled_size(h, s), scaled_size(w, s)) for s in scales]
-    small = min(sizes)
-    if min(min(sz) for sz in sizes) < MIN_HW:
-        raise ValueError(f"deeplab: {h} x {w} images at scales {scales} give a {small[0]} x {small[1]} input, below the network's {MIN_HW} px")
-    maps = [logits(prep(images, sz), wts) for sz in sizes]
-    return tta_argmax(maps, sizes, (h, w) if size is None else tuple(size))

@@ -1,8 +1,9 @@
-"""The fp32 NHWC layer format of the scoring networks (LPIPS's AlexNet, the classifier's ResNet, the segmenter's RefineNet-LW),
-stated once: the `[Kpad][Cout_pad]` weight repack and `PackedConvF32`, the launch wrappers of csrc/f32_layers.hip, the state-dict
-checks with the conv + BatchNorm fold, and the torchvision-layout ResNet backbone that two of the networks share.  What belongs
-to one metric alone (its preprocess, its head, its formula) stays in lpips.py, classify.py and segment.py; the next scoring
-network is written against this module.
+"""The fp32 NHWC layer format of the scoring networks (LPIPS's AlexNet, the classifier's ResNet, the segmenters' RefineNet-LW and
+DeepLabV3+), stated once: the `[Kpad][Cout_pad]` weight repack and `PackedConvF32`, the launch wrappers of csrc/f32_layers.hip
+(the table-driven bilinear resize with either table, dense or into a channel slice, among them), the state-dict checks with the
+conv + BatchNorm fold, and the torchvision-layout ResNet backbone that three of the networks share.  What belongs to one metric
+alone (its preprocess, its head, its formula) stays in lpips.py, classify.py, segment.py and deeplab.py; the next scoring network
+is written against this module.
 """
 import ctypes as C
 import functools
@@ -167,17 +168,49 @@ def _device_tables(n_ins: tuple, n_out: int, dev_index: int):
     return torch.cat([t[0] for t in tabs]).to(dev), torch.cat([t[1] for t in tabs]).float().contiguous().to(dev)
 
 
+def _upsample_bilinear(who, x, size, tables_h, tables_w, out, entry):
+    """The table-driven resize of NHWC fp32 x to `size` with the (idx, wt) device tables of the two axes.  out = (buffer,
+    channel_offset) or None for a new dense tensor; entry(x ptr, y ptr, n, h, w, c, oh, ow, ldy, *table ptrs, stream) launches."""
+    n, h, w, c = x.shape
+    oh, ow = size
+    buf, off = (torch.empty(n, oh, ow, c, dtype=torch.float32, device=x.device), 0) if out is None else out
+    if (buf.ndim != 4 or tuple(buf.shape[:3]) != (n, oh, ow) or buf.dtype != torch.float32 or not buf.is_contiguous() or buf.device != x.device
+            or not 0 <= off <= buf.shape[3] - c):
+        raise ValueError(f"{who}: out must be a contiguous fp32 [{n}, {oh}, {ow}, >= offset + {c}] tensor on {x.device}, got "
+                         f"{buf.dtype} {tuple(buf.shape)} on {buf.device}, offset {off}")
+    check(entry(x.data_ptr(), buf.data_ptr() + 4 * off, n, h, w, c, oh, ow, buf.shape[3], *(t.data_ptr() for t in (*tables_h, *tables_w)),
+                stream()))
+    return buf
+
+
 def upsample_bilinear_ac_f32(x: torch.Tensor, size) -> torch.Tensor:
     """NHWC fp32 [N,h,w,C] -> [N,H,W,C], bilinear with align_corners=True; the same size is the identity, bit for bit, while the
     values are finite (0 x inf from a neighbour is NaN, as in torch; a -0.0 may come out as +0.0)."""
-    n, h, w, c = x.shape
-    oh, ow = size
-    iy, wy = _device_tables((h,), oh, x.device.index)
-    ix, wx = _device_tables((w,), ow, x.device.index)
-    y = torch.empty(n, oh, ow, c, dtype=torch.float32, device=x.device)
-    check(lib.ur_upsample_bilinear_ac_f32(x.data_ptr(), y.data_ptr(), n, h, w, c, oh, ow, iy.data_ptr(), wy.data_ptr(), ix.data_ptr(),
-                                          wx.data_ptr(), stream()))
-    return y
+    def dense(xp, yp, n, h, w, c, oh, ow, _ldy, *tables_and_stream):          # the dense export has no ldy: it is C
+        return lib.ur_upsample_bilinear_ac_f32(xp, yp, n, h, w, c, oh, ow, *tables_and_stream)
+    dev = x.device.index
+    return _upsample_bilinear("upsample_bilinear_ac_f32", x, size, _device_tables((x.shape[1],), size[0], dev),
+                              _device_tables((x.shape[2],), size[1], dev), None, dense)
+
+
+def upsample_bilinear_hp_f32(x: torch.Tensor, size, out=None) -> torch.Tensor:
+    """NHWC fp32 [N,h,w,C] -> [N,H,W,C], bilinear with align_corners=False (half-pixel centres, hp_table).  out = (buffer,
+    channel_offset): the result goes to that channel slice of a contiguous fp32 [N,H,W,C_all] buffer, which is returned."""
+    dev = x.device.index
+    return _upsample_bilinear("upsample_bilinear_hp_f32", x, size, _device_tables_hp(((x.shape[1], size[0]),), dev),
+                              _device_tables_hp(((x.shape[2], size[1]),), dev), out, lib.ur_dlv3_upsample_f32)
+
+
+def broadcast_f32(v: torch.Tensor, out, channel_offset: int) -> torch.Tensor:
+    """v fp32 [N,C] -> channels channel_offset .. channel_offset + C - 1 of every pixel of `out` (contiguous fp32 [N,H,W,C_all]);
+    returns `out`.  The bilinear resize of a 1 x 1 map, which is the value itself whatever align_corners says."""
+    n, c = v.shape
+    if (out.ndim != 4 or out.shape[0] != n or out.dtype != torch.float32 or not out.is_contiguous() or out.device != v.device
+            or not v.is_contiguous() or v.dtype != torch.float32 or not 0 <= channel_offset <= out.shape[3] - c):
+        raise ValueError(f"broadcast_f32: needs a contiguous fp32 [{n}, C] vector and a contiguous fp32 [{n}, H, W, >= offset + C] buffer on one "
+                         f"device, got {v.dtype} {tuple(v.shape)} and {out.dtype} {tuple(out.shape)}, offset {channel_offset}")
+    check(lib.ur_dlv3_broadcast_f32(v.data_ptr(), out.data_ptr() + 4 * channel_offset, n, out.shape[1] * out.shape[2], c, out.shape[3], stream()))
+    return out
 
 
 # ---- state dicts: checks, and the conv + BatchNorm fold ------------------------------------------------------------------------

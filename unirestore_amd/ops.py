@@ -1157,6 +1157,22 @@ def top1(logits: torch.Tensor, labels: torch.Tensor):
     return pred, counts[0], counts[1], counts[2]
 
 
+def _segmenter(who, images, weights, cls, size, scales):
+    """`segment` and `deeplab` behind their names: the checks on images, weights (a `cls` of module `who`), size and scales, then
+    the one test-time augmentation of segment.py."""
+    from . import segment as _segment
+    _check_images(who, "images", images)
+    n, c, h, w = images.shape
+    if n < 1 or c != 3 or h < 1 or w < 1:
+        raise ValueError(f"{who}: needs [N>=1, 3, H>=1, W>=1] images, got {tuple(images.shape)}")
+    _check_scorer(who, "weights", weights, cls, f"{who}.load_weights / {who}.random_weights")
+    if size is not None and not (isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(v, int) and v >= 1 for v in size)):
+        raise ValueError(f"{who}: size must be (H, W) with H, W >= 1, got {size!r}")
+    if not (isinstance(scales, (tuple, list)) and 1 <= len(scales) <= 3 and all(isinstance(v, (int, float)) and 0 < v <= 8 for v in scales)):
+        raise ValueError(f"{who}: scales must be 1 to 3 numbers in (0, 8], got {scales!r}")
+    return _segment.segment(images, weights, size, scales)
+
+
 def segment(images: torch.Tensor, weights, size=None, scales=(1, 0.8, 0.6)) -> torch.Tensor:
     """Predicted classes uint8 [N,H,W] (on the device) of fp32 NCHW images in [0,1]: the segmentation evaluator's test-time
     augmentation in exact fp32 on the GPU - for each scale a bilinear align_corners=True resize to floor(size * scale), RefineNet-LW's
@@ -1166,17 +1182,8 @@ def segment(images: torch.Tensor, weights, size=None, scales=(1, 0.8, 0.6)) -> t
     bytes.  No host sync - except on the FIRST call for a new image size, target size or set of scales, which builds that shape's
     tap tables on the host and uploads them with a blocking copy: run a shape once eagerly before capturing it in a graph.  The
     tables (a few KB per shape) stay on the device for the life of the process, so a captured graph never loses the ones it reads."""
-    from . import segment as _segment
-    _check_images("segment", "images", images)
-    n, c, h, w = images.shape
-    if n < 1 or c != 3 or h < 1 or w < 1:
-        raise ValueError(f"segment: needs [N>=1, 3, H>=1, W>=1] images, got {tuple(images.shape)}")
-    _check_scorer("segment", "weights", weights, _segment.SegmenterWeights, "segment.load_weights / segment.random_weights")
-    if size is not None and not (isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(v, int) and v >= 1 for v in size)):
-        raise ValueError(f"segment: size must be (H, W) with H, W >= 1, got {size!r}")
-    if not (isinstance(scales, (tuple, list)) and 1 <= len(scales) <= 3 and all(isinstance(v, (int, float)) and 0 < v <= 8 for v in scales)):
-        raise ValueError(f"segment: scales must be 1 to 3 numbers in (0, 8], got {scales!r}")
-    return _segment.segment(images, weights, size, scales)
+    from .segment import SegmenterWeights
+    return _segmenter("segment", images, weights, SegmenterWeights, size, scales)
 
 
 def deeplab(images: torch.Tensor, weights, size=None, scales=(1, 0.8, 0.6)) -> torch.Tensor:
@@ -1187,17 +1194,8 @@ def deeplab(images: torch.Tensor, weights, size=None, scales=(1, 0.8, 0.6)) -> t
     W), averages and takes the argmax (ties to the lowest class).  weights: what deeplab.load_weights / deeplab.random_weights
     return.  ValueError when the smallest scale's input falls below 16 px on a side.  The same guarantees and the same first-call
     table upload as `segment`: run a shape once eagerly before capturing it in a graph."""
-    from . import deeplab as _deeplab
-    _check_images("deeplab", "images", images)
-    n, c, h, w = images.shape
-    if n < 1 or c != 3 or h < 1 or w < 1:
-        raise ValueError(f"deeplab: needs [N>=1, 3, H>=1, W>=1] images, got {tuple(images.shape)}")
-    _check_scorer("deeplab", "weights", weights, _deeplab.DeepLabWeights, "deeplab.load_weights / deeplab.random_weights")
-    if size is not None and not (isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(v, int) and v >= 1 for v in size)):
-        raise ValueError(f"deeplab: size must be (H, W) with H, W >= 1, got {size!r}")
-    if not (isinstance(scales, (tuple, list)) and 1 <= len(scales) <= 3 and all(isinstance(v, (int, float)) and 0 < v <= 8 for v in scales)):
-        raise ValueError(f"deeplab: scales must be 1 to 3 numbers in (0, 8], got {scales!r}")
-    return _deeplab.segment(images, weights, size, scales)
+    from .deeplab import DeepLabWeights
+    return _segmenter("deeplab", images, weights, DeepLabWeights, size, scales)
 
 
 def checked_targets(target: torch.Tensor, classes: int = 19, ignore_index: int = 255) -> torch.Tensor:

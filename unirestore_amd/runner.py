@@ -144,10 +144,9 @@ class LitUniFIE:
         self.segmenters = {}
         for name, spec in (segmenters or {}).items():
             from . import deeplab, segment
-            if isinstance(spec, (segment.SegmenterWeights, deeplab.DeepLabWeights)):
-                w = spec
-            else:
-                w = deeplab.load_weights(*spec) if isinstance(spec[0], str) and spec[0] in deeplab.ARCHS else segment.load_weights(*spec)
+            w = spec
+            if not isinstance(spec, (segment.SegmenterWeights, deeplab.DeepLabWeights)):      # (arch, path): the arch's table names its module
+                w = (deeplab if isinstance(spec[0], str) and spec[0] in deeplab.ARCHS else segment).load_weights(*spec)
             self.segmenters[name] = w
             for key in self.segmenter_keys(name):
                 self.totals[key] = torch.zeros(w.num_classes, w.num_classes, dtype=torch.int64, device=w.device)
@@ -320,7 +319,7 @@ class LitUniFIE:
         if label_maps is None or not torch.is_tensor(label_maps) or label_maps.ndim != 3:
             raise ValueError("the segmenters need the batch's label maps (gt is None or no [N,H,W] tensor): build the dataset with "
                              "labels: map on an `lq hq label.png` list")
-        from . import deeplab, ops, segment
+        from . import ops, segment
         if self.need_crop:
             inputs, label_maps = self._crop(inputs), self._crop(label_maps)
         if tuple(label_maps.shape) != (seg_preds.shape[0], *seg_preds.shape[2:]):
@@ -328,7 +327,7 @@ class LitUniFIE:
         for name, w in self.segmenters.items():
             # the targets are checked once per batch; ops.segment's / ops.deeplab's own predictions always lie in [0, classes)
             target = ops.checked_targets(label_maps.to(device=w.device, dtype=torch.int64).contiguous(), w.num_classes)
-            predict = ops.deeplab if isinstance(w, deeplab.DeepLabWeights) else ops.segment
+            predict = getattr(ops, w.name)                           # ops.segment or ops.deeplab: each takes its own weights class
             for key, images in zip(self.segmenter_keys(name), (seg_preds, inputs)):
                 pred = predict(images.to(device=w.device, dtype=torch.float32).contiguous(), w)
                 self.totals[key] = self.totals[key] + segment.confusion(pred, target, w.num_classes)

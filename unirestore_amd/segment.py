@@ -1,9 +1,11 @@
-"""Segmenter scoring of the `seg` output on the GPU in exact fp32: RefineNet-LightWeight (ResNet-50 / 101 / 152 backbone) on the
-fp32 layers and the ResNet backbone of f32net.py and the kernels of csrc/segment.hip - weight loading, the evaluator's
-three-scale test-time augmentation, the launch wrappers, and the mIoU formula.  What the reference's `SemanticSegmentationMetric`
-builds (eval_semantic_segmentation.py:170-251): quantised image -> scales (1, 0.8, 0.6), bilinear align_corners=True -> the
-segmenter (x * 255 - mean, BGR, ResNetLW) -> every scale's logits resized to the label map -> mean -> argmax ->
-MulticlassJaccardIndex(19, ignore_index=255).
+"""Segmenter scoring of the `seg` output on the GPU in exact fp32: the module of the segmenter family.  It holds once what the
+two networks share - the evaluator's three-scale test-time augmentation (`segment`, written against the small surface both
+weights classes expose: `name`, `min_hw`, `prep`, `logits`, `tta_argmax`), the arch and class-count checks, the launch wrappers
+of csrc/segment.hip, the confusion matrix and the mIoU formula - and RefineNet-LightWeight (ResNet-50 / 101 / 152 backbone) on
+the fp32 layers and the ResNet backbone of f32net.py; DeepLabV3+ is deeplab.py.  What the reference's
+`SemanticSegmentationMetric` builds (eval_semantic_segmentation.py:170-251): quantised image -> scales (1, 0.8, 0.6), bilinear
+align_corners=True -> the segmenter (x * 255 - mean, BGR, ResNetLW) -> every scale's logits resized to the label map -> mean ->
+argmax -> MulticlassJaccardIndex(19, ignore_index=255).
 
 The project ships NO weights.  `load_weights` reads the state dict (or Lightning checkpoint) a user of the metric already has;
 `random_weights` makes seeded stand-ins for tests and timing, which say nothing about any published mIoU.
@@ -23,13 +25,25 @@ SCALES = (1, 0.8, 0.6)                                   # the reference's test-
 CRP_STAGES = 4
 
 
-def depths_of(arch):
-    """ARCHS[arch], or `arch` itself when it is a tuple of four block counts (tests build a (1, 1, 1, 1) network)."""
+def depths_of(arch, archs=ARCHS, noun="segmenter"):
+    """archs[arch], or `arch` itself when it is a tuple of four block counts (tests build a (1, 1, 1, 1) network).  archs, noun:
+    the network's arch table and what the error calls it."""
     if isinstance(arch, (tuple, list)) and len(arch) == 4 and all(isinstance(d, int) and d >= 1 for d in arch):
         return tuple(arch)
-    if not isinstance(arch, str) or arch not in ARCHS:
-        raise ValueError(f"unknown segmenter arch {arch!r}: choose from {sorted(ARCHS)}")
-    return ARCHS[arch]
+    if not isinstance(arch, str) or arch not in archs:
+        raise ValueError(f"unknown {noun} arch {arch!r}: choose from {sorted(archs)}")
+    return archs[arch]
+
+
+def class_count(sd, source, key, filter_shape):
+    """The number of classes: the output channels of the last convolution `key`, a [classes, *filter_shape] filter.  ValueError
+    (`source` named) when it is missing, is no 4-D tensor or has more classes than the one-byte prediction holds."""
+    clf = sd.get(f"{key}.weight") if isinstance(sd, dict) else None
+    if not torch.is_tensor(clf) or clf.ndim != 4:
+        raise ValueError(f"{source}: key '{key}.weight' is missing or is no [classes, {filter_shape}] filter")
+    if not 1 <= clf.shape[0] <= 255:
+        raise ValueError(f"{source}: '{key}.weight' has {clf.shape[0]} classes, the one-byte prediction holds 1..255")
+    return int(clf.shape[0])
 
 
 def conv_plan(arch):
@@ -54,19 +68,17 @@ def head_plan(num_classes: int = 19):
 class SegmenterWeights:
     """One RefineNet-LW ready for the fp32 kernels: every backbone convolution with its BatchNorm folded in (fp64 fold, rounded to
     fp32, repacked, on the device), the head's bias-free convolutions with a zero bias, clf_conv with its own.  `cpu` keeps the
-    UNFUSED state dict (fp32 tensors under the reference module's keys): what a host restatement of the network needs."""
+    UNFUSED state dict (fp32 tensors under the reference module's keys): what a host restatement of the network needs.  `name`,
+    `min_hw`, `prep`, `logits` and `tta_argmax` are what the test-time augmentation (`segment`) reads; deeplab.DeepLabWeights has
+    the same five."""
+    name, min_hw = "segment", MIN_HW
 
     def __init__(self, arch, sd: dict, dev=None, source: str = "state dict"):
         dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else torch.device(dev)
         self.arch, self.device, self.depths = arch, dev, depths_of(arch)
         self.cpu, self.convs = {}, {}
         ready = f32net.fold_convs(conv_plan(arch), sd, source, self.cpu)      # every check first: nothing is uploaded for a bad file
-        clf = sd.get("clf_conv.weight")
-        if not torch.is_tensor(clf) or clf.ndim != 4:
-            raise ValueError(f"{source}: key 'clf_conv.weight' is missing or is no [classes, 256, 3, 3] filter")
-        self.num_classes = int(clf.shape[0])
-        if not 1 <= self.num_classes <= 255:
-            raise ValueError(f"{source}: 'clf_conv.weight' has {self.num_classes} classes, the one-byte prediction holds 1..255")
+        self.num_classes = class_count(sd, source, "clf_conv", "256, 3, 3")
         for ckey, cout, cin, k in head_plan(self.num_classes):
             w = take(sd, source, f"{ckey}.weight", (cout, cin, k, k), keep=self.cpu)
             b = take(sd, source, "clf_conv.bias", (cout,), keep=self.cpu) if ckey == "clf_conv" else torch.zeros(cout)
@@ -75,6 +87,15 @@ class SegmenterWeights:
             self.convs[ckey] = PackedConvF32(w, b, stride, pad, dev)
         # the backbone's blocks in execution order, by stage: (conv keys of the main path, downsample key or None)
         self.stages = f32net.resnet_stages("bottleneck", self.depths, self.convs)
+
+    def prep(self, images, size):
+        return prep(images, size)
+
+    def logits(self, x):
+        return logits(x, self)
+
+    def tta_argmax(self, maps, in_sizes, size, want_avg=False):
+        return tta_argmax(maps, size, want_avg)                      # the evaluator resizes this network's logits once: no in_sizes
 
 
 def load_weights(arch, path, dev=None) -> SegmenterWeights:
@@ -124,17 +145,36 @@ def scaled_size(n: int, s) -> int:
 
 # ---- launch wrappers of csrc/segment.hip (fp32 device tensors, NHWC behind the preprocess) --------------------------------------
 
-def prep(x: torch.Tensor, size=None) -> torch.Tensor:
+def prep(x: torch.Tensor, size=None, entry=lib.ur_seg_prep) -> torch.Tensor:
     """fp32 NCHW [N,3,H,W] in [0,1] -> NHWC [N,h,w,3] (size = (h, w), default the input's): bilinear align_corners=True resize, then
-    v * 255 - mean_c, channels in B, G, R order.  At the input's own size the resize is the identity, bit for bit (finite images).  The first call
-    for a new pair of sizes uploads its tables: run a shape once eagerly before capturing it in a graph."""
+    the network's own arithmetic - with `entry` ur_seg_prep, RefineNet-LW's v * 255 - mean_c, channels in B, G, R order; with
+    ur_dlv3_prep, DeepLabV3+'s (deeplab.prep).  At the input's own size the resize is the identity, bit for bit (finite images).
+    The first call for a new pair of sizes uploads its tables: run a shape once eagerly before capturing it in a graph."""
     n, c, h, w = x.shape
     oh, ow = (h, w) if size is None else size
     iy, wy = f32net._device_tables((h,), oh, x.device.index)
     ix, wx = f32net._device_tables((w,), ow, x.device.index)
     y = torch.empty(n, oh, ow, 3, dtype=torch.float32, device=x.device)
-    check(lib.ur_seg_prep(x.data_ptr(), y.data_ptr(), n, c, h, w, oh, ow, iy.data_ptr(), wy.data_ptr(), ix.data_ptr(), wx.data_ptr(), stream()))
+    check(entry(x.data_ptr(), y.data_ptr(), n, c, h, w, oh, ow, iy.data_ptr(), wy.data_ptr(), ix.data_ptr(), wx.data_ptr(), stream()))
     return y
+
+
+def tta_setup(maps, size, want_avg, in_sizes=None):
+    """What both `tta_argmax`s start with: the checks on one to three NHWC fp32 maps [N,h_i,w_i,C] (and, when given, on as many
+    input sizes) -> (maps as a list, pred uint8 [N,H,W], avg fp32 [N,H,W,C] or None, the map pointers padded to three)."""
+    maps = list(maps)
+    if not 1 <= len(maps) <= 3 or (in_sizes is not None and len(in_sizes) != len(maps)):
+        raise ValueError(f"tta_argmax: needs 1 to 3 logit maps, got {len(maps)}" if in_sizes is None else
+                         f"tta_argmax: needs 1 to 3 maps and as many input sizes, got {len(maps)} and {len(in_sizes)}")
+    n, _h, _w, c = maps[0].shape
+    dev = maps[0].device
+    for m in maps:
+        if m.ndim != 4 or m.dtype != torch.float32 or not m.is_contiguous() or m.shape[0] != n or m.shape[3] != c or m.device != dev:
+            raise ValueError(f"tta_argmax: every map must be a contiguous fp32 [{n}, h, w, {c}] tensor on {dev}, got "
+                             f"{m.dtype} {tuple(m.shape)} on {m.device}")
+    pred = torch.empty(n, *size, dtype=torch.uint8, device=dev)
+    avg = torch.empty(n, *size, c, dtype=torch.float32, device=dev) if want_avg else None
+    return maps, pred, avg, [m.data_ptr() for m in maps] + [None] * (3 - len(maps))
 
 
 def tta_argmax(maps, size, want_avg: bool = False):
@@ -142,21 +182,10 @@ def tta_argmax(maps, size, want_avg: bool = False):
     sampled bilinearly (align_corners=True) and averaged as ((a + b) + c) / len(maps); ties go to the lowest class and a NaN is the
     maximum, as torch.argmax has it.  want_avg: also return the averaged logits fp32 [N,H,W,C] - for tests; without it no
     full-resolution logit tensor is ever written."""
-    maps = list(maps)
-    if not 1 <= len(maps) <= 3:
-        raise ValueError(f"tta_argmax: needs 1 to 3 logit maps, got {len(maps)}")
-    n, _h, _w, c = maps[0].shape
-    for m in maps:
-        if m.ndim != 4 or m.dtype != torch.float32 or not m.is_contiguous() or m.shape[0] != n or m.shape[3] != c or m.device != maps[0].device:
-            raise ValueError(f"tta_argmax: every map must be a contiguous fp32 [{n}, h, w, {c}] tensor on {maps[0].device}, got "
-                             f"{m.dtype} {tuple(m.shape)} on {m.device}")
-    oh, ow = size
-    dev = maps[0].device
+    maps, pred, avg, ptr = tta_setup(maps, size, want_avg)
+    (n, oh, ow), c, dev = pred.shape, maps[0].shape[3], pred.device
     iy, wy = f32net._device_tables(tuple(m.shape[1] for m in maps), oh, dev.index)
     ix, wx = f32net._device_tables(tuple(m.shape[2] for m in maps), ow, dev.index)
-    pred = torch.empty(n, oh, ow, dtype=torch.uint8, device=dev)
-    avg = torch.empty(n, oh, ow, c, dtype=torch.float32, device=dev) if want_avg else None
-    ptr = [m.data_ptr() for m in maps] + [None] * (3 - len(maps))
     hw = [v for m in maps for v in m.shape[1:3]] + [0] * (2 * (3 - len(maps)))
     check(lib.ur_seg_tta_argmax(*ptr, len(maps), n, c, *hw, oh, ow, iy.data_ptr(), wy.data_ptr(), ix.data_ptr(), wx.data_ptr(), pred.data_ptr(),
                                 None if avg is None else avg.data_ptr(), stream()))
@@ -205,20 +234,23 @@ def logits(x: torch.Tensor, wts: SegmenterWeights) -> torch.Tensor:
     return f32net.conv2d_f32(x, cv["clf_conv"], relu=False)
 
 
-def segment(images: torch.Tensor, wts: SegmenterWeights, size=None, scales=SCALES) -> torch.Tensor:
-    """ops.segment after its argument checks: pred uint8 [N,H,W] at `size` (default: the images' own).  For each scale s the image
-    is resized to (floor(H s), floor(W s)) and run through the network; one kernel resizes the scales' logits to `size`, averages
-    them and takes the argmax.  ValueError when the smallest scale's input falls below 32 px on a side."""
+def segment(images: torch.Tensor, wts, size=None, scales=SCALES) -> torch.Tensor:
+    """ops.segment and ops.deeplab after their argument checks, for either network's weights: pred uint8 [N,H,W] at `size`
+    (default: the images' own).  For each scale s the image is resized to (floor(H s), floor(W s)), preprocessed and run through
+    the network; one kernel resizes the scales' maps to `size` (DeepLabV3+'s through its own half-pixel resize to the scale's
+    input first), averages them and takes the argmax.  ValueError when the smallest scale's input falls below the network's
+    `min_hw` (32 px for RefineNet-LW, 16 for DeepLabV3+) on a side."""
     n, _c, h, w = images.shape
     scales = tuple(scales)
     if not 1 <= len(scales) <= 3:
-        raise ValueError(f"segment: needs 1 to 3 scales, got {scales}")
+        raise ValueError(f"{wts.name}: needs 1 to 3 scales, got {scales}")
     sizes = [(scaled_size(h, s), scaled_size(w, s)) for s in scales]
     small = min(sizes)
-    if min(min(sz) for sz in sizes) < MIN_HW:
-        raise ValueError(f"segment: {h} x {w} images at scales {scales} give a {small[0]} x {small[1]} input, below the network's {MIN_HW} px")
-    maps = [logits(prep(images, sz), wts) for sz in sizes]
-    return tta_argmax(maps, (h, w) if size is None else tuple(size))
+    if min(min(sz) for sz in sizes) < wts.min_hw:
+        raise ValueError(f"{wts.name}: {h} x {w} images at scales {scales} give a {small[0]} x {small[1]} input, below the network's "
+                         f"{wts.min_hw} px")
+    maps = [wts.logits(wts.prep(images, sz)) for sz in sizes]
+    return wts.tta_argmax(maps, sizes, (h, w) if size is None else tuple(size))
 
 
 def miou(conf):
