@@ -435,7 +435,15 @@ long long ur_image_metrics_ws_size(int N, int C, int H, int W, int win);
  *   w is the host's repack [Kpad][Cout_pad] of the OIHW filter: row k = (kh * KW + kw) * Cin + cin, column cout, zero-filled up to
  *   the sizes ur_conv2d_f32_wpack_dims gives (K to a multiple of 16, Cout to a multiple of 64), 16-byte aligned.  The
  *   activations are read as they are: padding, the K tail and the M tail cost no copy.  bias fp32 [Cout].
- * ur_maxpool2d_f32: 3x3 window, stride 2, no padding, floor mode: x [N,H,W,C] -> y [N,(H-3)/2+1,(W-3)/2+1,C].
+ *   Non-finite inputs (this convolution under all three of its names, and the three max-pools): every output element is finite,
+ *   +inf, -inf or NaN exactly where the fp64 computation of the same layer in torch is (F.conv2d + bias + res, torch.relu;
+ *   F.max_pool2d) - NaN payload bits apart - and an image that holds no non-finite value gets the bits it gets in a clean batch.
+ *   relu = 1 is IEEE 754-2019 maximum(v, 0): NaN stays NaN, +inf stays, -inf becomes 0 (and -0.0 becomes +0.0).  A NaN or an
+ *   infinity in any of the K products or in res reaches the output; an input element that no filter tap reads (padding, stride,
+ *   dilation) reaches none.
+ * ur_maxpool2d_f32: 3x3 window, stride 2, no padding, floor mode: x [N,H,W,C] -> y [N,(H-3)/2+1,(W-3)/2+1,C].  A NaN in any tap
+ *   of a window is that window's maximum, as in torch.max_pool2d; a window of -inf gives -inf; a row or column the floor drops
+ *   is not read.
  * ur_lpips_layer: feat [2N][P][C] (one tap; images 0..N-1 predictions, N..2N-1 targets), lin fp32 [C] ->
  *   part fp64 [N][ur_lpips_layer_parts(P)]: partial sums over pixels of sum_c lin_c (u_c^pred - u_c^tgt)^2.
  * ur_lpips_finish: ws holds the five taps' partials one after the other (tap t of an H x W input has ur_lpips_tap_hw pixels, its
@@ -469,7 +477,8 @@ int ur_lpips_finish(const void* ws, long long ws_bytes, int N, int H, int W, dou
  *   .224, .225).  Each axis has a table on the device: first[224] (first input index of an output index), count[224] (its taps,
  *   <= taps) and wt[224][taps] (fp32 weights, taps of one output consecutive, summed in ascending order).  The host builds them
  *   (torch's antialiased bilinear rule in fp64, rounded to fp32); indices read from a table are clamped to the axis.  taps <= 64.
- * ur_maxpool2d_pad_f32: 3x3 window, stride 2, padding 1 (-inf, not 0): x [N,H,W,C] -> y [N,(H-1)/2+1,(W-1)/2+1,C].
+ * ur_maxpool2d_pad_f32: 3x3 window, stride 2, padding 1 (-inf, not 0): x [N,H,W,C] -> y [N,(H-1)/2+1,(W-1)/2+1,C].  NaN and -inf as
+ *   in ur_maxpool2d_f32.
  * ur_avgpool_f32: x [N,P,C] -> y [N,C], the mean over the P pixels: ascending order in fp64, rounded to fp32 once.
  * ur_top1_counts: logits fp32 [N,C], labels int64 [N] (the CALLER checks 0 <= label < C) -> pred int64 [N], the argmax with ties
  *   to the lowest index and NaN as the maximum (torch.argmax), and counts int64 [3][C] of THIS batch: tp_c (pred = label = c),
@@ -500,7 +509,8 @@ int ur_top1_counts(const float* logits, const long long* labels, int N, int C, l
  * ur_seg_prep: x fp32 NCHW [N,3,H,W] in [0,1] -> y fp32 NHWC [N,OH,OW,3]: the bilinear resize, then v * 255 - mean_c with the
  *   mean (123.68, 116.779, 103.939) of R, G, B, written in B, G, R order.
  * ur_upsample_bilinear_ac_f32: x [N,h,w,C] -> y [N,H,W,C], any C.
- * ur_maxpool5_f32: 5x5 window, stride 1, padding 2 (-inf): x [N,H,W,C] -> y of the same shape.
+ * ur_maxpool5_f32: 5x5 window, stride 1, padding 2 (-inf): x [N,H,W,C] -> y of the same shape.  NaN and -inf as in
+ *   ur_maxpool2d_f32, on the float4 path (C % 4 == 0) and the scalar one.
  * ur_add_f32: y[i] = a[i] + b[i] over n fp32 values; y is neither a nor b.
  * ur_seg_tta_argmax: nmaps (1..3) logit maps m_k fp32 [N,h_k,w_k,C], 1 <= C <= 255 (unused maps NULL, sizes ignored) -> pred
  *   uint8 [N,H,W]: per pixel and class every map is sampled bilinearly, the samples averaged as ((a + b) + c) / nmaps, and the

@@ -5,6 +5,15 @@
 // and a + b.  No atomics, no split-K; every sum runs in a fixed order, so the same inputs give the
 // same bits on every run, eagerly and under graph replay, and an image's results do not depend on its place in the batch.
 // What belongs to one metric alone (its preprocess, its distance or counts) is in lpips.hip, classify.hip and segment.hip.
+//
+// Non-finite inputs.  Every kernel here treats NaN, +inf and -inf as torch's operator of the same name does, so a non-finite pixel
+// of a scored image reaches the score instead of being erased on the way: each output element is finite, +inf, -inf or NaN exactly
+// where the fp64 restatement of the layer is (tests/nonfinite_cases.py; NaN payload bits are not part of the contract), the finite
+// ones keep their bounds, and an image that holds no non-finite value gives the bits it gives in a clean batch - the "does not
+// depend on its place in the batch" promise with a poisoned neighbour.  In particular the convolution's ReLU is maximum(v, 0)
+// (NaN stays NaN, as torch.relu; fmaxf(NaN, 0) would be 0), the blocked sum carries a NaN or an infinity from
+// every K tile, a pixel no filter tap reads (padding, stride, dilation) does not reach any output, and the max-pools take a NaN
+// in any tap of a window as the window's maximum (torch.max_pool2d; fmaxf would drop it); a window of -inf gives -inf.
 #include "common.h"
 #include "f32_layers.h"
 
@@ -42,6 +51,11 @@ struct ConvArgs {
 // VEC = 1: any Cin (conv1's 3): one k per thread and tile, eight rows.
 // DIL: the taps are p.dil apart; false (dil = 1) keeps the two multiplies per tile out of the undilated networks' gather, which
 // measured 1.4 % on the classifier and the RefineNet-LW segmenter with the multiply in it.
+// ReLU that keeps NaN, as torch.relu: IEEE 754-2019 maximum(v, 0), one v_maximum3_f32 on gfx950 - where fmaxf (maxNum) returns
+// the other operand for a NaN.  v < 0 ? 0 : v says the same in a compare and a select, which measured 0.7 - 1.0 % on every
+// network's convolutions (profiles/nonfinite_timing.txt).  A -0.0 comes out as +0.0.
+__device__ __forceinline__ float relu_keep_nan(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+
 template <int VEC, bool DIL>
 __global__ __launch_bounds__(256) void conv2d_f32_kernel(ConvArgs p) {
   __shared__ float As[2][CV_BK][CV_LDA];
@@ -146,11 +160,15 @@ __global__ __launch_bounds__(256) void conv2d_f32_kernel(ConvArgs p) {
       if (m < p.M) {
         float v = (sum[j][r] + acc[j][r]) + bv;
         if (p.res) v += p.res[(long long)m * p.Cout + n];
-        p.y[(long long)m * p.ldy + n] = p.relu ? fmaxf(v, 0.f) : v;
+        p.y[(long long)m * p.ldy + n] = p.relu ? relu_keep_nan(v) : v;
       }
     }
   }
 }
+
+// ------------------------------------------------------------------------------------------ the max-pools' fold
+// max(v, t) as torch.max_pool2d folds a window: a NaN tap wins and stays (fmaxf would drop it).
+__device__ __forceinline__ float pool_max(float v, float t) { return (t > v || t != t) ? t : v; }
 
 // ------------------------------------------------------------------------------------------ max-pool 3x3 / 2, floor, no padding
 __global__ __launch_bounds__(256) void maxpool2d_f32_kernel(const float* __restrict__ x, float* __restrict__ y, int total, int H,
@@ -163,11 +181,11 @@ __global__ __launch_bounds__(256) void maxpool2d_f32_kernel(const float* __restr
   r /= OW;
   const int oh = r % OH, n = r / OH;
   const float* src = x + (((long long)n * H + 2 * oh) * W + 2 * ow) * C + c;
-  float v = src[0];
+  float v = -INFINITY;                     // every tap is inside the map, so every output is a real input value
 #pragma unroll
   for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-    for (int dx = 0; dx < 3; ++dx) v = fmaxf(v, src[((long long)dy * W + dx) * C]);
+    for (int dx = 0; dx < 3; ++dx) v = pool_max(v, src[((long long)dy * W + dx) * C]);
   y[i] = v;
 }
 
@@ -187,7 +205,7 @@ __global__ __launch_bounds__(256) void maxpool2d_pad_f32_kernel(const float* __r
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx) {
       const int ih = 2 * oh - 1 + dy, iw = 2 * ow - 1 + dx;
-      if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W) v = fmaxf(v, x[(((long long)n * H + ih) * W + iw) * C + c]);
+      if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W) v = pool_max(v, x[(((long long)n * H + ih) * W + iw) * C + c]);
     }
   y[i] = v;
 }
@@ -215,9 +233,9 @@ __global__ __launch_bounds__(256) void maxpool5_f32_kernel(const float* __restri
         const float* src = x + (((long long)n * H + ih) * W + iw) * C + c;
         if constexpr (V == 4) {
           const float4 t = *(const float4*)src;
-          v[0] = fmaxf(v[0], t.x); v[1] = fmaxf(v[1], t.y); v[2] = fmaxf(v[2], t.z); v[3] = fmaxf(v[3], t.w);
+          v[0] = pool_max(v[0], t.x); v[1] = pool_max(v[1], t.y); v[2] = pool_max(v[2], t.z); v[3] = pool_max(v[3], t.w);
         } else {
-          v[0] = fmaxf(v[0], *src);
+          v[0] = pool_max(v[0], *src);
         }
       }
     }

@@ -57,7 +57,10 @@ def conv2d_f32(x: torch.Tensor, pc: PackedConvF32, res: torch.Tensor = None, rel
     """act(conv(x) + bias + res) on NHWC fp32; res None: no residual.  out = (buffer, channel_offset): the result goes to channels
     channel_offset .. channel_offset + Cout - 1 of `buffer`, a contiguous fp32 [N,OH,OW,C >= offset + Cout] tensor whose other
     channels stay as they are, and `buffer` is returned.  An undilated convolution without `out` is ur_conv2d_f32_res; a dilated
-    one, or one with `out`, is ur_dlv3_conv2d_f32 - the same kernel."""
+    one, or one with `out`, is ur_dlv3_conv2d_f32 - the same kernel.
+    Non-finite inputs: every output is finite, +inf, -inf or NaN exactly where torch's F.conv2d (+ res) and torch.relu are in fp64
+    (relu keeps NaN and +inf and turns -inf into 0); a value no filter tap reads reaches no output; an image without a non-finite
+    value gets the bits it gets in a clean batch (tests/test_nonfinite_gpu.py)."""
     n, h, w, cin = x.shape
     if cin != pc.cin:
         raise ValueError(f"conv2d_f32: input has {cin} channels, the filter {pc.cin}")
@@ -84,6 +87,9 @@ def conv2d_f32(x: torch.Tensor, pc: PackedConvF32, res: torch.Tensor = None, rel
 
 
 def maxpool2d_f32(x: torch.Tensor) -> torch.Tensor:
+    """3x3 / stride 2 / no padding, floor mode, on NHWC fp32.  As torch.max_pool2d, a NaN in any tap of a window is the window's
+    maximum (the three max-pools share this: a non-finite pixel is not dropped on the way to a score); a window of -inf gives
+    -inf; the rows and columns the floor drops are not read."""
     n, h, w, c = x.shape
     y = torch.empty(n, max((h - 3) // 2 + 1, 0), max((w - 3) // 2 + 1, 0), c, dtype=torch.float32, device=x.device)
     check(lib.ur_maxpool2d_f32(x.data_ptr(), y.data_ptr(), n, h, w, c, stream()))
@@ -91,7 +97,7 @@ def maxpool2d_f32(x: torch.Tensor) -> torch.Tensor:
 
 
 def maxpool2d_pad_f32(x: torch.Tensor) -> torch.Tensor:
-    """3x3 / stride 2 / padding 1 (-inf) on NHWC fp32."""
+    """3x3 / stride 2 / padding 1 (-inf) on NHWC fp32.  NaN and -inf as in maxpool2d_f32."""
     n, h, w, c = x.shape
     y = torch.empty(n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c, dtype=torch.float32, device=x.device)
     check(lib.ur_maxpool2d_pad_f32(x.data_ptr(), y.data_ptr(), n, h, w, c, stream()))
@@ -99,7 +105,7 @@ def maxpool2d_pad_f32(x: torch.Tensor) -> torch.Tensor:
 
 
 def maxpool5_f32(x: torch.Tensor) -> torch.Tensor:
-    """5x5 / stride 1 / padding 2 (-inf) on NHWC fp32."""
+    """5x5 / stride 1 / padding 2 (-inf) on NHWC fp32.  NaN and -inf as in maxpool2d_f32, with C % 4 == 0 (float4) or not."""
     n, h, w, c = x.shape
     y = torch.empty_like(x)
     check(lib.ur_maxpool5_f32(x.data_ptr(), y.data_ptr(), n, h, w, c, stream()))

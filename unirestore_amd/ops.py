@@ -1084,7 +1084,9 @@ def image_metrics(pred: torch.Tensor, target: torch.Tensor, data_range: float = 
 def lpips(pred: torch.Tensor, target: torch.Tensor, weights) -> torch.Tensor:
     """LPIPS (AlexNet, normalize=True: inputs in [0,1]) of fp32 NCHW batches on the GPU -> fp64 [N] device tensor.  weights: what
     lpips.load_weights / lpips.random_weights return.  Predictions and targets go through the network as one batch of 2N; exact
-    fp32 (fp32-input MFMA convolutions), fixed-order sums, so two calls give the same bits.  No host sync."""
+    fp32 (fp32-input MFMA convolutions), fixed-order sums, so two calls give the same bits.  No host sync.  A NaN or an infinity
+    in an image of either batch makes that image's distance NaN, as the fp64 restatement of the metric in torch does; the other
+    images' distances are the bits a clean batch gives."""
     from . import lpips as _lpips
     for name, t in (("pred", pred), ("target", target)):
         _check_images("lpips", name, t)
@@ -1120,7 +1122,9 @@ def classify(images: torch.Tensor, weights) -> torch.Tensor:
     """Logits [N, classes] (fp32, on the device) of fp32 NCHW images in [0,1], any H, W >= 1: the classification evaluator's
     preprocess (antialiased bilinear resize to 224 x 224, ImageNet normalisation) and a ResNet, in exact fp32 on the GPU.  weights:
     what classify.load_weights / classify.random_weights return.  An image's logits do not depend on its place in the batch, and
-    two calls give the same bits.  No host sync."""
+    two calls give the same bits.  No host sync.  A non-finite pixel is not erased on the way: every logit is finite, infinite or
+    NaN exactly where the fp64 restatement in torch is (one NaN pixel: every logit of that image is NaN, and `top1`, as
+    torch.argmax, then predicts the first NaN's class); the other images' logits are the bits a clean batch gives."""
     from . import classify as _classify
     _check_images("classify", "images", images)
     n, c, h, w = images.shape
@@ -1181,7 +1185,10 @@ def segment(images: torch.Tensor, weights, size=None, scales=(1, 0.8, 0.6)) -> t
     input falls below 32 px on a side.  An image's result does not depend on its place in the batch, and two calls give the same
     bytes.  No host sync - except on the FIRST call for a new image size, target size or set of scales, which builds that shape's
     tap tables on the host and uploads them with a blocking copy: run a shape once eagerly before capturing it in a graph.  The
-    tables (a few KB per shape) stay on the device for the life of the process, so a captured graph never loses the ones it reads."""
+    tables (a few KB per shape) stay on the device for the life of the process, so a captured graph never loses the ones it reads.
+    A non-finite pixel is not erased on the way: the averaged logits are finite, infinite or NaN exactly where the fp64 restatement
+    in torch is, a pixel whose class vector holds a NaN is given its first NaN's class (torch.argmax), and the other images'
+    predictions are the bytes a clean batch gives."""
     from .segment import SegmenterWeights
     return _segmenter("segment", images, weights, SegmenterWeights, size, scales)
 
@@ -1192,8 +1199,8 @@ def deeplab(images: torch.Tensor, weights, size=None, scales=(1, 0.8, 0.6)) -> t
     scale), the ImageNet Normalize and the network; then one kernel takes every scale's classifier map through the model's own
     half-pixel resize to that scale's input and the evaluator's align_corners=True resize to `size` (default: the images' own H,
     W), averages and takes the argmax (ties to the lowest class).  weights: what deeplab.load_weights / deeplab.random_weights
-    return.  ValueError when the smallest scale's input falls below 16 px on a side.  The same guarantees and the same first-call
-    table upload as `segment`: run a shape once eagerly before capturing it in a graph."""
+    return.  ValueError when the smallest scale's input falls below 16 px on a side.  The same guarantees - for non-finite pixels
+    too - and the same first-call table upload as `segment`: run a shape once eagerly before capturing it in a graph."""
     from .deeplab import DeepLabWeights
     return _segmenter("deeplab", images, weights, DeepLabWeights, size, scales)
 
