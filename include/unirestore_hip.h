@@ -82,19 +82,23 @@ typedef struct ur_conv_desc {
   const float* bias;    /* fp32 [Cout] or NULL */
   const void* residual; /* bf16 [M, ldr] or NULL (M = N*OH*OW) */
   void* y;              /* 16-bit (or fp32 if out_f32) [M, ldy]; may be NULL if only gn_part is wanted */
-  void* yt;             /* bf16 transposed output for columns >= n_split: [M/t_rows][Cout-n_split][t_ld] or NULL */
+  void* yt;             /* bf16 transposed output for columns >= n_split: [M/t_rows][Cout-n_split][t_ld] or NULL
+                           (nbatch == 1 only: yt has no batch stride) */
   float* gn_part;       /* fp32 [N][P][nbatch*Cout_out][2] = partial (sum, sum of squares) of the 16-bit outputs per image,
                            row chunk and channel, plain stores (P = ur_conv_plan.gn_parts): statistics for the GroupNorm /
                            InstanceNorm / AdaptiveAvgPool2d(1) that consumes y (ur_groupnorm_finalize), or NULL.  With
                            ur_conv_plan.gn_fused the epilogue writes them and y may be NULL (pooled output only:
-                           taskeditor.py:35); otherwise one extra pass over y does */
+                           taskeditor.py:35); otherwise one extra pass over y does.  Needs Cout_out % 8 == 0 (the statistics run
+                           on vectors of 8 channels), whichever source writes them: UR_E_INVALID otherwise.  The extra pass of
+                           a batched launch (nbatch > 1) needs the batches side by side in y's rows (bs_y == Cout_out) */
   const float* gn_ab;   /* fp32 [N][2][C1+C2] per-(image, input channel) affine (a | b) from ur_groupnorm_finalize, or NULL:
                            the conv reads act(a*x + b) instead of x (GroupNorm apply [+ SiLU] of ResnetBlock2D fused into the
                            conv's loader; zero padding stays zero).  Only where ur_conv_plan.prologue_ok */
   int gn_silu;          /* 1: SiLU after the gn_ab affine */
   float* row_stats;     /* fp32 [parts][M][2] = per-row (sum, sum of squares) of this GEMM's output, one partial plane per N
                            tile (plain stores; parts = ur_conv_plan.row_stat_parts from ur_conv2d_plan): the LayerNorm statistics of the
-                           GEMM that consumes y (BasicTransformerBlock norm1-3) or NULL */
+                           GEMM that consumes y (BasicTransformerBlock norm1-3) or NULL.  With yt the sums cover only y's
+                           columns below n_split: the transposed columns are not part of them */
   const float* ln_stats;  /* fp32 [ln_parts][M][2] row sums of x (a producer's row_stats): this GEMM computes W.LayerNorm(x) as
                              rstd*(acc - mean*ln_colsum[n]) + bias[n] with w = W*gamma, bias = W.beta + b prefolded; or NULL */
   const float* ln_colsum; /* fp32 [Cout]: sum_k of the (bf16) folded weight row */
@@ -118,7 +122,8 @@ typedef struct ur_conv_desc {
   int k_chunk_major;    /* 1: weight K index runs (64-channel chunk, tap, channel) instead of (tap, channel): the taps of
                            one chunk are consecutive K tiles, so re-reads of a pixel hit L2 (needs C1, C1+C2 % 64 == 0) */
   long long bias_img_stride; /* 0: one bias row; else bias row of image n = m/(OH*OW) is bias + n*stride
-                                (per-sample time embeddings, unifie.py:91-105) */
+                                (per-sample time embeddings, unifie.py:91-105).  Not with pair activations, ln_stats, yt
+                                or row_stats */
   int dtype;            /* UR_DT_BF16 | UR_DT_F16: type of x, x2, w, residual, y (unless out_f32), yt */
   const void* w_frag;   /* optional second packing of the SAME weights for the weight-streaming kernel of the 8 x 8 maps (3x3, stride 1,
                            Cout % 128 == 0, (C1+C2) % 256 == 0), or NULL: MFMA-fragment-major
@@ -140,14 +145,17 @@ int ur_conv2d_plan(const ur_conv_desc* d, ur_conv_plan* plan);
 
 /* host-only query (no launch, no HIP call): which launcher runs `d` and how it splits the work, by the same workspace rule as
  * the launch (d->workspace / d->workspace_bytes).  Fill d as for ur_conv2d_plan.  A grouped conv that runs one launch per group
- * (group_loop) reports the launch of one group. */
+ * (group_loop) reports the launch of one group.  It refuses, with the launch's own error, what the launch refuses and
+ * ur_conv2d_plan only reports: gn_ab without prologue_ok, y == NULL without a fused gn_part, row_stats / ln_stats without a
+ * staged 16-bit output of one batch. */
 typedef struct ur_conv_launch_info {
   int launcher;       /* index of the launcher: ur_conv_launcher_name(launcher) */
   int splitk;         /* K splits (1: no split, no reduce pass) */
   int nk_per_split;   /* 64-deep K tiles per split */
   int reduce;         /* reduce pass after the splits: -1 none, 0 plain, 1 row-wise (LayerNorm statistics), 2 GroupNorm partials */
   int reduce_ri;      /* reduce 2: 16 * reduce_ri output rows per block (4, 2 or 1); else 0 */
-  int gn_pass;        /* 1: the GroupNorm partials come from an extra pass over y (ur_conv_plan.gn_fused == 0) */
+  int gn_pass;        /* 1: the GroupNorm partials come from an extra pass over y (ur_conv_plan.gn_fused == 0); the launch then
+                         needs a dense y (ldy == nbatch * Cout_out) and refuses any other before it runs anything */
   int group_loop;     /* 1: one halo launch per group on its channel slice */
 } ur_conv_launch_info;
 int ur_conv2d_plan_launch(const ur_conv_desc* d, ur_conv_launch_info* info);

@@ -7,6 +7,9 @@ for the launcher they name; the features are the ones that launcher's dispatch a
 workspace sizes: WS_FULL (the size ops.workspace passes), "less" (one split fewer than the full plan, only for split launches) and
 "none" (a NULL workspace, as C callers may pass), plus any `ws` entries of its own.  `launchers` names the launcher of a workspace
 variant where it is not the case's own (the unsplit twin of a split launcher, or the kernel that runs when the weight stream does not fit).
+
+The first 61 cases are the bases of tests/conv_launcher_space.py; the cases with a "+" in their id add features to a base's geometry so
+that every feature and feature pair the plan accepts on a launch path is run (the gate in tests/test_conv_plan_cpu.py names what is missing).
 """
 
 MiB = 1 << 20
@@ -69,7 +72,7 @@ def geometry(c, gn_pass=False):
     g["ldx"] = c["C1"] + c["ldx_pad"]
     g["ldw"] = K
     g["ldy"] = ldy(c, gn_pass)
-    g["ldr"] = cout_out(c) + 8 if c["res"] else 0
+    g["ldr"] = cout_out(c) * (c["groups"] or 1) + 8 if c["res"] else 0      # (grouped: the groups' residual columns side by side)
     if c["groups"]:
         G = c["groups"]
         g.update(ldx=c["C1"] * G, ldw=K, bs_x=c["C1"], bs_w=c["Cout"] * K, bs_bias=c["Cout"], bs_y=c["Cout"], bs_r=c["Cout"])
@@ -80,7 +83,7 @@ def geometry(c, gn_pass=False):
         ns, tr = c["yt"]
         g.update(n_split=ns, t_rows=tr, t_ld=tr + 8)
     if c["bias_img"]:
-        g["bias_img_stride"] = c["Cout"]
+        g["bias_img_stride"] = c["Cout"] * (c["groups"] or 1)
     if c["ln"]:
         g.update(ln_dim=K, ln_parts=2, ln_eps=1e-5)
     if c["gn_ab"]:
@@ -213,4 +216,148 @@ CASES = [
     case("group_halo_loop", "halo_8x32_128", 1, 128, 128, 128, 128, groups=2, act=SILU),
     case("bmm_f32_scale", "g1_64x64", 1, 1, 100, 64, 72, KH=1, bmm=3, out_f32=True, out_scale=0.125, bias=False),
     case("bmm_split", "v1_64x64", 1, 1, 200, 1024, 96, KH=1, bmm=2, bias=False, launchers={"none": "g1_64x64"}),
+    # ---- feature pairs (tests/conv_launcher_space.py): the id is "<base id>+<features added>".  A case is its base - geometry AND every
+    # feature the base's own line sets, whether or not the base's id spells it (g1_128x128_ragged_res_gelu has out_scale=0.5, g1_64x64_gn
+    # has res) - with the features after the "+" switched on as well; its line repeats all of them.  Chosen greedily, so that together with the cases above they run every (launch path, feature) and
+    # (launch path, feature pair) the plan accepts with up to two features added to a base; ordered by launcher.
+    case("wstream_n3_cat_rowbias_silu+out_f32", "v1_128x128", 3, 8, 8, 256, 128, C2=256, act=SILU, wfrag=True, bias_img=True, out_f32=True),
+    case("v1_128x128_3x3_split+bias_img+gn+out_scale", "v1_128x128", 1, 16, 16, 64, 128, act=SILU, res=True, bias_img=True, gn=True, out_scale=0.5),
+    case("v1_128x128_3x3_s2_asym+gn+rows", "v1_128x128", 2, 33, 33, 64, 128, stride=2, pad=(0, 1), act=GELU, gn=True, rows=True),
+    case("v1_128x128_3x3_s2_asym+res+bias_img+gn+out_scale", "v1_128x128", 2, 33, 33, 64, 128, stride=2, pad=(0, 1), act=GELU, res=True,
+         bias_img=True, gn=True, out_scale=0.5),
+    case("v1_128x128_3x3_s2_asym+res+bias_img+out_f32+out_scale", "v1_128x128", 2, 33, 33, 64, 128, stride=2, pad=(0, 1), act=GELU, res=True,
+         bias_img=True, out_f32=True, out_scale=0.5),
+    case("v1_128x128_3x3_s2_asym+res+rows+out_scale", "v1_128x128", 2, 33, 33, 64, 128, stride=2, pad=(0, 1), act=GELU, res=True, rows=True,
+         out_scale=0.5),
+    case("v1_128x128_3x3_split_gn+rows", "v1_128x128", 1, 16, 16, 128, 128, res=True, gn=True, rows=True),
+    case("v1_128x128_ln_rows_split+act+gn+out_scale", "v1_128x128", 1, 1, 250, 2048, 256, KH=1, act=SILU, res=True, gn=True, rows=True, ln=True,
+         out_scale=0.5),
+    case("v1_128x128_ln_rows_split+act+yt+out_scale", "v1_128x128", 1, 1, 250, 2048, 256, KH=1, act=SILU, res=True, rows=True, ln=True, yt=(128, 50),
+         out_scale=0.5),
+    case("v1_128x128_f32_scale_split+res+act+yt", "v1_128x128", 1, 1, 250, 2048, 256, KH=1, act=SILU, res=True, yt=(128, 50), out_f32=True,
+         out_scale=0.5),
+    case("v1_128x160_3x3_split_gn+act+bias_img+out_scale", "v1_128x160", 1, 16, 16, 64, 160, act=SILU, res=True, bias_img=True, gn=True,
+         out_scale=0.5),
+    case("v1_128x160_3x3_split_gn+act+rows+out_scale", "v1_128x160", 1, 16, 16, 64, 160, act=SILU, res=True, gn=True, rows=True, out_scale=0.5),
+    case("v1_128x160_cat+bias_img+gn+out_scale", "v1_128x160", 1, 1, 4000, 160, 960, KH=1, C2=160, act=GELU, res=True, bias_img=True, gn=True,
+         out_scale=0.5),
+    case("v1_128x160_cat+bias_img+out_f32", "v1_128x160", 1, 1, 4000, 160, 960, KH=1, C2=160, act=GELU, res=True, bias_img=True, out_f32=True),
+    case("v1_128x160_cat+gn+rows", "v1_128x160", 1, 1, 4000, 160, 960, KH=1, C2=160, act=GELU, res=True, gn=True, rows=True),
+    case("v1_128x160_cat+rows+yt", "v1_128x160", 1, 1, 4000, 160, 960, KH=1, C2=160, act=GELU, res=True, rows=True, yt=(480, 100)),
+    case("v1_128x160_cat+yt+out_f32+out_scale", "v1_128x160", 1, 1, 4000, 160, 960, KH=1, C2=160, act=GELU, res=True, yt=(480, 100), out_f32=True,
+         out_scale=0.5),
+    case("v1_128x64_ktail+gn+ln+out_scale", "v1_128x64", 1, 1, 4100, 200, 64, KH=1, act=GELU, res=True, gn=True, rows=True, ln=True, out_scale=0.5),
+    case("v1_128x64_ktail+ln+yt+out_scale", "v1_128x64", 1, 1, 4100, 200, 64, KH=1, act=GELU, res=True, rows=True, ln=True, yt=(32, 100),
+         out_scale=0.5),
+    case("v1_128x64_gn+res+act+bias_img+out_scale", "v1_128x64", 4, 32, 32, 200, 64, KH=1, act=SILU, res=True, bias_img=True, gn=True, out_scale=0.5),
+    case("v1_128x64_gn+rows+ln", "v1_128x64", 4, 32, 32, 200, 64, KH=1, gn=True, rows=True, ln=True),
+    case("v1_256x32_ragged_n_f32+res+act+bias_img+out_scale", "v1_256x32", 1, 1, 4100, 200, 20, KH=1, act=SILU, res=True, bias_img=True,
+         out_f32=True, out_scale=0.5, ldy_pad=4),
+    case("v1_256x32_ragged_n_f32+res+act+yt+out_scale", "v1_256x32", 1, 1, 4100, 200, 20, KH=1, act=SILU, res=True, yt=(8, 100), out_f32=True,
+         out_scale=0.5, ldy_pad=4),
+    case("v1_256x32_rows_gn+res+act+ln+out_scale", "v1_256x32", 4, 32, 32, 200, 32, KH=1, act=SILU, res=True, gn=True, rows=True, ln=True,
+         out_scale=0.5),
+    case("v1_64x64_cat_split+act+bias_img+gn+out_scale", "v1_64x64", 1, 1, 1024, 320, 640, KH=1, C2=320, act=SILU, res=True, bias_img=True, gn=True,
+         out_scale=0.5),
+    case("v1_64x64_cat_split+act+bias_img+out_f32+out_scale", "v1_64x64", 1, 1, 1024, 320, 640, KH=1, C2=320, act=SILU, res=True, bias_img=True,
+         out_f32=True, out_scale=0.5),
+    case("v1_64x64_cat_split+act+rows+yt+out_scale", "v1_64x64", 1, 1, 1024, 320, 640, KH=1, C2=320, act=SILU, res=True, rows=True, yt=(320, 64),
+         out_scale=0.5),
+    case("v1_64x64_cat_split+act+yt+out_f32+out_scale", "v1_64x64", 1, 1, 1024, 320, 640, KH=1, C2=320, act=SILU, res=True, yt=(320, 64),
+         out_f32=True, out_scale=0.5),
+    case("v1_64x64_cat_split+gn+rows", "v1_64x64", 1, 1, 1024, 320, 640, KH=1, C2=320, res=True, gn=True, rows=True),
+    case("v1_64x64_rows_split+res+act+gn+ln+out_scale", "v1_64x64", 1, 1, 500, 640, 256, KH=1, act=SILU, res=True, gn=True, rows=True, ln=True,
+         out_scale=0.5, launchers={"none": "g1_64x64"}),
+    case("v1_64x64_rows_split+res+act+ln+yt+out_scale", "v1_64x64", 1, 1, 500, 640, 256, KH=1, act=SILU, res=True, rows=True, ln=True, yt=(128, 100),
+         out_scale=0.5, launchers={"none": "g1_64x64"}),
+    case("bmm_split+res+act+out_f32+out_scale", "v1_64x64", 1, 1, 200, 1024, 96, KH=1, act=SILU, bias=False, res=True, out_f32=True, out_scale=0.5,
+         bmm=2, launchers={"none": "g1_64x64"}),
+    case("v2_256x32_s2_asym_f32+res+act+bias_img+out_scale", "v2_256x32", 2, 33, 33, 40, 20, stride=2, pad=(1, 0), act=SILU, res=True, bias_img=True,
+         out_f32=True, out_scale=0.5, ldy_pad=4),
+    case("v2_256x32_split_gn+act+bias_img+out_scale", "v2_256x32", 1, 16, 16, 128, 32, act=SILU, res=True, bias_img=True, gn=True, out_scale=0.5),
+    case("v2_256x32_split_gn+act+rows+out_scale", "v2_256x32", 1, 16, 16, 128, 32, act=SILU, res=True, gn=True, rows=True, out_scale=0.5),
+    case("v2_128x64_split_gn+res+bias_img+out_scale", "v2_128x64", 1, 16, 16, 128, 64, act=SILU, res=True, bias_img=True, gn=True, out_scale=0.5),
+    case("v2_128x64_split_gn+rows+out_scale", "v2_128x64", 1, 16, 16, 128, 64, act=SILU, gn=True, rows=True, out_scale=0.5),
+    case("group_generic+res+bias_img+out_f32+out_scale", "v2_128x64", 1, 16, 16, 32, 36, act=SILU, res=True, bias_img=True, out_f32=True,
+         out_scale=0.5, groups=4),
+    case("v2_256x160_s2_gnpass+bias_img+out_scale", "v2_256x160", 1, 406, 406, 32, 160, stride=2, act=SILU, res=True, bias_img=True, gn=True,
+         out_scale=0.5),
+    case("v2_256x160_s2_gnpass+rows+out_scale", "v2_256x160", 1, 406, 406, 32, 160, stride=2, act=SILU, res=True, gn=True, rows=True, out_scale=0.5),
+    case("v2_256x128_asym_f32_scale+res+act+bias_img", "v2_256x128", 2, 144, 144, 32, 128, pad=(0, 1), act=SILU, res=True, bias_img=True,
+         out_f32=True, out_scale=0.25),
+    case("v2_256x128_rowbias_gn+res+act+out_scale", "v2_256x128", 2, 144, 144, 32, 128, act=SILU, res=True, bias_img=True, gn=True, out_scale=0.5),
+    case("gemm256_geglu_res_rows+gn+ln+out_scale", "gemm_256x256", 1, 1, 25700, 72, 512, KH=1, act=GEGLU, res=True, gn=True, rows=True, ln=True,
+         out_scale=0.5),
+    case("gemm256_geglu_res_rows+ln+out_scale", "gemm_256x256", 1, 1, 25700, 72, 512, KH=1, act=GEGLU, res=True, rows=True, ln=True, out_scale=0.5),
+    case("gemm320_geglu_res+gn+rows+ln+out_scale", "gemm_256x320_pair", 1, 1, 8100, 72, 2560, KH=1, act=GEGLU, res=True, gn=True, rows=True, ln=True,
+         out_scale=0.5),
+    case("gemm320_geglu_res+rows+ln+out_scale", "gemm_256x320_pair", 1, 1, 8100, 72, 2560, KH=1, act=GEGLU, res=True, rows=True, ln=True,
+         out_scale=0.5),
+    case("g1_128x128_ragged_res_gelu+bias_img+gn", "g1_128x128", 1, 1, 4100, 200, 1288, KH=1, act=GELU, res=True, bias_img=True, gn=True,
+         out_scale=0.5),
+    case("g1_128x128_ragged_res_gelu+bias_img+out_f32", "g1_128x128", 1, 1, 4100, 200, 1288, KH=1, act=GELU, res=True, bias_img=True, out_f32=True,
+         out_scale=0.5),
+    case("g1_128x128_ragged_res_gelu+gn+rows+ln", "g1_128x128", 1, 1, 4100, 200, 1288, KH=1, act=GELU, res=True, gn=True, rows=True, ln=True,
+         out_scale=0.5),
+    case("g1_128x128_ragged_res_gelu+rows+ln", "g1_128x128", 1, 1, 4100, 200, 1288, KH=1, act=GELU, res=True, rows=True, ln=True, out_scale=0.5),
+    case("g1_128x128_ragged_res_gelu+yt+out_f32", "g1_128x128", 1, 1, 4100, 200, 1288, KH=1, act=GELU, res=True, yt=(644, 100), out_f32=True,
+         out_scale=0.5),
+    case("g1_128x160_ragged+act+gn+ln+out_scale", "g1_128x160", 1, 1, 4100, 200, 960, KH=1, act=SILU, res=True, gn=True, rows=True, ln=True,
+         out_scale=0.5),
+    case("g1_128x160_ragged+act+ln+yt+out_scale", "g1_128x160", 1, 1, 4100, 200, 960, KH=1, act=SILU, res=True, rows=True, ln=True, yt=(480, 100),
+         out_scale=0.5),
+    case("g1_128x64_ragged+bias_img+gn", "g1_128x64", 1, 1, 4100, 200, 1280, KH=1, act=SILU, res=True, bias_img=True, gn=True),
+    case("g1_128x64_ragged+bias_img+out_f32+out_scale", "g1_128x64", 1, 1, 4100, 200, 1280, KH=1, act=SILU, res=True, bias_img=True, out_f32=True,
+         out_scale=0.5),
+    case("g1_128x64_ragged+gn+rows+ln+out_scale", "g1_128x64", 1, 1, 4100, 200, 1280, KH=1, act=SILU, res=True, gn=True, rows=True, ln=True,
+         out_scale=0.5),
+    case("g1_128x64_ragged+rows+ln+yt+out_scale", "g1_128x64", 1, 1, 4100, 200, 1280, KH=1, act=SILU, res=True, rows=True, ln=True, yt=(640, 100),
+         out_scale=0.5),
+    case("g1_128x64_ragged+yt+out_f32", "g1_128x64", 1, 1, 4100, 200, 1280, KH=1, act=SILU, res=True, yt=(640, 100), out_f32=True),
+    case("g1_64x64_ragged_yt+out_f32", "g1_64x64", 1, 1, 1000, 200, 1288, KH=1, yt=(1032, 100), out_f32=True),
+    case("g1_64x64_gn+act+bias_img+out_scale", "g1_64x64", 4, 16, 16, 200, 1288, KH=1, act=SILU, res=True, bias_img=True, gn=True, out_scale=0.5),
+    case("g1_64x64_gn+rows+ln", "g1_64x64", 4, 16, 16, 200, 1288, KH=1, res=True, gn=True, rows=True, ln=True),
+    case("g1_64x64_deep_ragged_ln+res+act+gn+out_scale", "g1_64x64_deep", 1, 1, 500, 520, 1040, KH=1, act=SILU, res=True, gn=True, rows=True,
+         ln=True, out_scale=0.5),
+    case("g1_64x64_deep_ragged_ln+res+act+yt+out_scale", "g1_64x64_deep", 1, 1, 500, 520, 1040, KH=1, act=SILU, res=True, rows=True, ln=True,
+         yt=(520, 100), out_scale=0.5),
+    case("g1_128x64_deep_ragged+bias_img+gn", "g1_128x64_deep", 1, 1, 2000, 1608, 1040, KH=1, act=GELU, res=True, bias_img=True, gn=True),
+    case("g1_128x64_deep_ragged+bias_img+out_f32+out_scale", "g1_128x64_deep", 1, 1, 2000, 1608, 1040, KH=1, act=GELU, res=True, bias_img=True,
+         out_f32=True, out_scale=0.5),
+    case("g1_128x64_deep_ragged+gn+rows+ln+out_scale", "g1_128x64_deep", 1, 1, 2000, 1608, 1040, KH=1, act=GELU, res=True, gn=True, rows=True,
+         ln=True, out_scale=0.5),
+    case("g1_128x64_deep_ragged+rows+ln+yt+out_scale", "g1_128x64_deep", 1, 1, 2000, 1608, 1040, KH=1, act=GELU, res=True, rows=True, ln=True,
+         yt=(520, 100), out_scale=0.5),
+    case("g1_128x64_deep_ragged+yt+out_f32", "g1_128x64_deep", 1, 1, 2000, 1608, 1040, KH=1, act=GELU, res=True, yt=(520, 100), out_f32=True),
+    case("h160_ups_cat_rowbias_silu_gn+res+out_scale", "halo_8x32_160", 2, 32, 32, 64, 320, C2=64, ups=True, act=SILU, res=True, bias_img=True,
+         gn=True, out_scale=0.5),
+    case("h160_chunksplit_res_gn+act+bias_img+out_scale", "halo_8x32_160", 2, 64, 64, 256, 320, act=SILU, res=True, bias_img=True, gn=True,
+         out_scale=0.5),
+    case("h160_chunksplit_res_gn+act+rows+out_scale", "halo_8x32_160", 2, 64, 64, 256, 320, act=SILU, res=True, gn=True, rows=True, out_scale=0.5),
+    case("h128_ups_cat_rowbias_gelu_gnab+res+out_scale", "halo_8x32_128", 2, 32, 32, 64, 256, C2=64, ups=True, act=GELU, res=True, bias_img=True,
+         gn=True, gn_ab=True, out_scale=0.5),
+    case("h128_chunksplit_gnab_res_gn+act+bias_img+out_scale", "halo_8x32_128", 2, 64, 64, 256, 256, act=SILU, res=True, bias_img=True, gn=True,
+         gn_ab=True, out_scale=0.5),
+    case("h128_chunksplit_gnab_res_gn+act+rows+out_scale", "halo_8x32_128", 2, 64, 64, 256, 256, act=SILU, res=True, gn=True, gn_ab=True, rows=True,
+         out_scale=0.5),
+    case("group_halo_loop+res+out_scale", "halo_8x32_128", 1, 128, 128, 128, 128, act=SILU, res=True, out_scale=0.5, groups=2),
+    case("thin_c32_f32_res+act+out_scale", "halo_thin_32", 2, 64, 256, 64, 32, act=SILU, res=True, out_f32=True, out_scale=0.5, zero_rows=4),
+    case("himg16_n3_cat_rowbias_silu_gn+res+gn_ab+out_scale", "himg_16x16", 3, 16, 16, 128, 256, C2=128, act=SILU, res=True, bias_img=True, gn=True,
+         gn_ab=True, out_scale=0.5),
+    case("himg16_n4_gelu+res+bias_img+gn_ab+out_scale", "himg_16x16", 4, 16, 16, 256, 128, act=GELU, res=True, bias_img=True, gn_ab=True,
+         out_scale=0.5),
+    case("himg16_n4_gelu+res+gn_ab+rows+out_scale", "himg_16x16", 4, 16, 16, 256, 128, act=GELU, res=True, gn_ab=True, rows=True, out_scale=0.5),
+    case("himg16_n5_ups_gnab_gn+res+act+bias_img+out_scale", "himg_16x16", 5, 8, 8, 256, 128, ups=True, act=SILU, res=True, bias_img=True, gn=True,
+         gn_ab=True, out_scale=0.5),
+    case("himg16_n5_ups_gnab_gn+res+act+rows+out_scale", "himg_16x16", 5, 8, 8, 256, 128, ups=True, act=SILU, res=True, gn=True, gn_ab=True,
+         rows=True, out_scale=0.5),
+    case("himg16_n16_res_gn+act+bias_img+gn_ab+out_scale", "himg_16x16", 16, 16, 16, 256, 256, act=SILU, res=True, bias_img=True, gn=True,
+         gn_ab=True, out_scale=0.5),
+    case("himg8_n4_res_gn+act+rows+out_scale", "himg_8x8x4", 4, 8, 8, 256, 128, act=SILU, res=True, gn=True, rows=True, out_scale=0.5),
+    case("himg8_n16_cat_rowbias_silu_gn+res+out_scale", "himg_8x8x4", 16, 8, 8, 128, 256, C2=128, act=SILU, res=True, bias_img=True, gn=True,
+         out_scale=0.5),
+    case("wstream_n3_cat_rowbias_silu+res+gn+out_scale", "wstream_8x8", 3, 8, 8, 256, 128, C2=256, act=SILU, wfrag=True, res=True, bias_img=True,
+         gn=True, out_scale=0.5, launchers={"less": "v1_128x128", "none": "v1_128x128"}),
+    case("wstream_n3_cat_rowbias_silu+res+out_scale", "wstream_8x8", 3, 8, 8, 256, 128, C2=256, act=SILU, wfrag=True, res=True, bias_img=True,
+         out_scale=0.5, launchers={"less": "v1_128x128", "none": "v1_128x128"}),
 ]

@@ -12,6 +12,9 @@ fewer splits, none, and any edge sizes of the case):
   * runs twice into fresh NaN buffers and requires bit-identical outputs and planes;
   * checks every output element against the bound, the whole output against the rel-L2 tolerance of tests/test_ops_gpu.py, and the
     GroupNorm / row-sum planes per (image, channel) / per row against fp64 sums of the kernel's own 16-bit output.
+
+The table also runs every (launch path, feature) and (launch path, feature pair) that planning accepts around its base cases
+(tests/conv_launcher_space.py; the CPU gate in tests/test_conv_plan_cpu.py holds the table against that space).
 """
 import ctypes
 import math
@@ -143,7 +146,8 @@ def _reference(c, t, xs, wl, dt_out):
             mean = st[:, 0] / dim
             var = (st[:, 1] / dim - mean * mean).clamp_min(0)
             ln = (mean, 1.0 / torch.sqrt(var + 1e-5), t["ln_colsum"].double().cuda())
-        res = t["residual"].double().cuda()[:, :T.cout_out(c)] if c["res"] else None
+        rc0 = b * T.cout_out(c) if c["groups"] else 0             # (bmm_nt descriptors have no residual stride: one tile for every batch)
+        res = t["residual"].double().cuda()[:, rc0:rc0 + T.cout_out(c)] if c["res"] else None
         ref, Ao, eps = R.epilogue(acc, A, c["act"], bias, c["out_scale"], res, ln)
         bnd = R.bound(ref, Ao, eps, K, dt_out)
         if amb is not None:
@@ -239,6 +243,8 @@ def test_launcher_parity(capi, c, dtype):
     t, xs, wl = _inputs(c, dt)
     ydt = torch.float32 if c["out_f32"] else dt
     ref, bnd, K = _reference(c, t, xs, wl, ydt)
+    # the transposed columns are 16-bit whatever y is: the same bound with the 16-bit output terms (u_out |ref| + abs_out)
+    bnd_t = bnd + (R.U_OUT[dt] - R.U_OUT[ydt]) * ref.abs() + (R.ABS_OUT[dt] - R.ABS_OUT[ydt])
     ws_full = torch.empty(T.WS_FULL // 4, dtype=torch.float32, device="cuda")
     d = capi.ConvDesc()
     ph = dict(T.placeholders(c), workspace=T.P)
@@ -266,7 +272,7 @@ def test_launcher_parity(capi, c, dtype):
             ns, tr = c["yt"]
             yt = b["yt"]
             vt = yt[..., :tr].permute(0, 2, 1).reshape(M, c["Cout"] - ns).double()
-            worst = max(worst, R.compare(vt[None], ref[..., ns:], bnd[..., ns:], what + " yt"))
+            worst = max(worst, R.compare(vt[None], ref[..., ns:], bnd_t[..., ns:], what + " yt"))
             assert bool(torch.isnan(yt[..., tr:].float()).all()), what + ": yt padding written"
         y16 = got if not c["out_f32"] else None
         if c["gn"]:
@@ -276,11 +282,12 @@ def test_launcher_parity(capi, c, dtype):
             worst = max(worst, R.compare_sums(s[..., 0], s[..., 1], yy, M // c["N"], what + f" GroupNorm plane (P = {P})"))
         if c["rows"]:
             s = b["row_stats"].double().sum(0)                             # [M][2]
-            worst = max(worst, R.compare_sums(s[:, 0], s[:, 1], y16[0], co, what + " row sums"))
+            worst = max(worst, R.compare_sums(s[:, 0], s[:, 1], y16[0], width, what + " row sums"))     # (with yt: the columns below n_split)
         key = (capi.launcher_names()[info.launcher], dtype)
         WORST[key] = max(WORST.get(key, 0.0), worst)
     # ur_groupconv3x3_nhwc builds the same descriptor (its weights are tap-major: the chunk-major group loop is reachable only raw)
-    if c["groups"] and not c["kcm"]:
+    wrapper = not (c["res"] or c["bias_img"] or c["out_f32"] or c["out_scale"] != 1.0)       # (the wrapper takes none of these)
+    if c["groups"] and not c["kcm"] and wrapper:
         dev = {k: v.cuda() for k, v in t.items()}
         y = torch.empty(M, co * G, dtype=dt, device="cuda")
         capi.check(capi.lib.ur_groupconv3x3_nhwc(dev["x"].data_ptr(), dev["w"].data_ptr(), dev["bias"].data_ptr(), y.data_ptr(), c["N"], c["H"],

@@ -8,6 +8,7 @@ import re
 import pytest
 
 import conv_launcher_cases as LC
+import conv_launcher_space as LS
 from unirestore_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -173,6 +174,61 @@ def test_launcher_matrix_covers_every_launcher_and_path(dtype):
     assert want <= paths, f"paths no case reaches: {want - paths}"
 
 
+# (path, feature pair) combinations the plan accepts and no case runs: combo id (conv_launcher_space.combo_id) -> reason.  The only
+# reasons allowed: the plan accepts the combination only at a shape too large for a few-second test, or the combination has been
+# turned into a refusal.  At most 5 % of the reachable pairs, no single feature; an entry that is covered or no longer reachable fails.
+EXEMPT = {
+}
+EXEMPT_CAP = 0.05
+
+
+def _gate(dtype, pairs):
+    reach = {i for i in LS.reachable(capi, dtype) if LS.is_pair_id(i) == pairs}
+    cov = LS.covered(capi, dtype) & reach
+    what = "pairs" if pairs else "singles"
+    print(f"\nconv launcher space [{'fp16' if dtype == capi.UR_DT_F16 else 'bf16'}]: {len(reach)} reachable (path, feature"
+          f"{' pair' if pairs else ''}) combinations, {len(cov)} covered")
+    exempt = {i for i in EXEMPT if LS.is_pair_id(i) == pairs}
+    stale = sorted(i for i in exempt if i in cov or i not in reach)
+    assert not stale, f"exemptions that are covered or no longer reachable: {stale}"
+    missing = sorted(reach - cov - exempt)
+    assert not missing, f"{len(missing)} reachable {what} no case of conv_launcher_cases.CASES runs:\n" + "\n".join(missing)
+    return reach, exempt
+
+
+@pytest.mark.parametrize("dtype", [capi.UR_DT_BF16, capi.UR_DT_F16])
+def test_launcher_matrix_covers_every_reachable_feature(dtype):
+    """Every (path, feature) the plan accepts on a base case's launcher (tests/conv_launcher_space.py) has a case.  No exemptions."""
+    assert not [i for i in EXEMPT if not LS.is_pair_id(i)], "single features cannot be exempted"
+    _gate(dtype, pairs=False)
+
+
+@pytest.mark.parametrize("dtype", [capi.UR_DT_BF16, capi.UR_DT_F16])
+def test_launcher_matrix_covers_every_reachable_feature_pair(dtype):
+    """Every (path, feature pair) the plan accepts on a base case's launcher has a case, but for the listed exemptions."""
+    reach, exempt = _gate(dtype, pairs=True)
+    assert len(exempt) <= EXEMPT_CAP * len(reach), f"{len(exempt)} exemptions for {len(reach)} reachable pairs: above 5 %"
+
+
+def test_launcher_space_is_fixed():
+    """The bases are the 61 cases the space was defined on, all still in the table; the enumeration is deterministic."""
+    ids = [c["id"] for c in LC.CASES]
+    assert len(ids) == len(set(ids)) and set(LS.BASES) <= set(ids)
+    assert len(LS.TOGGLES) == 10
+    # a "<base>+<features>" id says what the case is: exactly its base with those toggles applied, nothing more and nothing less
+    by_id = {c["id"]: c for c in LC.CASES}
+    for c in LC.CASES:
+        base, *added = c["id"].split("+")
+        if added:
+            v = by_id[base]
+            for f in added:
+                v = LS.TOGGLES[f](v)
+                assert v is not None, (c["id"], f)
+            skip = ("id", "launcher", "launchers")
+            assert {k: x for k, x in v.items() if k not in skip} == {k: x for k, x in c.items() if k not in skip}, c["id"]
+    assert LS.reachable(capi, capi.UR_DT_BF16) == LS.reachable(capi, capi.UR_DT_BF16)
+
+
 @pytest.mark.parametrize("dt", ["bf16", "fp16"])
 def test_comparator_rejects_subtle_errors(dt):
     """The per-element bound of tests/conv_reference.py accepts the fp64 reference after 16-bit rounding and rejects a ragged tile
@@ -234,3 +290,55 @@ def test_plan_refusals():
     assert capi.lib.ur_conv2d_nhwc(d, None) == capi.UR_E_UNSUPPORTED
     assert capi.lib.ur_last_error().decode() == \
         "ur_conv2d_nhwc: y == NULL needs a launch whose epilogue writes gn_part (see ur_conv2d_plan)"
+    # GroupNorm statistics run on vectors of 8 channels: 4 output channels divided by zero while planning the extra pass (the
+    # process died), 12 / 20 would have left the last four channels' sums unwritten.  Refused, whichever source writes the sums.
+    for cout in (4, 12, 20):
+        d = _desc(N=2, H=64, W=256, cin=64, cout=cout, kh=3, kcm=1, residual=P, ldr=cout + 8, gn_part=P)
+        for rc in (capi.lib.ur_conv2d_plan(d, capi.ConvPlan()), capi.lib.ur_conv2d_plan_launch(d, capi.ConvLaunchInfo()),
+                   capi.lib.ur_conv2d_nhwc(d, None)):
+            assert rc == capi.UR_E_INVALID, cout
+            assert "gn_part needs output channels % 8 == 0" in capi.lib.ur_last_error().decode()
+    d = _desc(N=2, H=64, W=256, cin=64, cout=8, kh=3, kcm=1, residual=P, ldr=16, gn_part=P)
+    assert _plan(d)[1] > 0
+    def refused(d, code, words):
+        for rc in (capi.lib.ur_conv2d_plan(d, capi.ConvPlan()), capi.lib.ur_conv2d_plan_launch(d, capi.ConvLaunchInfo()),
+                   capi.lib.ur_conv2d_nhwc(d, None)):
+            assert rc == code, words
+            assert words in capi.lib.ur_last_error().decode()
+
+    def accepted(d):
+        assert capi.lib.ur_conv2d_plan(d, capi.ConvPlan()) == 0, capi.lib.ur_last_error()
+        info = capi.ConvLaunchInfo()
+        assert capi.lib.ur_conv2d_plan_launch(d, info) == 0, capi.lib.ur_last_error()
+        return info
+
+    # per-image bias rows with row sums: 2 x 16 x 17 outputs in 128-row tiles straddle images, take the unstaged epilogue, and that one
+    # writes no row sums (the row_stats plane would stay as it was).  Either feature alone is accepted.
+    asym = dict(N=2, H=33, W=33, cin=64, cout=128, kh=3, stride=2, pad_t=0, pad_l=1, OH=16, OW=17, bias=P)
+    refused(_desc(**asym, bias_img_stride=128, row_stats=P), capi.UR_E_INVALID, "per-image bias rows do not combine with row_stats")
+    accepted(_desc(**asym, bias_img_stride=128))
+    accepted(_desc(**asym, row_stats=P))
+    # transposed columns of a batched launch: yt has no batch stride, every batch would write the same block
+    bmm = dict(N=1, H=1, W=200, cin=1024, cout=96, kh=1)
+    yt = dict(yt=P, n_split=48, t_rows=100, t_ld=108)
+    refused(_desc(**bmm, nbatch=2, **yt), capi.UR_E_INVALID, "transposed columns (yt) need nbatch == 1")
+    accepted(_desc(**bmm, **yt))
+    # GroupNorm sums of a batched launch that cannot fuse them (200 rows: no whole tile per image): the extra pass reads one dense
+    # [M][nbatch * Cout] tensor, which a batch-major y (bs_y = M * Cout) is not at any ldy; batches side by side (bs_y == Cout) are
+    # accepted, planned onto the extra pass, and launched only with a dense ldy - refused before anything runs otherwise
+    refused(_desc(**bmm, nbatch=2, gn_part=P, bs_y=200 * 96, ldy=96), capi.UR_E_UNSUPPORTED,
+            "gn_part of a batched launch that cannot fuse the statistics needs bs_y == output channels per batch")
+    side = _desc(**bmm, nbatch=2, gn_part=P)
+    assert (side.bs_y, side.ldy) == (96, 192) and accepted(side).gn_pass == 1 and _plan(side)[2] == 0
+    side.ldy = 200
+    assert accepted(side).gn_pass == 1
+    assert capi.lib.ur_conv2d_nhwc(side, None) == capi.UR_E_INVALID
+    assert "gn_part fallback needs a dense output (ldy == channels)" in capi.lib.ur_last_error().decode()
+    # what the launch refuses, the launch plan refuses with the same words
+    d = _desc(N=1, H=1, W=4096, cin=320, cout=1280, kh=1, gn_ab=P)
+    assert capi.lib.ur_conv2d_plan_launch(d, capi.ConvLaunchInfo()) == capi.UR_E_UNSUPPORTED
+    assert "gn_ab is not supported by this launch" in capi.lib.ur_last_error().decode()
+    d = _desc(N=1, H=1, W=4096, cin=320, cout=1280, kh=1, row_stats=P, out_f32=1)     # row sums are taken from the staged 16-bit tile
+    assert capi.lib.ur_conv2d_plan_launch(d, capi.ConvLaunchInfo()) == capi.UR_E_INVALID
+    assert "row_stats / ln fusion need a bf16 staged output" in capi.lib.ur_last_error().decode()
+    assert capi.lib.ur_conv2d_nhwc(d, None) == capi.UR_E_INVALID

@@ -143,6 +143,7 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, ur_conv_plan* pl
   UR_REQUIRE(!d->y || (d->out_f32 ? d->ldy % 4 == 0 : d->ldy % 4 == 0), "ldy%4");
   UR_REQUIRE(!d->residual || d->ldr % 4 == 0, "ldr%4");
   UR_REQUIRE(!d->yt || (d->t_rows > 0 && d->n_split % 4 == 0 && !pair), "bad transposed-output spec");
+  UR_REQUIRE(!d->yt || d->nbatch == 1, "transposed columns (yt) need nbatch == 1 (yt has no batch stride)");
   // Size limits (include/unirestore_hip.h, "size limits"), checked before any int product of the dimensions, one factor at a time
   // (every partial product is below 2^31 before the next int is multiplied in, so no 64-bit product can wrap either):
   //  * output rows M = N * OH * OW: row indices are int and a tile may start up to one tile (<= 256 rows) short of M and run past it.
@@ -190,10 +191,18 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, ur_conv_plan* pl
   UR_REQUIRE(!d->ln_stats || (d->ln_colsum && d->ln_dim > 0), "ln_stats needs ln_colsum / ln_dim");
   // feature combinations the specialised epilogues cover (each is one compiled instance; see epi_frag_pass)
   UR_REQUIRE(!(d->bias_img_stride && (pair || d->ln_stats || d->yt)), "per-image bias rows do not combine with pair activations / LayerNorm folding / transposed columns");
+  // (a tile that straddles images of another size than its own takes the unstaged epilogue (igemm_epilogue: bias_geom_ok), which
+  //  writes no row sums: 2 x 16 x 17 outputs in 128-row tiles would leave the row_stats plane as it was.  The plan does not know the
+  //  tile height before dispatch and no caller pairs the two - refused, never computed wrongly.)
+  UR_REQUIRE(!(d->bias_img_stride && d->row_stats), "per-image bias rows do not combine with row_stats");
   // staged (LDS-tiled, 16-byte row stores) epilogue: 16-bit y with aligned rows, or no y at all (statistics-only launch)
   k.staged_ok_ = (d->y ? (!d->out_f32 && ((d->ldy | d->bs_y) & 7) == 0) : d->gn_part != nullptr) &&
                  (!d->residual || ((d->ldr | d->bs_r) & 7) == 0);
   UR_REQUIRE(!d->gn_part || (!d->out_f32 && !d->yt), "gn_part needs a plain 16-bit output (or none)");
+  // the statistics pass (csrc/norms.hip gn_geom) works on vectors of 8 channels: 4 output channels divided by zero there (SIGFPE
+  // while planning) and 12 / 20 would leave their last four channels' sums unwritten.  No fused source is exercised at such a width either, so the rule
+  // holds for every source of the partials (refused, never computed wrongly); before dispatch_conv, whose plan sizes the pass
+  UR_REQUIRE(!d->gn_part || (pair ? d->Cout / 2 : d->Cout) % 8 == 0, "gn_part needs output channels % 8 == 0 (GroupNorm statistics run on 8-channel vectors)");
   hipStream_t s = (hipStream_t)stream;
   const double flops = 2.0 * k.M * (double)k.Cout * k.Ktot * k.nbatch;
   const double bytes = 2.0 * ((double)k.M * k.Cin + (double)k.Cout * k.Ktot + (double)k.M * k.Cout) * k.nbatch;
@@ -224,6 +233,10 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, ur_conv_plan* pl
     kb.bs_x = kb.bs_w = kb.bs_bias = kb.bs_y = kb.bs_r = 0;
     return kb;
   };
+  // The extra statistics pass reads y as one dense [M][nbatch * channels] tensor: batches must sit side by side in its rows (the
+  // grouped conv's layout), not one after the other (bmm_nt's): no ldy makes that layout dense, so both plans refuse it.
+  if (k.gn_part && !k.gn_fused && !group_loop && k.nbatch > 1 && d->y && d->bs_y != (pair ? k.Cout / 2 : k.Cout))
+    return ur::fail(UR_E_UNSUPPORTED, "ur_conv2d_nhwc: gn_part of a batched launch that cannot fuse the statistics needs bs_y == output channels per batch");
   if (plan) {      // row-stat planes: one per N tile, or the single one of a split-K reduce pass
     plan->row_stat_parts = d->row_stats ? (k.splitk > 1 ? 1 : k.tiles_n) : 0;
     plan->gn_parts = k.gn_parts; plan->gn_fused = k.gn_fused; plan->prologue_ok = launch.prologue_ok;
@@ -237,14 +250,20 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, ur_conv_plan* pl
     info->gn_pass = k.gn_part && !k.gn_fused && !group_loop;
     info->group_loop = group_loop;
   }
-  if (plan || info) return UR_OK;
+  if (plan) return UR_OK;
+  // What the launch refuses, ur_conv2d_plan_launch refuses too: it answers what runs (ur_conv2d_plan only sizes the planes).
   // statistics-only launch: only where the epilogue itself produces the partials
   if (!d->y && d->gn_part && (!k.gn_fused || k.splitk > 1))
     return ur::fail(UR_E_UNSUPPORTED, "ur_conv2d_nhwc: y == NULL needs a launch whose epilogue writes gn_part (see ur_conv2d_plan)");
   if (d->gn_ab && !launch.prologue_ok)
     return ur::fail(UR_E_UNSUPPORTED, "ur_conv2d_nhwc: gn_ab is not supported by this launch (see ur_conv2d_plan.prologue_ok)");
+  UR_REQUIRE(!(d->row_stats || d->ln_stats) || (k.staged_ok_ && k.nbatch == 1), "row_stats / ln fusion need a bf16 staged output");
+  if (info) return UR_OK;
+  // The extra statistics pass needs a dense y.  Checked before anything runs (it used to fail after the conv had written y); the two
+  // plans do not refuse it - they report gn_pass / gn_fused for a descriptor whose ldy the caller may still choose.
+  const int gn_pass_ctot = (pair ? k.Cout / 2 : k.Cout) * k.nbatch;
+  UR_REQUIRE(!(k.gn_part && !k.gn_fused) || (k.y && k.ldy == gn_pass_ctot), "gn_part fallback needs a dense output (ldy == channels)");
   ur::ProfScope prof(fam, flops, bytes, s);
-  UR_REQUIRE(!(d->row_stats || d->ln_stats) || (k.staged_ok_ && k.nbatch == 1 && !d->yt == !d->yt), "row_stats / ln fusion need a bf16 staged output");
   if (group_loop) {
     for (int b = 0; b < d->nbatch; ++b) {
       ConvK kb = group_k(b);
@@ -255,11 +274,8 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, ur_conv_plan* pl
   }
   const int rc = launch.launch(&k, s);
   if (rc != UR_OK) return rc;
-  if (k.gn_part && !k.gn_fused) {   // this launch could not fuse the statistics: one extra pass over the output
-    const int ctot = (pair ? k.Cout / 2 : k.Cout) * k.nbatch;
-    UR_REQUIRE(k.y && k.ldy == ctot, "gn_part fallback needs a dense output (ldy == channels)");
-    return ur::gn_stats_launch(k.y, k.gn_part, k.N, k.OHW, ctot, d->dtype, s);
-  }
+  if (k.gn_part && !k.gn_fused)     // this launch could not fuse the statistics: one extra pass over the (dense, checked above) output
+    return ur::gn_stats_launch(k.y, k.gn_part, k.N, k.OHW, gn_pass_ctot, d->dtype, s);
   return UR_OK;
 }
 
