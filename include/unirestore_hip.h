@@ -592,6 +592,35 @@ int ur_dlv3_tta_argmax(const float* q0, const float* q1, const float* q2, int nm
                        const float* ac_wt_h, const int* ac_idx_w, const float* ac_wt_w, const int* hp_idx_h, const float* hp_wt_h,
                        const int* hp_idx_w, const float* hp_wt_w, unsigned char* pred, float* avg, ur_stream_t stream);
 
+/* ---- ViT scoring of the cls output (torchvision's VisionTransformer; exact fp32, token-major, no atomics, fixed-order sums) ---
+ * The network's Linears (patch embedding, in_proj, out_proj, fc1, fc2, head) are the convolution above on tokens [N,1,S,D]; the
+ * residual sums ride its res input.  What is new here is csrc/vit.hip.  The same inputs give the same bits, eagerly and under
+ * graph replay; an image's results do not depend on its place in the batch.
+ *
+ * The layer-norm entry point: row r of x starts at x + r * ldx (ldx >= D: ldx = S * D normalises the class-token rows of [N,S,D]
+ *   alone), y is dense [rows][D], not x.  y = (x - mean) / sqrt(var + eps) * gamma + beta per row, with the mean first and then
+ *   the biased variance of the centred values, both in fp64, rounded to fp32 once.  Any D >= 1; float4 accesses when D and ldx are
+ *   multiples of 4 and the four pointers 16-byte aligned.  A row that holds a NaN or an infinity is all NaN, as F.layer_norm.
+ * The GELU entry point: y = 0.5 x (1 + erf(x / sqrt 2)) with libm's erff over n values; y may be x.  NaN -> NaN, +inf -> +inf,
+ *   -inf -> NaN (the formula's own result).
+ * The embedding entry point: patches [N,P,D], class_token [D], pos [P+1,D] -> y [N,P+1,D]: token 0 = class_token + pos[0], token
+ *   1 + p = patch p + pos[1 + p].
+ * The attention entry point: qkv [N,S,3D] as nn.MultiheadAttention's in_proj writes it (q | k | v, head h in columns h d .. h d +
+ *   d - 1 of each) -> out [N,S,D] = softmax(q k^T / sqrt d) v per (image, head), heads concatenated.  Both products run on
+ *   v_mfma_f32_32x32x2_f32 with K and V of the head in LDS; the softmax is exact (row maximum, libm expf, fixed-order sum, IEEE
+ *   division).  A score row with a NaN or +inf is all NaN, a -inf score has weight 0, a NaN in V reaches every query of its
+ *   (image, head).  The size limit of S is what the s_max entry point returns: UR_VIT_S_MAX.
+ * Limits (64-bit arithmetic, before any HIP call): layer norm: rows below 2^31 - 256, ldx >= D, eps >= 0.  GELU: n in
+ *   [1, 2^31 - 256).  Embedding: N*(P+1)*D below 2^31 - 256.  Attention: d = 64, D = H * d, 1 <= S <= UR_VIT_S_MAX, N*H <= 2^22,
+ *   qkv 16-byte aligned, out not qkv. */
+#define UR_VIT_S_MAX 256
+int ur_vit_attention_s_max(void);
+int ur_layernorm_f32(const float* x, const float* gamma, const float* beta, float* y, int rows, int D, double eps, long long ldx,
+                     ur_stream_t stream);
+int ur_gelu_f32(const float* x, float* y, long long n, ur_stream_t stream);
+int ur_vit_embed_f32(const float* patches, const float* class_token, const float* pos, float* y, int N, int P, int D, ur_stream_t stream);
+int ur_vit_attention_f32(const float* qkv, float* out, int N, int S, int H, int d, int D, ur_stream_t stream);
+
 /* ---- colour correction of a restored image (between the decoder's conv_out and the egress kernels) ----------------------
  * c fp32 NHWC [N,H,W,ld_c]: the restored image; src 16-bit NHWC [src_n,H,W,ld_s]: the image the encoder saw, image n is corrected
  * against source n % src_n (a task-major K*B batch against B sources); out fp32 NHWC [N,H,W,ld_c], not c.  Channels 0..2 are RGB;

@@ -144,6 +144,11 @@ SIGNATURES = {
     "ur_dlv3_broadcast_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "ur_dlv3_upsample_f32": (_I, [_P, _P] + [_I] * 7 + [_P, _P, _P, _P, _P]),
     "ur_dlv3_tta_argmax": (_I, [_P, _P, _P] + [_I] * 17 + [_P] * 8 + [_P, _P, _P]),
+    "ur_vit_attention_s_max": (_I, []),
+    "ur_layernorm_f32": (_I, [_P, _P, _P, _P, _I, _I, C.c_double, _LL, _P]),
+    "ur_gelu_f32": (_I, [_P, _P, _LL, _P]),
+    "ur_vit_embed_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "ur_vit_attention_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "ur_color_fix_wavelet": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "ur_color_fix_adain": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "ur_color_fix_adain_ws_bytes": (_SZ, [_I, _I, _I]),

@@ -1,6 +1,7 @@
 """The fp32 NHWC layer format of the scoring networks (LPIPS's AlexNet, the classifier's ResNet, the segmenters' RefineNet-LW and
 DeepLabV3+), stated once: the `[Kpad][Cout_pad]` weight repack and `PackedConvF32`, the launch wrappers of csrc/f32_layers.hip
-(the table-driven bilinear resize with either table, dense or into a channel slice, among them), the state-dict checks with the
+(the table-driven bilinear resize with either table, dense or into a channel slice, among them) and of the two generic layers of
+csrc/vit.hip (LayerNorm and the exact-erf GELU, which the ViT scorer of vit.py brought), the state-dict checks with the
 conv + BatchNorm fold, and the torchvision-layout ResNet backbone that three of the networks share.  What belongs to one metric
 alone (its preprocess, its head, its formula) stays in lpips.py, classify.py, segment.py and deeplab.py; the next scoring network
 is written against this module.
@@ -124,6 +125,43 @@ def add_f32(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """a + b on contiguous fp32 tensors of one shape."""
     y = torch.empty_like(a)
     check(lib.ur_add_f32(a.data_ptr(), b.data_ptr(), y.data_ptr(), a.numel(), stream()))
+    return y
+
+
+def _check_rows(who, x):
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous() or x.ndim < 1 or x.numel() < 1:
+        raise ValueError(f"{who}: needs a non-empty contiguous fp32 device tensor, got {getattr(x, 'dtype', type(x))} "
+                         f"{tuple(getattr(x, 'shape', ()))} on {getattr(x, 'device', 'the host')}")
+
+
+def layernorm_f32(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, first_row_of: int = 1) -> torch.Tensor:
+    """F.layer_norm over the last axis of a contiguous fp32 [..., D] tensor: (x - mean) / sqrt(var + eps) * gamma + beta, the mean
+    first and then the biased variance of the centred values, in fp64, rounded to fp32 once.  first_row_of = S > 1: x is [N, S, D]
+    and only row 0 of every image is normalised (a ViT's class token) -> [N, D].
+    Non-finite inputs: a row that holds a NaN or an infinity is all NaN, as F.layer_norm; the other rows keep their bits."""
+    _check_rows("layernorm_f32", x)
+    d = x.shape[-1]
+    for name, t in (("gamma", gamma), ("beta", beta)):
+        if not torch.is_tensor(t) or tuple(t.shape) != (d,) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"layernorm_f32: {name} must be a contiguous fp32 ({d},) tensor on {x.device}, got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    if first_row_of == 1:
+        rows, ldx, shape = x.numel() // d, d, x.shape
+    else:
+        if x.ndim != 3 or x.shape[1] != first_row_of:
+            raise ValueError(f"layernorm_f32: first_row_of={first_row_of} needs an [N, {first_row_of}, D] tensor, got {tuple(x.shape)}")
+        rows, ldx, shape = x.shape[0], first_row_of * d, (x.shape[0], d)
+    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    check(lib.ur_layernorm_f32(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), rows, d, float(eps), ldx, stream()))
+    return y
+
+
+def gelu_f32(x: torch.Tensor, inplace: bool = False) -> torch.Tensor:
+    """The exact-erf GELU 0.5 x (1 + erf(x / sqrt 2)) of a contiguous fp32 tensor, with libm's erff; inplace: x is overwritten and
+    returned.  Non-finite inputs: NaN -> NaN, +inf -> +inf, -inf -> NaN (-inf * 0, the formula's own result and torch's in fp64)."""
+    _check_rows("gelu_f32", x)
+    y = x if inplace else torch.empty_like(x)
+    check(lib.ur_gelu_f32(x.data_ptr(), y.data_ptr(), x.numel(), stream()))
     return y
 
 
