@@ -621,6 +621,32 @@ int ur_gelu_f32(const float* x, float* y, long long n, ur_stream_t stream);
 int ur_vit_embed_f32(const float* patches, const float* class_token, const float* pos, float* y, int N, int P, int D, ur_stream_t stream);
 int ur_vit_attention_f32(const float* qkv, float* out, int N, int S, int H, int d, int D, ur_stream_t stream);
 
+/* ---- Swin-V2 scoring of the cls output (torchvision's SwinTransformer with SwinTransformerBlockV2 / PatchMergingV2; exact fp32,
+ * NHWC tokens [N,H,W,C], no atomics, fixed-order sums) ---------------------------------------------------------------------------
+ * The network's Linears (patch embedding 4x4 / 4, qkv, proj, mlp.0, mlp.3, the patch-merging reduction as a 2x2 / 2 convolution,
+ * head) are the convolution above; LayerNorm and GELU are the ViT block's.  What is new is csrc/swin.hip and the residual layer norm.
+ *
+ * The residual layer-norm entry point: y = res + LN(x) over dense [rows][D]: the layer-norm entry point's fp64 moments and single
+ *   rounding to fp32, then one fp32 addition - the post-norm residual x + norm(f(x)) of a V2 block in one pass.  y is neither x
+ *   nor res.  A row of x that holds a NaN or an infinity is all NaN; a non-finite res element stays in its place.
+ * The window-attention entry point: qkv [N,H,W,3C] (q | k | v, head h in columns 32 h .. 32 h + 31 of each; C = 32 heads), qkv_bias
+ *   [3C], scale [heads], bias [heads,64,64] -> out [N,H,W,C], all fp32.  Attention inside 8 x 8 windows of the map, zero-padded on
+ *   the bottom and right to multiples of 8 and rolled by (-shift, -shift) (per axis the shift is 0 when the padded axis is one
+ *   window): score = normalize(q) . normalize(k) * scale[h] + bias[h][i][j] - 100 where the two tokens' regions differ (only when
+ *   a shift is in force), normalize(v) = v / max(|v|, 1e-12); softmax over the window's 64 slots; P V; each real token's result
+ *   goes back to its own (i, j).  A padded token takes its q, k, v from qkv_bias (the Linear of a zero row) and is NOT masked, as
+ *   in torchvision; the caller zeroes the k third of qkv_bias as torchvision's forward does.  No padded, rolled or partitioned
+ *   tensor is ever written.  Both products run on v_mfma_f32_32x32x2_f32 with the window's K and V in LDS; the softmax is exact
+ *   (row maximum, libm expf, fixed-order sum, IEEE division).  A score row with a NaN or +inf is all NaN, a NaN in V reaches every
+ *   query of its (window, head); other images keep their bits.
+ * Limits (64-bit arithmetic, before any HIP call): residual layer norm: rows below 2^31 - 256, eps >= 0.  Window attention: N, H,
+ *   W, heads >= 1, shift 0 or 4, N*H*W below 2^31, N * ceil(H/8) * ceil(W/8) * heads below 2^31 - 256 (one workgroup per (image,
+ *   window, head)), qkv, qkv_bias and bias 16-byte aligned, out not qkv. */
+int ur_layernorm_res_f32(const float* x, const float* res, const float* gamma, const float* beta, float* y, int rows, int D, double eps,
+                         ur_stream_t stream);
+int ur_swin_attention_f32(const float* qkv, const float* qkv_bias, const float* scale, const float* bias, float* out, int N, int H,
+                          int W, int heads, int shift, ur_stream_t stream);
+
 /* ---- colour correction of a restored image (between the decoder's conv_out and the egress kernels) ----------------------
  * c fp32 NHWC [N,H,W,ld_c]: the restored image; src 16-bit NHWC [src_n,H,W,ld_s]: the image the encoder saw, image n is corrected
  * against source n % src_n (a task-major K*B batch against B sources); out fp32 NHWC [N,H,W,ld_c], not c.  Channels 0..2 are RGB;

@@ -7,6 +7,7 @@
 //
 // Limits, checked before any HIP call:
 //   ur_layernorm_f32: rows, D >= 1, ldx >= D, rows below 2^31 - 256 (one wave per row, four rows per workgroup); 64-bit offsets.
+//   ur_layernorm_res_f32 (y = res + LN(x), the post-norm residual of the Swin-V2 scorer): the same with ldx = D; y is not res.
 //   ur_gelu_f32: n in [1, 2^31 - 256).
 //   ur_vit_embed_f32: N, P, D >= 1, N * (P + 1) * D below 2^31 - 256.
 //   ur_vit_attention_f32: d = 64, D = H * d, 1 <= S <= UR_VIT_S_MAX = 256 (K and V of one head stay in LDS: S rounded up to 32
@@ -39,10 +40,12 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 
 constexpr int LN_KEEP = 4;      // vectors per lane held in registers
 
-template <int V>
+// RES: y = res + LN(x), the post-norm residual of a Swin-V2 block - LN(x) rounded to fp32 once as without RES, then one fp32 addition
+// (res is dense [rows][D], not y).
+template <int V, bool RES = false>
 __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, float* __restrict__ y, int rows, int D,
-                                                            double eps, long long ldx) {
+                                                            double eps, long long ldx, const float* __restrict__ res) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;                       // whole waves leave: no barrier follows
@@ -109,6 +112,11 @@ __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restr
 #pragma unroll
     for (int k = 0; k < V; ++k)
       o[k] = (float)(((double)v[k] - mean) * rstd * (double)gamma[(long long)i * V + k] + (double)beta[(long long)i * V + k]);
+    if constexpr (RES) {
+      const float* rp = res + (long long)row * D + (long long)i * V;
+#pragma unroll
+      for (int k = 0; k < V; ++k) o[k] = rp[k] + o[k];
+    }
     if constexpr (V == 4) *reinterpret_cast<float4*>(dst + 4ll * i) = make_float4(o[0], o[1], o[2], o[3]);
     else dst[i] = o[0];
   };
@@ -315,9 +323,26 @@ int ur_layernorm_f32(const float* x, const float* gamma, const float* beta, floa
   hipStream_t s = (hipStream_t)stream;
   ur::ProfScope prof("layernorm_f32", 8.0 * rows * (double)D, 8.0 * rows * (double)D, s);
   const bool vec = D % 4 == 0 && ldx % 4 == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0;
-  if (vec) hipLaunchKernelGGL(layernorm_f32_kernel<4>, dim3(blocks), dim3(256), 0, s, x, gamma, beta, y, rows, D, eps, ldx);
-  else hipLaunchKernelGGL(layernorm_f32_kernel<1>, dim3(blocks), dim3(256), 0, s, x, gamma, beta, y, rows, D, eps, ldx);
+  if (vec) hipLaunchKernelGGL(layernorm_f32_kernel<4>, dim3(blocks), dim3(256), 0, s, x, gamma, beta, y, rows, D, eps, ldx, nullptr);
+  else hipLaunchKernelGGL(layernorm_f32_kernel<1>, dim3(blocks), dim3(256), 0, s, x, gamma, beta, y, rows, D, eps, ldx, nullptr);
   return ur::check_launch("ur_layernorm_f32");
+}
+
+int ur_layernorm_res_f32(const float* x, const float* res, const float* gamma, const float* beta, float* y, int rows, int D, double eps,
+                         ur_stream_t stream) {
+  UR_REQUIRE(x && res && gamma && beta && y, "null pointer");
+  UR_REQUIRE(x != y && res != y, "y must not be the same buffer as x or res");
+  UR_REQUIRE(rows >= 1 && D >= 1, "rows and D must be >= 1");
+  UR_REQUIRE(eps >= 0.0 && eps == eps, "eps must be >= 0");
+  UR_REQUIRE((long long)rows < ur::GRID_1D_LIMIT, "too many rows: rows must be below 2^31 - 256");
+  UR_GRID_1D(blocks, rows, 4);
+  hipStream_t s = (hipStream_t)stream;
+  ur::ProfScope prof("layernorm_res_f32", 9.0 * rows * (double)D, 12.0 * rows * (double)D, s);
+  const long long ldx = D;
+  const bool vec = D % 4 == 0 && (((uintptr_t)x | (uintptr_t)res | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0;
+  if (vec) hipLaunchKernelGGL((layernorm_f32_kernel<4, true>), dim3(blocks), dim3(256), 0, s, x, gamma, beta, y, rows, D, eps, ldx, res);
+  else hipLaunchKernelGGL((layernorm_f32_kernel<1, true>), dim3(blocks), dim3(256), 0, s, x, gamma, beta, y, rows, D, eps, ldx, res);
+  return ur::check_launch("ur_layernorm_res_f32");
 }
 
 int ur_gelu_f32(const float* x, float* y, long long n, ur_stream_t stream) {

@@ -1151,6 +1151,24 @@ def vit(images: torch.Tensor, weights) -> torch.Tensor:
     return _vit.forward(images, weights)
 
 
+def swin(images: torch.Tensor, weights) -> torch.Tensor:
+    """`classify` with a Swin-V2: logits [N, classes] (fp32, on the device) of fp32 NCHW images in [0,1], any H, W >= 1 - the
+    classification evaluator's preprocess (antialiased bilinear resize to 224 x 224, ImageNet normalisation) and a torchvision-
+    layout SwinTransformer V2 in exact fp32 on the GPU (the fp32 convolution as every Linear, patch embedding and patch merging;
+    LayerNorm and GELU of csrc/vit.hip; the fused shifted-window cosine attention of csrc/swin.hip).  weights: what
+    swin.load_weights / swin.random_weights return; `top1` takes the logits as it takes `classify`'s.  An image's logits do not
+    depend on its place in the batch, and two calls give the same bits.  No host sync.  A non-finite pixel is not erased on the
+    way: every logit of that image is NaN, as in the fp64 restatement in torch; the other images' logits are the bits a clean
+    batch gives."""
+    from . import swin as _swin
+    _check_images("swin", "images", images)
+    n, c, h, w = images.shape
+    if n < 1 or c != 3 or h < 1 or w < 1:
+        raise ValueError(f"swin: needs [N>=1, 3, H>=1, W>=1] images, got {tuple(images.shape)}")
+    _check_scorer("swin", "weights", weights, _swin.SwinWeights, "swin.load_weights / swin.random_weights")
+    return _swin.forward(images, weights)
+
+
 def top1(logits: torch.Tensor, labels: torch.Tensor):
     """(pred, tp, targets, predicted) of one batch: pred int64 [N] = the argmax of logits fp32 [N,C] (ties to the lowest index, as
     torch.argmax), and the three int64 [C] per-class counts of classify.accuracy - tp_c (pred = label = c), targets_c, predicted_c.
