@@ -647,6 +647,32 @@ int ur_layernorm_res_f32(const float* x, const float* res, const float* gamma, c
 int ur_swin_attention_f32(const float* qkv, const float* qkv_bias, const float* scale, const float* bias, float* out, int N, int H,
                           int W, int heads, int shift, ur_stream_t stream);
 
+/* ---- RVT scoring of the cls output (the reference's own PoolingTransformer, src/modules/rvt/robust_models.py; exact fp32, NHWC
+ * tokens [N,H,W,C] = [N,S,C], no atomics, fixed-order sums) ---------------------------------------------------------------------
+ * The network's Linears and 1 x 1 convolutions (the two stem convolutions, qkv, proj, fc1, fc2, head) are the convolution above
+ * with every BatchNorm folded in; LayerNorm, GELU, the padded max-pool and the mean over the map exist.  What is new is csrc/rvt.hip.
+ *
+ * The attention entry point: qkv [N,S,3 H d] (q | k | v, head h in columns h d .. h d + d - 1 of each), gate [H,S,S] or NULL ->
+ *   out [N,S,H d], all fp32.  score[i][j] = ((q_i . k_j) * d^-0.5) * gate[h][i][j] (without a gate: the scaled dot product), then
+ *   an exact softmax over the S keys and P V, per (image, head) - RVT's position-aware attention scaling with gate =
+ *   sigmoid(att_mask).  d = 64: q is scaled by 1/8 before the product (exact); d = 32: the finished dot product is multiplied by
+ *   fp32(32^-0.5); the gate is one more fp32 multiplication.  With gate NULL and d = 64 the result equals the ViT attention entry
+ *   point's bit for bit.  Both products run on v_mfma_f32_32x32x2_f32 with K and V of the head in LDS (rows d + 1 and d floats
+ *   apart); the gate is read from global memory, as float4 when S % 4 == 0 and gate is 16-byte aligned.  Non-finite values as the
+ *   ViT entry point; a gate of exactly 0 against an infinite score is NaN, as in torch.
+ * The depthwise entry point: x NHWC [N,H,W,C], w [9][C mult] (tap-major: w[3 ky + kx][o] is the OIHW filter's [o][0][ky][kx]),
+ *   bias [C mult] -> y [N,OH,OW,C mult], OH = (H - 1) / stride + 1 (3 x 3, pad 1).  Output channel o reads input channel o / mult
+ *   (groups = C).  y = act(sum over the taps inside the map, in row-major tap order with fmaf from 0, + bias); act 0: none, 1: the
+ *   GELU entry point's function (the same bits as act 0 followed by it).  A tap in the padding is skipped, so a non-finite input
+ *   reaches only the outputs whose window holds it.  float4 accesses when mult == 1, C % 4 == 0 and the four pointers are 16-byte
+ *   aligned.
+ * Limits (64-bit arithmetic, before any HIP call): attention: d 32 or 64, 1 <= S <= UR_VIT_S_MAX, N, H >= 1, N*H <= 2^22, qkv
+ *   16-byte aligned, out and gate 4-byte aligned, out overlapping neither qkv nor gate.  Depthwise: N, H, W, C, mult >= 1, stride 1
+ *   or 2, act 0 or 1, N*H*W*C and N*OH*OW*C*mult below 2^31 - 256, pointers 4-byte aligned, y overlapping none of x, w, bias. */
+int ur_rvt_attention_f32(const float* qkv, const float* gate, float* out, int N, int S, int H, int d, ur_stream_t stream);
+int ur_dwconv3x3_f32(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int C, int mult, int stride, int act,
+                     ur_stream_t stream);
+
 /* ---- colour correction of a restored image (between the decoder's conv_out and the egress kernels) ----------------------
  * c fp32 NHWC [N,H,W,ld_c]: the restored image; src 16-bit NHWC [src_n,H,W,ld_s]: the image the encoder saw, image n is corrected
  * against source n % src_n (a task-major K*B batch against B sources); out fp32 NHWC [N,H,W,ld_c], not c.  Channels 0..2 are RGB;

@@ -151,6 +151,8 @@ SIGNATURES = {
     "ur_vit_attention_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "ur_layernorm_res_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, C.c_double, _P]),
     "ur_swin_attention_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "ur_rvt_attention_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "ur_dwconv3x3_f32": (_I, [_P, _P, _P, _P] + [_I] * 7 + [_P]),
     "ur_color_fix_wavelet": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "ur_color_fix_adain": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "ur_color_fix_adain_ws_bytes": (_SZ, [_I, _I, _I]),

@@ -1169,6 +1169,24 @@ def swin(images: torch.Tensor, weights) -> torch.Tensor:
     return _swin.forward(images, weights)
 
 
+def rvt(images: torch.Tensor, weights) -> torch.Tensor:
+    """`classify` with a Robust Vision Transformer: logits [N, classes] (fp32, on the device) of fp32 NCHW images in [0,1], any H,
+    W >= 1 - the classification evaluator's preprocess (antialiased bilinear resize to 224 x 224, ImageNet normalisation) and the
+    reference's own PoolingTransformer (rvt_tiny / rvt_small / rvt_base and their `_plus` variants) in exact fp32 on the GPU (the
+    fp32 convolution as the stem, every Linear and every 1 x 1 convolution, BatchNorm folded in; LayerNorm and GELU of csrc/vit.hip;
+    the gated attention and the depthwise 3 x 3 convolution of csrc/rvt.hip).  weights: what rvt.load_weights / rvt.random_weights
+    return; `top1` takes the logits as it takes `classify`'s.  An image's logits do not depend on its place in the batch, and two
+    calls give the same bits.  No host sync.  A non-finite pixel is not erased on the way: every logit of that image is NaN, as in
+    the fp64 restatement in torch; the other images' logits are the bits a clean batch gives."""
+    from . import rvt as _rvt
+    _check_images("rvt", "images", images)
+    n, c, h, w = images.shape
+    if n < 1 or c != 3 or h < 1 or w < 1:
+        raise ValueError(f"rvt: needs [N>=1, 3, H>=1, W>=1] images, got {tuple(images.shape)}")
+    _check_scorer("rvt", "weights", weights, _rvt.RVTWeights, "rvt.load_weights / rvt.random_weights")
+    return _rvt.forward(images, weights)
+
+
 def top1(logits: torch.Tensor, labels: torch.Tensor):
     """(pred, tp, targets, predicted) of one batch: pred int64 [N] = the argmax of logits fp32 [N,C] (ties to the lowest index, as
     torch.argmax), and the three int64 [C] per-class counts of classify.accuracy - tp_c (pred = label = c), targets_c, predicted_c.
