@@ -129,7 +129,22 @@ typedef struct ur_conv_desc {
                            Cout % 128 == 0, (C1+C2) % 256 == 0), or NULL: MFMA-fragment-major
                            [Cout/128][(C1+C2)/64][tap 9][k-step 4][row block 4][lane 64][8], lane = (cout % 32) + 32 * ((cin % 16) / 8),
                            element = cin % 8 - one coalesced 1-KiB load per 32 x 16 weight fragment (csrc/conv_wstream.hip) */
+  const void* w_up4;    /* optional folded weights of an upsampling 3x3 conv, honoured only with upsample2x (ignored otherwise), or
+                           NULL: a nearest-2x upsample followed by the 3x3 conv (pad 1) is, for the output pixels of parity (py, px), a 2x2
+                           conv over the source image, W4[py][px][co][a][b][ci] = sum of the taps (ky, kx) that fall on source pixel
+                           (y - 1 + py + a, x - 1 + px + b): py = 0: {ky 0} -> a 0, {ky 1, 2} -> a 1; py = 1: {ky 0, 1} -> a 0, {ky 2} -> a 1;
+                           the columns likewise.  Summed in fp32 from the fp32 weights, rounded once to the 16-bit type, laid out
+                           [phase = 2 py + px][Cout][(C1)/64][tap = 2 a + b][64].  One launch then runs the four phases on the 8 x 32
+                           halo kernels at 4/9 of the MACs (H % 8 == 0, W % 32 == 0, C1 % 64 == 0, C2 == 0, stride 1, pad 1,
+                           k_chunk_major, nbatch == 1, 16-bit y, no gn_ab / row_stats / ln_stats / yt; ur_conv_plan.up4 says whether it will; a
+                           batched / grouped launch, nbatch > 1, never reads w_up4: it has no batch stride);
+                           every other launch, and every launch with w_up4 == NULL, runs as without it.  The result is not
+                           bit-identical to the 9-tap launch: the tap sums are rounded once, where that launch rounds each tap and
+                           adds the products in fp32.  gn_part then has 4 x patches partials per image */
 } ur_conv_desc;
+/* ur_conv_desc grows by trailing fields (w_frag: ur_version 101, w_up4: 102).  Zero-initialise the whole descriptor (ur_conv_desc d = {0};
+ * or memset) before filling it, and rebuild callers against this header: a field left uninitialised, or a descriptor laid out by an older
+ * header, hands the library a wild pointer. */
 
 int ur_conv2d_nhwc(const ur_conv_desc* d, ur_stream_t stream);
 
@@ -140,6 +155,7 @@ typedef struct ur_conv_plan {
   int gn_parts;       /* partials per image (P) the launch writes into d->gn_part */
   int gn_fused;       /* 1: written by the conv epilogue itself (y may be NULL); 0: by an extra pass over y */
   int prologue_ok;    /* 1: d->gn_ab is honoured inside this launch; 0: apply the GroupNorm separately */
+  int up4;            /* 1: the launch runs the folded kernel on d->w_up4 (four 2x2 phase convs); 0: w_up4 is not read */
 } ur_conv_plan;
 int ur_conv2d_plan(const ur_conv_desc* d, ur_conv_plan* plan);
 

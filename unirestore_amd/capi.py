@@ -38,13 +38,14 @@ class ConvDesc(C.Structure):
         ("nbatch", C.c_int),
         ("bs_x", C.c_longlong), ("bs_x2", C.c_longlong), ("bs_w", C.c_longlong), ("bs_bias", C.c_longlong),
         ("bs_y", C.c_longlong), ("bs_r", C.c_longlong), ("k_chunk_major", C.c_int), ("bias_img_stride", C.c_longlong),
-        ("dtype", C.c_int), ("w_frag", C.c_void_p),
+        ("dtype", C.c_int), ("w_frag", C.c_void_p), ("w_up4", C.c_void_p),
     ]
 
 
 class ConvPlan(C.Structure):
     """Mirror of `ur_conv_plan`."""
-    _fields_ = [("row_stat_parts", C.c_int), ("gn_parts", C.c_int), ("gn_fused", C.c_int), ("prologue_ok", C.c_int)]
+    _fields_ = [("row_stat_parts", C.c_int), ("gn_parts", C.c_int), ("gn_fused", C.c_int), ("prologue_ok", C.c_int),
+                ("up4", C.c_int)]
 
 
 class ConvLaunchInfo(C.Structure):

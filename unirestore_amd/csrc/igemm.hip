@@ -27,6 +27,21 @@ namespace {
 
 // The launcher for k, planned (host only: no HIP call).
 ConvLaunch dispatch_conv(ConvK& k, bool pair, size_t ws_bytes) {
+  // Nearest-2x upsample + 3x3 with the caller's folded weights (ur_conv_desc.w_up4): four 2x2 phase convs over the SOURCE image on the
+  // 8 x 32 halo kernels, 4/9 of the MACs.  The source image must be whole patches; the epilogue writes through a strided view of y
+  // (up4_out_view), so the features that index rows of other planes (row sums, LayerNorm folding, transposed columns) and the
+  // in-loader GroupNorm stay on the 9-tap path.  Any Cout runs (a ragged last tile on the 128-wide kernel).
+  k.fold = 0;
+  if (k.w4 && k.ups && k.KH == 3 && k.stride == 1 && k.pad_t == 1 && k.pad_l == 1 && k.kcm && k.staged_ok_ && !pair && k.nbatch == 1 &&
+      k.C2 == 0 && k.Cin % 64 == 0 && k.W % 32 == 0 && k.H % 8 == 0 && k.OH == 2 * k.H && k.OW == 2 * k.W && !k.yt && !k.gn_ab && !k.row_stats &&
+      !k.ln_stats) {
+    k.fold = 1;
+    const long long tm = 4ll * k.N * (k.H / 8) * (k.W / 32);
+    auto fill = [](long long t) { return (double)t / (double)(((t + 255) / 256) * 256); };
+    const bool ok128 = k.Cout % 128 == 0, ok160 = k.Cout % 160 == 0;
+    if (ok160 && (!ok128 || fill(tm * (k.Cout / 160)) >= fill(tm * (k.Cout / 128)))) return urk::halo_8x32_160(k, ws_bytes);
+    return urk::halo_8x32_128(k, ws_bytes);
+  }
   if (k.KH == 3 && k.stride == 1 && k.pad_t == 1 && k.pad_l == 1 && k.kcm && k.staged_ok_ && !pair && k.nbatch == 1 &&
       k.OW % 32 == 0 && k.OH % 8 == 0 && k.OH == (k.ups ? 2 * k.H : k.H) && k.OW == (k.ups ? 2 * k.W : k.W) && !k.yt) {
     // tile width: 128 or 160 output channels, whichever divides Cout; when both do, the one whose tile count fills whole
@@ -184,6 +199,8 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, ur_conv_plan* pl
   UR_REQUIRE(k.M > 0, "empty problem");
 
   k.kcm = d->k_chunk_major; k.wf = (const uint16_t*)d->w_frag; k.wmajor = 0; k.xgm = 0; k.xbn = 0; k.patch_tw = 0;
+  // (w_up4 has no batch stride: a batched / grouped launch never reads it - neither here nor in the per-group launches of the group loop)
+  k.w4 = d->upsample2x && d->nbatch == 1 ? (const uint16_t*)d->w_up4 : nullptr; k.fold = 0;
   UR_REQUIRE(!k.kcm || (k.Cin % 64 == 0 && d->C1 % 64 == 0), "k_chunk_major needs C1 and C1+C2 to be multiples of 64");
   k.gn_part = d->gn_part; k.gn_ab = d->gn_ab; k.gn_silu = d->gn_silu; k.f16 = d->dtype == UR_DT_F16; k.gn_fused = 0; k.gn_parts = 0;
   k.ln_parts = d->ln_parts;
@@ -204,18 +221,19 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, ur_conv_plan* pl
   // holds for every source of the partials (refused, never computed wrongly); before dispatch_conv, whose plan sizes the pass
   UR_REQUIRE(!d->gn_part || (pair ? d->Cout / 2 : d->Cout) % 8 == 0, "gn_part needs output channels % 8 == 0 (GroupNorm statistics run on 8-channel vectors)");
   hipStream_t s = (hipStream_t)stream;
-  const double flops = 2.0 * k.M * (double)k.Cout * k.Ktot * k.nbatch;
-  const double bytes = 2.0 * ((double)k.M * k.Cin + (double)k.Cout * k.Ktot + (double)k.M * k.Cout) * k.nbatch;
+  const ConvLaunch launch = dispatch_conv(k, pair, d->workspace_bytes);
+  const int kprof = k.fold ? 4 * k.Cin : k.Ktot;      // K the launch executes: a folded upsampling conv runs 4 taps per channel, not 9
+  const double flops = 2.0 * k.M * (double)k.Cout * kprof * k.nbatch;
+  const double bytes = 2.0 * ((double)k.M * k.Cin + (double)k.Cout * kprof + (double)k.M * k.Cout) * k.nbatch;
   const char* fam = d->KH == 3 ? "conv3x3_igemm" : "gemm1x1_igemm";
   static const bool prof_shapes = getenv("UR_PROF_SHAPES") != nullptr;
   if (prof_shapes) {           // per-shape families for offline analysis (interned strings keep the pointers stable)
     static std::map<std::string, int> interned;
     char buf[128];
-    snprintf(buf, sizeof buf, "%s M%d N%d K%d s%d u%d b%d a%d", d->KH == 3 ? "c3" : "g1", k.M, k.Cout, k.Ktot, d->stride, d->upsample2x,
+    snprintf(buf, sizeof buf, "%s M%d N%d K%d s%d u%d b%d a%d", d->KH == 3 ? "c3" : "g1", k.M, k.Cout, kprof, d->stride, d->upsample2x,
              k.nbatch, d->act);
     fam = interned.emplace(buf, 0).first->first.c_str();
   }
-  const ConvLaunch launch = dispatch_conv(k, pair, d->workspace_bytes);
   // (the grid's x dimension is tiles_m * tiles_n; groups and K splits sit in y and z.  Workgroups have at most 512 threads.)
   UR_REQUIRE((long long)k.tiles_m * k.tiles_n < (1ll << 23),
              "ur_conv2d_nhwc: tile grid too large: the planned launcher's row tiles x column tiles must be below 2^23");
@@ -226,7 +244,7 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, ur_conv_plan* pl
                           !k.yt && !k.gn_ab && !k.out_f32 && k.staged_ok_ && k.Cout % 128 == 0 && !k.bias_img && k.C2 == 0;
   auto group_k = [&](int b) {      // the single-group problem of group b
     ConvK kb = k;
-    kb.nbatch = 1;
+    kb.nbatch = 1; kb.w4 = nullptr;
     kb.x = k.x + b * k.bs_x; kb.w = k.w + b * k.bs_w; kb.bias = k.bias ? k.bias + b * k.bs_bias : nullptr;
     kb.res = k.res ? k.res + b * k.bs_r : nullptr;
     kb.y = reinterpret_cast<uint16_t*>(k.y) + b * k.bs_y;
@@ -239,7 +257,7 @@ static int conv_impl(const ur_conv_desc* d, ur_stream_t stream, ur_conv_plan* pl
     return ur::fail(UR_E_UNSUPPORTED, "ur_conv2d_nhwc: gn_part of a batched launch that cannot fuse the statistics needs bs_y == output channels per batch");
   if (plan) {      // row-stat planes: one per N tile, or the single one of a split-K reduce pass
     plan->row_stat_parts = d->row_stats ? (k.splitk > 1 ? 1 : k.tiles_n) : 0;
-    plan->gn_parts = k.gn_parts; plan->gn_fused = k.gn_fused; plan->prologue_ok = launch.prologue_ok;
+    plan->gn_parts = k.gn_parts; plan->gn_fused = k.gn_fused; plan->prologue_ok = launch.prologue_ok; plan->up4 = k.fold;
   }
   if (info) {      // what runs: the launcher (per group, for the group loop), its split and reduce pass, the GroupNorm pass
     ConvK kb = group_loop ? group_k(0) : k;

@@ -51,6 +51,8 @@ struct ConvK {
   const uint16_t* wf;   // fragment-major copy of w (ur_conv_desc.w_frag) or null
   int wmajor;           // 1: weight-major XCD map (igemm_halo_img_kernel: 1-D grid; GEMM kernels: an XCD owns a band of columns)
   int xgm, xbn;         // xgm > 0: 2-D XCD partition of the tile grid (xcd_tile_map): xgm row bands x (8 / xgm) column bands, xbn = tiles_n * xgm / 8
+  const uint16_t* w4;   // folded weights of an upsampling 3x3 conv (ur_conv_desc.w_up4) or null
+  int fold;             // 1: the plan runs the four 2x2 phase convs of w4 (halo kernels with NTAP = 4, blockIdx.y = phase)
 };
 
 // blockIdx.x -> (row tile, column tile).  Workgroup id runs on XCD id % 8; every XCD has its own L2, so which tiles an XCD owns decides
@@ -1474,6 +1476,26 @@ template <int FM, int FN> __device__ __forceinline__ void kpipe_init(KPipeRings<
   for (int i = 0; i < 4; ++i) r.rb[i] = ig_u32x4{0u, 0u, 0u, 0u};
 }
 
+// Folded upsampling conv (NTAP = 4): phase (py, px) of the 2H x 2W output as the epilogues see it.  The tile's rows are 8 x 32
+// pixels of the SOURCE grid, pixel (y, x) -> output pixel (2y + py, 2x + px): with rows counted in PAIRS of output pixels (row stride
+// 2 * ldy, base advanced by px pixels) that is a patch of a (2H) x W image whose patch rows lie 2W pairs apart - exactly what
+// tile_row_to_m, the staged tile copies and the GroupNorm slot arithmetic already do with OW = 2W, so none of them changes.
+// The partial slot comes out as ty * 2 * tiles_x + py * tiles_x + tx in [0, 2 * patches); px selects the upper half of the 4 * patches.
+__device__ __forceinline__ ConvK up4_out_view(const ConvK& p, int py, int px, int patches) {
+  ConvK q = p;
+  q.OW = 2 * p.W; q.OHW = 2 * p.H * p.W; q.M = p.N * q.OHW;
+  if (p.y) q.y = reinterpret_cast<uint16_t*>(p.y) + (long long)px * p.ldy;
+  q.ldy = 2 * p.ldy;
+  if (p.res) q.res = p.res + (long long)px * p.ldr;
+  q.ldr = 2 * p.ldr;
+  if (p.gn_part) q.gn_part = p.gn_part + (long long)px * 2 * patches * p.Cout * 2;
+  return q;
+}
+// first row (in pixel pairs, see up4_out_view) of source patch (img, ty, tx) in phase row py
+__device__ __forceinline__ int up4_m0(const ConvK& p, int img, int ty, int tx, int TH, int TW, int py) {
+  return img * 2 * p.H * p.W + (2 * ty * TH + py) * p.W + tx * TW;
+}
+
 // =====================================================================================================================
 // Halo-tile 3x3 convolution (stride 1, pad 1, optional nearest-2x upsampled input).
 // The L2 -> CU ingest path, not the MFMA pipe, bounds the implicit GEMM (about 13 B/clk/CU: ~8 KB in flight against
@@ -1484,8 +1506,15 @@ template <int FM, int FN> __device__ __forceinline__ void kpipe_init(KPipeRings<
 // K tile (3-stage ring).  Ingest per K tile drops from (256+BN)*128 B to ~BN*128 B + 5 KB.
 // A fragment is one 32-pixel patch row, so its LDS rows are consecutive for every tap and the (row>>1)&7 slot swizzle
 // stays conflict-free (tools/lds_conflicts.py model; a 16x16 patch would be 2-way conflicted on every tap).
-template <int TH, int BN, int WM, int WN, bool F16, bool GNP>
+// NTAP = 4: the folded form of "nearest-2x upsample, then 3x3" (ur_conv_desc.w_up4): the same patch loader on the SOURCE image
+// (no >> 1), blockIdx.y = output phase (py, px), four taps (a, b) per chunk reading the patch at (py + a, px + b), the phase's own
+// [Cout][chunk][4][64] weights, and an epilogue that scatters the tile to the pixels (2y + py, 2x + px) (up4_out_view).  The weight
+// ring slot is then K tile % 3 computed at run time (4 % 3 != 0), and a chunk's patch pieces ride on taps 0 .. NTAP - 2, HPT each:
+// the last tap's second half already prefetches the next chunk's first fragments.
+template <int TH, int BN, int WM, int WN, bool F16, bool GNP, int NTAP = 9>
 __global__ __launch_bounds__(WM* WN * 64) void igemm_halo_kernel(const ConvK p) {
+  constexpr bool UP4 = NTAP == 4;
+  static_assert((NTAP == 9 || NTAP == 4) && !(UP4 && GNP), "tap count");
   constexpr int NW = WM * WN, TW = 32, BM = TH * TW, PW = TW + 2, HPIX = (TH + 2) * PW;   // 340 (TH=8) / 204 (TH=4) halo pixels
   constexpr int HSLOTS = (HPIX + 8 * NW - 1) / (8 * NW);                              // tap slots that carry a halo piece
   constexpr int HPIECES = HSLOTS * NW, HBYTES = HPIECES * 1024;   // surplus pieces are never read (zero fill)
@@ -1502,26 +1531,31 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_halo_kernel(const ConvK p) 
   // (GNP is a compile-time variant: with a run-time flag the plain kernel's tap loop scheduled 20 % slower)
   constexpr bool gnp = GNP;
   static_assert(HSLOTS <= 7, "the in-LDS GroupNorm pass needs taps 2 .. HSLOTS+1 <= 8");
+  constexpr int HPT = UP4 ? (HSLOTS + NTAP - 2) / (NTAP - 1) : 1;      // patch pieces per wave and tap (taps 0 .. NTAP - 2 when UP4)
+  static_assert(HPT <= 2, "vmcnt cases of dma_wait");
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid % WM, wn = wid / WM;
-  const int sz = blockIdx.y;
+  const int sz = UP4 ? 0 : blockIdx.y;
+  const int phase = UP4 ? blockIdx.y : 0, py = phase >> 1, px = phase & 1;
+  const int IH = UP4 ? p.H : p.OH, IW = UP4 ? p.W : p.OW;             // the grid the patches tile: the source image when folded
   int id = blockIdx.x;
   {
     const int nt = p.tiles_m * p.tiles_n, q = nt >> 3, r = nt & 7, xcd = id & 7, idx = id >> 3;
     id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
   const int tn = id % p.tiles_n, tmi = id / p.tiles_n;
-  const int tiles_x = p.OW / TW, tiles_y = p.OH / TH;
+  const int tiles_x = IW / TW, tiles_y = IH / TH;
   const int tx = tmi % tiles_x, ty = (tmi / tiles_x) % tiles_y, img = tmi / (tiles_x * tiles_y);
   const int n0 = tn * BN;
-  const int m0 = img * p.OHW + ty * TH * p.OW + tx * TW;         // first output pixel of the patch
+  const int m0 = UP4 ? up4_m0(p, img, ty, tx, TH, TW, py) : img * p.OHW + ty * TH * p.OW + tx * TW;         // first output pixel of the patch
+  const int ldw = UP4 ? 4 * p.Cin : p.ldw;                       // (folded: [phase][Cout][4 * Cin])
 
   typedef __attribute__((address_space(1))) const void* gptr_t;
   typedef __attribute__((address_space(3))) void* lptr_t;
   const uint16_t* __restrict__ X1 = p.x;
   const uint16_t* __restrict__ X2 = p.x2;
-  const uint16_t* __restrict__ Wt = p.w;
+  const uint16_t* __restrict__ Wt = UP4 ? p.w4 + (long long)phase * p.Cout * ldw : p.w;
   const uint16_t* zero = reinterpret_cast<const uint16_t*>(g_zero_page);
   const int lr = lane >> 3, ps = lane & 7;
   // Every piece this wave issues has index == wid (mod NW, NW even), so its rows share one parity pattern and the lane's logical
@@ -1535,8 +1569,8 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_halo_kernel(const ConvK p) 
     const int hr = (t * NW + wid) * 8 + lr;
     const int hy = hr / PW, hx = hr - hy * PW;
     int iy = ty * TH - 1 + hy, ix = tx * TW - 1 + hx;               // coordinates in the (possibly upsampled) input
-    const bool v = hr < HPIX && (unsigned)iy < (unsigned)p.OH && (unsigned)ix < (unsigned)p.OW;
-    if (p.ups) { iy >>= 1; ix >>= 1; }
+    const bool v = hr < HPIX && (unsigned)iy < (unsigned)IH && (unsigned)ix < (unsigned)IW;
+    if (!UP4 && p.ups) { iy >>= 1; ix >>= 1; }
     hpix[t] = v ? (img * p.H + iy) * p.W + ix : -1;
   }
   int woff[WPW];
@@ -1544,11 +1578,11 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_halo_kernel(const ConvK p) 
   for (int i = 0; i < WPW; ++i) {
     const int qq = (wid + NW * i < WPIECES) ? wid + NW * i : wid;     // surplus slot: repeat this wave's first piece
     const int row = n0 + qq * 8 + lr;
-    woff[i] = row < p.Cout ? row * p.ldw : -1;
+    woff[i] = row < p.Cout ? row * ldw : -1;
   }
   // blockIdx.y splits the channel-chunk range (few-tile layers: tiles * splits <= one round of CUs)
-  const int cps = p.nk_per_split / 9, c_begin = sz * cps, nchunk = min(p.nk / 9, c_begin + cps) - c_begin;
-  const int nk = nchunk * 9, kt0 = c_begin * 9;
+  const int cps = p.nk_per_split / NTAP, c_begin = sz * cps, nchunk = min(p.nk / NTAP, c_begin + cps) - c_begin;
+  const int nk = nchunk * NTAP, kt0 = c_begin * NTAP;
 
 #ifdef UR_HALO_DMA_BUILTIN                                  // A/B: the global_load_lds loaders of rounds 1-2
   auto issue_w = [&](int kt, int ring) {
@@ -1572,7 +1606,7 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_halo_kernel(const ConvK p) 
 #else
   // buffer-descriptor LDS-DMA (ig_lds_dma16): per piece one scalar M0 value, one lane offset kept in a register, one scalar K offset
   const int wid_s = __builtin_amdgcn_readfirstlane(wid);
-  const ig_u32x4 rs_w = ig_make_rsrc(Wt, (unsigned long long)p.Cout * p.ldw * 2);
+  const ig_u32x4 rs_w = ig_make_rsrc(Wt, (unsigned long long)p.Cout * ldw * 2);
   const ig_u32x4 rs_x1 = ig_make_rsrc(X1, (unsigned long long)p.N * p.H * p.W * p.ldx * 2);
   const ig_u32x4 rs_x2 = ig_make_rsrc(X2 ? X2 : X1, (unsigned long long)p.N * p.H * p.W * (X2 ? p.ldx2 : p.ldx) * 2);
   const unsigned wring_lds = (unsigned)(uintptr_t)(lptr_t)wring, hbuf_lds = (unsigned)(uintptr_t)(lptr_t)hbuf;
@@ -1641,14 +1675,15 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_halo_kernel(const ConvK p) 
   __builtin_amdgcn_s_barrier();
 
   // LDS addresses (k-step 0) of the fragments tap tp of chunk cc reads: activation rows shifted by (dy, dx), weight ring slot tp % 3
-  auto tap_addr = [&](int cc, int tp, unsigned (&ab)[FM]) -> unsigned {
-    const int dy = tp / 3, dx = tp % 3;
+  // (folded: (dy, dx) = (py + a, px + b), and the caller names the ring slot - K tile % 3)
+  auto tap_addr = [&](int cc, int tp, unsigned (&ab)[FM], int ring = 0) -> unsigned {
+    const int dy = UP4 ? py + tp / 2 : tp / 3, dx = UP4 ? px + tp % 2 : tp % 3;
 #pragma unroll
     for (int b = 0; b < FM; ++b) {
       const int hrow = (wm * FM + b + dy) * PW + dx + frow;
       ab[b] = hb_lds + (cc & 1) * HBYTES + hrow * 128 + ((fhalf ^ ((hrow >> 1) & 7)) << 4);
     }
-    return aw_lds + (tp % 3) * WBYTES;
+    return aw_lds + (UP4 ? ring : tp % 3) * WBYTES;
   };
 #if defined(UR_HALO_DMA_BUILTIN) || !defined(UR_HALO_STAGGER)     // (staggering measured no gain: DESIGN.md 6c)
   constexpr bool stagger = false;
@@ -1668,20 +1703,31 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_halo_kernel(const ConvK p) 
   // K loop as chunks x 9 UNROLLED taps: the tap decides everything that used to be run-time control in the loop body (which
   // halo piece to prefetch, the fragment row offset, the weight-ring slot = tap % 3 because 9 % 3 == 0), so each tap's body
   // is straight-line code with immediate LDS offsets instead of a branch ladder in front of every 20 MFMAs.
+  int r0 = 0;                                              // UP4: ring slot of the current K tile (kt % 3)
   for (int c = 0; c < nchunk; ++c) {
     const unsigned char* hb = hbuf + (c & 1) * HBYTES;
     const bool next_chunk = c + 1 < nchunk;
 #pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      const int kt = c * 9 + tap;
+    for (int tap = 0; tap < NTAP; ++tap) {
+      const int kt = c * NTAP + tap;
+      const int r1 = r0 == 2 ? 0 : r0 + 1, r2 = r1 == 2 ? 0 : r1 + 1;      // slots of K tiles kt + 1, kt + 2
       const bool more_w = kt + 2 < nk;
-      const bool more_h = tap < HSLOTS && next_chunk;
+      const bool more_h = (UP4 ? tap * HPT < HSLOTS && tap < NTAP - 1 : tap < HSLOTS) && next_chunk;
+      const int nh = !UP4 ? 1 : (tap + 1) * HPT <= HSLOTS ? HPT : HSLOTS - tap * HPT;        // pieces this tap carries when more_h
       // The DMA path of a CU takes ~24 cycles per 1-KiB piece and a wave sits in its buffer_load until the queue has room: with all
       // eight waves issuing at the top of the tap nobody feeds the matrix pipe meanwhile (0.37 us of a 1.2 us tap, measured against a build without the DMA).
       // So the two waves of a SIMD issue half a tap apart: waves 0..NW/2-1 here, the others between the two MFMA halves.
       auto issue_tap = [&]() {
-        if (more_w) issue_w(kt + 2, (tap + 2) % 3);
-        if (tap < HSLOTS) { if (next_chunk) issue_h(c + 1, tap < HSLOTS ? tap : 0); }
+        if (more_w) issue_w(kt + 2, UP4 ? r2 : (tap + 2) % 3);
+        if constexpr (UP4) {
+          if (more_h) {
+#pragma unroll
+            for (int j = 0; j < HPT; ++j)
+              if (tap * HPT + j < HSLOTS) issue_h(c + 1, tap * HPT + j < HSLOTS ? tap * HPT + j : 0);
+          }
+        } else {
+          if (tap < HSLOTS) { if (next_chunk) issue_h(c + 1, tap < HSLOTS ? tap : 0); }
+        }
       };
       if (!stagger || early_grp) issue_tap();
       const bool ab_now = gnp && tap == 0 && next_chunk;    // (+1 DMA op in this iteration, counted in the wait below)
@@ -1694,8 +1740,10 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_halo_kernel(const ConvK p) 
         if (ab_now) {                                       // tap 0 with the next chunk's affine table in flight as well
           if (more_w) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WPW + 2) : "memory");
           else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        } else if (more_w && more_h) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WPW + 1) : "memory");
+        } else if (more_w && more_h && nh == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WPW + 2) : "memory");
+        else if (more_w && more_h) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WPW + 1) : "memory");
         else if (more_w) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WPW) : "memory");
+        else if (more_h && nh == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
         else if (more_h) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       };
@@ -1705,7 +1753,7 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_halo_kernel(const ConvK p) 
         // tells everyone this tap's weight tile has been read: its ring slot is the next tap's DMA target.  This tap's own reads
         // are retired by then (its MFMAs consumed them); the in-place GroupNorm writes are older than those reads (LDS is in-order).
         unsigned ab[FM], abn[FM];
-        const unsigned aw = tap_addr(c, tap, ab), awn = tap_addr(c + (tap == 8 ? 1 : 0), (tap + 1) % 9, abn);
+        const unsigned aw = tap_addr(c, tap, ab, r0), awn = tap_addr(c + (tap == NTAP - 1 ? 1 : 0), (tap + 1) % NTAP, abn, r1);
         kpipe<FM, FN, F16, 1>(acc, rings, ab, aw, abn, awn);
         if (stagger && !early_grp) issue_tap();
         dma_wait();
@@ -1713,8 +1761,8 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_halo_kernel(const ConvK p) 
         kpipe<FM, FN, F16, 2>(acc, rings, ab, aw, abn, awn);      // (the last tap prefetches too - valid LDS, never used: one code path)
         __builtin_amdgcn_s_barrier();
       } else {
-        const int dy = tap / 3, dx = tap % 3;
-        const unsigned char* wsm = wring + (tap % 3) * WBYTES;
+        const int dy = UP4 ? py + tap / 2 : tap / 3, dx = UP4 ? px + tap % 2 : tap % 3;
+        const unsigned char* wsm = wring + (UP4 ? r0 : tap % 3) * WBYTES;
         typedef typename Frag<F16>::type frag_t;
         auto load_frags = [&](int ks, frag_t (&bfr)[FM], frag_t (&afr)[FN]) {
           const int slot = ks * 2 + fhalf;
@@ -1746,12 +1794,18 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_halo_kernel(const ConvK p) 
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
       }
+      if constexpr (UP4) r0 = r1;
     }
   }
   if constexpr (ktile_asm_ok<FM, FN>()) kpipe_drain(rings);      // the last tap's prefetch lands in the rings: they stay reserved until here
   asm volatile("s_waitcnt vmcnt(0)\n\ts_nop 15\n\ts_nop 7" ::: "memory");      // last MFMA of the asm tap body -> VALU reads of the accumulators
   // (BN == 32: the thin tile of the conv_out layers - fp32 output, 4-8 channels - leaves through the direct stores)
-  igemm_epilogue<FM, FN, WTM, WTN, BM, BN, NT, F16, BN == 32>(p, acc, m0, n0, wm, wn, lane, 0, sz, smem);
+  if constexpr (UP4) {
+    const ConvK q = up4_out_view(p, py, px, tiles_x * tiles_y);
+    igemm_epilogue<FM, FN, WTM, WTN, BM, BN, NT, F16, false>(q, acc, m0, n0, wm, wn, lane, 0, 0, smem);
+  } else {
+    igemm_epilogue<FM, FN, WTM, WTN, BM, BN, NT, F16, BN == 32>(p, acc, m0, n0, wm, wn, lane, 0, sz, smem);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1764,18 +1818,23 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_halo_kernel(const ConvK p) 
 // weight tile + the tap's halo pieces before the mid-tap barrier, the other half behind it), waits with a counted vmcnt for the
 // previous tap's pieces and takes part in the two barriers, which publish them.  It always issues the same number of pieces per
 // tap position (tile / chunk indices clamped at the end: a re-fetch into a slot nobody reads), so its counts are immediates.
-template <int TH, int BN, int WM, int WN, bool F16, bool GNP>
+// NTAP = 4: the folded upsampling conv (see igemm_halo_kernel).  Loader and compute waves still meet at one prologue barrier and two
+// barriers per tap for nchunk * NTAP taps; the patch pieces ride on the 2 * (NTAP - 1) half-taps before the last tap.
+template <int TH, int BN, int WM, int WN, bool F16, bool GNP, int NTAP = 9>
 __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const ConvK p) {
+  constexpr bool UP4 = NTAP == 4;
+  static_assert((NTAP == 9 || NTAP == 4) && !(UP4 && GNP), "tap count");
   constexpr int NW = WM * WN, TW = 32, BM = TH * TW, PW = TW + 2, HPIX = (TH + 2) * PW;
   constexpr int HSLOTS = (HPIX + 8 * NW - 1) / (8 * NW), HNEED = (HPIX + 7) / 8;          // (LDS layout of the plain kernel); pieces actually read
   constexpr int HPIECES = HSLOTS * NW, HBYTES = HPIECES * 1024;
   // The loader spreads a chunk's HNEED patch pieces over the 16 half-taps of taps 0..7 of the previous chunk (HPER per half-tap:
   // a patch piece costs the loader ~85 cycles, a weight piece ~38 - profiles/r3_halo_phase_timers.txt - so each half-tap carries
   // about as much issue time as its 10 MFMAs per wave take); tap 8 carries none (its pieces would land after the prefetch).
-  constexpr int HPER = (HNEED + 15) / 16, HTAP = 2 * HPER;
+  constexpr int NHALF = 2 * (NTAP - 1);                                                   // half-taps that carry patch pieces
+  constexpr int HPER = (HNEED + NHALF - 1) / NHALF, HTAP = 2 * HPER;
   constexpr int WBYTES = BN * 128, WPIECES = BN / 8, WH = WPIECES / 2;
   constexpr int WTM = BM / WM, WTN = BN / WN, FM = WTM / 32, FN = WTN / 32, NT = NW * 64;
-  static_assert(NW == 8 && WTM % 32 == 0 && WTN % 32 == 0 && HTAP <= NW && ktile_asm_ok<FM, FN>(), "wave layout");
+  static_assert(NW == 8 && WTM % 32 == 0 && WTN % 32 == 0 && (UP4 || HTAP <= NW) && ktile_asm_ok<FM, FN>(), "wave layout");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* const hbuf = smem;                      // 2 halo patches
   unsigned char* const wring = smem + 2 * HBYTES;        // 3 weight tiles
@@ -1785,19 +1844,23 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wid_s = __builtin_amdgcn_readfirstlane(wid);
-  const int sz = blockIdx.y;
+  const int sz = UP4 ? 0 : blockIdx.y;
+  const int phase = UP4 ? blockIdx.y : 0, py = phase >> 1, px = phase & 1;
+  const int IH = UP4 ? p.H : p.OH, IW = UP4 ? p.W : p.OW;             // the grid the patches tile: the source image when folded
   int id = blockIdx.x;
   {
     const int nt = p.tiles_m * p.tiles_n, q = nt >> 3, r = nt & 7, xcd = id & 7, idx = id >> 3;
     id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
   const int tn = id % p.tiles_n, tmi = id / p.tiles_n;
-  const int tiles_x = p.OW / TW, tiles_y = p.OH / TH;
+  const int tiles_x = IW / TW, tiles_y = IH / TH;
   const int tx = tmi % tiles_x, ty = (tmi / tiles_x) % tiles_y, img = tmi / (tiles_x * tiles_y);
   const int n0 = tn * BN;
-  const int m0 = img * p.OHW + ty * TH * p.OW + tx * TW;         // first output pixel of the patch
-  const int cps = p.nk_per_split / 9, c_begin = sz * cps, nchunk = min(p.nk / 9, c_begin + cps) - c_begin;
-  const int nk = nchunk * 9, kt0 = c_begin * 9;
+  const int m0 = UP4 ? up4_m0(p, img, ty, tx, TH, TW, py) : img * p.OHW + ty * TH * p.OW + tx * TW;         // first output pixel of the patch
+  const int ldw = UP4 ? 4 * p.Cin : p.ldw;                       // (folded: [phase][Cout][4 * Cin])
+  const uint16_t* const Wt = UP4 ? p.w4 + (long long)phase * p.Cout * ldw : p.w;
+  const int cps = p.nk_per_split / NTAP, c_begin = sz * cps, nchunk = min(p.nk / NTAP, c_begin + cps) - c_begin;
+  const int nk = nchunk * NTAP, kt0 = c_begin * NTAP;
   const unsigned wring_lds = (unsigned)(uintptr_t)(lptr_t)wring, hbuf_lds = (unsigned)(uintptr_t)(lptr_t)hbuf;
   const unsigned abuf_lds = (unsigned)(uintptr_t)(lptr_t)abuf;
   const int lr = lane >> 3, ps = lane & 7;
@@ -1805,8 +1868,8 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const
   auto halo_pixel = [&](int hr) -> int {
     const int hy = hr / PW, hx = hr - hy * PW;
     int iy = ty * TH - 1 + hy, ix = tx * TW - 1 + hx;               // coordinates in the (possibly upsampled) input
-    const bool v = hr < HPIX && (unsigned)iy < (unsigned)p.OH && (unsigned)ix < (unsigned)p.OW;
-    if (p.ups) { iy >>= 1; ix >>= 1; }
+    const bool v = hr < HPIX && (unsigned)iy < (unsigned)IH && (unsigned)ix < (unsigned)IW;
+    if (!UP4 && p.ups) { iy >>= 1; ix >>= 1; }
     return v ? (img * p.H + iy) * p.W + ix : -1;
   };
 
@@ -1820,7 +1883,7 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const
     const bool do_w = wid_s == NW, do_h = two ? wid_s == NW + 1 : true;
     // piece q = LDS rows 8q .. 8q+7; the lane's physical 16-byte slot ps holds logical K chunk ps ^ ((row >> 1) & 7): two parities
     const unsigned ck0 = (ps ^ ((lr >> 1) & 7)) * 16u, ck1 = (ps ^ ((4 + (lr >> 1)) & 7)) * 16u;
-    const ig_u32x4 rs_w = ig_make_rsrc(p.w, (unsigned long long)p.Cout * p.ldw * 2);
+    const ig_u32x4 rs_w = ig_make_rsrc(Wt, (unsigned long long)p.Cout * ldw * 2);
     const ig_u32x4 rs_x1 = ig_make_rsrc(p.x, (unsigned long long)p.N * p.H * p.W * p.ldx * 2);
     const ig_u32x4 rs_x2 = ig_make_rsrc(p.x2 ? p.x2 : p.x, (unsigned long long)p.N * p.H * p.W * (p.x2 ? p.ldx2 : p.ldx) * 2);
     const ig_u32x4 rs_ab = ig_make_rsrc(gnp ? (const void*)p.gn_ab : (const void*)p.w, gnp ? (unsigned long long)p.N * 2 * p.Cin * 4 : 16ull);
@@ -1828,7 +1891,7 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const
 #pragma unroll
     for (int q = 0; q < WPIECES; ++q) {
       const int row = n0 + q * 8 + lr;
-      wvo[q] = row < p.Cout ? (unsigned)row * (unsigned)p.ldw * 2u + ((q & 1) ? ck1 : ck0) : IG_OOB;
+      wvo[q] = row < p.Cout ? (unsigned)row * (unsigned)ldw * 2u + ((q & 1) ? ck1 : ck0) : IG_OOB;
     }
     int hpx[HNEED];
     auto dma_w = [&](int kt, int ring, int q0, int q1) {            // pieces [q0, q1) of weight tile kt (clamped) -> ring slot
@@ -1836,7 +1899,7 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const
 #pragma unroll
       for (int q = q0; q < q1; ++q) ig_lds_dma16(wring_lds + ring * WBYTES + q * 1024, wvo[q], rs_w, so);
     };
-    auto dma_h = [&](int c, int h) {                                // patch pieces of half-tap h (0..15), chunk c (clamped) -> halo buffer c & 1
+    auto dma_h = [&](int c, int h) {                                // patch pieces of half-tap h (0..NHALF-1), chunk c (clamped) -> halo buffer c & 1
       const int cb = (c_begin + min(c, nchunk - 1)) * 64;           // first channel of the chunk: decides the source (C1 % 64 == 0)
       const bool second = cb >= p.C1;
       const unsigned ld2 = (unsigned)(second ? p.ldx2 : p.ldx) * 2u;
@@ -1844,7 +1907,7 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const
 #pragma unroll
       for (int j = 0; j < HPER; ++j) {
         const int q = h * HPER + j;
-        if (h < 16 && q < HNEED) {
+        if (h < NHALF && q < HNEED) {
           const unsigned vo = hpx[q] >= 0 ? (unsigned)hpx[q] * ld2 + ((q & 1) ? ck1 : ck0) : IG_OOB;
           const unsigned m0v = hbuf_lds + (c & 1) * HBYTES + q * 1024;
           if (second) ig_lds_dma16(m0v, vo, rs_x2, so);
@@ -1852,7 +1915,7 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const
         }
       }
     };
-    auto halo_count = [](int h) -> int { return (h >= 16 || h * HPER >= HNEED) ? 0 : (HNEED - h * HPER < HPER ? HNEED - h * HPER : HPER); };
+    auto halo_count = [](int h) -> int { return (h >= NHALF || h * HPER >= HNEED) ? 0 : (HNEED - h * HPER < HPER ? HNEED - h * HPER : HPER); };
     auto dma_ab = [&](int c) {                                      // affine table of chunk c: lanes 0-15 a[64], 16-31 b[64] (fp32)
       const unsigned vo = lane < 32 ? (unsigned)((img * 2 + (lane >> 4 & 1)) * p.Cin + (lane & 15) * 4) * 4u : IG_OOB;
       ig_lds_dma16(abuf_lds + (c & 1) * 1024, vo, rs_ab, (unsigned)((c_begin + min(c, nchunk - 1)) * 64) * 4u);
@@ -1872,11 +1935,13 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const
     }
     __builtin_amdgcn_s_barrier();
     if (gnp) __builtin_amdgcn_s_barrier();                              // (the compute waves normalise patch 0 in between)
+    int r2 = 2;                                                         // UP4: ring slot of K tile kt + 2 ((kt + 2) % 3)
     for (int c = 0; c < nchunk; ++c) {
 #pragma unroll
-      for (int tap = 0; tap < 9; ++tap) {
-        const int kt = c * 9 + tap;
-        if (do_w) dma_w(kt + 2, (tap + 2) % 3, 0, WH);
+      for (int tap = 0; tap < NTAP; ++tap) {
+        const int kt = c * NTAP + tap;
+        const int ring2 = UP4 ? r2 : (tap + 2) % 3;
+        if (do_w) dma_w(kt + 2, ring2, 0, WH);
         if (do_h) {
           dma_h(c + 1, 2 * tap);
           if (gnp && tap == 0) dma_ab(c + 1);
@@ -1888,10 +1953,11 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(halo_count(2 * tap) + ((gnp && tap == 0) ? 1 : 0)) : "memory");
         __builtin_amdgcn_s_barrier();
         if (kt + 1 < nk) {
-          if (do_w) dma_w(kt + 2, (tap + 2) % 3, WH, WPIECES);
+          if (do_w) dma_w(kt + 2, ring2, WH, WPIECES);
           if (do_h) dma_h(c + 1, 2 * tap + 1);
         }
         __builtin_amdgcn_s_barrier();
+        if constexpr (UP4) r2 = r2 == 2 ? 0 : r2 + 1;
       }
     }
     return;
@@ -1903,28 +1969,31 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const
   // t * HTAP + wid for wave wid < HTAP) were published by the barriers of tap t + 1 and are rewritten at the top of tap t + 2.
   const int chunk = ps ^ ((((wid & 1) << 2) + (lr >> 1)) & 7);      // (HTAP is even: the pieces of a wave share the parity of wid)
   static_assert(HTAP % 2 == 0, "piece parity");
+  // pieces of patch 0 per compute wave: piece t * PSTR + wid for waves < PSTR (folded: all NW waves share them; PSTR stays even)
+  constexpr int PSTR = UP4 ? NW : HTAP;
+  static_assert(8 * PSTR >= HNEED, "patch 0 fits the prologue fetch");
   int hpix[8];                                            // (GNP: kept for the whole kernel; otherwise only for the prologue fetch below)
 #pragma unroll
-  for (int t = 0; t < 8; ++t) hpix[t] = (wid < HTAP && t * HTAP + wid < HNEED) ? halo_pixel((t * HTAP + wid) * 8 + lr) : -1;
+  for (int t = 0; t < 8; ++t) hpix[t] = (wid < PSTR && t * PSTR + wid < HNEED) ? halo_pixel((t * PSTR + wid) * 8 + lr) : -1;
   {
-    // prologue fetch: patch 0 (piece t * HTAP + wid, waves < HTAP) and weight tile 0 (pieces wid, wid + NW, ..) - see the loader
-    const ig_u32x4 rs_w = ig_make_rsrc(p.w, (unsigned long long)p.Cout * p.ldw * 2);
+    // prologue fetch: patch 0 (piece t * PSTR + wid, waves < PSTR) and weight tile 0 (pieces wid, wid + NW, ..) - see the loader
+    const ig_u32x4 rs_w = ig_make_rsrc(Wt, (unsigned long long)p.Cout * ldw * 2);
     const int cb = c_begin * 64;
     const bool second = cb >= p.C1;
     const ig_u32x4 rs_x = second ? ig_make_rsrc(p.x2, (unsigned long long)p.N * p.H * p.W * p.ldx2 * 2) : ig_make_rsrc(p.x, (unsigned long long)p.N * p.H * p.W * p.ldx * 2);
     const unsigned ld2 = (unsigned)(second ? p.ldx2 : p.ldx) * 2u, so = (unsigned)(second ? cb - p.C1 : cb) * 2u;
-    if (wid_s < HTAP) {
+    if (wid_s < PSTR) {
 #pragma unroll
       for (int t = 0; t < 8; ++t)
-        if (t * HTAP + wid_s < HNEED)
-          ig_lds_dma16(hbuf_lds + (t * HTAP + wid_s) * 1024, hpix[t] >= 0 ? (unsigned)hpix[t] * ld2 + chunk * 16u : IG_OOB, rs_x, so);
+        if (t * PSTR + wid_s < HNEED)
+          ig_lds_dma16(hbuf_lds + (t * PSTR + wid_s) * 1024, hpix[t] >= 0 ? (unsigned)hpix[t] * ld2 + chunk * 16u : IG_OOB, rs_x, so);
     }
 #pragma unroll
     for (int j = 0; j < (WPIECES + NW - 1) / NW; ++j) {
       const int q = wid_s + NW * j;
       if (q < WPIECES) {
         const int row = n0 + q * 8 + lr;
-        ig_lds_dma16(wring_lds + q * 1024, row < p.Cout ? (unsigned)row * (unsigned)p.ldw * 2u + chunk * 16u : IG_OOB, rs_w, (unsigned)kt0 * 128u);
+        ig_lds_dma16(wring_lds + q * 1024, row < p.Cout ? (unsigned)row * (unsigned)ldw * 2u + chunk * 16u : IG_OOB, rs_w, (unsigned)kt0 * 128u);
       }
     }
   }
@@ -1943,14 +2012,15 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const
   const unsigned aw_lds = wring_lds + (wn * WTN + frow) * 128 + ((fhalf ^ ((frow >> 1) & 7)) << 4);
   static_assert(((WTN >> 1) & 7) == 0, "the wave's weight rows must keep the swizzle phase of fragment row 0");
   // LDS addresses (k-step 0) of the fragments tap tp of chunk cc reads: activation rows shifted by (dy, dx), weight ring slot tp % 3
-  auto tap_addr = [&](int cc, int tp, unsigned (&ab)[FM]) -> unsigned {
-    const int dy = tp / 3, dx = tp % 3;
+  // (folded: (dy, dx) = (py + a, px + b), and the caller names the ring slot - K tile % 3)
+  auto tap_addr = [&](int cc, int tp, unsigned (&ab)[FM], int ring = 0) -> unsigned {
+    const int dy = UP4 ? py + tp / 2 : tp / 3, dx = UP4 ? px + tp % 2 : tp % 3;
 #pragma unroll
     for (int b = 0; b < FM; ++b) {
       const int hrow = (wm * FM + b + dy) * PW + dx + frow;
       ab[b] = hbuf_lds + (cc & 1) * HBYTES + hrow * 128 + ((fhalf ^ ((hrow >> 1) & 7)) << 4);
     }
-    return aw_lds + (tp % 3) * WBYTES;
+    return aw_lds + (UP4 ? ring : tp % 3) * WBYTES;
   };
   KPipeRings<FM, FN> rings;
   kpipe_init(rings);
@@ -1967,25 +2037,33 @@ __global__ __launch_bounds__((WM * WN + 2) * 64) void igemm_halo_ws_kernel(const
     const unsigned aw0 = tap_addr(0, 0, ab0);
     kpipe<FM, FN, F16, 0>(acc, rings, ab0, aw0, ab0, aw0);
   }
+  int r0 = 0;                                              // UP4: ring slot of the current K tile (kt % 3)
   for (int c = 0; c < nchunk; ++c) {
     const bool next_chunk = c + 1 < nchunk;
 #pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
+    for (int tap = 0; tap < NTAP; ++tap) {
+      const int r1 = r0 == 2 ? 0 : r0 + 1;
       // the pieces issued two taps ago were published by the previous tap's barriers: normalise them next to this tap's MFMAs
       // (tap 0: the ones of tap 7 of the previous chunk - this chunk's own patch, first read by its tap 6)
       if (gnp && tap >= 2 && next_chunk) gn_slot(c + 1, tap >= 2 ? tap - 2 : 0);
       if (gnp && tap == 0 && c > 0) gn_slot(c, 7);
       unsigned ab[FM], abn[FM];
-      const unsigned aw = tap_addr(c, tap, ab), awn = tap_addr(c + (tap == 8 ? 1 : 0), (tap + 1) % 9, abn);
+      const unsigned aw = tap_addr(c, tap, ab, r0), awn = tap_addr(c + (tap == NTAP - 1 ? 1 : 0), (tap + 1) % NTAP, abn, r1);
       kpipe<FM, FN, F16, 1>(acc, rings, ab, aw, abn, awn);
       __builtin_amdgcn_s_barrier();                       // weight tile kt + 1 (and every older piece) is in LDS
       kpipe<FM, FN, F16, 2>(acc, rings, ab, aw, abn, awn);
       __builtin_amdgcn_s_barrier();                       // everyone has read weight tile kt: its slot takes tile kt + 3
+      if constexpr (UP4) r0 = r1;
     }
   }
   kpipe_drain(rings);
   asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");       // last MFMA of the asm tap body -> VALU reads of the accumulators
-  igemm_epilogue<FM, FN, WTM, WTN, BM, BN, NT, F16, false>(p, acc, m0, n0, wm, wn, lane, 0, sz, smem);
+  if constexpr (UP4) {
+    const ConvK q = up4_out_view(p, py, px, tiles_x * tiles_y);
+    igemm_epilogue<FM, FN, WTM, WTN, BM, BN, NT, F16, false>(q, acc, m0, n0, wm, wn, lane, 0, 0, smem);
+  } else {
+    igemm_epilogue<FM, FN, WTM, WTN, BM, BN, NT, F16, false>(p, acc, m0, n0, wm, wn, lane, 0, sz, smem);
+  }
 }
 
 // Thin-N halo launch (round 5): 3x3 convolutions onto <= 32 output channels - the three conv_out layers (VAE decoder 128 -> 3 at 512 x 512:
@@ -2028,6 +2106,17 @@ struct Halo {
   // in-loader GroupNorm: the 128-wide tile only (the 160-wide variant's 5 x 16 accumulators leave no registers for it: it spilled)
   static constexpr bool GN_OK = BN <= 128;
   static int plan(ConvK& k, size_t ws_bytes) {
+    if (k.fold) {
+      // folded upsampling conv (dispatch_conv): patches of the SOURCE image x 4 output phases (grid y), four K tiles per chunk, never
+      // split; one GroupNorm partial per (phase, patch); no in-loader GroupNorm variant
+      k.tiles_m = k.N * (k.H / TH) * (k.W / 32);
+      k.tiles_n = (k.Cout + BN - 1) / BN;
+      k.nk = (k.Cin / 64) * 4;
+      k.splitk = 1;
+      k.nk_per_split = k.nk;
+      set_gn_plan(k, true, 4 * (k.H / TH) * (k.W / 32));
+      return 0;
+    }
     k.tiles_m = k.N * (k.OH / TH) * (k.OW / 32);
     k.tiles_n = (k.Cout + BN - 1) / BN;
     const int nchunk = k.nk / 9;
@@ -2045,8 +2134,16 @@ struct Halo {
       hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_kernel<TH, BN, WM, WN, UR_TU_F16 != 0, GN_OK>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
       hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_ws_kernel<TH, BN, WM, WN, UR_TU_F16 != 0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
       hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_ws_kernel<TH, BN, WM, WN, UR_TU_F16 != 0, GN_OK>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_kernel<TH, BN, WM, WN, UR_TU_F16 != 0, false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_halo_ws_kernel<TH, BN, WM, WN, UR_TU_F16 != 0, false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     }
     static const bool no_ws = getenv("UR_HALO_NOWS") != nullptr;          // A/B: every wave loads for itself (rounds 1-2 structure)
+    if (k.fold) {                                                          // (grid y = output phase)
+      const dim3 grid(k.tiles_m * k.tiles_n, 4);
+      if (no_ws) UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_kernel<TH, BN, WM, WN, F16, false, 4>), grid, dim3(NW * 64), lds, s, k));
+      else UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_ws_kernel<TH, BN, WM, WN, F16, false, 4>), grid, dim3((NW + 2) * 64), lds, s, k));
+      return ur::check_launch("ur_conv2d_nhwc");
+    }
     if (no_ws) {
       if (GN_OK && k.gn_ab) UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_kernel<TH, BN, WM, WN, F16, GN_OK>), dim3(k.tiles_m * k.tiles_n, k.splitk), dim3(NW * 64), lds, s, k));
       else UR_F16_SWITCH(k, hipLaunchKernelGGL((igemm_halo_kernel<TH, BN, WM, WN, F16, false>), dim3(k.tiles_m * k.tiles_n, k.splitk), dim3(NW * 64), lds, s, k));

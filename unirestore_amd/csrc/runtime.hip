@@ -76,7 +76,7 @@ ProfScope::~ProfScope() {
 
 extern "C" {
 
-int ur_version(void) { return 101; }
+int ur_version(void) { return 102; }
 const char* ur_last_error(void) { return ur::g_err.c_str(); }
 
 int ur_profile_enable(int on) {

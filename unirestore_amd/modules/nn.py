@@ -207,7 +207,14 @@ class Upsample2D(nn.Module):
         self.conv = Conv2d(c, c, 3, padding=1)
 
     def run(self, x):
-        return ops.conv(x, self.conv.packed(), upsample=True, gn=True)      # nearest-2x gather fused into the loader
+        pc = self.conv.packed()
+        n, h, w, c = x.shape
+        # Folded form: four 2x2 phase convs over the source image, 4/9 of the MACs (ops.up4_fold).  UR_UPS_FOLD=0 keeps the 9-tap launch
+        # (A/B).  The second copy of the weights is built only once the plan has taken the folded kernel.
+        if os.environ.get("UR_UPS_FOLD", "1") == "1" and ops.wants_up4(pc, n, h, w, c, 0, 1, True, 1):
+            if pc.w_up4 is not None or ops.conv_plan(x, pc, upsample=True, gn=True, up4=True).up4:
+                return ops.conv(x, pc, upsample=True, gn=True, up4=pc.up4(self.conv.weight))
+        return ops.conv(x, pc, upsample=True, gn=True)      # nearest-2x gather fused into the loader
 
 
 # ----------------------------------------------------------------------------------------------- attention

@@ -111,6 +111,48 @@ class PackedConv:
             self.w_frag = w.permute(0, 3, 4, 5, 1, 6, 2, 7).contiguous()  # lane = half * 32 + row
         return self.w_frag
 
+    w_up4: Optional[torch.Tensor] = None       # the four 2x2 phase convs of "nearest-2x upsample, then this 3x3 conv" (built on first use)
+
+    def up4(self, weight: torch.Tensor) -> torch.Tensor:
+        """ur_conv_desc.w_up4 from the fp32 master `weight` [Cout, Cin, 3, 3] of these packed weights: folded in fp32, rounded once
+        (up4_fold / up4_pack).  Call it once the plan has taken the folded path (ConvPlan.up4): it is a second copy of the weights."""
+        if self.w_up4 is None:
+            w = weight.detach().to(self.w.device, torch.float32).permute(0, 2, 3, 1)
+            if w.shape[0] != self.cout or w.shape[3] != self.cin:              # the padding pack_conv added (zero rows / channels)
+                w = torch.nn.functional.pad(w, (0, self.cin - w.shape[3], 0, 0, 0, 0, 0, self.cout - w.shape[0]))
+            self.w_up4 = up4_pack(up4_fold(w), self.w.dtype)
+        return self.w_up4
+
+
+def up4_fold(w: torch.Tensor) -> torch.Tensor:
+    """w [Cout][3][3][Cin] (fp32 / fp64) -> W4 [py][px][Cout][a][b][Cin]: a nearest-2x upsample followed by the 3x3 conv (pad 1) is,
+    for the output pixels of parity (py, px), a 2x2 conv over the source image - the 3x3 window of output row 2y + py covers the
+    source rows y - 1 + py + a, a in {0, 1}, and the taps that fall on one source row add up:
+    py = 0: {ky 0} -> a 0, {ky 1, 2} -> a 1;  py = 1: {ky 0, 1} -> a 0, {ky 2} -> a 1;  the columns likewise with px."""
+    sel = w.new_tensor([[[1, 0, 0], [0, 1, 1]], [[1, 1, 0], [0, 0, 1]]])       # [parity][a][k]
+    return torch.einsum("pay,qbx,oyxc->pqoabc", sel, sel, w)
+
+
+def up4_pack(w4: torch.Tensor, dtype) -> torch.Tensor:
+    """W4 [py][px][Cout][a][b][Cin] -> 16-bit [phase = 2 py + px][Cout][4 Cin], K chunk-major like the halo kernels' weights with four
+    taps per 64-channel chunk: K tile = chunk * 4 + (2 a + b)."""
+    _, _, cout, _, _, cin = w4.shape
+    assert cin % 64 == 0
+    return w4.to(dtype).reshape(4, cout, 4, cin // 64, 64).permute(0, 1, 3, 2, 4).reshape(4, cout, 4 * cin).contiguous()
+
+
+def up4_unpack(packed: torch.Tensor, cin: int) -> torch.Tensor:
+    """Inverse of up4_pack: [4][Cout][4 Cin] -> [py][px][Cout][a][b][Cin]."""
+    cout = packed.shape[1]
+    return packed.reshape(2, 2, cout, cin // 64, 2, 2, 64).permute(0, 1, 2, 4, 5, 3, 6).reshape(2, 2, cout, 2, 2, cin)
+
+
+def wants_up4(pc: "PackedConv", n, h, w_, c1, c2, stride, upsample, groups, pad=(1, 1)) -> bool:
+    """The upsampling launches csrc/igemm.hip can run folded (it also checks, and ConvPlan.up4 says what it chose): 3x3, pad 1, one
+    source of whole 64-channel chunks, and a source image of whole 8 x 32 patches."""
+    return (pc.k == 3 and pc.kcm and groups == 1 and stride == 1 and bool(upsample) and tuple(pad) == (1, 1) and not pc.pair
+            and c2 == 0 and c1 % 64 == 0 and w_ % 32 == 0 and h % 8 == 0)
+
 
 def wants_frag(pc: "PackedConv", n, h, w_, c1, c2, stride, upsample, groups) -> bool:
     """The launches csrc/igemm.hip sends to the weight-streaming kernel (it also checks): 3x3 on 8 x 8 maps of <= 16 images."""
@@ -198,12 +240,13 @@ def _conv_desc(x, pc: PackedConv, x2, stride, pad, upsample, out_hw, plan_only) 
 
 def conv(x: torch.Tensor, pc: PackedConv, *, x2=None, residual=None, bias=None, act=UR_ACT_NONE, stride=1, pad=None,
          out_hw=None, upsample=False, out_f32=False, out_scale=1.0, out=None, yt=None, n_split=0, t_rows=0,
-         gn=False, store=True, rows=False, ln_stats=None, gn_ab=None, gn_silu=False):
+         gn=False, store=True, rows=False, ln_stats=None, gn_ab=None, gn_silu=False, up4=None):
     """x: [N,H,W,C1] 16-bit (x2 optional [N,H,W,C2], virtual concat).  Returns [N,OH,OW,cout_out].
     gn=True: the consumer of the output is a GroupNorm / InstanceNorm / global average pool - leave its partial statistics
     (out._gn); store=False (with gn): only the statistics are wanted, the output tensor is not written (returns the plane).
     rows=True: leave per-row sums for a LayerNorm-folded consumer GEMM (out._ln).
-    gn_ab / gn_silu: read act(a*x+b) instead of x (GroupNorm apply fused into the loader; only where conv_plan says so)."""
+    gn_ab / gn_silu: read act(a*x+b) instead of x (GroupNorm apply fused into the loader; only where conv_plan says so).
+    up4 (with upsample): pc.up4(...) - the folded weights of the four 2x2 phase convs; taken where conv_plan(..., up4=True).up4."""
     if x.dtype not in (BF16, F16) or x.dtype != pc.w.dtype or not x.is_contiguous() or x.dim() != 4:
         raise ValueError(f"conv: x must be a contiguous 4-d {pc.w.dtype} tensor, got {x.dtype} {tuple(x.shape)}")
     n, h, w_, c1 = x.shape
@@ -227,6 +270,8 @@ def conv(x: torch.Tensor, pc: PackedConv, *, x2=None, residual=None, bias=None, 
         d.ln_stats, d.ln_colsum, d.ln_eps, d.ln_dim, d.ln_parts = st.data_ptr(), pc.ln_colsum.data_ptr(), pc.ln_eps, pc.cin, parts
     if gn_ab is not None:
         d.gn_ab, d.gn_silu = gn_ab.data_ptr(), int(gn_silu)
+    if up4 is not None:
+        d.w_up4 = up4.data_ptr()
     if out is not None:
         d.ldy = out.shape[-1]
     d.ldr = residual.shape[-1] if residual is not None else 0
@@ -259,7 +304,7 @@ def conv(x: torch.Tensor, pc: PackedConv, *, x2=None, residual=None, bias=None, 
     return out
 
 
-def conv_plan(x: torch.Tensor, pc: PackedConv, *, x2=None, stride=1, pad=None, upsample=False, gn=False, gn_ab=False,
+def conv_plan(x: torch.Tensor, pc: PackedConv, *, x2=None, stride=1, pad=None, upsample=False, gn=False, gn_ab=False, up4=False,
               act=UR_ACT_NONE, residual=False, store=True) -> ConvPlan:
     """What `conv` would do for this (shape, weights) - used to decide whether the GroupNorm apply can ride in the conv."""
     d = _conv_desc(x, pc, x2, stride, pad, upsample, None, plan_only=True)
@@ -267,6 +312,7 @@ def conv_plan(x: torch.Tensor, pc: PackedConv, *, x2=None, stride=1, pad=None, u
     d.residual = 16 if residual else None
     d.gn_part = 16 if gn else None
     d.gn_ab = 16 if gn_ab else None
+    d.w_up4 = 16 if up4 else None
     d.ldr = pc.cout_out if residual else 0
     d.act = act
     plan = ConvPlan()
@@ -274,7 +320,7 @@ def conv_plan(x: torch.Tensor, pc: PackedConv, *, x2=None, stride=1, pad=None, u
     return plan
 
 
-def conv_launch(x: torch.Tensor, pc: PackedConv, *, x2=None, stride=1, pad=None, upsample=False, gn=False, gn_ab=False,
+def conv_launch(x: torch.Tensor, pc: PackedConv, *, x2=None, stride=1, pad=None, upsample=False, gn=False, gn_ab=False, up4=False,
                 act=UR_ACT_NONE, residual=False, store=True):
     """Which launcher `conv` would run for this (shape, weights), and its split (capi.ConvLaunchInfo; name: capi.launcher_names())."""
     d = _conv_desc(x, pc, x2, stride, pad, upsample, None, plan_only=True)
@@ -282,6 +328,7 @@ def conv_launch(x: torch.Tensor, pc: PackedConv, *, x2=None, stride=1, pad=None,
     d.residual = 16 if residual else None
     d.gn_part = 16 if gn else None
     d.gn_ab = 16 if gn_ab else None
+    d.w_up4 = 16 if up4 else None
     d.ldr = pc.cout_out if residual else 0
     d.act = act
     return capi.plan_launch(d)
