@@ -689,6 +689,37 @@ int ur_rvt_attention_f32(const float* qkv, const float* gate, float* out, int N,
 int ur_dwconv3x3_f32(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int C, int mult, int stride, int act,
                      ur_stream_t stream);
 
+/* ---- VGG scoring of the cls output (torchvision's VGG 11 / 13 / 16 / 19, with or without BatchNorm; exact fp32, NHWC, no atomics,
+ * fixed-order sums) ------------------------------------------------------------------------------------------------------------
+ * The 3 x 3 convolutions are the convolution above with the BatchNorm folded in.  What is new is csrc/vgg.hip.
+ *
+ * The Linear: y[M][N] = act(x[M][K] . W^T + bias), relu 0 or 1 (maximum(v, 0): NaN and +inf stay, -inf becomes 0), for a few rows
+ *   against a large matrix.  The weights are streamed once per 32 rows: K is split into S = ceil(K / 512) parts over the grid
+ *   (ceil(N / 128) x S x ceil(M / 32) workgroups; S and every tile boundary depend on K and N alone, never on M), each part is a
+ *   k-ordered chain on v_mfma_f32_32x32x2_f32 restarted every 256 products, the fp32 partial sums go to ws[S][M][N] with plain
+ *   stores, and a second launch adds them in ascending s in fp64, adds the bias, rounds to fp32 once and applies the ReLU.  An output
+ *   row depends on its own input row alone: it has the same bits alone, in any batch and at any position, and a NaN or an infinity
+ *   in one row of x reaches that row only.  Rows >= M, columns >= N and k >= K are zeros made in registers, never read.
+ *   wp is the kernel's own layout, made once on the host: float4 [npad / 32][kpad / 8][64], element j of lane l in (column tile c,
+ *   k block b) = W[32 c + (l & 31)][8 b + 4 (l >> 5) + j] of the [N][K] matrix, zero for a column >= N or k >= K;
+ *   ur_vgg_linear_wpack_dims gives kpad (K rounded up to 64), npad (N rounded up to 32) and S.  ws: ur_vgg_linear_ws_bytes(M, K, N)
+ *   = 4 S M N bytes (0 for sizes outside the limits).
+ * The max-pool: 2 x 2 / stride 2, no padding, floor mode: [N,H,W,C] -> [N,H/2,W/2,C]; an odd last row or column is not read; a NaN
+ *   tap is the window's maximum and a window of -inf gives -inf, as the max-pools above.  float4 accesses when C % 4 == 0 and both
+ *   pointers are 16-byte aligned.
+ * The adaptive average pool: [N,H,W,C] -> [N,7,7,C], output (i, j) is the mean of rows [floor(i H / 7), ceil((i + 1) H / 7)) and the
+ *   columns likewise (F.adaptive_avg_pool2d), summed row-major in fp64, divided by the count, rounded to fp32 once.  On a 7 x 7 map
+ *   it returns the input's bits; smaller maps replicate values.
+ * Limits (64-bit arithmetic, before any HIP call): Linear: 1 <= M <= 2^20, 1 <= K, N <= 2^24, M*N below 2^31 - 256, wp 16-byte and
+ *   x, bias, y, ws 4-byte aligned, ws_bytes >= ur_vgg_linear_ws_bytes, y, ws and x not overlapping.  Max-pool: N, C >= 1, H, W >= 2,
+ *   N*H*W*C below 2^31 - 256, y not x.  Average pool: N, C, H, W >= 1, N*H*W*C and N*49*C below 2^31 - 256, y not x. */
+int ur_vgg_linear_wpack_dims(int K, int N, int* kpad, int* npad, int* splits);
+long long ur_vgg_linear_ws_bytes(int M, int K, int N);
+int ur_vgg_linear_f32(const float* x, const float* wp, const float* bias, float* y, void* ws, long long ws_bytes, int M, int K, int N,
+                      int relu, ur_stream_t stream);
+int ur_vgg_maxpool2_f32(const float* x, float* y, int N, int H, int W, int C, ur_stream_t stream);
+int ur_vgg_avgpool7_f32(const float* x, float* y, int N, int H, int W, int C, ur_stream_t stream);
+
 /* ---- colour correction of a restored image (between the decoder's conv_out and the egress kernels) ----------------------
  * c fp32 NHWC [N,H,W,ld_c]: the restored image; src 16-bit NHWC [src_n,H,W,ld_s]: the image the encoder saw, image n is corrected
  * against source n % src_n (a task-major K*B batch against B sources); out fp32 NHWC [N,H,W,ld_c], not c.  Channels 0..2 are RGB;

@@ -154,6 +154,11 @@ SIGNATURES = {
     "ur_swin_attention_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ur_rvt_attention_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "ur_dwconv3x3_f32": (_I, [_P, _P, _P, _P] + [_I] * 7 + [_P]),
+    "ur_vgg_linear_wpack_dims": (_I, [_I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "ur_vgg_linear_ws_bytes": (_LL, [_I, _I, _I]),
+    "ur_vgg_linear_f32": (_I, [_P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _P]),
+    "ur_vgg_maxpool2_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "ur_vgg_avgpool7_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "ur_color_fix_wavelet": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "ur_color_fix_adain": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "ur_color_fix_adain_ws_bytes": (_SZ, [_I, _I, _I]),

@@ -15,7 +15,7 @@ is an error, not a fallback.  Prints one JSON line on rank 0.  `validate --lpips
 NAME=ARCH:WEIGHTS.pth` the top-1 accuracy of a user-supplied ResNet on the `cls` output (unirestore_amd.classify), `--vit
 NAME=ARCH:WEIGHTS.pth` that of a user-supplied VisionTransformer (unirestore_amd.vit), `--swin NAME=ARCH:WEIGHTS.pth` that of a
 user-supplied Swin-V2 (unirestore_amd.swin), `--rvt NAME=ARCH:WEIGHTS.pth` that of a user-supplied Robust Vision Transformer
-(unirestore_amd.rvt), `validate --tasks
+(unirestore_amd.rvt), `--vgg NAME=ARCH:WEIGHTS.pth` that of a user-supplied torchvision VGG (unirestore_amd.vgg), `validate --tasks
 ir,seg --segment NAME=ARCH:WEIGHTS.pth` the mIoU of a user-supplied RefineNet-LW on the `seg` output (unirestore_amd.segment) and
 `--deeplab NAME=ARCH:WEIGHTS.pth` that of a user-supplied DeepLabV3+ (unirestore_amd.deeplab), `validate --niqe PARAMS` the no-reference NIQE score of the restored images and of the
 inputs against a user-supplied pristine model (unirestore_amd.niqe); all opt-in.
@@ -308,17 +308,33 @@ def check_rvt_arg(rvt, classify=None, vit=None, swin=None):
     return out
 
 
-def check_classifiers_arg(classify, vit, swin=None, rvt=None):
-    """The checked --classify, --vit, --swin and --rvt arguments (each may be None) as the one dict of classifiers the evaluator
-    takes - it tells the networks apart - and the option that errors about the run name: (None, None) when none is given."""
-    if classify is None and vit is None and swin is None and rvt is None:
+def check_vgg_arg(vgg, classify=None, vit=None, swin=None, rvt=None):
+    """--vgg NAME=ARCH:WEIGHTS.pth[,NAME=ARCH:OTHER.pth] (or a dict NAME -> (ARCH, path) | a loaded vgg.VGGWeights) -> {name: (arch,
+    path) | VGGWeights}.  ValueError for a malformed item, an unknown arch, a missing file, a name given twice or a name that
+    `classify`, `vit`, `swin` or `rvt` (the checked arguments of those options) already uses: all write val_lq/NAME.  ARCH is one of
+    vgg.ARCHS (torchvision's vgg11 / vgg13 / vgg16 / vgg19 and their _bn variants); the weights are the user's."""
+    from .vgg import ARCHS
+    out = _check_scorer_arg("--vgg", vgg, ARCHS, "a torchvision VGG state dict")
+    for flag, other in (("--classify", classify), ("--vit", vit), ("--swin", swin), ("--rvt", rvt)):
+        both = sorted(set(out) & set(other or {}))
+        if both:
+            raise ValueError(f"--vgg: the name {both[0]!r} is used by {flag} too; every classifier needs a name of its own")
+    return out
+
+
+def check_classifiers_arg(classify, vit, swin=None, rvt=None, vgg=None):
+    """The checked --classify, --vit, --swin, --rvt and --vgg arguments (each may be None) as the one dict of classifiers the
+    evaluator takes - it tells the networks apart - and the option that errors about the run name: (None, None) when none is given."""
+    if classify is None and vit is None and swin is None and rvt is None and vgg is None:
         return None, None
-    flag = "--classify" if classify is not None else "--vit" if vit is not None else "--swin" if swin is not None else "--rvt"
+    flag = ("--classify" if classify is not None else "--vit" if vit is not None else "--swin" if swin is not None
+            else "--rvt" if rvt is not None else "--vgg")
     classify = {} if classify is None else check_classify_arg(classify)
     vit = {} if vit is None else check_vit_arg(vit, classify)
     swin = {} if swin is None else check_swin_arg(swin, classify, vit)
     rvt = {} if rvt is None else check_rvt_arg(rvt, classify, vit, swin)
-    return {**classify, **vit, **swin, **rvt}, flag
+    vgg = {} if vgg is None else check_vgg_arg(vgg, classify, vit, swin, rvt)
+    return {**classify, **vit, **swin, **rvt, **vgg}, flag
 
 
 def check_segment_arg(segment):
@@ -379,7 +395,8 @@ def check_crop_arg(crop):
 
 
 def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_16bit=False, metrics_device="cpu", tasks=None,
-             model=None, lpips=None, classify=None, segment=None, crop=None, niqe=None, deeplab=None, vit=None, swin=None, rvt=None) -> dict:
+             model=None, lpips=None, classify=None, segment=None, crop=None, niqe=None, deeplab=None, vit=None, swin=None, rvt=None,
+             vgg=None) -> dict:
     """tasks: a list of task names - every batch is restored once and decoded for each of them (DiffUIE.forward_tasks).  PSNR / SSIM
     come from the "ir" output, so the list must hold "ir"; images_per_s counts input images.  model: a ready DiffUIE to use instead
     of building the config's.  With data.CorruptedImageFiles (and data.DistortedImageFiles: "snow/3") the result also holds by_corruption ("fog/3" -> psnr, ssim, images)
@@ -394,7 +411,8 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
     vit: the same form with vit.ARCHS and vit.ViTWeights - a VisionTransformer scored under the same keys (a name may be used by only
     one of the two).  swin: the same form with swin.ARCHS and swin.SwinWeights - a Swin-V2, likewise (a name may be used by only
     one of the three).  rvt: the same form with rvt.ARCHS and rvt.RVTWeights - a Robust Vision Transformer, likewise (a name may be
-    used by only one of the four).
+    used by only one of the four).  vgg: the same form with vgg.ARCHS and vgg.VGGWeights - a torchvision VGG, likewise (a name may be
+    used by only one of the five).
     segment: "NAME=ARCH:WEIGHTS.pth,..." or {NAME: (ARCH, path) | segment.SegmenterWeights} - RefineNet-LW mIoU of the "seg" output
     against the data's label maps (tasks must hold "seg", the data must be built with labels: map): the result and every
     by_corruption entry gain, per NAME, the mIoU (the reference's MulticlassJaccardIndex(19, ignore_index=255)) and NAME_acc (pixel
@@ -411,7 +429,7 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
         niqe = check_niqe_arg(niqe)                       # before the model is built
     if lpips is not None and isinstance(lpips, (str, tuple, list)):
         lpips = check_lpips_arg(lpips)                    # before the model is built
-    classify, cls_flag = check_classifiers_arg(classify, vit, swin, rvt)       # before the model is built; from here on one dict of classifiers
+    classify, cls_flag = check_classifiers_arg(classify, vit, swin, rvt, vgg)  # before the model is built; from here on one dict of classifiers
     segment, seg_flag = check_segmenters_arg(segment, deeplab)      # from here on one dict of segmenters
     crop_args = {} if crop is None else dict(crop=check_crop_arg(crop))
     r = resolve(cfg, allow_16bit=allow_16bit)
@@ -886,6 +904,11 @@ def main(argv=None):
                          "the data's labels; ARCH is rvt_tiny, rvt_small, rvt_base or one of their _plus variants, WEIGHTS a user-supplied "
                          "RVT checkpoint; needs --tasks with cls and a dataset built with labels: true; a NAME may not be one of "
                          "--classify's, --vit's or --swin's")
+    ap.add_argument("--vgg", default=None, metavar="NAME=ARCH:WEIGHTS.pth[,...]",
+                    help="validate: also report VGG top-1 accuracy of the 'cls' output (fp32, on the GPU) against the data's labels; ARCH "
+                         "is vgg11, vgg13, vgg16, vgg19 or one of their _bn variants, WEIGHTS a user-supplied torchvision state dict; "
+                         "needs --tasks with cls and a dataset built with labels: true; a NAME may not be one of --classify's, --vit's, "
+                         "--swin's or --rvt's")
     ap.add_argument("--segment", default=None, metavar="NAME=ARCH:WEIGHTS.pth[,...]",
                     help="validate: also report RefineNet-LW mIoU and pixel accuracy of the 'seg' output (fp32, on the GPU) against the "
                          "data's label maps; ARCH is rflw50, rflw101 or rflw152, WEIGHTS a user-supplied state dict; needs --tasks with "
@@ -926,7 +949,7 @@ def main(argv=None):
     ap.add_argument("--quality", default=None, metavar="10,25,s3", help="jpeg: qualities 1..100 and / or s1..s5 (the reference's severities)")
     ap.add_argument("--subsampling", default="4:2:0", help="jpeg: 4:2:0 (Pillow's and the reference's default) or 4:4:4")
     a = ap.parse_args(argv)
-    for flag in ("classify", "vit", "swin", "rvt", "segment", "deeplab", "crop", "niqe"):
+    for flag in ("classify", "vit", "swin", "rvt", "vgg", "segment", "deeplab", "crop", "niqe"):
         if getattr(a, flag) is not None and a.command != "validate":
             ap.error(f"--{flag} belongs to validate")
     if a.command in FILE_COMMANDS:
@@ -957,7 +980,7 @@ def main(argv=None):
     tasks = [t for t in a.tasks.split(",") if t] if a.tasks is not None else None
     cfg = apply_color_fix(load_config(a.config, a.set), a.color_fix)
     try:
-        classifiers, cls_flag = check_classifiers_arg(a.classify, a.vit, a.swin, a.rvt)
+        classifiers, cls_flag = check_classifiers_arg(a.classify, a.vit, a.swin, a.rvt, a.vgg)
         if classifiers is not None:
             check_classify_run(classifiers, tasks, resolve(cfg, allow_16bit=a.allow_16bit), flag=cls_flag)
     except ValueError as e:
@@ -985,7 +1008,7 @@ def main(argv=None):
         return 0
     res = validate(cfg, hf_root=a.hf_root, max_batches=a.max_batches, allow_16bit=a.allow_16bit, metrics_device=a.metrics_device,
                    tasks=tasks, lpips=a.lpips, classify=a.classify, segment=a.segment, crop=a.crop, niqe=a.niqe, deeplab=a.deeplab, vit=a.vit, swin=a.swin,
-                   rvt=a.rvt)
+                   rvt=a.rvt, vgg=a.vgg)
     if res is not None:
         print(json.dumps(res))
     return 0

@@ -1234,6 +1234,24 @@ def rvt(images: torch.Tensor, weights) -> torch.Tensor:
     return _rvt.forward(images, weights)
 
 
+def vgg(images: torch.Tensor, weights) -> torch.Tensor:
+    """`classify` with a VGG: logits [N, classes] (fp32, on the device) of fp32 NCHW images in [0,1], any H, W >= 1 - the
+    classification evaluator's preprocess (antialiased bilinear resize to 224 x 224, ImageNet normalisation) and a torchvision-
+    layout VGG 11 / 13 / 16 / 19 (with or without BatchNorm) in exact fp32 on the GPU (the fp32 convolution with the BatchNorm
+    folded in; the 2 x 2 max-pool, the adaptive average pool and the split-K Linear of csrc/vgg.hip).  weights: what
+    vgg.load_weights / vgg.random_weights return; `top1` takes the logits as it takes `classify`'s.  An image's logits do not
+    depend on its place in the batch, and two calls give the same bits.  No host sync.  A non-finite pixel is not erased on the
+    way: it reaches its image's logits as in the fp64 restatement in torch (one NaN pixel: every logit of that image is NaN); the
+    other images' logits are the bits a clean batch gives."""
+    from . import vgg as _vgg
+    _check_images("vgg", "images", images)
+    n, c, h, w = images.shape
+    if n < 1 or c != 3 or h < 1 or w < 1:
+        raise ValueError(f"vgg: needs [N>=1, 3, H>=1, W>=1] images, got {tuple(images.shape)}")
+    _check_scorer("vgg", "weights", weights, _vgg.VGGWeights, "vgg.load_weights / vgg.random_weights")
+    return _vgg.forward(images, weights)
+
+
 def top1(logits: torch.Tensor, labels: torch.Tensor):
     """(pred, tp, targets, predicted) of one batch: pred int64 [N] = the argmax of logits fp32 [N,C] (ties to the lowest index, as
     torch.argmax), and the three int64 [C] per-class counts of classify.accuracy - tp_c (pred = label = c), targets_c, predicted_c.

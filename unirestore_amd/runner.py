@@ -129,13 +129,13 @@ class LitUniFIE:
         # inputs ("cls_input/<name>").  A total is REPLACED by a new tensor, never changed in place: callers keep the old one to
         # take differences.  A vit.ViTWeights, or an (arch, path) whose arch is one of vit.ARCHS, is a VisionTransformer under the same
         # keys, a swin.SwinWeights or an arch of swin.ARCHS a Swin-V2, an rvt.RVTWeights or an arch of rvt.ARCHS a Robust Vision
-        # Transformer: update_classification tells the networks apart by the weights' type.
+        # Transformer, a vgg.VGGWeights or an arch of vgg.ARCHS a VGG: update_classification tells the networks apart by the weights' type.
         self.classifiers = {}
         for name, spec in (classifiers or {}).items():
-            from . import classify, rvt, swin, vit
+            from . import classify, rvt, swin, vgg, vit
             w = spec
-            if not isinstance(spec, (classify.ClassifierWeights, vit.ViTWeights, swin.SwinWeights, rvt.RVTWeights)):      # (arch, path): the arch's table names its module
-                module = next((m for m in (vit, swin, rvt) if isinstance(spec[0], str) and spec[0] in m.ARCHS), classify)
+            if not isinstance(spec, (classify.ClassifierWeights, vit.ViTWeights, swin.SwinWeights, rvt.RVTWeights, vgg.VGGWeights)):      # (arch, path): the arch's table names its module
+                module = next((m for m in (vit, swin, rvt, vgg) if isinstance(spec[0], str) and spec[0] in m.ARCHS), classify)
                 w = module.load_weights(*spec)
             self.classifiers[name] = w
             for key in self.classifier_keys(name):
@@ -305,12 +305,13 @@ class LitUniFIE:
         if labels is None:
             raise ValueError("the classifiers need the batch's labels (gt is None): build the dataset with labels: true on an "
                              "`lq hq label` list")
-        from . import ops, rvt, swin, vit
+        from . import ops, rvt, swin, vgg, vit
         if self.need_crop:
             inputs = self._crop(inputs)
         for name, w in self.classifiers.items():
             predict = (ops.vit if isinstance(w, vit.ViTWeights) else ops.swin if isinstance(w, swin.SwinWeights)
-                       else ops.rvt if isinstance(w, rvt.RVTWeights) else ops.classify)                 # each takes its own weights class
+                       else ops.rvt if isinstance(w, rvt.RVTWeights) else ops.vgg if isinstance(w, vgg.VGGWeights)
+                       else ops.classify)                 # each takes its own weights class
             for key, images in zip(self.classifier_keys(name), (cls_preds, inputs)):
                 logits = predict(images.to(device=w.device, dtype=torch.float32).contiguous(), w)
                 _pred, tp, targets, predicted = ops.top1(logits, labels)
