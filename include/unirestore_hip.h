@@ -950,6 +950,53 @@ int ur_niqe_halve(const double* y, double* out, int N, int h, int w, ur_stream_t
 int ur_niqe_fit(const double* moments, const double* rho, const double* scale, const double* mean_ratio, double* features,
                 int* alpha_index, long long rows, int block_pixels, int ld, int col_off, ur_stream_t stream);
 
+/* ---- RetinaNet scoring of the det output (csrc/detect.hip; the network and the host side are unirestore_amd/detect.py) ----------
+ * fp32 throughout, maps NHWC and contiguous.  No allocation, no synchronisation, no global atomics; every floating-point sum in a
+ * fixed order: the same inputs give the same bits, and an image's results depend on that image alone.
+ * ur_det_prep: x NCHW [N,3,H,W] in [0,1] -> y NHWC [N,HP,WP,3]: (v - mean_c) / std_c (ImageNet), then the half-pixel bilinear resize
+ *     to RH x RW with the tables iy int32 [RH] / wy fp32 [RH][2] and ix [RW] / wx [RW][2] (output o reads sources i[o] and
+ *     min(i[o] + 1, last) with the weights w[o]), as wy0 (wx0 a + wx1 b) + wy1 (wx0 c + wx1 d); zeros beyond RH x RW.
+ * ur_upsample_nearest_add_f32: y [N,OH,OW,C] = a [N,OH,OW,C] + b [N,h,w,C] at (iy[oh], ix[ow]); iy int32 [OH] and ix int32 [OW] are
+ *     built on the host and must lie inside b.  y is a buffer of its own.
+ * ur_groupnorm_relu_f32: GroupNorm of x [N,HW,C] over G groups of C / G neighbouring channels: per (image, group) the mean, then
+ *     the biased variance of the centred values, in fp64 in a fixed order; y = (x - mean) / sqrt(var + eps) * gamma_c + beta_c in
+ *     fp64, rounded to fp32 once; relu 1: maximum(y, 0), a NaN stays.  Any 4-byte aligned pointers.  y is not x.
+ * ur_det_select: logits [N][HWA][K], reg [N][HWA][4] (or NULL).  Per image the candidates are the logits > lt (a NaN is none; -0
+ *     equals +0); the first min(k, count) of them in the order (logit descending, flat index ascending) are written in that order to
+ *     row n (row stride ld >= k elements) of scores (sigmoid of the logit, evaluated in fp64 and rounded to fp32), anchors (index /
+ *     K), labels (index % K) and, unless NULL, index; entries from the count up to k are zero.  counts[n] = min(k, count);
+ *     nonfinite[n] = 1 when any logit or any regression of the image is not finite, else 0.  k <= ur_det_select_kmax() = 1024.
+ *     The result is exact whatever share of the logits passes.  ws: ur_det_select_ws_bytes(N, HWA * K) bytes, 16-byte aligned.
+ * ur_det_decode: for j < counts[n], candidate (n, j) with anchor index an = anchors[n * ld + j]: a = an % A, cell = an / A, anchor =
+ *     base[a] (fp32 [A][4], x1 y1 x2 y2) shifted by ((cell % WF) * stride_w, (cell / WF) * stride_h); torchvision's BoxCoder with
+ *     weights (1, 1, 1, 1) and dw, dh clamped at log(1000 / 16) on reg[n][an] gives `raw` (or NULL), clamped to [0, img_w] x [0,
+ *     img_h] `clipped`, and times (ratio_w, ratio_h) `scaled`: rows of ld boxes, zeros from counts[n] up to k.
+ * ur_det_nms: class-aware greedy NMS of the candidates of each image among its M <= ur_det_nms_mmax() = 8192 positions; position p is
+ *     a candidate when p % seg < counts[(p / seg) * N + n] (counts int32 [levels][N], seg * levels >= M).  Order: (score descending,
+ *     position ascending).  A box is dropped when a kept box of its label has inter / (area_a + area_b - inter) > thresh, areas
+ *     and inter as in torchvision's nms, on `boxes`; the first D kept are written: y_boxes (from out_boxes), y_scores, y_labels
+ *     (int64), y_keep (the positions; -1 beyond the count), zeros beyond y_count[n].  flags int32 [levels][N] or NULL: any set ->
+ *     y_nonfinite[n] = 1 and the image has no detections.  ws: ur_det_nms_ws_bytes(N, M) bytes, 8-byte aligned.
+ * UR_E_INVALID before any HIP call for a null required pointer, a size out of range, a misaligned pointer or a small workspace. */
+int ur_det_prep(const float* x, float* y, int N, int H, int W, int RH, int RW, int HP, int WP, const int32_t* iy, const float* wy,
+                const int32_t* ix, const float* wx, ur_stream_t stream);
+int ur_upsample_nearest_add_f32(const float* a, const float* b, float* y, int N, int OH, int OW, int C, int h, int w, const int32_t* iy,
+                                const int32_t* ix, ur_stream_t stream);
+int ur_groupnorm_relu_f32(const float* x, const float* gamma, const float* beta, float* y, int N, int HW, int C, int G, double eps, int relu,
+                          ur_stream_t stream);
+int ur_det_select_kmax(void);
+long long ur_det_select_ws_bytes(int N, long long L);
+int ur_det_select(const float* logits, const float* reg, int N, long long HWA, int K, float lt, int k, float* scores, int32_t* anchors,
+                  int32_t* labels, int32_t* index, int ld, int32_t* counts, int32_t* nonfinite, void* ws, long long ws_bytes, ur_stream_t stream);
+int ur_det_decode(const float* reg, const int32_t* anchors, const int32_t* counts, const float* base, float* raw, float* clipped,
+                  float* scaled, int N, long long HWA, int k, int ld, int A, int WF, int stride_h, int stride_w, float img_h, float img_w,
+                  float ratio_h, float ratio_w, ur_stream_t stream);
+int ur_det_nms_mmax(void);
+long long ur_det_nms_ws_bytes(int N, int M);
+int ur_det_nms(const float* boxes, const float* out_boxes, const float* scores, const int32_t* labels, const int32_t* counts,
+               const int32_t* flags, int N, int M, int seg, int levels, float thresh, int D, float* y_boxes, float* y_scores,
+               long long* y_labels, int32_t* y_keep, int32_t* y_count, int32_t* y_nonfinite, void* ws, long long ws_bytes, ur_stream_t stream);
+
 /* ---- live per-kernel-family timing (HIP events on the launch stream) ------------------------------*/
 int ur_profile_enable(int on);
 /* writes a JSON object {family: {launches, ms, flops, bytes}} into buf (host); synchronises the events */

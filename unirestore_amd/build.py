@@ -21,7 +21,7 @@ SOURCES = [(u, [f"-DUR_TU_F16={t}"], u.replace(".hip", "_f16.o" if t else "_bf16
           [("attention.hip", [f"-DUR_TU_F16={t}"], "attention_f16.o" if t else "attention_bf16.o") for t in (0, 1)] + \
           [("attention_pp.hip", [f"-DUR_TU_F16={t}"], "attention_pp_f16.o" if t else "attention_pp_bf16.o") for t in (0, 1)] + \
           [("attention512.hip", [f"-DUR_TU_F16={t}"], "attention512_f16.o" if t else "attention512_bf16.o") for t in (0, 1)] + \
-          [(u, [], u.replace(".hip", ".o")) for u in ("tchain.hip", "igemm.hip", "norms.hip", "elementwise.hip", "runtime.hip", "metrics.hip", "f32_layers.hip", "lpips.hip", "classify.hip", "segment.hip", "vit.hip", "swin.hip", "rvt.hip", "vgg.hip", "colorfix.hip", "noise.hip", "corrupt.hip", "jpeg.hip", "resize.hip", "distort.hip", "niqe.hip")]
+          [(u, [], u.replace(".hip", ".o")) for u in ("tchain.hip", "igemm.hip", "norms.hip", "elementwise.hip", "runtime.hip", "metrics.hip", "f32_layers.hip", "lpips.hip", "classify.hip", "segment.hip", "vit.hip", "swin.hip", "rvt.hip", "vgg.hip", "detect.hip", "colorfix.hip", "noise.hip", "corrupt.hip", "jpeg.hip", "resize.hip", "distort.hip", "niqe.hip")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value",
          "-Wno-unused-result"]
 

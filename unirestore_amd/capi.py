@@ -159,6 +159,16 @@ SIGNATURES = {
     "ur_vgg_linear_f32": (_I, [_P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _P]),
     "ur_vgg_maxpool2_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "ur_vgg_avgpool7_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "ur_det_prep": (_I, [_P, _P] + [_I] * 7 + [_P, _P, _P, _P, _P]),
+    "ur_upsample_nearest_add_f32": (_I, [_P, _P, _P] + [_I] * 6 + [_P, _P, _P]),
+    "ur_groupnorm_relu_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, C.c_double, _I, _P]),
+    "ur_det_select_kmax": (_I, []),
+    "ur_det_select_ws_bytes": (_LL, [_I, _LL]),
+    "ur_det_select": (_I, [_P, _P, _I, _LL, _I, _F, _I, _P, _P, _P, _P, _I, _P, _P, _P, _LL, _P]),
+    "ur_det_decode": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _LL] + [_I] * 6 + [_F] * 4 + [_P]),
+    "ur_det_nms_mmax": (_I, []),
+    "ur_det_nms_ws_bytes": (_LL, [_I, _I]),
+    "ur_det_nms": (_I, [_P] * 6 + [_I] * 4 + [_F, _I] + [_P] * 7 + [_LL, _P]),
     "ur_color_fix_wavelet": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "ur_color_fix_adain": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "ur_color_fix_adain_ws_bytes": (_SZ, [_I, _I, _I]),

@@ -17,7 +17,8 @@ NAME=ARCH:WEIGHTS.pth` that of a user-supplied VisionTransformer (unirestore_amd
 user-supplied Swin-V2 (unirestore_amd.swin), `--rvt NAME=ARCH:WEIGHTS.pth` that of a user-supplied Robust Vision Transformer
 (unirestore_amd.rvt), `--vgg NAME=ARCH:WEIGHTS.pth` that of a user-supplied torchvision VGG (unirestore_amd.vgg), `validate --tasks
 ir,seg --segment NAME=ARCH:WEIGHTS.pth` the mIoU of a user-supplied RefineNet-LW on the `seg` output (unirestore_amd.segment) and
-`--deeplab NAME=ARCH:WEIGHTS.pth` that of a user-supplied DeepLabV3+ (unirestore_amd.deeplab), `validate --niqe PARAMS` the no-reference NIQE score of the restored images and of the
+`--deeplab NAME=ARCH:WEIGHTS.pth` that of a user-supplied DeepLabV3+ (unirestore_amd.deeplab), `validate --tasks ir,det --detect
+NAME=ARCH:WEIGHTS.pth` the mAP of a user-supplied torchvision RetinaNet on the `det` output (unirestore_amd.detect), `validate --niqe PARAMS` the no-reference NIQE score of the restored images and of the
 inputs against a user-supplied pristine model (unirestore_amd.niqe); all opt-in.
 """
 import argparse
@@ -382,6 +383,52 @@ def check_segmenters_arg(segment, deeplab):
     return {**segment, **deeplab}, flag
 
 
+def check_detect_arg(detect, det_score=0.05, det_iou=0.5):
+    """--detect NAME=ARCH:WEIGHTS.pth[,NAME=ARCH:OTHER.pth] (or a dict NAME -> (ARCH, path) | a loaded detect.DetectorWeights) ->
+    {name: (arch, path) | DetectorWeights}.  ValueError for a malformed item, an unknown arch, a missing file or a name given twice,
+    a --det-score outside [0, 1) or a --det-iou outside (0, 1].  ARCH is one of detect.ARCHS (torchvision's
+    retinanet_resnet50_fpn_v2); the weights are the user's."""
+    from .detect import ARCHS
+    out = _check_scorer_arg("--detect", detect, ARCHS, "a torchvision RetinaNet state dict")
+    if not (isinstance(det_score, (int, float)) and 0.0 <= float(det_score) < 1.0):
+        raise ValueError(f"--det-score {det_score!r}: the score threshold must be in [0, 1)")
+    if not (isinstance(det_iou, (int, float)) and 0.0 < float(det_iou) <= 1.0):
+        raise ValueError(f"--det-iou {det_iou!r}: the IoU threshold must be in (0, 1]")
+    return out
+
+
+def check_detect_run(detect, tasks, r: dict, flag="--detect"):
+    """What a detector run needs besides its weights, checked before the model is built: `det` among the tasks (it is not added
+    silently, and `ir` stays required for PSNR), a config whose task editor knows `det`, and a dataset that yields boxes.
+    r = resolve(cfg)."""
+    if tasks is None or "det" not in tasks:
+        raise ValueError(f"{flag} scores the 'det' output: pass --tasks with 'det' in it, e.g. ir,det (got "
+                         f"{'none' if tasks is None else ','.join(tasks)}; it is not added silently)")
+    known = list((r["model_kwargs"].get("tedit") or {}).get("task") or [])
+    if "det" not in known:
+        raise ValueError(f"{flag} needs the 'det' output, and the config's task editor knows {known}: add det to model tedit.task")
+    cls_name = r["data_class"].rsplit(".", 1)[1]
+    if cls_name not in LABELLED_DATA or r["data_args"].get("labels") != "boxes":
+        raise ValueError(f"{flag} needs boxes, and data.{cls_name} yields none as configured: use an `lq hq annotation.json` list with "
+                         f"one of {list(LABELLED_DATA)} and set `labels: boxes` in data.init_args")
+
+
+def merge_detection_states(everyone, det_iou):
+    """The detector states of every rank as one: everyone[q] = (rank q's {totals key: detect.MeanAP}, its [restored, input] counts
+    of non-finite images, its {"fog/3": {totals key: MeanAP}}), merged in rank order into fresh states -> (totals, det_nonfinite,
+    by_corruption).  The per-class lists are concatenated, so the result is what one rank would hold had it seen every batch."""
+    from .detect import MeanAP
+    totals, bad, by = {}, [0, 0], {}
+    for totals_q, bad_q, by_q in everyone:
+        for k, ap in totals_q.items():
+            totals.setdefault(k, MeanAP(det_iou)).merge(ap)
+        bad = [a + b for a, b in zip(bad, bad_q)]
+        for c, aps in by_q.items():
+            for k, ap in aps.items():
+                by.setdefault(c, {}).setdefault(k, MeanAP(det_iou)).merge(ap)
+    return totals, bad, by
+
+
 def check_crop_arg(crop):
     """--crop H,W (or a pair of integers) -> (H, W): the evaluator's centre crop, 512,512 unless given (the reference's seg and
     multi-task evaluators use 960,1664)."""
@@ -396,7 +443,7 @@ def check_crop_arg(crop):
 
 def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_16bit=False, metrics_device="cpu", tasks=None,
              model=None, lpips=None, classify=None, segment=None, crop=None, niqe=None, deeplab=None, vit=None, swin=None, rvt=None,
-             vgg=None) -> dict:
+             vgg=None, detect=None, det_score=0.05, det_iou=0.5) -> dict:
     """tasks: a list of task names - every batch is restored once and decoded for each of them (DiffUIE.forward_tasks).  PSNR / SSIM
     come from the "ir" output, so the list must hold "ir"; images_per_s counts input images.  model: a ready DiffUIE to use instead
     of building the config's.  With data.CorruptedImageFiles (and data.DistortedImageFiles: "snow/3") the result also holds by_corruption ("fog/3" -> psnr, ssim, images)
@@ -419,6 +466,12 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
     accuracy) of the restored images (val_lq/NAME; by_corruption: NAME) and of the unrestored inputs (val_input/NAME;
     by_corruption: input/NAME).  deeplab: the same form with deeplab.ARCHS and deeplab.DeepLabWeights - the reference's other
     segmenter, DeepLabV3+, scored under the same keys (a name may be used by only one of the two).
+    detect: "NAME=ARCH:WEIGHTS.pth,..." or {NAME: (ARCH, path) | detect.DetectorWeights} - RetinaNet mAP of the "det" output against
+    the data's boxes (tasks must hold "det", the config's tedit.task too, the data must be built with labels: boxes): the result and
+    every by_corruption entry gain, per NAME, the mAP at the one IoU threshold det_iou (0.5; the reference's
+    MeanAveragePrecision(iou_thresholds=[t])) of the restored images (val_lq/NAME; by_corruption: NAME) and of the unrestored inputs
+    (val_input/NAME; by_corruption: input/NAME) over the detections scoring above det_score (0.05, torchvision's default), and
+    det_nonfinite = [restored, input], the images whose detector outputs were not finite.
     crop: (H, W) or "H,W", the centre crop's size instead of 512 x 512.
     niqe: a file of NIQE model parameters (.pt / .pth / .npz / .mat with mu_prisparam and cov_prisparam; the user's, none ship with
     the project) or a loaded niqe.NiqeParams - the no-reference NIQE score (fp64 on the GPU) of the restored images (val_lq/niqe;
@@ -431,6 +484,10 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
         lpips = check_lpips_arg(lpips)                    # before the model is built
     classify, cls_flag = check_classifiers_arg(classify, vit, swin, rvt, vgg)  # before the model is built; from here on one dict of classifiers
     segment, seg_flag = check_segmenters_arg(segment, deeplab)      # from here on one dict of segmenters
+    det_args = {}
+    if detect is not None:
+        detect = check_detect_arg(detect, det_score, det_iou)     # before the model is built
+        det_args = dict(detectors=detect, det_score=det_score, det_iou=det_iou)
     crop_args = {} if crop is None else dict(crop=check_crop_arg(crop))
     r = resolve(cfg, allow_16bit=allow_16bit)
     if tasks is not None:
@@ -442,6 +499,8 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
         check_classify_run(classify, tasks, r, flag=cls_flag)
     if segment is not None:
         check_segment_run(segment, tasks, r, flag=seg_flag)
+    if detect is not None:
+        check_detect_run(detect, tasks, r)
     niqe_args = {}
     if niqe is not None:
         check_niqe_run(crop_args.get("crop"), r)
@@ -449,7 +508,8 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
     from . import data as data_mod
     from .dist import all_gather_images, shard_range
     rank, world, dev, dist, lit = _start(r, hf_root, random_init, model, metrics_device=metrics_device, lpips_weights=lpips,
-                                         classifiers=classify, segmenters=segment, **crop_args, **niqe_args, **r["caller_args"])
+                                         classifiers=classify, segmenters=segment, **crop_args, **niqe_args, **det_args,
+                                         **r["caller_args"])
     pairs = lit.NIQE_KEYS if niqe is not None else ()     # the NIQE states: fp64 [2] device tensors (sum of finite scores, count)
     sums = ("psnr", "ssim") + (("lpips",) if lpips is not None else ())          # the metric states, in all-reduce order
     counts = [k for name in (classify or {}) for k in lit.classifier_keys(name)]  # the classifiers' int64 [3, classes] count states
@@ -462,6 +522,7 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
     # a dataset of files degraded on the GPU says what its last batch was: "fog/3" (data.JpegImageFiles: "jpeg/10", the quality)
     # -> metric sums of its batches
     by_corruption = {} if hasattr(data, "last") else None
+    det_by = {}                                           # "fog/3" -> {totals key: detect.MeanAP of its batches}
     for i, batch in enumerate(data.batches(rank, world, dev)):
         if max_batches is not None and i >= max_batches:
             break
@@ -483,6 +544,12 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
             lit.update_classification(by_task["cls"], batch[0], batch[2])
         if segment is not None:
             lit.update_segmentation(by_task["seg"], batch[0], batch[2])
+        if detect is not None:                            # the metric update is host fp64, untimed like the others
+            batch_ap = lit.update_detection(by_task["det"], batch[0], batch[2])
+            if by_corruption is not None:
+                mine = det_by.setdefault("%s/%d" % data.last, {})
+                for k, ap in batch_ap.items():
+                    mine[k] = mine[k].merge(ap) if k in mine else ap
         lit.update_niqe(by_task["ir"], batch[0])              # (nothing without --niqe)
         if by_corruption is not None:                     # the batch is homogeneous: its increment of the totals belongs to one key
             acc = by_corruption.setdefault("%s/%d" % data.last, dict({k: 0.0 for k in sums}, **{k: 0 for k in counts},
@@ -500,6 +567,12 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
             dist.all_reduce(flat)
             for k, part in zip(counts, flat.split([lit.totals[k].numel() for k in counts])):
                 lit.totals[k] = part.view_as(lit.totals[k])
+        if detect is not None:                            # the per-class (score, tp) lists: every rank's, merged in rank order
+            mine = ({k: lit.totals[k] for name in detect for k in lit.detector_keys(name)}, lit.det_nonfinite, det_by)
+            everyone = [None] * world
+            dist.all_gather_object(everyone, mine)
+            totals, lit.det_nonfinite, det_by = merge_detection_states(everyone, det_iou)
+            lit.totals.update(totals)
         if pairs:                                         # the NIQE sums and counts, and the images they were asked for
             flat = torch.cat([lit.totals[k].to(dev) for k in pairs] + [torch.tensor([lit.niqe_seen], dtype=torch.float64, device=dev)])
             dist.all_reduce(flat)
@@ -522,6 +595,9 @@ def validate(cfg: dict, hf_root=None, max_batches=None, random_init=True, allow_
                 from .segment import miou
                 for prefix, key in zip(("", "input/"), lit.segmenter_keys(name)):
                     res["by_corruption"][k][f"{prefix}{name}"], res["by_corruption"][k][f"{prefix}{name}_acc"] = miou(v[key])[:2]
+            for name in (detect or {}):
+                for prefix, key in zip(("", "input/"), lit.detector_keys(name)):
+                    res["by_corruption"][k][f"{prefix}{name}"] = det_by[k][key].compute()["map"]
             for prefix, key in zip(("", "input/"), pairs):    # the mean over this key's images with a finite score
                 total, count = v[key].tolist()
                 res["by_corruption"][k][f"{prefix}niqe"] = total / count if count else float("nan")
@@ -917,13 +993,21 @@ def main(argv=None):
                     help="validate: also report DeepLabV3+ (output stride 16) mIoU and pixel accuracy of the 'seg' output (fp32, on the "
                          "GPU) against the data's label maps; ARCH is dlv3pr50 or dlv3pr101, WEIGHTS a user-supplied checkpoint; needs "
                          "--tasks with seg and a dataset built with labels: map; a NAME may not be one of --segment's")
+    ap.add_argument("--detect", default=None, metavar="NAME=ARCH:WEIGHTS.pth[,...]",
+                    help="validate: also report RetinaNet mAP of the 'det' output (fp32, on the GPU; the metric in fp64 on the host) "
+                         "against the data's boxes; ARCH is retinanet_resnet50_fpn_v2, WEIGHTS a user-supplied torchvision state dict; "
+                         "needs --tasks with det, a config whose tedit.task holds det and a dataset built with labels: boxes")
+    ap.add_argument("--det-score", type=float, default=None, metavar="T",
+                    help="validate --detect: the detector's score threshold (default 0.05, torchvision's own)")
+    ap.add_argument("--det-iou", type=float, default=None, metavar="T",
+                    help="validate --detect: the IoU threshold of the mAP (default 0.5)")
     ap.add_argument("--crop", default=None, metavar="H,W",
                     help="validate: the evaluator's centre crop (default 512,512; the reference's seg evaluator uses 960,1664)")
     ap.add_argument("--niqe", default=None, metavar="PARAMS",
                     help="validate: also report the no-reference NIQE score (fp64, on the GPU) of the restored images and of the inputs; "
                          "PARAMS is a user-supplied file of model parameters (.pt / .pth / .npz / .mat with mu_prisparam and "
                          "cov_prisparam); the crop must hold two 96 x 96 blocks")
-    ap.add_argument("--tasks", default=None, metavar="ir,cls,seg",
+    ap.add_argument("--tasks", default=None, metavar="ir,cls,seg,det",
                     help="restore every batch once and decode it for each of these tasks (forward_tasks); validate: must hold 'ir', which "
                          "feeds PSNR / SSIM; restore: one sub-folder of --output per task")
     ap.add_argument("--task", default=None, help="restore: the task to decode for (default ir)")
@@ -949,9 +1033,13 @@ def main(argv=None):
     ap.add_argument("--quality", default=None, metavar="10,25,s3", help="jpeg: qualities 1..100 and / or s1..s5 (the reference's severities)")
     ap.add_argument("--subsampling", default="4:2:0", help="jpeg: 4:2:0 (Pillow's and the reference's default) or 4:4:4")
     a = ap.parse_args(argv)
-    for flag in ("classify", "vit", "swin", "rvt", "vgg", "segment", "deeplab", "crop", "niqe"):
+    for flag in ("classify", "vit", "swin", "rvt", "vgg", "segment", "deeplab", "crop", "niqe", "detect", "det_score", "det_iou"):
         if getattr(a, flag) is not None and a.command != "validate":
-            ap.error(f"--{flag} belongs to validate")
+            ap.error(f"--{flag.replace('_', '-')} belongs to validate")
+    if a.detect is None and (a.det_score is not None or a.det_iou is not None):
+        ap.error("--det-score and --det-iou belong to --detect")
+    a.det_score = 0.05 if a.det_score is None else a.det_score
+    a.det_iou = 0.5 if a.det_iou is None else a.det_iou
     if a.command in FILE_COMMANDS:
         check, run, errors = FILE_COMMANDS[a.command]
         kw = dict(inp=a.input, output=a.output, batch=a.batch, resize=a.resize)
@@ -989,6 +1077,8 @@ def main(argv=None):
         segmenters, seg_flag = check_segmenters_arg(a.segment, a.deeplab)
         if segmenters is not None:
             check_segment_run(segmenters, tasks, resolve(cfg, allow_16bit=a.allow_16bit), flag=seg_flag)
+        if a.detect is not None:
+            check_detect_run(check_detect_arg(a.detect, a.det_score, a.det_iou), tasks, resolve(cfg, allow_16bit=a.allow_16bit))
         if a.crop is not None:
             a.crop = check_crop_arg(a.crop)
         if a.niqe is not None:
@@ -1008,7 +1098,7 @@ def main(argv=None):
         return 0
     res = validate(cfg, hf_root=a.hf_root, max_batches=a.max_batches, allow_16bit=a.allow_16bit, metrics_device=a.metrics_device,
                    tasks=tasks, lpips=a.lpips, classify=a.classify, segment=a.segment, crop=a.crop, niqe=a.niqe, deeplab=a.deeplab, vit=a.vit, swin=a.swin,
-                   rvt=a.rvt, vgg=a.vgg)
+                   rvt=a.rvt, vgg=a.vgg, detect=a.detect, det_score=a.det_score, det_iou=a.det_iou)
     if res is not None:
         print(json.dumps(res))
     return 0

@@ -4,7 +4,9 @@ JPEG-compressed on the GPU at a list of qualities (unirestore_amd.jpeg), and `Di
 snow and elastic transform (unirestore_amd.distort).  The last three share `_DegradedImageFiles`: the constructor checks and the load /
 degrade / yield loop are written once there.  The four file datasets take `labels=True`: gt is then the int64 labels of the list's
 third column (what a classifier is scored against) instead of None; `labels="map"`: the third column is the path of a label PNG
-and gt the int64 [B,H,W] label maps (what a segmenter is scored against), Cityscapes labelIds mapped to trainIds by default.
+and gt the int64 [B,H,W] label maps (what a segmenter is scored against), Cityscapes labelIds mapped to trainIds by default;
+`labels="boxes"`: the third column is the path of an annotation JSON and gt a list of {boxes, labels} (what a detector is scored
+against), the names mapped to COCO ids by `box_classes`.
 
 `SyntheticImages` yields the evaluator's batch tuple `(lq, hq, gt, fname, task)` (reference
 src/core/base/eval_image_restoration.py:56) from seeded random images: hq = torch.rand (what the reference's own smoke
@@ -85,11 +87,75 @@ CITYSCAPES_TRAIN_ID = {7: 0, 8: 1, 11: 2, 12: 3, 13: 4, 17: 5, 19: 6, 20: 7, 21:
                        31: 16, 32: 17, 33: 18}
 
 
-def check_labels_arg(labels, label_encoding):
-    if labels not in (False, True, "map"):
-        raise ValueError(f"labels must be false, true (an integer per line) or \"map\" (a label PNG per line), got {labels!r}")
+BOX_CLASSES = ("rtts", "coco")
+# the reference's two name -> COCO id tables (dataset_det.py): RTTS's five classes, and the 91-entry COCO category list by position
+RTTS_COCO_IDS = {"person": 1, "bicycle": 2, "car": 3, "bus": 6, "motorbike": 4}
+COCO_NAMES = ("__background__", "person", "bicycle", "car", "motorcycle", "airplane", "bus", "train", "truck", "boat", "traffic light",
+              "fire hydrant", "N/A", "stop sign", "parking meter", "bench", "bird", "cat", "dog", "horse", "sheep", "cow", "elephant", "bear",
+              "zebra", "giraffe", "N/A", "backpack", "umbrella", "N/A", "N/A", "handbag", "tie", "suitcase", "frisbee", "skis", "snowboard",
+              "sports ball", "kite", "baseball bat", "baseball glove", "skateboard", "surfboard", "tennis racket", "bottle", "N/A",
+              "wine glass", "cup", "fork", "knife", "spoon", "bowl", "banana", "apple", "sandwich", "orange", "broccoli", "carrot", "hot dog",
+              "pizza", "donut", "cake", "chair", "couch", "potted plant", "bed", "N/A", "dining table", "N/A", "N/A", "toilet", "N/A", "tv",
+              "laptop", "mouse", "remote", "keyboard", "cell phone", "microwave", "oven", "toaster", "sink", "refrigerator", "N/A", "book",
+              "clock", "vase", "scissors", "teddy bear", "hair drier", "toothbrush")
+COCO_IDS = {name: i for i, name in enumerate(COCO_NAMES)}
+
+
+def check_labels_arg(labels, label_encoding, box_classes="rtts"):
+    if labels not in (False, True, "map", "boxes"):
+        raise ValueError("labels must be false, true (an integer per line), \"map\" (a label PNG per line) or \"boxes\" (an annotation "
+                         f"JSON per line), got {labels!r}")
     if label_encoding not in LABEL_ENCODINGS:
         raise ValueError(f"unknown label_encoding {label_encoding!r}: choose from {LABEL_ENCODINGS}")
+    if box_classes not in BOX_CLASSES:
+        raise ValueError(f"unknown box_classes {box_classes!r}: choose from {BOX_CLASSES}")
+
+
+def load_boxes(path: str, box_classes: str, where: str) -> dict:
+    """One annotation JSON in the reference's format as {boxes float32 [n,4] (xmin, ymin, xmax, ymax), labels int64 [n]}: every
+    top-level key that contains `object` holds {"name", "bndbox": {xmin, ymin, xmax, ymax}}; a box with xmax <= xmin or ymax <= ymin
+    is skipped.  ValueError naming `where` (file:line of the list) when the file is missing or malformed, a name is not in the
+    class table, or no box is left (the reference refuses such an image as well)."""
+    import json
+    import os
+    if not os.path.isfile(path):
+        raise ValueError(f"{where}: the annotation file {path!r} does not exist")
+    table = RTTS_COCO_IDS if box_classes == "rtts" else COCO_IDS
+    boxes, labels = [], []
+    try:
+        with open(path) as f:
+            ann = json.load(f)
+        for key, v in ann.items():
+            if "object" not in key:
+                continue
+            bb = v["bndbox"]
+            try:
+                x0, y0, x1, y1 = (float(bb[k]) for k in ("xmin", "ymin", "xmax", "ymax"))
+            except ValueError as e:
+                raise TypeError(f"a coordinate of {key!r} is no number: {e}") from None
+            if x1 > x0 and y1 > y0:
+                if v["name"] not in table:
+                    raise ValueError(f"{where}: {path!r}: the class {v['name']!r} is not in the {box_classes!r} table")
+                boxes.append([x0, y0, x1, y1])
+                labels.append(table[v["name"]])
+    except (KeyError, TypeError, AttributeError, json.JSONDecodeError) as e:
+        raise ValueError(f"{where}: {path!r} is no annotation file of the expected form ({type(e).__name__}: {e})") from None
+    if not boxes:
+        raise ValueError(f"{where}: {path!r} holds no valid box")
+    return {"boxes": torch.tensor(boxes, dtype=torch.float32).view(-1, 4), "labels": torch.tensor(labels, dtype=torch.int64)}
+
+
+def crop_boxes(gt: list, top: int, left: int, height: int, width: int) -> list:
+    """The targets of a batch under a crop of its images to rows top .. top + height, columns left .. left + width: the boxes
+    shifted by the offset and clipped to the crop; a box left without area is dropped with its label."""
+    out = []
+    for t in gt:
+        b = t["boxes"].clone().view(-1, 4)
+        b[:, 0::2] = (b[:, 0::2] - left).clamp(0, width)
+        b[:, 1::2] = (b[:, 1::2] - top).clamp(0, height)
+        keep = (b[:, 2] > b[:, 0]) & (b[:, 3] > b[:, 1])
+        out.append({"boxes": b[keep], "labels": t["labels"][keep]})
+    return out
 
 
 def read_label_paths(list_file: str) -> List[Tuple[str, int]]:
@@ -139,14 +205,16 @@ def load_label_map(path: str, encoding: str, hw, where: str) -> torch.Tensor:
 class _Labels:
     """The `labels` / `label_encoding` arguments of the file datasets: gt of a batch from the list's third column."""
 
-    def __init__(self, list_file, labels, label_encoding):
-        check_labels_arg(labels, label_encoding)
-        self.kind, self.encoding, self.list_file = labels, label_encoding, list_file
-        self.values = read_label_paths(list_file) if labels == "map" else read_labels(list_file) if labels else None
+    def __init__(self, list_file, labels, label_encoding, box_classes="rtts"):
+        check_labels_arg(labels, label_encoding, box_classes)
+        self.kind, self.encoding, self.list_file, self.box_classes = labels, label_encoding, list_file, box_classes
+        self.values = read_label_paths(list_file) if labels in ("map", "boxes") else read_labels(list_file) if labels else None
 
     def gt(self, idx, hw):
         if self.values is None:
             return None
+        if self.kind == "boxes":
+            return [load_boxes(self.values[i][0], self.box_classes, f"{self.list_file}:{self.values[i][1]}") for i in idx]
         if self.kind == "map":
             return torch.stack([load_label_map(self.values[i][0], self.encoding, hw, f"{self.list_file}:{self.values[i][1]}") for i in idx])
         return torch.tensor([self.values[i] for i in idx], dtype=torch.int64)
@@ -159,13 +227,16 @@ class ImageListFiles:
     group, so every batch is one tensor (the evaluator's centre crop makes nearly everything 512 x 512).  labels=True: gt is an
     int64 [B] tensor of the lines' third column (a classifier's targets) instead of None.  labels="map": the third column is the
     path of a label PNG of the lq image's size and gt the int64 [B,H,W] maps (a segmenter's targets); label_encoding "cityscapes"
-    (the default) maps labelIds to trainIds, 255 for the rest, "train_id" takes the values as they are."""
+    (the default) maps labelIds to trainIds, 255 for the rest, "train_id" takes the values as they are.  labels="boxes": the third
+    column is the path of an annotation JSON (load_boxes) and gt a list of {boxes float32 [n,4], labels int64 [n]} (a detector's
+    targets), the class names mapped to COCO ids by box_classes "rtts" (the default) or "coco".  The three degrading datasets take
+    the same two arguments; a degradation never touches the boxes."""
 
     def __init__(self, list_file: str, batch_size: int = 8, task: str = "ir", num_batches: int = None, labels=False,
-                 label_encoding: str = "cityscapes"):
+                 label_encoding: str = "cityscapes", box_classes: str = "rtts"):
         import os
         self.list_file, self.batch_size, self.task, self.num_batches = list_file, int(batch_size), task, num_batches
-        self._labels = _Labels(list_file, labels, label_encoding)
+        self._labels = _Labels(list_file, labels, label_encoding, box_classes)
         self.labels = self._labels.values
         base = os.path.dirname(os.path.abspath(list_file))
         self.pairs = []
@@ -215,14 +286,15 @@ class _DegradedImageFiles:
     length and the loop over it.  A subclass gives `_plan()` -> the batches, each a tuple that ends in the batch's file indices,
     and `_degrade(hq, stems, *what)` -> (lq, label): `what` is the rest of that tuple, `label` what `last` holds after the batch."""
 
-    def __init__(self, source, batch_size, task, seed, num_batches, resize, min_side, labels=False, label_encoding="cityscapes"):
+    def __init__(self, source, batch_size, task, seed, num_batches, resize, min_side, labels=False, label_encoding="cityscapes",
+                 box_classes="rtts"):
         from . import resize as rz
         self.resize = None if resize is None else rz.check_range(resize, min_side)
         self.source, self.batch_size, self.task, self.seed, self.num_batches = source, int(batch_size), task, int(seed), num_batches
         if self.batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
         self.paths = corrupt.check_inputs(source)
-        self._labels = _Labels(source, labels, label_encoding)         # one per line of the list, the order of `paths`
+        self._labels = _Labels(source, labels, label_encoding, box_classes)         # one per line of the list, the order of `paths`
         self.labels = self._labels.values
         self.last = None
 
@@ -264,8 +336,8 @@ class CorruptedImageFiles(_DegradedImageFiles):
     _planner = corrupt                             # the module whose expand / degrade this class uses (DistortedImageFiles: distort)
 
     def __init__(self, source: str, corruptions="common", severity=3, batch_size: int = 8, task: str = "ir", seed: int = 42,
-                 num_batches: int = None, labels=False, label_encoding: str = "cityscapes", resize=None):
-        super().__init__(source, batch_size, task, seed, num_batches, resize, 32, labels, label_encoding)
+                 num_batches: int = None, labels=False, label_encoding: str = "cityscapes", box_classes: str = "rtts", resize=None):
+        super().__init__(source, batch_size, task, seed, num_batches, resize, 32, labels, label_encoding, box_classes)
         self.names = self._planner.expand(corruptions)
         self.skipped = corrupt.skipped(corruptions)
         self.severity = severity if severity == "mixed" else corrupt.check_severity(severity)
@@ -287,8 +359,8 @@ class DistortedImageFiles(CorruptedImageFiles):
     _planner = distort
 
     def __init__(self, source: str, corruptions="all", severity=3, batch_size: int = 8, task: str = "ir", seed: int = 42,
-                 num_batches: int = None, labels=False, label_encoding: str = "cityscapes", resize=None):
-        super().__init__(source, corruptions, severity, batch_size, task, seed, num_batches, labels, label_encoding, resize)
+                 num_batches: int = None, labels=False, label_encoding: str = "cityscapes", box_classes: str = "rtts", resize=None):
+        super().__init__(source, corruptions, severity, batch_size, task, seed, num_batches, labels, label_encoding, box_classes, resize)
         self.skipped = []
 
 
@@ -303,8 +375,8 @@ class JpegImageFiles(_DegradedImageFiles):
     [lo, hi) by (`seed`, stem), the only use of `seed`; lq keeps hq's shape."""
 
     def __init__(self, source: str, quality=(10, 25, 50), batch_size: int = 8, task: str = "ir", num_batches: int = None,
-                 labels=False, label_encoding: str = "cityscapes", resize=None, seed: int = 42):
-        super().__init__(source, batch_size, task, seed, num_batches, resize, jpeg.MIN_SIDE, labels, label_encoding)
+                 labels=False, label_encoding: str = "cityscapes", box_classes: str = "rtts", resize=None, seed: int = 42):
+        super().__init__(source, batch_size, task, seed, num_batches, resize, jpeg.MIN_SIDE, labels, label_encoding, box_classes)
         specs = [s for s in quality.split(",") if s] if isinstance(quality, str) else \
             list(quality) if isinstance(quality, (list, tuple)) else [quality]
         self.qualities = []

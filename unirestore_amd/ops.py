@@ -1361,6 +1361,33 @@ def confusion(pred: torch.Tensor, target: torch.Tensor, classes: int = 19, ignor
     return _segment.confusion(pred, target, classes, ignore_index)
 
 
+def detect(images: torch.Tensor, weights, score_thresh: float = 0.05, topk_candidates: int = 1000, nms_thresh: float = 0.5,
+           detections_per_img: int = 300) -> list:
+    """RetinaNet detections of fp32 NCHW images [N,3,H,W] in [0,1] (one size per batch), torchvision's result: per image {boxes
+    [n,4] (x1, y1, x2, y2 in the image's own pixels), scores [n] descending, labels int64 [n]} on the device.  weights: what
+    detect.load_weights / detect.random_weights return.  The defaults are torchvision's own.  An image whose logits or regressions
+    were not finite has no detections (detect.forward also returns that flag; detect.raw is the padded, sync-free form)."""
+    from . import detect as _detect
+    if not isinstance(weights, _detect.DetectorWeights):
+        raise ValueError(f"detect: weights must be a detect.DetectorWeights, got {type(weights).__name__}")
+    if not isinstance(images, torch.Tensor) or images.dtype != torch.float32 or images.ndim != 4 or images.shape[1] != 3 or images.numel() < 1:
+        raise ValueError(f"detect: images must be a non-empty fp32 [N,3,H,W] tensor, got {getattr(images, 'dtype', type(images))} "
+                         f"{tuple(getattr(images, 'shape', ()))}")
+    if images.device != weights.device:
+        raise ValueError(f"detect: images are on {images.device}, the weights on {weights.device}")
+    return _detect.forward(images.contiguous(), weights, score_thresh=score_thresh, topk_candidates=topk_candidates, nms_thresh=nms_thresh,
+                           detections_per_img=detections_per_img)[0]
+
+
+def mean_ap(detections, targets, iou: float = 0.5) -> float:
+    """The mean average precision at one IoU threshold of per-image detections against per-image targets {boxes, labels}: one
+    detect.MeanAP update (host fp64; pycocotools' algorithm, area range all, 100 detections per image and class)."""
+    from .detect import MeanAP
+    m = MeanAP(iou)
+    m.update(detections, targets)
+    return m.compute()["map"]
+
+
 def profile_enable(on: bool):
     check(lib.ur_profile_enable(int(on)))
 

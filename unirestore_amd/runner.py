@@ -105,7 +105,8 @@ class LitUniFIE:
 
     def __init__(self, model_kwargs: dict, save_image: bool = False, eval_mode: str = "FR", need_crop: bool = True,
                  dtype: str = "bf16", hf_root: str = None, model=None, metrics_device: str = "cpu", lpips_weights=None,
-                 classifiers=None, segmenters=None, crop=DEFAULT_CROP, niqe_params=None, **_ignored):
+                 classifiers=None, segmenters=None, crop=DEFAULT_CROP, niqe_params=None, detectors=None, det_score: float = 0.05,
+                 det_iou: float = 0.5, **_ignored):
         from . import checkpoint
         if metrics_device not in METRICS_DEVICES:
             raise ValueError(f"metrics_device={metrics_device!r}: choose from {METRICS_DEVICES}")
@@ -156,6 +157,17 @@ class LitUniFIE:
             for key in self.segmenter_keys(name):
                 self.totals[key] = torch.zeros(w.num_classes, w.num_classes, dtype=torch.int64, device=w.device)
 
+        # Detector scoring of the "det" output (RetinaNet mAP at one IoU threshold, exact fp32 HIP kernels; the metric itself is host
+        # fp64) is off unless detectors are given: {name: (arch, state-dict path) | detect.DetectorWeights}.  Per name the totals hold
+        # a detect.MeanAP for the restored images ("det/<name>") and one for the unrestored inputs ("det_input/<name>");
+        # det_nonfinite counts the images of either kind whose detector outputs were not finite (they have no detections).
+        self.detectors, self.det_score, self.det_iou, self.det_nonfinite = {}, float(det_score), float(det_iou), [0, 0]
+        for name, spec in (detectors or {}).items():
+            from . import detect
+            self.detectors[name] = spec if isinstance(spec, detect.DetectorWeights) else detect.load_weights(*spec)
+            for key in self.detector_keys(name):
+                self.totals[key] = detect.MeanAP(self.det_iou)
+
         # NIQE (no reference, fp64 HIP kernels) is off unless a pristine model is given: a path niqe.load_params reads or a loaded
         # niqe.NiqeParams.  It needs no hq and runs whatever eval_mode says.  totals["niqe"] (the restored images) and
         # totals["niqe_input"] (the unrestored inputs) are fp64 [2] device tensors, the sum of the finite scores and their count -
@@ -173,6 +185,11 @@ class LitUniFIE:
     def segmenter_keys(name: str):
         """The two `totals` keys of segmenter `name`: the restored images' confusion matrix, the unrestored inputs'."""
         return f"seg/{name}", f"seg_input/{name}"
+
+    @staticmethod
+    def detector_keys(name: str):
+        """The two `totals` keys of detector `name`: the restored images' MeanAP state, the unrestored inputs'."""
+        return f"det/{name}", f"det_input/{name}"
 
     def _crop(self, t):
         return crop_tensor(t, self.crop)
@@ -198,6 +215,9 @@ class LitUniFIE:
         if self.segmenters and metrics and (tasks is None or "seg" not in tasks):
             raise ValueError(f"tasks={None if tasks is None else list(tasks)}: the segmenters score the 'seg' output - pass tasks "
                              "with 'seg' in it")
+        if self.detectors and metrics and (tasks is None or "det" not in tasks):
+            raise ValueError(f"tasks={None if tasks is None else list(tasks)}: the detectors score the 'det' output - pass tasks "
+                             "with 'det' in it")
         if tasks is not None:
             if "ir" not in tasks:
                 raise ValueError(f"tasks={list(tasks)}: PSNR / SSIM are computed on the 'ir' output - add 'ir' to the list")
@@ -208,6 +228,8 @@ class LitUniFIE:
                 self.update_classification(outs[-1]["cls"], lq, gt)
             if metrics and self.segmenters:
                 self.update_segmentation(outs[-1]["seg"], lq, gt)
+            if metrics and self.detectors:
+                self.update_detection(outs[-1]["det"], lq, gt)
             if metrics:
                 self.update_niqe(outs[-1]["ir"], lq)
             return outs
@@ -340,6 +362,34 @@ class LitUniFIE:
                 pred = predict(images.to(device=w.device, dtype=torch.float32).contiguous(), w)
                 self.totals[key] = self.totals[key] + segment.confusion(pred, target, w.num_classes)
 
+    def update_detection(self, det_preds: torch.Tensor, inputs: torch.Tensor, targets) -> dict:
+        """The mAP states of one batch, for every detector: of `det_preds`, the quantised "det" output (the tensor the reference's
+        evaluator hands to its detector), and of `inputs`, the unrestored lq images it was restored from.  targets: the batch's list
+        of {boxes [n,4], labels [n]} in the uncropped images' coordinates; with need_crop the inputs are centre-cropped with the
+        restoration's own box and the boxes shifted by its offset, clipped to it and dropped when nothing is left.  The metric
+        update is host fp64 (untimed, like NIQE's algebra).  Returns {totals key: this batch's own detect.MeanAP} - what a caller
+        that splits the totals by batch merges elsewhere; {} when no detector is configured."""
+        if not self.detectors:
+            return {}
+        if not isinstance(targets, (list, tuple)) or len(targets) != det_preds.shape[0] or not all(isinstance(t, dict) for t in targets):
+            raise ValueError("the detectors need the batch's boxes (gt is no list of {boxes, labels}, one per image): build the dataset "
+                             "with labels: boxes on an `lq hq annotation.json` list")
+        from . import data, detect
+        if self.need_crop:
+            t, b, l, r = crop_box(inputs.shape[-2], inputs.shape[-1], self.crop[0], self.crop[1])
+            inputs, targets = self._crop(inputs), data.crop_boxes(targets, t, l, b - t, r - l)
+        if tuple(inputs.shape[2:]) != tuple(det_preds.shape[2:]):
+            raise ValueError(f"the inputs are {tuple(inputs.shape)}, the det output {tuple(det_preds.shape)}")
+        batch = {}
+        for name, w in self.detectors.items():
+            for j, (key, images) in enumerate(zip(self.detector_keys(name), (det_preds, inputs))):
+                dets, bad = detect.forward(images.to(device=w.device, dtype=torch.float32).contiguous(), w, score_thresh=self.det_score)
+                self.det_nonfinite[j] += int(bad.sum())
+                batch[key] = detect.MeanAP(self.det_iou)
+                batch[key].update(dets, targets)
+                self.totals[key].merge(batch[key])
+        return batch
+
     def update_niqe(self, preds: torch.Tensor, lq: torch.Tensor):
         """The NIQE states of one batch: of `preds`, the quantised "ir" output, and of `lq`, the unrestored inputs it was restored
         from (centre-cropped as the restoration's input is when need_crop is on), so the two scores cover the same pixels.  An
@@ -371,6 +421,11 @@ class LitUniFIE:
             from .segment import miou
             for prefix, key in zip(("val_lq", "val_input"), self.segmenter_keys(name)):
                 res[f"{prefix}/{name}"], res[f"{prefix}/{name}_acc"] = miou(self.totals[key])[:2]
+        for name in self.detectors:                       # mAP = the reference's MeanAveragePrecision(iou_thresholds=[det_iou])
+            for prefix, key in zip(("val_lq", "val_input"), self.detector_keys(name)):
+                res[f"{prefix}/{name}"] = self.totals[key].compute()["map"]
+        if self.detectors:
+            res["det_nonfinite"] = list(self.det_nonfinite)
         if self.niqe_params is not None:                  # the mean over the images with a finite score; the others are counted
             res["niqe_skipped"] = []
             for prefix, key in zip(("val_lq", "val_input"), self.NIQE_KEYS):
